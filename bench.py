@@ -9,7 +9,10 @@ temperature 0.1, SGD lr 0.001, uniform ids, synthetic counter-based data (SURVEY
 `--config cfg1|cfg2|cfg3` selects another single-GPU configuration.
 
 Inputs (tables, weights, id batches) are resident in HBM before the timed region.  A step is one
-pass of the hot path over one batch.  The `roofline` object is measured live, inside the timed
+pass of the hot path over one batch.  A plain run sets up, warms up, times the K steps and prints the
+headline line; `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
+Everything else below (roofline, detail passes, the bf16x3 line, cpu_baseline) runs with `--full`.
+The `roofline` object is measured live, inside the timed
 steps: sampled launches of the dominant kernel go out through hipExtLaunchKernelGGL with a HIP event
 pair that the runtime fills with the dispatch's own begin / end timestamps on its stream
 (tt_profile_enable; r04 - the figures rocprofv3 --kernel-trace reports, no barrier packets; through
@@ -72,7 +75,12 @@ def parse():
                     help="N>1: in-batch negatives over the all-gathered GLOBAL batch (the loss of the single device on the global "
                          "batch; default for cfg4 / cfg5, BASELINE's fixed global problems) or over each rank's own batch (what a "
                          "data-parallel Keras replica computes; default for the weak-scaled cfg3 family: per-GPU work fixed as N "
-                         "grows).  The other mode is timed in the same run and reported as `other_negatives`")
+                         "grows).  With --full the other mode is timed in the same run and reported as `other_negatives`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline timestamps inside the timed steps, the untimed "
+                         "detail passes, the bf16x3 line, cpu_baseline (N>1: collectives, other_negatives)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -164,6 +172,41 @@ def mean(xs):
     return sum(xs) / max(len(xs), 1)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROWS = 4096            # embedding rows dumped per table: those of the first ids of the last batch (cfg5: 4 MB each)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float32, float64 kept), at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def step_outputs(trainer, uid, iid):
+    """What the last step computed, as a caller of TwoTowerTrainer.step receives it: the summed loss it returns, the
+    per-pair losses, and the parameters it updated in place (dense towers whole; of each table, the rows at the first
+    DUMP_ROWS ids of the step's batch)."""
+    u, i = uid[:DUMP_ROWS], iid[:DUMP_ROWS]
+    out = {"loss": trainer.loss, "per_pair_loss": trainer.per_row, "dense_params": trainer.dense_flat,
+           "user_rows": trainer.user_table[u], "item_rows": trainer.item_table[i]}
+    if trainer.cat_table is not None:
+        out["category_table"] = trainer.cat_table
+    if trainer.cfg.optimizer == "adagrad":
+        out.update(dense_accum=trainer.dense_accum, user_accum_rows=trainer.user_accum[u], item_accum_rows=trainer.item_accum[i])
+        if trainer.cat_accum is not None:
+            out["category_accum"] = trainer.cat_accum
+    return out
+
+
 def cpu_baseline(trainer, cfg, seed, args, batch):
     """torch-CPU restatement on the same model state and batches (bounded sample)."""
     from oracle.torch_cpu import TorchCpuTwoTower, time_cpu_steps      # bench's cpu_baseline leg only
@@ -233,19 +276,22 @@ def run_ops_engine(args, cfg, seed, dev):
     for s in range(args.warmup):
         step(s)
     torch.cuda.synchronize()
-    _lib.profile_set_stride(4 if args.steps >= 8 else 1)
-    _lib.profile_enable("score_fused", capacity=2 * args.steps + 8)
+    if args.full:
+        _lib.profile_set_stride(4 if args.steps >= 8 else 1)
+        _lib.profile_enable("score_fused", capacity=2 * args.steps + 8)
     t0 = time.perf_counter()
     for s in range(args.warmup, total):
         loss = step(s)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    tf_ = mean(_lib.profile_read("score_fused", 2 * args.steps + 8)[0]) * 1e-3
-    _lib.profile_set_stride(1)
-    _lib.profile_enable("")
-    sd = dims[-1]
-    a = 4.0 * batch * batch * sd / tf_ / 1e12 if tf_ > 0 else None
-    print(json.dumps({
+    if args.dump_outputs:
+        u, i = ids[(total - 1) % len(ids)]
+        arrays = {"loss": loss, "user_rows": tables[0][u[:DUMP_ROWS]], "item_rows": tables[1][i[:DUMP_ROWS]]}
+        for name, (ws, bs) in zip(("user", "item"), towers):
+            for l, (w, b) in enumerate(zip(ws, bs)):
+                arrays[f"{name}_w{l}"], arrays[f"{name}_b{l}"] = w, b
+        dump_outputs(args.dump_outputs, arrays)
+    out = {
         "metric": "user-item pairs/sec (train step) + embedding-gather HBM GB/s, 1/2/4/8 MI355X",
         "value": batch / (dt / args.steps), "unit": "pairs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -257,10 +303,19 @@ def run_ops_engine(args, cfg, seed, dev):
                              "retrieval_loss, sparse_update_) + a stock torch optimizer on the Dense parameters",
                    "global_batch": batch, "parallelism": "single GPU"},
         "note": "EXTRA line (the boundary itself), not the headline: the headline engine is the explicit trainer behind tt_train_step_f32",
-        "roofline": {"bound": "mfma", "kernel": f"score_kernel<{sd},FUSED_S> (loss + dq pass of torch.ops.twotower.retrieval_loss)",
-                     "achieved": a, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": (a / MFMA_F32_PEAK_TFLOPS) if a else None,
-                     "traffic": None, "avg_launch_us": tf_ * 1e6},
-        "loss_per_pair": float(loss.item()) / batch}))
+        "loss_per_pair": float(loss.item()) / batch}
+    if not args.full:
+        print(json.dumps(out))
+        return
+    tf_ = mean(_lib.profile_read("score_fused", 2 * args.steps + 8)[0]) * 1e-3
+    _lib.profile_set_stride(1)
+    _lib.profile_enable("")
+    sd = dims[-1]
+    a = 4.0 * batch * batch * sd / tf_ / 1e12 if tf_ > 0 else None
+    out["roofline"] = {"bound": "mfma", "kernel": f"score_kernel<{sd},FUSED_S> (loss + dq pass of torch.ops.twotower.retrieval_loss)",
+                       "achieved": a, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": (a / MFMA_F32_PEAK_TFLOPS) if a else None,
+                       "traffic": None, "avg_launch_us": tf_ * 1e6}
+    print(json.dumps(out))
 
 
 def main():
@@ -284,7 +339,7 @@ def main():
 
     if world > 1 or os.environ.get("TT_FORCE_DIST"):      # TT_FORCE_DIST=1: exercise the sharded path on one rank
         from bench_dist import run_distributed          # row-sharded tables + RCCL all-to-all
-        return run_distributed(args, rank, world, dev)
+        return run_distributed(args, rank, world, dev, dump_outputs)
 
     n_users, n_items, dim, tower_dims, batch = CONFIGS[args.config]
     seed = 1000 + (9 if args.config == "ref" else int(args.config[3:]))
@@ -329,7 +384,7 @@ def main():
     torch.cuda.synchronize()
     trainer.check_ids()
 
-    # Timed region: only the DOMINANT kernel is timestamped (hipExtLaunchKernelGGL with an event pair: the dispatch's own begin /
+    # Timed region (--full): only the DOMINANT kernel is timestamped (hipExtLaunchKernelGGL with an event pair: the dispatch's own begin /
     # end timestamps - no barrier packets, but a timestamped dispatch still costs the stream ~4 us: with all five kernel families
     # on at stride 4 the step was 0.5642 ms against 0.5584, r04 call 1).  The other kernels' durations come from an untimed detail
     # pass of the same steps right after it.
@@ -339,14 +394,34 @@ def main():
     # event records of consecutive launches sit back to back and the bracket itself reads ~20 us long (BENCH_r01: 290.6 us
     # at stride 1 in a 20-step run vs 269 us in rocprof and 271 us at stride 4)
     stride = 4 if args.steps >= 8 else 1
-    _lib.profile_set_stride(stride)
-    _lib.profile_enable(timed_tags, capacity=2 * args.steps + 8)
+    if args.full:
+        _lib.profile_set_stride(stride)
+        _lib.profile_enable(timed_tags, capacity=2 * args.steps + 8)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(args.warmup, total):
         step(s)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(trainer, uids[total - 1], iids[total - 1]))
+    out = {
+        "metric": "user-item pairs/sec (train step) + embedding-gather HBM GB/s, 1/2/4/8 MI355X",
+        "value": batch / (dt / args.steps), "unit": "pairs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.config}: {n_users} users x {n_items} items, emb_dim {dim}, towers "
+                               f"{dim}->{'->'.join(map(str, tower_dims))}, batch {batch}, in-batch sampled softmax T=0.1, "
+                               f"{args.optimizer} lr 1e-3, ids {args.ids}"
+                               + (f", + {cfg.n_category_buckets}-bucket hashed category feature summed into the item input"
+                                  if cfg.n_category_buckets else ""),
+                   "global_batch": batch, "parallelism": "single GPU"},
+    }
+    if not args.full:
+        out["loss_per_pair"] = float(trainer.loss.item()) / batch
+        trainer.check_ids()
+        print(json.dumps(out))
+        return
     prof = {t: _lib.profile_read(t, 2 * args.steps + 8)[0] for t in timed_tags.split(",") if t in all_tags}
     detail_steps = min(args.steps, 100)
     rest = [t for t in all_tags if t not in prof]
@@ -405,7 +480,6 @@ def main():
     loss = float(trainer.loss.item())
     trainer.check_ids()
 
-    ms_per_step = dt / args.steps * 1e3
     sd = tower_dims[-1]
     b2d = float(batch) * batch * sd
     if args.config == "ref":
@@ -470,17 +544,7 @@ def main():
             gs_bytes += plan_bytes
     rp_opt = rocprof_avg_us("optimizer_ids_kernel") if (args.config == "cfg3" and args.optimizer == "sgd" and fused_sort) else None
     rp_lookup = rocprof_lookup_share_us() if (args.config == "cfg3" and args.optimizer == "sgd" and fused_sort and lookup_fused) else None
-    out = {
-        "metric": "user-item pairs/sec (train step) + embedding-gather HBM GB/s, 1/2/4/8 MI355X",
-        "value": batch / (dt / args.steps), "unit": "pairs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.config}: {n_users} users x {n_items} items, emb_dim {dim}, towers "
-                               f"{dim}->{'->'.join(map(str, tower_dims))}, batch {batch}, in-batch sampled softmax T=0.1, "
-                               f"{args.optimizer} lr 1e-3, ids {args.ids}"
-                               + (f", + {cfg.n_category_buckets}-bucket hashed category feature summed into the item input"
-                                  if cfg.n_category_buckets else ""),
-                   "global_batch": batch, "parallelism": "single GPU"},
+    out.update({
         "timing_note": f"kernel durations = the dispatch's own begin/end timestamps (hipExtLaunchKernelGGL event pair: what "
                        f"rocprofv3 --kernel-trace reports; no barrier packets). Inside the timed region: {timed_tags} only, every "
                        f"{stride}th step ({len(prof['score_fused'])} samples: a timestamped dispatch still costs the stream ~4 us); "
@@ -535,7 +599,7 @@ def main():
                          "frac_without_plan": (gs_bytes - (plan_bytes if (plan_on_main or fused_sort) else 0)) / t_gs_noplan / 1e9 / HBM_PEAK_GBS,
                          "algorithmic_bytes": gs_bytes},
         "loss_per_pair": loss / batch,
-    }
+    })
     # the tower GEMMs (K3): forward + dx + dw of every layer of both towers = 3 * 2*B*sum(in*out) * 2 FLOPs,
     # over the timestamped launches of the untimed detail pass
     dims_all = [dim] + list(cfg.user_dims)

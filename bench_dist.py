@@ -13,8 +13,8 @@ The weak-scaled cfg3 family scores each rank's queries against its OWN batch (``
 of the reference's stack computes) - since r04: "weak" means the work per GPU is fixed as N grows, and with global negatives
 every GPU's scorer would do N times the N = 1 work (B_local x N B_local logits; through r03 that was this line, its numbers
 are the ``other_negatives`` object now).  ``--negatives global|local`` overrides; the mode is named in ``config.workload``
-and the OTHER mode is timed in the same run (``other_negatives``).
-value = global batch * steps / max-over-ranks time.  The line carries the scorer's ``roofline`` on the per-GPU slab
+and with ``--full`` the OTHER mode is timed in the same run (``other_negatives``).
+value = global batch * steps / max-over-ranks time.  With ``--full`` the line carries the scorer's ``roofline`` on the per-GPU slab
 (B_local x B_global) from live dispatch timestamps (hipExtLaunchKernelGGL event pair, r04) on rank 0, and per-collective stream time from an untimed detail pass.
 """
 import json
@@ -76,7 +76,7 @@ def collective_detail(trainer, batches, steps):
     return out
 
 
-def run_distributed(args, rank, world, dev):
+def run_distributed(args, rank, world, dev, dump_outputs):
     from two_tower_amazon_recommender_amd import _lib
     from two_tower_amazon_recommender_amd.sharded import ShardedTwoTowerTrainer
     from two_tower_amazon_recommender_amd.trainer import TwoTowerConfig
@@ -131,7 +131,7 @@ def run_distributed(args, rank, world, dev):
     torch.cuda.synchronize()
     trainer.check_ids()
     stride = 4 if args.steps >= 40 else 1
-    if rank == 0:
+    if rank == 0 and args.full:
         _lib.profile_set_stride(stride)
         _lib.profile_enable("score_fused", capacity=2 * args.steps + 8)
     dist.barrier()
@@ -146,20 +146,22 @@ def run_distributed(args, rank, world, dev):
     dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     loss = trainer.loss.double().clone()
     dist.all_reduce(loss, op=dist.ReduceOp.SUM)
+    if args.dump_outputs and rank == 0:     # the global loss; rank 0's per-pair losses and its copy of the dense parameters
+        dump_outputs(args.dump_outputs, {"loss": loss, "per_pair_loss_rank0": trainer.per_row, "dense_params": trainer.dense_flat})
     trainer.check_ids()
     fused = []
-    if rank == 0:
+    if rank == 0 and args.full:
         fused = _lib.profile_read("score_fused", 2 * args.steps + 8)[0]
         _lib.profile_enable("")
     detail_steps = min(args.steps, 20)
-    coll = collective_detail(trainer, batches[total - detail_steps:], detail_steps) if trainer.collectives else {}
+    coll = collective_detail(trainer, batches[total - detail_steps:], detail_steps) if (args.full and trainer.collectives) else {}
     trainer.check_ids()
     # second, separately labelled region: the same steps with the OTHER negatives mode (global <-> local).  With the
     # weak-scaled family and global negatives the scorer's work per GPU grows with N (B_local x N*B_local logits); the
     # local line shows the exchange + towers + optimizer scaling alone.
     other = "local" if negatives == "global" else "global"
     alt = None
-    if trainer.collectives and world > 1:
+    if args.full and trainer.collectives and world > 1:
         trainer.set_negatives(other)
         alt_steps = min(args.steps, 50)
         for s in range(min(args.warmup, 5)):
@@ -198,22 +200,23 @@ def run_distributed(args, rank, world, dev):
         # kernel times (profiles/), the scorer part rescaled by that factor, + this run's measured stream time of every
         # collective of a step: what the step would take if nothing but the model's terms changed.
         work_model = None
-        try:
-            prof_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-            ref = next(f for f in ("r04_n1_reference.json", "r03_n1_reference.json") if os.path.exists(os.path.join(prof_dir, f)))
-            n1 = json.load(open(os.path.join(prof_dir, ref)))[name]
-            factor = (nc / batch) * (batch / n1["batch_per_gpu"]) ** 2      # Bq*Bc*D against the N = 1 launch's
-            other = n1["ms_per_step"] - n1["scorer_ms"]
-            if name != "cfg3":
-                other *= batch / n1["batch_per_gpu"]                        # towers / lookup / optimizer scale with the local batch
-            coll_ms = sum(v["us_per_call"] * v["calls_per_step"] for v in coll.values()) * 1e-3 if coll else 0.0
-            work_model = {"scorer_flops_per_gpu_vs_n1": factor, "n1_reference": n1,
-                          "collectives_ms_per_step_measured": coll_ms,
-                          "ms_expected_from_n1": n1["scorer_ms"] * factor + other + coll_ms,
-                          "note": "a model: N = 1 kernel times rescaled + measured per-collective stream time; exposed waits "
-                                  "between ranks are what the difference to ms_per_step shows"}
-        except (OSError, KeyError, ValueError, ZeroDivisionError, TypeError, StopIteration):
-            pass
+        if args.full:
+            try:
+                prof_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+                ref = next(f for f in ("r04_n1_reference.json", "r03_n1_reference.json") if os.path.exists(os.path.join(prof_dir, f)))
+                n1 = json.load(open(os.path.join(prof_dir, ref)))[name]
+                factor = (nc / batch) * (batch / n1["batch_per_gpu"]) ** 2      # Bq*Bc*D against the N = 1 launch's
+                other = n1["ms_per_step"] - n1["scorer_ms"]
+                if name != "cfg3":
+                    other *= batch / n1["batch_per_gpu"]                        # towers / lookup / optimizer scale with the local batch
+                coll_ms = sum(v["us_per_call"] * v["calls_per_step"] for v in coll.values()) * 1e-3 if coll else 0.0
+                work_model = {"scorer_flops_per_gpu_vs_n1": factor, "n1_reference": n1,
+                              "collectives_ms_per_step_measured": coll_ms,
+                              "ms_expected_from_n1": n1["scorer_ms"] * factor + other + coll_ms,
+                              "note": "a model: N = 1 kernel times rescaled + measured per-collective stream time; exposed waits "
+                                      "between ranks are what the difference to ms_per_step shows"}
+            except (OSError, KeyError, ValueError, ZeroDivisionError, TypeError, StopIteration):
+                pass
         out = {
             "metric": "user-item pairs/sec (train step) + embedding-gather HBM GB/s, 1/2/4/8 MI355X",
             "value": world * batch * args.steps / sec, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
