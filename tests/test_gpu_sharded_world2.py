@@ -1,8 +1,10 @@
-"""Two ranks of the row-sharded trainer on ONE GPU (both processes use cuda:0): every HIP kernel of the N>1 path runs
-with world = 2 — routing, owner gather, row/gradient exchange buffers, owner-side sort + fused update with duplicates
-across ranks, dense all-reduce — and the result is compared with the f64 oracle on the GLOBAL batch.  RCCL refuses
-two ranks on one device, so the collectives go through gloo on host copies (a test-local shim around
-torch.distributed); the exchange CODE under test is the product's."""
+"""Several ranks of the row-sharded trainer on ONE GPU (every process uses cuda:0): every HIP kernel of the N>1 path runs
+with world = 2, 3, 4 and 8 - routing, owner gather, row/gradient exchange buffers, owner-side sort + fused update with
+duplicates across ranks, dense all-reduce - and the result is compared with the f64 oracle on the GLOBAL batch.  RCCL
+refuses two ranks on one device, so the collectives go through gloo on host copies (a test-local shim around
+torch.distributed); the exchange CODE under test is the product's.  World 2 alone would hide arithmetic on world and rank
+that only goes wrong for rank >= 2, at a world that is not a power of two, or when rows % world is neither 0 nor 1."""
+import datetime
 import os
 import pathlib
 import socket
@@ -70,7 +72,7 @@ def _install_host_bounce():
 
 
 def _init(rank, world, port, real):
-    """real=False: two ranks share cuda:0, collectives bounced through gloo.  real=True: one GPU per rank, the product's
+    """real=False: all ranks share cuda:0, collectives bounced through gloo.  real=True: one GPU per rank, the product's
     own RCCL collectives with their real stream ordering (needs >= world GPUs); objects travel over a gloo side group."""
     sys.path.insert(0, str(ROOT))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -79,9 +81,17 @@ def _init(rank, world, port, real):
         torch.cuda.set_device(dev)
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         return dev, dist.new_group(backend="gloo")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    # a rank whose assertion failed leaves its peers waiting in their next collective: 5 minutes, not gloo's default 30
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(minutes=5))
     _install_host_bounce()
     return torch.device("cuda:0"), None
+
+
+def _shape(world):
+    """(n_users, n_items, per-rank batch) of the trainer cases.  World 2 keeps its first shape; at every other world the shards are
+    ragged (rows % world is neither 0 nor 1), and world * batch <= 4096 (every rank computes the oracle on the global batch).  World
+    3's batch of 700 is not a multiple of 32: the diagonal offset rank * batch of global negatives is unaligned."""
+    return {2: (3001, 2000, 1024), 3: (3002, 2003, 700), 4: (3003, 2002, 1024), 8: (3005, 2003, 512)}[world]
 
 
 def _worker(rank, world, port, opt, variant, negatives, nb, ret, real=False):
@@ -90,7 +100,7 @@ def _worker(rank, world, port, opt, variant, negatives, nb, ret, real=False):
         from oracle import synth, two_tower as tt
         from two_tower_amazon_recommender_amd.sharded import ShardedTwoTowerTrainer
         from two_tower_amazon_recommender_amd.trainer import TwoTowerConfig
-        n_users, n_items, dim, tower_dims, b, seed = 3001, 2000, 64, [128, 64], 1024, 41
+        (n_users, n_items, b), dim, tower_dims, seed = _shape(world), 64, [128, 64], 41
         cfg = TwoTowerConfig(n_users=n_users, n_items=n_items, embedding_dim=dim, tower_dims=tower_dims, temperature=0.1,
                              l2_regularization=1e-6, learning_rate=0.001, optimizer=opt, batch_size=b, n_category_buckets=nb)
         tr = ShardedTwoTowerTrainer(cfg, dev, seed=seed, negatives=negatives, capacity_factor=3.0)
@@ -100,8 +110,8 @@ def _worker(rank, world, port, opt, variant, negatives, nb, ret, real=False):
         def cats(step, r):          # category buckets of rank r's sub-batch (None when the model has no such feature)
             return synth.batch_ids(seed, synth.TID_CATEGORY_IDS, step * world + r, b, nb, "Z") if nb else None
         # each rank holds exactly its rows of the synthetic tables
-        assert np.array_equal(tr.user_table.cpu().numpy(),
-                              ref.user_table[rank::world].astype(np.float32))
+        for shard, full in ((tr.user_table, ref.user_table), (tr.item_table, ref.item_table)):
+            assert np.array_equal(shard.cpu().numpy(), full[rank::world].astype(np.float32))
         batches = [tr.synthetic_batch(seed, step, variant) for step in range(2)]
         for step in range(2):
             u, i = batches[step]
@@ -197,7 +207,7 @@ def _worker(rank, world, port, opt, variant, negatives, nb, ret, real=False):
         # replicas of the dense parameters stay bit-identical across ranks
         flat = [None] * world
         dist.all_gather_object(flat, tr.dense_flat.cpu().numpy(), group=og)
-        assert np.array_equal(flat[0], flat[1])
+        assert all(np.array_equal(flat[0], f) for f in flat[1:])
         ret[rank] = "ok"
     except Exception:                                             # noqa: BLE001
         import traceback
@@ -272,6 +282,47 @@ def _worker_options(rank, world, port, negatives, ret, real=False):
             dist.destroy_process_group()
 
 
+def _worker_skew(rank, world, port, ret):
+    """The owner-side skew switch at world > 1 (ShardedTables._poll_skew: each rank decides for itself from the ids IT received):
+    two trainers from one seed on one group, one never probing (skew_limit 0: always the one-launch apply_ids), one probing every
+    3 lookups; power-law ids, then uniform ids.  Losses and every rank's state stay bit-identical after every step."""
+    try:
+        dev, og = _init(rank, world, port, False)
+        from two_tower_amazon_recommender_amd.sharded import ShardedTwoTowerTrainer
+        from two_tower_amazon_recommender_amd.trainer import TwoTowerConfig
+        # the world-1 test's shape per rank: every owner receives as many ids as that test's one rank, and its row ranges are
+        # 1 / world as wide over local rows id // world, so power-law ids crowd its first range past the limit of 384 alike
+        cfg = TwoTowerConfig(n_users=2_000_000, n_items=1_000_000, embedding_dim=64, tower_dims=[128, 64], temperature=0.1,
+                             l2_regularization=1e-6, learning_rate=0.001, optimizer="adagrad", batch_size=8192)
+        fixed = ShardedTwoTowerTrainer(cfg, dev, seed=43)
+        probed = ShardedTwoTowerTrainer(TwoTowerConfig(**cfg.__dict__), dev, seed=43)
+        fixed.emb.skew_limit = 0
+        probed.emb.probe_every = 3
+        assert probed.emb.fused_apply and probed.emb.probe_segs is not None and probed.emb.skew_limit > 0
+        seen = []
+        for step in range(12):
+            u, i = fixed.synthetic_batch(43, step, "Z" if step < 6 else "U")
+            la = fixed.step(u, i).clone()
+            lp = probed.step(u, i).clone()
+            seen.append(probed.emb._fused_now)
+            assert fixed.emb._fused_now
+            assert torch.equal(la, lp), step
+            assert torch.equal(fixed.emb.table, probed.emb.table) and torch.equal(fixed.emb.accum, probed.emb.accum), step
+            assert torch.equal(fixed.dense_flat, probed.dense_flat) and torch.equal(fixed.dense_accum, probed.dense_accum), step
+        fixed.check_ids(); probed.check_ids()
+        allseen = [None] * world
+        dist.all_gather_object(allseen, seen, group=og)
+        assert any(not s for r in allseen for s in r), allseen            # some rank took plan() + apply() under skew
+        assert all(r[-1] for r in allseen), allseen                       # every rank back on apply_ids after uniform ids
+        ret[rank] = "ok"
+    except Exception:                                             # noqa: BLE001
+        import traceback
+        ret[rank] = traceback.format_exc()
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
 def _spawn(fn, args, world=2):
     mgr = mp.Manager()
     ret = mgr.dict()
@@ -287,6 +338,14 @@ def test_sharded_step_sample_weight_logq_and_accidental_hits_two_ranks(negatives
     _spawn(_worker_options, (negatives,))
 
 
+@pytest.mark.parametrize("world,negatives", [(4, "global"), (4, "local"), (8, "global")])
+def test_sharded_step_sample_weight_logq_and_accidental_hits_more_ranks(world, negatives):
+    """300 items: accidental hits between the candidates of different ranks."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    _spawn(_worker_options, (negatives,), world)
+
+
 def _worker_real(rank, world, port, opt, variant, negatives, nb, ret):
     _worker(rank, world, port, opt, variant, negatives, nb, ret, real=True)
 
@@ -295,22 +354,17 @@ def _worker_options_real(rank, world, port, negatives, ret):
     _worker_options(rank, world, port, negatives, ret, real=True)
 
 
+@pytest.mark.parametrize("world", [2, 4, 8], ids=lambda w: f"world{w}")
 @pytest.mark.parametrize("opt,variant,negatives,nb", [("sgd", "U", "local", 0), ("adagrad", "Z", "global", 0),
                                                       ("sgd", "Z", "global", 30)])
-def test_sharded_trainer_real_rccl_one_gpu_per_rank(opt, variant, negatives, nb):
+def test_sharded_trainer_real_rccl_one_gpu_per_rank(opt, variant, negatives, nb, world):
     """The same 2-step comparison against the f64 oracle with the product's OWN collectives: a real "nccl" (RCCL) group,
     one GPU per rank, inline synchronous C1/C2/C6, asynchronous C3 beside the dw GEMMs, the side-stream sort plans.
-    Needs >= 2 visible GPUs: skipped on the 1-GPU test box, runs the first time a multi-GPU lease is available."""
-    if not torch.cuda.is_available() or torch.cuda.device_count() < 2:
-        pytest.skip("needs >= 2 GPUs (multi-GPU RCCL correctness is UNVERIFIED until this runs)")
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker_real, args=(2, _free_port(), opt, variant, negatives, nb, ret), nprocs=2, join=True)
-    for r in range(2):
-        assert ret.get(r) == "ok", f"rank {r}: {ret.get(r)}"
-    mp.spawn(_worker_options_real, args=(2, _free_port(), negatives, ret), nprocs=2, join=True)
-    for r in range(2):
-        assert ret.get(r) == "ok", f"rank {r}: {ret.get(r)}"
+    Needs >= world visible GPUs: skipped on the 1-GPU test box, runs the first time a multi-GPU lease is available."""
+    if not torch.cuda.is_available() or torch.cuda.device_count() < world:
+        pytest.skip(f"needs >= {world} GPUs, one per rank (multi-GPU RCCL correctness at world {world} is UNVERIFIED until this runs)")
+    _spawn(_worker_real, (opt, variant, negatives, nb), world)
+    _spawn(_worker_options_real, (negatives,), world)
 
 
 @pytest.mark.parametrize("opt,variant,negatives,nb", [("sgd", "U", "local", 0), ("adagrad", "Z", "local", 30),
@@ -318,8 +372,77 @@ def test_sharded_trainer_real_rccl_one_gpu_per_rank(opt, variant, negatives, nb)
 def test_sharded_trainer_two_ranks_on_one_gpu(opt, variant, negatives, nb):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(2, _free_port(), opt, variant, negatives, nb, ret), nprocs=2, join=True)
-    for r in range(2):
-        assert ret.get(r) == "ok", f"rank {r}: {ret.get(r)}"
+    _spawn(_worker, (opt, variant, negatives, nb))
+
+
+@pytest.mark.parametrize("world,opt,variant,negatives,nb", [(3, "adagrad", "Z", "global", 0), (3, "sgd", "U", "local", 30),
+                                                            (4, "sgd", "Z", "global", 30), (4, "adagrad", "Z", "local", 30),
+                                                            (8, "adagrad", "Z", "global", 30)])
+def test_sharded_trainer_more_ranks_on_one_gpu(world, opt, variant, negatives, nb):
+    """Shapes of _shape(world): ragged shards, and at world 3 an unaligned rank * batch."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    _spawn(_worker, (opt, variant, negatives, nb), world)
+
+
+def test_sharded_owner_side_skew_switch_four_ranks():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    _spawn(_worker_skew, (), 4)
+
+
+def _np_route_tables(ids_list, world, offsets, cap):
+    """Stable partition of every table's positions by owner id % world (in-range ids only): send [world][n_tables][cap] with
+    local rows id // world + offset and -1 padding, pos_flat per table (-1 = past the owner's capacity), overflow flag."""
+    nt = len(ids_list)
+    send = np.full(world * nt * cap, -1, dtype=np.int64)
+    pos, over = [], 0
+    for t, ids in enumerate(ids_list):
+        fill = [0] * world
+        p = np.full(len(ids), -1, dtype=np.int64)
+        for k, v in enumerate(ids):
+            o = int(v % world)
+            if fill[o] < cap:
+                p[k] = (o * nt + t) * cap + fill[o]
+                send[p[k]] = v // world + offsets[t]
+            else:
+                over = 1
+            fill[o] += 1
+        pos.append(p)
+    return send, pos, over
+
+
+def test_route_overflow_at_world8_drops_exactly_the_positions_past_capacity(dev):
+    """Kernel level only (a trainer step must never consume a pos_flat of -1): three tables of power-law ids, 8 owners, a
+    capacity that some owner buckets overflow and others do not, 10000 positions (two of the kernel's 8192-position rounds).
+    The first cap positions of every owner keep their slots in ascending position order, exactly the later ones get -1, the
+    overflow flag (and only it) is raised, and nothing past send_ids or the pos_flat buffer is written."""
+    from oracle import synth
+    from two_tower_amazon_recommender_amd import ops
+    world, n, cap, rows = 8, 10_000, 1216, [100_000, 3001, 2003]
+    offsets = [0, 12_500, 12_876]                          # ShardedTables: ceil(rows / world) rows reserved per table
+    ids = [synth.ids_powerlaw(67, 3 + t, n, r) for t, r in enumerate(rows)]
+    counts = np.stack([np.bincount(x % world, minlength=world) for x in ids])
+    assert (counts > cap).any() and (counts <= cap).any()
+    nsend, canary = world * 3 * cap, 4096
+    send = torch.full((nsend + canary,), -7, dtype=torch.int64, device=dev)
+    pos = torch.full((3 * n + canary,), -7, dtype=torch.int64, device=dev)
+    flags = torch.zeros(2, dtype=torch.int32, device=dev)
+    ops.route_tables_by_owner([torch.from_numpy(x).to(dev) for x in ids], world, rows, offsets, cap, send,
+                              [pos[t * n:(t + 1) * n] for t in range(3)], flags)
+    got_send, got_pos = send.cpu().numpy(), pos.cpu().numpy()
+    assert flags.tolist() == [0, 1]
+    assert (got_send[nsend:] == -7).all() and (got_pos[3 * n:] == -7).all()
+    want_send, want_pos, over = _np_route_tables(ids, world, offsets, cap)
+    assert over == 1
+    assert np.array_equal(got_send[:nsend], want_send)
+    for t in range(3):
+        p, x = got_pos[t * n:(t + 1) * n], ids[t]
+        assert np.array_equal(p, want_pos[t]), t
+        owner = x % world
+        for o in range(world):
+            mine = np.flatnonzero(owner == o)                  # this owner's positions, ascending
+            k = min(len(mine), cap)
+            assert np.array_equal(p[mine[:k]], (o * 3 + t) * cap + np.arange(k)), (t, o)
+            assert (p[mine[k:]] == -1).all(), (t, o)
+        assert np.array_equal(got_send[p[p >= 0]], x[p >= 0] // world + offsets[t]), t
