@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TT_ABI_VERSION 9
+#define TT_ABI_VERSION 10
 
 enum {
   TT_OK = 0,
@@ -55,7 +55,8 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * tt_profile_enable("score_bwd,gather", 4096) makes every launch of the kernels carrying one
  * of those tags record a hipEvent pair on ITS OWN stream (capacity = launches kept per tag);
  * tags: fill, gather, sparse_plan, sparse_apply, dense_fwd, dense_bwd (dx+dw in one launch), dense_bwd_dx, dense_bwd_dw,
- * dense_update, optimizer (sparse + dense in one launch), score_fwd, score_bwd, score_fused, score_rank, score_aux, route, scatter_rows, encode_ids.
+ * dense_update, optimizer (sparse + dense in one launch), score_fwd, score_bwd, score_fused, score_rank, score_aux, route, scatter_rows, encode_ids,
+ * topk_select, topk_merge (and the scope topk around a whole tt_retrieval_topk_f32 call).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -547,6 +548,22 @@ int tt_retrieval_rank_f32(const float* q, const float* c, int64_t nq, int64_t nc
 int tt_retrieval_batch_rank_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim, int64_t diag_offset,
                                 float inv_temperature, const float* cand_prob, const int64_t* cand_ids,
                                 void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream);
+
+/* Exact top-K retrieval (tfrs.layers.factorized_top_k.BruteForce; ABI v10): the k best candidates of every query,
+ * scored and selected in one pass over the corpus (no [nq x nc] score matrix) and merged across corpus splits.
+ * score[i][j] = q_i . c_j (plain dot product, exact f32 products on the f32 MFMA).  q [nq, dim], c [nc, dim] f32, 16-byte
+ * aligned; nq >= 1, 1 <= nc < 2^31, dim in {32, 64, 128, 256}, 1 <= k <= TT_TOPK_MAX_K, k <= nc.
+ * out_scores f32 [nq, k], out_idx int64 [nq, k]: score descending, equal scores by ascending candidate index (also at the
+ * cut at position k): the answer is unique, and a query's row is bit-identical whatever the batch it is sent in.
+ * Exclusions (optional; both NULL or both set): CSR excl_offsets int64 [nq + 1] (non-decreasing, within excl_idx),
+ * excl_idx int64 sorted ascending within each query's segment; duplicates and values outside [0, nc) match nothing.
+ * Excluded candidates never enter the result; when fewer than k candidates remain the tail is (-inf, -1).
+ * Workspace (256-byte aligned): tt_retrieval_topk_workspace_bytes(nq, nc, dim, k) (0 for arguments the call refuses). */
+#define TT_TOPK_MAX_K 256
+int64_t tt_retrieval_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t dim, int32_t k);
+int tt_retrieval_topk_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim, int32_t k,
+                          const int64_t* excl_offsets, const int64_t* excl_idx, void* workspace, int64_t workspace_bytes,
+                          float* out_scores, int64_t* out_idx, tt_stream_t stream);
 
 #ifdef __cplusplus
 }

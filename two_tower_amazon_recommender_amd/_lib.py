@@ -15,13 +15,14 @@ import threading
 _PKG = pathlib.Path(__file__).resolve().parent
 # TT_LIB_PATH: load another build of the same C ABI (kernel A/B experiments); the product default is the in-tree library
 LIB_PATH = pathlib.Path(os.environ["TT_LIB_PATH"]) if os.environ.get("TT_LIB_PATH") else _PKG / "libtwotower_hip.so"
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 TT_OK, TT_ERR_INVALID_ARG, TT_ERR_LAUNCH, TT_ERR_UNSUPPORTED, TT_ERR_WORKSPACE = range(5)
 TT_OPT_SGD, TT_OPT_ADAGRAD = 0, 1
 TT_IDS_UNIFORM, TT_IDS_POWERLAW = 0, 1
 TT_MAX_DENSE_SEGS = 16
 TT_MAX_TOWER_LAYERS = 8
+TT_TOPK_MAX_K = 256
 
 
 class IdBuckets(C.Structure):
@@ -161,6 +162,8 @@ SIGNATURES = {
     "tt_retrieval_hard_negative_thresholds_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _i32, _p, _i64, _p, _i64, _p, _p]),
     "tt_retrieval_rank_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _f, _p, _p, _p, _i64, _p, _p]),
     "tt_retrieval_batch_rank_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _i64, _p, _p]),
+    "tt_retrieval_topk_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "tt_retrieval_topk_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p]),
     "tt_retrieval_bwd_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _p, _p, _f, _p, _i64, _p, _p, _p]),
 }
 

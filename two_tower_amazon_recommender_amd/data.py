@@ -56,6 +56,15 @@ def category_buckets(codes: np.ndarray, values: list, n_buckets: int, device) ->
     return b[codes]
 
 
+def item_categories(item_idx: np.ndarray, category_bucket: np.ndarray, n_items: int) -> np.ndarray:
+    """Category bucket of every item row (int64 [n_items]): the bucket of the item's first interaction; items never seen
+    get bucket 0."""
+    out = np.zeros(n_items, dtype=np.int64)
+    first = np.unique(item_idx, return_index=True)
+    out[first[0]] = category_bucket[first[1]]
+    return out
+
+
 class BatchIterator:
     """Shuffled fixed-size batches of (user_idx, item_idx), resident on the device; the last partial batch
     of an epoch is dropped (the kernels' buffers are sized for one batch size)."""

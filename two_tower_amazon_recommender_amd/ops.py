@@ -717,6 +717,81 @@ def retrieval_rank(q, c, inv_temperature: float, pos_index, workspace=None, cand
     return out
 
 
+TOPK_MAX_K = _lib.TT_TOPK_MAX_K
+
+
+def retrieval_topk_workspace_bytes(nq: int, nc: int, dim: int, k: int) -> int:
+    """Workspace of ``retrieval_topk`` (0 for a shape the call refuses)."""
+    return int(_lib.load().tt_retrieval_topk_workspace_bytes(nq, nc, dim, k))
+
+
+def exclusions_csr(exclusions, nq: int):
+    """(offsets int64 [nq + 1], indices int64) with every query's segment sorted ascending, from either a CSR pair
+    (offsets[0] == 0, non-decreasing, offsets[nq] <= len(indices)) or a padded [nq, E] int64 tensor (-1 = padding; any
+    value outside the corpus matches nothing).  Sorted on the device; (None, None) when there is nothing to exclude."""
+    if exclusions is None:
+        return None, None
+    if isinstance(exclusions, torch.Tensor):
+        _chk(exclusions, torch.int64, "exclusions", 2)
+        if exclusions.shape[0] != nq:
+            raise ValueError(f"exclusions: padded form needs {nq} rows, got shape {tuple(exclusions.shape)}")
+        e = exclusions.shape[1]
+        if e == 0:
+            return None, None
+        idx = torch.sort(exclusions, dim=1).values.reshape(-1)
+        offsets = torch.arange(0, (nq + 1) * e, e, dtype=torch.int64, device=exclusions.device)
+        return offsets, idx
+    if not isinstance(exclusions, (tuple, list)) or len(exclusions) != 2:
+        raise TypeError("exclusions: expected a padded [nq, E] int64 tensor or a CSR pair (offsets, indices)")
+    offsets, idx = exclusions
+    _chk(offsets, torch.int64, "exclusion offsets", 1)
+    _chk(idx, torch.int64, "exclusion indices", 1)
+    if offsets.numel() != nq + 1:
+        raise ValueError(f"exclusion offsets: need nq + 1 = {nq + 1} entries, got {offsets.numel()}")
+    bad = (offsets[0] != 0) | (offsets[-1] > idx.numel()) | (offsets.diff() < 0).any()
+    if bool(bad):
+        raise ValueError("exclusion offsets must start at 0, be non-decreasing and end within the index array")
+    if idx.numel() == 0:
+        return None, None
+    # sort within segments: by value, then (stable) by segment
+    seg = torch.searchsorted(offsets[1:], torch.arange(idx.numel(), device=idx.device), right=True)
+    o1 = torch.argsort(idx, stable=True)
+    o2 = torch.argsort(seg[o1], stable=True)
+    return offsets.contiguous(), idx[o1][o2].contiguous()
+
+
+def retrieval_topk(q, c, k: int, exclusions=None, workspace=None, out=None):
+    """Exact top-k retrieval (tfrs BruteForce): (scores f32 [nq, k], indices int64 [nq, k]) of the plain dot products
+    q @ c.T, score descending, ties by ascending candidate index.  ``exclusions``: a CSR pair (offsets [nq + 1], indices)
+    or a padded [nq, E] int64 tensor with -1 padding - excluded candidates never appear; when fewer than k remain the
+    tail is (-inf, -1).  ``out``: optional (scores, indices) to write into."""
+    _chk(q, torch.float32, "query_embeddings", 2)
+    _chk(c, torch.float32, "candidate_embeddings", 2)
+    nq, nc, d = q.shape[0], c.shape[0], q.shape[1]
+    if q.shape[1] != c.shape[1]:
+        raise RuntimeError(f"retrieval_topk: embedding dims differ: {q.shape[1]} vs {c.shape[1]}")
+    k = int(k)
+    if not 1 <= k <= min(TOPK_MAX_K, nc):
+        raise ValueError(f"retrieval_topk: k = {k} must be in [1, min({TOPK_MAX_K}, nc = {nc})]")
+    off, idx = exclusions_csr(exclusions, nq)
+    need = retrieval_topk_workspace_bytes(nq, nc, d, k)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
+    else:
+        _chk(workspace, torch.uint8, "workspace", 1)
+    if out is None:
+        out = (torch.empty(nq, k, dtype=torch.float32, device=q.device), torch.empty(nq, k, dtype=torch.int64, device=q.device))
+    scores, indices = out
+    _chk(scores, torch.float32, "out scores", 2)
+    _chk(indices, torch.int64, "out indices", 2)
+    if tuple(scores.shape) != (nq, k) or tuple(indices.shape) != (nq, k):
+        raise ValueError(f"retrieval_topk: out tensors must be [{nq}, {k}]")
+    _lib.check(_lib.load().tt_retrieval_topk_f32(_p(q), _p(c), nq, nc, d, k, _p(off), _p(idx), _p(workspace),
+                                                 workspace.numel(), _p(scores), _p(indices), _stream()),
+               "tt_retrieval_topk_f32")
+    return scores, indices
+
+
 def retrieval_batch_rank(q, c, inv_temperature: float, cand_prob=None, cand_ids=None, diag_offset: int = 0, workspace=None, out=None):
     """In-batch rank of every query's positive (candidate i + diag_offset) under the scores the loss sees - temperature,
     sampling-probability correction, accidental hits removed (int32 [nq]); top-k accuracy = mean(rank < k)."""

@@ -1,0 +1,143 @@
+"""``python -m two_tower_amazon_recommender_amd.recommend`` — the top-k items of every requested user from a checkpoint
+written by ``train.py --save``: the model is rebuilt from the checkpoint's ``config``, the whole item corpus goes through
+the item tower once, and users are answered in batches by ``serving.BruteForce`` (one fused score-and-select pass over
+the corpus per batch; no [users x items] score matrix).
+
+    python -m two_tower_amazon_recommender_amd.recommend --checkpoint ck.pt --data interactions.parquet \\
+        --all-users --exclude-seen --k 10 --out recs.parquet
+
+Output parquet: one row per (user, rank) with columns user_idx, rank (0 = best), item_idx, score.  A user with fewer
+than k unexcluded items gets fewer rows.
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import logging
+import os
+import re
+import sys
+
+import numpy as np
+
+log = logging.getLogger("recommend")
+MAX_K = 256                         # TT_TOPK_MAX_K of include/twotower_hip.h
+_SHARDED = re.compile(r"\.rank\d+of\d+$")
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description="Top-k item recommendations from a trained two-tower checkpoint (HIP kernels).")
+    ap.add_argument("--checkpoint", required=True, help="a checkpoint written by train.py --save (single-GPU form)")
+    ap.add_argument("--k", type=int, default=10, help=f"items per user (1..{MAX_K})")
+    who = ap.add_mutually_exclusive_group(required=True)
+    who.add_argument("--users-file", default=None, help="a .npy of user_idx values to recommend for")
+    who.add_argument("--all-users", action="store_true", help="recommend for every user row of the model")
+    ap.add_argument("--data", default=None, help="interaction parquet (user_idx / item_idx columns): needed by "
+                                                 "--exclude-seen and by models trained with category buckets")
+    ap.add_argument("--exclude-seen", action="store_true", help="never recommend an item the user interacted with in --data")
+    ap.add_argument("--out", default="recs.parquet", help="output parquet (user_idx, rank, item_idx, score)")
+    ap.add_argument("--batch-users", type=int, default=4096, help="users per top-k call (bounds peak device memory)")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    if not 1 <= args.k <= MAX_K:
+        ap.error(f"--k must be in [1, {MAX_K}], got {args.k}")
+    if args.batch_users < 1:
+        ap.error("--batch-users must be positive")
+    if args.exclude_seen and args.data is None:
+        ap.error("--exclude-seen needs --data (the interactions that define what each user has seen)")
+    if _SHARDED.search(args.checkpoint) or (not os.path.exists(args.checkpoint)
+                                            and glob.glob(glob.escape(args.checkpoint) + ".rank*of*")):
+        ap.error(f"{args.checkpoint}: a per-rank checkpoint of the sharded trainer (*.rankRofW) is not supported; "
+                 "recommend reads the single-GPU form written by train.py --save without --distributed")
+    if not os.path.exists(args.checkpoint):
+        ap.error(f"--checkpoint {args.checkpoint}: no such file")
+    return args
+
+
+def seen_csr(user_idx: np.ndarray, item_idx: np.ndarray, n_users: int):
+    """(starts int64 [n_users + 1], items int64): user u's interacted items are items[starts[u]:starts[u + 1]]."""
+    order = np.argsort(user_idx, kind="stable")
+    items = item_idx[order].astype(np.int64, copy=False)
+    starts = np.searchsorted(user_idx[order], np.arange(n_users + 1), side="left").astype(np.int64)
+    return starts, items
+
+
+def batch_exclusions(starts: np.ndarray, items: np.ndarray, users: np.ndarray):
+    """CSR (offsets [len(users) + 1], indices) of the users' seen items, in the order of ``users``."""
+    lo, hi = starts[users], starts[users + 1]
+    n = hi - lo
+    offsets = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum(n, out=offsets[1:])
+    # position j of the result reads items[lo[user of j] + (j - offsets[user of j])]
+    seg = np.repeat(np.arange(len(users)), n)
+    idx = items[lo[seg] + (np.arange(offsets[-1]) - offsets[seg])] if offsets[-1] else np.zeros(0, dtype=np.int64)
+    return offsets, idx
+
+
+def main(argv=None) -> int:
+    args = parse(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    import torch
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    from . import data as datamod
+    from .serving import BruteForce
+    from .trainer import TwoTowerConfig, TwoTowerTrainer
+
+    dev = torch.device(args.device)
+    ck = torch.load(args.checkpoint, map_location=dev, weights_only=True)
+    if not isinstance(ck, dict) or "config" not in ck:
+        raise SystemExit(f"{args.checkpoint}: not a checkpoint written by train.py --save (no 'config')")
+    cfg = TwoTowerConfig(**ck["config"])
+    cfg.dropout_rate = 0.0
+    trainer = TwoTowerTrainer(cfg, dev)
+    trainer.load_state_dict(ck)
+    del ck
+
+    user_idx = item_idx = None
+    if args.data is not None:
+        user_idx, item_idx = datamod.read_interactions(args.data)
+    item_cat = None
+    if cfg.n_category_buckets > 0:
+        if args.data is None:
+            raise SystemExit("the checkpoint's model has category buckets: --data is needed to rebuild item categories")
+        cv = datamod.read_category_values(args.data)
+        if cv is None:
+            raise SystemExit(f"{args.data} has none of the columns {datamod.CATEGORY_COLUMNS} the model's categories need")
+        cat = datamod.category_buckets(cv[0], cv[1], cfg.n_category_buckets, dev)
+        item_cat = torch.from_numpy(datamod.item_categories(item_idx, cat, cfg.n_items)).to(dev)
+
+    if args.all_users:
+        users = np.arange(cfg.n_users, dtype=np.int64)
+    else:
+        users = np.asarray(np.load(args.users_file), dtype=np.int64).reshape(-1)
+        if users.size and (users.min() < 0 or users.max() >= cfg.n_users):
+            raise SystemExit(f"{args.users_file}: user ids must be in [0, {cfg.n_users})")
+    k = min(args.k, cfg.n_items)
+    bf = BruteForce(k=k).index_from_trainer(trainer, item_cat)
+    seen = seen_csr(user_idx, item_idx, cfg.n_users) if args.exclude_seen else None
+
+    cols = {"user_idx": [], "rank": [], "item_idx": [], "score": []}
+    for s in range(0, len(users), args.batch_users):
+        ub = users[s:s + args.batch_users]
+        ut = torch.from_numpy(ub).to(dev)
+        if seen is not None:
+            off, idx = batch_exclusions(seen[0], seen[1], ub)
+            scores, items = bf.query_with_exclusions(ut, (torch.from_numpy(off).to(dev), torch.from_numpy(idx).to(dev)))
+        else:
+            scores, items = bf(ut)
+        scores, items = scores.cpu().numpy(), items.cpu().numpy()
+        keep = items >= 0
+        cols["user_idx"].append(np.repeat(ub, k).reshape(-1, k)[keep])
+        cols["rank"].append(np.tile(np.arange(k, dtype=np.int32), (len(ub), 1))[keep])
+        cols["item_idx"].append(items[keep])
+        cols["score"].append(scores[keep])
+    trainer.check_ids()
+    table = pa.table({name: np.concatenate(v) if v else np.zeros(0) for name, v in cols.items()})
+    pq.write_table(table, args.out)
+    log.info("wrote %d recommendations for %d users to %s", table.num_rows, len(users), args.out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

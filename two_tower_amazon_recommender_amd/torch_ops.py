@@ -64,6 +64,7 @@ def release_workspaces() -> None:
     """Drop every cached scorer workspace and sort plan of the custom ops (they are re-allocated on the next call)."""
     _WS_CACHE.clear()
     _PLAN_CACHE.clear()
+    _TOPK_WS.clear()
 
 
 # --------------------------------------------------------------------------------------------- a1 lookup
@@ -187,6 +188,38 @@ def _(q, c, candidate_sampling_probability, candidate_ids, inv_temperature, diag
     return q.new_empty((q.shape[0],), dtype=torch.int32)
 
 
+_TOPK_WS: dict = {}
+
+
+def _topk_ws(nq: int, nc: int, d: int, k: int, device) -> Tensor:
+    """Workspace of the top-k op, kept per (device, stream) like the scorer's (the largest one seen)."""
+    n = max(ops.retrieval_topk_workspace_bytes(nq, nc, d, k), 1)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(n, dtype=torch.uint8, device=device)
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    hit = _TOPK_WS.get(key)
+    if hit is not None and hit.numel() >= n:
+        return hit
+    _TOPK_WS.pop(key, None)
+    buf = _TOPK_WS[key] = torch.empty(n, dtype=torch.uint8, device=device)
+    return buf
+
+
+@torch.library.custom_op(f"{NS}::retrieval_topk", mutates_args=(), device_types="cuda")
+def retrieval_topk(query_embeddings: Tensor, candidate_embeddings: Tensor, k: int, exclusion_offsets: Optional[Tensor],
+                   exclusion_indices: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """Exact top-k of q @ c.T (tfrs BruteForce): (scores f32 [nq, k], indices int64 [nq, k]), ties by ascending index;
+    optional CSR exclusions.  Not differentiable (serving)."""
+    q, c = query_embeddings.contiguous(), candidate_embeddings.contiguous()
+    ex = None if exclusion_offsets is None else (exclusion_offsets.contiguous(), exclusion_indices.contiguous())
+    return ops.retrieval_topk(q, c, k, exclusions=ex, workspace=_topk_ws(q.shape[0], c.shape[0], q.shape[1], k, q.device))
+
+
+@retrieval_topk.register_fake
+def _(q, c, k, exclusion_offsets, exclusion_indices):
+    return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
+
+
 # --------------------------------------------------------------------------------------------- a2 dense layers
 @torch.library.custom_op(f"{NS}::dense_fwd", mutates_args=(), device_types="cuda")
 def dense_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], relu: bool) -> Tensor:
@@ -253,5 +286,5 @@ def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: T
         ops.sparse_adagrad_(table, accum, grads.contiguous(), plan, lr, eps)
 
 
-OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "dense_fwd", "dense_bwd",
+OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "dense_fwd", "dense_bwd",
        "sparse_update_")

@@ -212,10 +212,7 @@ def main(argv=None) -> int:
         metric = FactorizedTopK(ks=tuple(loop["top_k_eval"]), temperature=cfg.temperature)
         item_cat = None
         if cat is not None:             # an item's category = the bucket of its first interaction (items never seen: bucket 0)
-            item_cat_np = np.zeros(n_items, dtype=np.int64)
-            first = np.unique(item_idx, return_index=True)
-            item_cat_np[first[0]] = cat[first[1]]
-            item_cat = torch.from_numpy(item_cat_np).to(trainer.dev)
+            item_cat = torch.from_numpy(datamod.item_categories(item_idx, cat, n_items)).to(trainer.dev)
         corpus = trainer.item_corpus_embeddings(item_cat)
         for batch in val_it:
             trainer.evaluate_topk(batch[0], batch[1], metric, corpus)

@@ -613,6 +613,22 @@ class TwoTowerTrainer:
         return out
 
     @torch.no_grad()
+    def user_embeddings(self, user_ids: torch.Tensor) -> torch.Tensor:
+        """User-tower output (inference: no dropout) for ANY number of user ids ([n, scorer_dim]), computed cfg.batch_size
+        ids at a time on the tower's buffers.  Out-of-range ids give the tower output of a zero row and set the trainer's
+        out-of-range flag (``check_ids``)."""
+        ut, b = self.user_tower, self.cfg.batch_size
+        ids = user_ids.to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
+        n = ids.numel()
+        out = torch.empty(n, ut.dims[-1], device=self.dev)
+        for s in range(0, n, b):
+            e = min(s + b, n)
+            ops.embedding_gather(self.user_table, ids[s:e], out=ut.acts[0][:e - s], oob_flag=self.oob)
+            ut.forward()
+            out[s:e].copy_(ut.acts[-1][:e - s])
+        return out
+
+    @torch.no_grad()
     def evaluate_topk(self, user_ids: torch.Tensor, item_ids: torch.Tensor, metric, corpus: torch.Tensor | None = None):
         """Updates ``metric`` (metrics.FactorizedTopK) with one batch of (user, true item) pairs scored against the
         whole item corpus; returns the ranks."""
