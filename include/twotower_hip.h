@@ -56,7 +56,8 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * of those tags record a hipEvent pair on ITS OWN stream (capacity = launches kept per tag);
  * tags: fill, gather, sparse_plan, sparse_apply, dense_fwd, dense_bwd (dx+dw in one launch), dense_bwd_dx, dense_bwd_dw,
  * dense_update, optimizer (sparse + dense in one launch), score_fwd, score_bwd, score_fused, score_rank, score_aux, route, scatter_rows, encode_ids,
- * topk_select, topk_merge (and the scope topk around a whole tt_retrieval_topk_f32 call).
+ * topk_select, topk_merge (and the scope topk around a whole tt_retrieval_topk_f32 call), ivf_bucket, ivf_select (and
+ * the scope ivf around a whole tt_ivf_search_f32 call).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -564,6 +565,23 @@ int64_t tt_retrieval_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t dim, i
 int tt_retrieval_topk_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim, int32_t k,
                           const int64_t* excl_offsets, const int64_t* excl_idx, void* workspace, int64_t workspace_bytes,
                           float* out_scores, int64_t* out_idx, tt_stream_t stream);
+
+/* IVF approximate top-K retrieval (added to v10: new symbols only, the version is unchanged): tt_retrieval_topk_f32's
+ * contract restricted to the items of the nprobe inverted lists whose centroids score highest for the query (the
+ * lists tt_retrieval_topk_f32(q, centroids, nlist, dim, nprobe) returns).  Index: centroids f32 [nlist, dim]; list_offsets int64 [nlist + 1] (0, non-decreasing, ending at n);
+ * list_vectors f32 [n, dim], the items reordered so that list l is rows list_offsets[l] .. list_offsets[l + 1]; list_ids
+ * int32 [n], the original item id of every reordered row, distinct.  q, centroids, list_vectors 16-byte aligned.
+ * out_scores f32 [nq, k], out_idx int64 [nq, k] (ORIGINAL ids): score descending, equal scores by ascending original id
+ * (also at the cut); a pair's score is bit-identical to tt_retrieval_topk_f32's; with nprobe = nlist the result equals
+ * tt_retrieval_topk_f32 over the whole corpus.  Exclusions as tt_retrieval_topk_f32, holding original ids; fewer than k
+ * candidates in the probed lists: the tail is (-inf, -1).  Limits: dim in {32, 64, 128, 256}, 1 <= k <= TT_TOPK_MAX_K,
+ * 1 <= nprobe <= min(nlist, TT_TOPK_MAX_K), 1 <= n < 2^31.  Launches only (no synchronisation, no copy to the host).
+ * Workspace (256-byte aligned): tt_ivf_search_workspace_bytes(...) (0 for arguments the call refuses). */
+int64_t tt_ivf_search_workspace_bytes(int64_t nq, int64_t nlist, int64_t n, int32_t dim, int32_t k, int32_t nprobe);
+int tt_ivf_search_f32(const float* q, int64_t nq, const float* centroids, int64_t nlist, const int64_t* list_offsets,
+                      const float* list_vectors, const int32_t* list_ids, int64_t n, int32_t dim, int32_t k, int32_t nprobe,
+                      const int64_t* excl_offsets, const int64_t* excl_idx, void* workspace, int64_t workspace_bytes,
+                      float* out_scores, int64_t* out_idx, tt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -36,21 +36,23 @@
 // at k = 256.  Launch 2: kMergeFan x k x 8 B <= 32 KB.  Split rule (topk_plan): enough (row block x split) waves for the
 // whole chip (kTargetWaves) - past the scorer's 64-split cap when nq is small - but at least kMinColsPerSplit candidates per
 // split.  It reads no environment variable.
-#include "common.h"
-#include <climits>
+#include "topk_select.h"
 
 namespace {
 
+// topk_select_kernel keeps its own copy of the select body (topk_select.h holds the same scheme for ivf.hip, with an id
+// hook): compiled from the shared template it allocated registers differently and ran 2-4 % slower in a same-box A/B.
 using tt::f32x4;
 using tt::f32x16;
+using tt::topk::beats;
+using tt::topk::kMaxEntries;
+using tt::topk::kMergeFan;
+using tt::topk::kMergeThreads;
+using tt::topk::kQueue;
 
-constexpr int kQueue = 48;               // survivor slots per query row (a tile adds at most 32)
-constexpr int kMaxEntries = (TT_TOPK_MAX_K + kQueue + 63) / 64;   // (list + queue) entries per lane in a merge
 constexpr int kTargetWaves = 2048;       // 256 CUs x 8
 constexpr int kMinColsPerSplit = 512;
 constexpr int kMaxSplits = 4096;
-constexpr int kMergeFan = 16;
-constexpr int kMergeThreads = 256;
 
 struct TopkPlan {
   int64_t rblocks;        // 32-query row blocks
@@ -63,11 +65,11 @@ struct TopkPlan {
 
 int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-TopkPlan topk_plan(int64_t nq, int64_t nc, int k) {
+TopkPlan topk_plan(int64_t nq, int64_t nc, int k, int min_cols = kMinColsPerSplit) {
   TopkPlan p{};
   p.rblocks = (nq + 31) / 32;
   int64_t ns = (kTargetWaves + p.rblocks - 1) / p.rblocks;
-  const int64_t by_cols = (nc + kMinColsPerSplit - 1) / kMinColsPerSplit;
+  const int64_t by_cols = (nc + min_cols - 1) / min_cols;
   if (ns > by_cols) ns = by_cols;
   if (ns > kMaxSplits) ns = kMaxSplits;
   if (ns < 1) ns = 1;
@@ -75,21 +77,13 @@ TopkPlan topk_plan(int64_t nq, int64_t nc, int k) {
   cps = (cps + 31) & ~(int64_t)31;
   p.c_per_split = cps;
   p.nsplit = (int)((nc + cps - 1) / cps);
-  int64_t lists = p.nsplit;
-  p.rounds = 0;
-  do {
-    lists = (lists + kMergeFan - 1) / kMergeFan;
-    ++p.rounds;
-  } while (lists > 1);
+  p.rounds = tt::topk_merge_rounds_count(p.nsplit);
   const int64_t bytes_a = align256(nq * p.nsplit * (int64_t)k * 4);         // one array (scores or indices)
-  const int64_t groups1 = (p.nsplit + kMergeFan - 1) / kMergeFan;
-  const int64_t bytes_b = p.rounds > 1 ? align256(nq * groups1 * (int64_t)k * 4) : 0;
+  const int64_t bytes_b = tt::topk_merge_b_bytes(nq, p.nsplit, k);
   p.off_b = 2 * bytes_a;
   p.total = 2 * bytes_a + 2 * bytes_b;
   return p;
 }
-
-__device__ __forceinline__ bool beats(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
 
 struct SelArgs {
   const float* q;
@@ -363,7 +357,7 @@ __global__ __launch_bounds__(kMergeThreads) void topk_merge_kernel(MergeArgs p) 
 
 template <int D>
 int launch_select(const SelArgs& a, int64_t blocks, hipStream_t stream) {
-  const int lds = a.rows_lds * 2 * (a.k + kQueue) * 4;
+  const int lds = tt::topk::select_lds_bytes(a.rows_lds, a.k);
   auto kern = topk_select_kernel<D>;
   if (lds > 64 * 1024) {   // above the 64 KiB default the limit must be raised (cheap, idempotent)
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
@@ -374,6 +368,83 @@ int launch_select(const SelArgs& a, int64_t blocks, hipStream_t stream) {
 }
 
 }  // namespace
+
+namespace tt {
+
+int topk_merge_rounds_count(int64_t nl) {
+  int rounds = 0;
+  do {
+    nl = (nl + kMergeFan - 1) / kMergeFan;
+    ++rounds;
+  } while (nl > 1);
+  return rounds;
+}
+
+int64_t topk_merge_b_bytes(int64_t nq, int64_t nl, int k) {
+  const int64_t groups1 = (nl + kMergeFan - 1) / kMergeFan;
+  return topk_merge_rounds_count(nl) > 1 ? align256(nq * groups1 * (int64_t)k * 4) : 0;
+}
+
+int topk_merge_launch(int64_t nq, int nl, int k, float* a_s, int32_t* a_i, float* b_s, int32_t* b_i, float* out_s,
+                      int64_t* out_i, hipStream_t stream) {
+  float* buf_s[2] = {a_s, b_s};
+  int32_t* buf_i[2] = {a_i, b_i};
+  const int rounds = topk_merge_rounds_count(nl);
+  for (int round = 0; round < rounds; ++round) {
+    const int groups = (nl + kMergeFan - 1) / kMergeFan;
+    const bool last = round == rounds - 1;
+    MergeArgs m{};
+    m.nq = nq; m.k = k; m.nl = nl; m.groups = groups;
+    m.in_s = buf_s[round & 1]; m.in_i = buf_i[round & 1];
+    if (last) {
+      m.out_s = out_s; m.out_i = nullptr; m.out_i64 = out_i;
+    } else {
+      m.out_s = buf_s[(round + 1) & 1]; m.out_i = buf_i[(round + 1) & 1]; m.out_i64 = nullptr;
+    }
+    const int lds = kMergeFan * k * 8 + kMergeFan * 4;
+    tt::launch("topk_merge", topk_merge_kernel, dim3((unsigned)(nq * groups)), dim3(kMergeThreads), (unsigned)lds, stream, m);
+    const int rc = tt::check_launch("topk_merge");
+    if (rc != TT_OK) return rc;
+    nl = groups;
+  }
+  return TT_OK;
+}
+
+}  // namespace tt
+
+namespace tt {
+
+int64_t topk_workspace_bytes_split(int64_t nq, int64_t nc, int k, int min_cols) { return topk_plan(nq, nc, k, min_cols).total; }
+
+int topk_run(const float* q, const float* c, int64_t nq, int64_t nc, int dim, int k, const int64_t* excl_offsets,
+             const int64_t* excl_idx, void* workspace, float* out_scores, int64_t* out_idx, hipStream_t stream, int min_cols) {
+  const TopkPlan pl = topk_plan(nq, nc, k, min_cols);
+  char* ws = static_cast<char*>(workspace);
+  const int64_t bytes_a = pl.off_b / 2;
+  const int64_t bytes_b = (pl.total - pl.off_b) / 2;
+  float* buf_s[2] = {reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + pl.off_b)};
+  int32_t* buf_i[2] = {reinterpret_cast<int32_t*>(ws + bytes_a), reinterpret_cast<int32_t*>(ws + pl.off_b + bytes_b)};
+
+  SelArgs a{};
+  a.q = q; a.c = c; a.nq = nq; a.nc = nc; a.k = k;
+  a.nsplit = pl.nsplit; a.c_per_split = pl.c_per_split;
+  a.rows_lds = nq < 32 ? (int)nq : 32;
+  a.excl_off = excl_offsets; a.excl_idx = excl_idx;
+  a.ws_s = buf_s[0]; a.ws_i = buf_i[0];
+  const int64_t blocks = pl.rblocks * pl.nsplit;
+  int rc;
+  switch (dim) {
+    case 32: rc = launch_select<32>(a, blocks, stream); break;
+    case 64: rc = launch_select<64>(a, blocks, stream); break;
+    case 128: rc = launch_select<128>(a, blocks, stream); break;
+    default: rc = launch_select<256>(a, blocks, stream); break;
+  }
+  if (rc != TT_OK) return rc;
+
+  return tt::topk_merge_launch(nq, pl.nsplit, k, buf_s[0], buf_i[0], buf_s[1], buf_i[1], out_scores, out_idx, stream);
+}
+
+}  // namespace tt
 
 extern "C" int64_t tt_retrieval_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t dim, int32_t k) {
   if (nq <= 0 || nc <= 0 || nc > INT32_MAX || k < 1 || k > TT_TOPK_MAX_K || k > nc || dim <= 0) return 0;
@@ -403,45 +474,5 @@ extern "C" int tt_retrieval_topk_f32(const float* q, const float* c, int64_t nq,
     return tt::fail(TT_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes", fn, (long long)workspace_bytes, (long long)pl.total);
   hipStream_t stream = tt::as_stream(stream_);
   tt::ProfScope scope("topk", stream);
-
-  char* ws = static_cast<char*>(workspace);
-  const int64_t bytes_a = pl.off_b / 2;
-  const int64_t bytes_b = (pl.total - pl.off_b) / 2;
-  float* buf_s[2] = {reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + pl.off_b)};
-  int32_t* buf_i[2] = {reinterpret_cast<int32_t*>(ws + bytes_a), reinterpret_cast<int32_t*>(ws + pl.off_b + bytes_b)};
-
-  SelArgs a{};
-  a.q = q; a.c = c; a.nq = nq; a.nc = nc; a.k = k;
-  a.nsplit = pl.nsplit; a.c_per_split = pl.c_per_split;
-  a.rows_lds = nq < 32 ? (int)nq : 32;
-  a.excl_off = excl_offsets; a.excl_idx = excl_idx;
-  a.ws_s = buf_s[0]; a.ws_i = buf_i[0];
-  const int64_t blocks = pl.rblocks * pl.nsplit;
-  int rc;
-  switch (dim) {
-    case 32: rc = launch_select<32>(a, blocks, stream); break;
-    case 64: rc = launch_select<64>(a, blocks, stream); break;
-    case 128: rc = launch_select<128>(a, blocks, stream); break;
-    default: rc = launch_select<256>(a, blocks, stream); break;
-  }
-  if (rc != TT_OK) return rc;
-
-  int nl = pl.nsplit;
-  for (int round = 0; round < pl.rounds; ++round) {
-    const int groups = (nl + kMergeFan - 1) / kMergeFan;
-    const bool last = round == pl.rounds - 1;
-    MergeArgs m{};
-    m.nq = nq; m.k = k; m.nl = nl; m.groups = groups;
-    m.in_s = buf_s[round & 1]; m.in_i = buf_i[round & 1];
-    if (last) {
-      m.out_s = out_scores; m.out_i = nullptr; m.out_i64 = out_idx;
-    } else {
-      m.out_s = buf_s[(round + 1) & 1]; m.out_i = buf_i[(round + 1) & 1]; m.out_i64 = nullptr;
-    }
-    const int lds = kMergeFan * k * 8 + kMergeFan * 4;
-    tt::launch("topk_merge", topk_merge_kernel, dim3((unsigned)(nq * groups)), dim3(kMergeThreads), (unsigned)lds, stream, m);
-    if ((rc = tt::check_launch("topk_merge")) != TT_OK) return rc;
-    nl = groups;
-  }
-  return TT_OK;
+  return tt::topk_run(q, c, nq, nc, dim, k, excl_offsets, excl_idx, workspace, out_scores, out_idx, stream, kMinColsPerSplit);
 }

@@ -792,6 +792,67 @@ def retrieval_topk(q, c, k: int, exclusions=None, workspace=None, out=None):
     return scores, indices
 
 
+def check_list_offsets(list_offsets, n: int, what: str) -> None:
+    """Raise unless list_offsets starts at 0, is non-decreasing and ends at n (checked on the device)."""
+    bad = (list_offsets[0] != 0) | (list_offsets[-1] != n) | (list_offsets.diff() < 0).any()
+    if bool(bad):
+        raise ValueError(f"{what}: list_offsets must start at 0, be non-decreasing and end at n = {n}")
+
+
+def ivf_search_workspace_bytes(nq: int, nlist: int, n: int, dim: int, k: int, nprobe: int) -> int:
+    """Workspace of ``ivf_search`` (0 for a shape the call refuses)."""
+    return int(_lib.load().tt_ivf_search_workspace_bytes(nq, nlist, n, dim, k, nprobe))
+
+
+def ivf_search(q, centroids, list_offsets, list_vectors, list_ids, k: int, nprobe: int, exclusions=None, workspace=None,
+               out=None, check_offsets: bool = True):
+    """IVF approximate top-k: ``retrieval_topk`` restricted to the items of the ``nprobe`` inverted lists whose centroids
+    score highest for each query.  Index: centroids f32 [nlist, D], list_offsets int64 [nlist + 1], list_vectors f32 [n, D]
+    (list l = rows list_offsets[l] .. list_offsets[l + 1]), list_ids int32 [n] (original item id of every row).  Returns
+    (scores f32 [nq, k], ORIGINAL item ids int64 [nq, k]), ties by ascending id, tail (-inf, -1) when fewer than k
+    candidates remain.  ``exclusions`` hold original ids, in either form ``retrieval_topk`` takes.  ``check_offsets``:
+    validate list_offsets on the device (a host synchronisation; an index that validated them once may skip it)."""
+    _chk(q, torch.float32, "query_embeddings", 2)
+    _chk(centroids, torch.float32, "centroids", 2)
+    _chk(list_offsets, torch.int64, "list_offsets", 1)
+    _chk(list_vectors, torch.float32, "list_vectors", 2)
+    _chk(list_ids, torch.int32, "list_ids", 1)
+    nq, d = q.shape
+    nlist, n = centroids.shape[0], list_vectors.shape[0]
+    if centroids.shape[1] != d or list_vectors.shape[1] != d:
+        raise RuntimeError(f"ivf_search: embedding dims differ: q {d}, centroids {centroids.shape[1]}, "
+                           f"list_vectors {list_vectors.shape[1]}")
+    if list_offsets.numel() != nlist + 1:
+        raise ValueError(f"ivf_search: list_offsets needs nlist + 1 = {nlist + 1} entries, got {list_offsets.numel()}")
+    if list_ids.numel() != n:
+        raise ValueError(f"ivf_search: list_ids needs {n} entries (one per list_vectors row), got {list_ids.numel()}")
+    k, nprobe = int(k), int(nprobe)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"ivf_search: k = {k} must be in [1, {TOPK_MAX_K}]")
+    if not 1 <= nprobe <= min(TOPK_MAX_K, nlist):
+        raise ValueError(f"ivf_search: nprobe = {nprobe} must be in [1, min({TOPK_MAX_K}, nlist = {nlist})]")
+    if check_offsets:
+        check_list_offsets(list_offsets, n, "ivf_search")
+    off, idx = exclusions_csr(exclusions, nq)
+    need = ivf_search_workspace_bytes(nq, nlist, n, d, k, nprobe)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
+    else:
+        _chk(workspace, torch.uint8, "workspace", 1)
+    if out is None:
+        out = (torch.empty(nq, k, dtype=torch.float32, device=q.device), torch.empty(nq, k, dtype=torch.int64, device=q.device))
+    scores, indices = out
+    _chk(scores, torch.float32, "out scores", 2)
+    _chk(indices, torch.int64, "out indices", 2)
+    if tuple(scores.shape) != (nq, k) or tuple(indices.shape) != (nq, k):
+        raise ValueError(f"ivf_search: out tensors must be [{nq}, {k}]")
+    _lib.check(_lib.load().tt_ivf_search_f32(_p(q), nq, _p(centroids), nlist, _p(list_offsets), _p(list_vectors), _p(list_ids),
+                                             n, d, k, nprobe, _p(off), _p(idx), _p(workspace), workspace.numel(), _p(scores),
+                                             _p(indices), _stream()),
+               "tt_ivf_search_f32")
+    return scores, indices
+
+
 def retrieval_batch_rank(q, c, inv_temperature: float, cand_prob=None, cand_ids=None, diag_offset: int = 0, workspace=None, out=None):
     """In-batch rank of every query's positive (candidate i + diag_offset) under the scores the loss sees - temperature,
     sampling-probability correction, accidental hits removed (int32 [nq]); top-k accuracy = mean(rank < k)."""

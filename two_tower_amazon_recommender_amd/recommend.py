@@ -1,7 +1,8 @@
 """``python -m two_tower_amazon_recommender_amd.recommend`` — the top-k items of every requested user from a checkpoint
 written by ``train.py --save``: the model is rebuilt from the checkpoint's ``config``, the whole item corpus goes through
 the item tower once, and users are answered in batches by ``serving.BruteForce`` (one fused score-and-select pass over
-the corpus per batch; no [users x items] score matrix).
+the corpus per batch; no [users x items] score matrix) or, with ``--index ivf``, by the approximate ``serving.IVF``
+(``--nlist`` k-means lists, ``--nprobe`` of them scanned per user; ``--nprobe`` = ``--nlist`` is exact).
 
     python -m two_tower_amazon_recommender_amd.recommend --checkpoint ck.pt --data interactions.parquet \\
         --all-users --exclude-seen --k 10 --out recs.parquet
@@ -38,11 +39,27 @@ def parse(argv=None):
     ap.add_argument("--out", default="recs.parquet", help="output parquet (user_idx, rank, item_idx, score)")
     ap.add_argument("--batch-users", type=int, default=4096, help="users per top-k call (bounds peak device memory)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--index", choices=("brute", "ivf"), default="brute",
+                    help="brute: exact top-k over the whole corpus; ivf: approximate inverted-file index")
+    ap.add_argument("--nlist", type=int, default=None, help="--index ivf: number of k-means lists (default 1024, at most the "
+                                                             "number of items)")
+    ap.add_argument("--nprobe", type=int, default=None, help=f"--index ivf: lists scanned per user (1..min({MAX_K}, nlist); "
+                                                              "default 32)")
+    ap.add_argument("--seed", type=int, default=0, help="--index ivf: k-means seed")
     args = ap.parse_args(argv)
     if not 1 <= args.k <= MAX_K:
         ap.error(f"--k must be in [1, {MAX_K}], got {args.k}")
     if args.batch_users < 1:
         ap.error("--batch-users must be positive")
+    if args.index != "ivf" and (args.nlist is not None or args.nprobe is not None):
+        ap.error("--nlist / --nprobe need --index ivf")
+    if args.index == "ivf":
+        args.nlist = 1024 if args.nlist is None else args.nlist
+        args.nprobe = min(32, args.nlist) if args.nprobe is None else args.nprobe
+        if args.nlist < 1:
+            ap.error(f"--nlist must be positive, got {args.nlist}")
+        if not 1 <= args.nprobe <= min(MAX_K, args.nlist):
+            ap.error(f"--nprobe must be in [1, min({MAX_K}, --nlist {args.nlist})], got {args.nprobe}")
     if args.exclude_seen and args.data is None:
         ap.error("--exclude-seen needs --data (the interactions that define what each user has seen)")
     if _SHARDED.search(args.checkpoint) or (not os.path.exists(args.checkpoint)
@@ -81,7 +98,7 @@ def main(argv=None) -> int:
     import pyarrow as pa
     import pyarrow.parquet as pq
     from . import data as datamod
-    from .serving import BruteForce
+    from .serving import IVF, BruteForce
     from .trainer import TwoTowerConfig, TwoTowerTrainer
 
     dev = torch.device(args.device)
@@ -114,7 +131,12 @@ def main(argv=None) -> int:
         if users.size and (users.min() < 0 or users.max() >= cfg.n_users):
             raise SystemExit(f"{args.users_file}: user ids must be in [0, {cfg.n_users})")
     k = min(args.k, cfg.n_items)
-    bf = BruteForce(k=k).index_from_trainer(trainer, item_cat)
+    if args.index == "ivf":
+        if args.nlist > cfg.n_items:
+            raise SystemExit(f"--nlist {args.nlist} exceeds the model's {cfg.n_items} items")
+        bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat)
+    else:
+        bf = BruteForce(k=k).index_from_trainer(trainer, item_cat)
     seen = seen_csr(user_idx, item_idx, cfg.n_users) if args.exclude_seen else None
 
     cols = {"user_idx": [], "rank": [], "item_idx": [], "score": []}

@@ -7,6 +7,12 @@
 
 Every call is one ``tt_retrieval_topk_f32`` (score-and-select fused on the f32 MFMA, then a merge across corpus splits):
 no [queries x corpus] score matrix is formed.  Ties are broken by the lower candidate index, so the answer is unique.
+
+``IVF`` is the approximate index next to it (an inverted file: spherical k-means lists, ``nprobe`` lists scanned per query,
+one ``tt_ivf_search_f32`` per call).  It has the same methods and answers exactly what ``BruteForce`` answers over the
+items of the probed lists; with ``nprobe = nlist`` the two agree bit for bit.
+
+    ivf = IVF(k=10, nlist=1024, nprobe=32).index_from_trainer(trainer)
 """
 from __future__ import annotations
 
@@ -81,3 +87,143 @@ class BruteForce:
         [nq, E] int64 tensor (-1 = padding) or a CSR pair (offsets [nq + 1], indices).  When fewer than k candidates
         remain, the tail is (-inf, -1)."""
         return self._query(queries, exclusions, k)
+
+
+class IVF(BruteForce):
+    """Inverted-file approximate top-k index (``tfrs.layers.factorized_top_k.ScaNN``'s role, without quantisation).
+
+    ``index`` runs ``iters`` rounds of spherical k-means on a seeded sample of at most 256 * nlist items (assignment with
+    ``tt_retrieval_topk_f32(sample, centroids, 1)``, each centroid the normalised mean of its members, an empty cluster
+    re-seeded from the largest one with a seeded perturbation), then places every item in the list of its best centroid
+    (ties to the lower list) and reorders the corpus list by list, items in ascending row order within a list.  The build
+    is deterministic: the same corpus, nlist and seed give bit-identical arrays (stable sorts and f64 prefix sums, no
+    atomics).  A query scans the ``nprobe`` lists whose centroids score highest for it."""
+
+    def __init__(self, query_model=None, k: int = 10, nlist: int = 1024, nprobe: int = 32, seed: int = 0, iters: int = 10):
+        super().__init__(query_model, k)
+        self.nlist, self.nprobe, self.seed, self.iters = int(nlist), int(nprobe), int(seed), int(iters)
+        if self.nlist < 1:
+            raise ValueError(f"IVF: nlist must be positive, got {self.nlist}")
+        if not 1 <= self.nprobe <= min(ops.TOPK_MAX_K, self.nlist):
+            raise ValueError(f"IVF: nprobe = {self.nprobe} must be in [1, min({ops.TOPK_MAX_K}, nlist = {self.nlist})]")
+        if self.iters < 0:
+            raise ValueError(f"IVF: iters must be >= 0, got {self.iters}")
+        self.centroids = self.list_offsets = self.list_vectors = self.list_ids = None
+
+    # ------------------------------------------------------------------ build
+    @staticmethod
+    def _assign(x: torch.Tensor, centroids: torch.Tensor, batch: int = 1 << 20) -> torch.Tensor:
+        """Best centroid of every row (int64 [n]; ties to the lower list), in batches of rows."""
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+        ws = None
+        for s in range(0, x.shape[0], batch):
+            xb = x[s:s + batch]
+            n = max(ops.retrieval_topk_workspace_bytes(xb.shape[0], centroids.shape[0], x.shape[1], 1), 1)
+            if ws is None or ws.numel() < n:
+                ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+            out[s:s + xb.shape[0]] = ops.retrieval_topk(xb, centroids, 1, workspace=ws)[1][:, 0]
+        return out
+
+    @staticmethod
+    def _segment_sums(x: torch.Tensor, assign: torch.Tensor, nlist: int):
+        """(f64 member sums [nlist, D], counts int64 [nlist]) by a stable sort and f64 prefix sums (deterministic)."""
+        order = torch.argsort(assign, stable=True)
+        counts = torch.bincount(assign, minlength=nlist)
+        ends = torch.cumsum(counts, 0)
+        # prefix sums along the rows of the transposed members (an inner-dimension scan: fast, and no atomics)
+        xt = x[order].to(torch.float64).T.contiguous()
+        csum = torch.cat([xt.new_zeros(x.shape[1], 1), torch.cumsum(xt, 1)], 1)
+        return (csum[:, ends] - csum[:, ends - counts]).T, counts
+
+    def index(self, candidates: torch.Tensor, identifiers=None) -> "IVF":
+        """candidates: [n, D] f32 device tensor (n >= nlist).  identifiers: as ``BruteForce.index``."""
+        if candidates.dim() != 2:
+            raise ValueError(f"IVF.index: candidates must be [n, D], got shape {tuple(candidates.shape)}")
+        x = candidates.detach().to(torch.float32).contiguous()
+        n, d = x.shape
+        if n < self.nlist:
+            raise ValueError(f"IVF.index: nlist = {self.nlist} exceeds the {n} candidates")
+        dev = x.device
+        g = torch.Generator(device=dev).manual_seed(self.seed)
+        m = min(n, 256 * self.nlist)
+        sample = x[torch.sort(torch.randperm(n, device=dev, generator=g)[:m]).values].contiguous()
+        cent = torch.nn.functional.normalize(sample[torch.randperm(m, device=dev, generator=g)[:self.nlist]], dim=1)
+        for _ in range(self.iters):
+            sums, counts = self._segment_sums(sample, self._assign(sample, cent.contiguous()), self.nlist)
+            norms = sums.norm(dim=1)
+            new = (sums / norms.clamp(min=1e-300)[:, None]).to(torch.float32)
+            empty = torch.nonzero((counts == 0) | (norms == 0)).flatten().tolist()
+            if empty:                                       # re-seed from the largest cluster, perturbed (seeded)
+                big = int(torch.argmax(counts))
+                noise = torch.randn(len(empty), d, device=dev, generator=g, dtype=torch.float32)
+                new[empty] = new[big][None] + 0.05 * noise
+            cent = torch.nn.functional.normalize(new, dim=1)
+        cent = cent.contiguous()
+        assign = self._assign(x, cent)
+        order = torch.argsort(assign, stable=True)
+        counts = torch.bincount(assign, minlength=self.nlist)
+        self.centroids = cent
+        self.list_offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).contiguous()
+        self.list_vectors = x[order].contiguous()
+        self.list_ids = order.to(torch.int32).contiguous()
+        self._candidates = self.list_vectors                # shape / device of the corpus for the base class
+        if identifiers is not None:
+            ids = torch.as_tensor(identifiers, device=dev)
+            if ids.dim() != 1 or ids.numel() != n:
+                raise ValueError(f"IVF.index: identifiers must be [{n}], got {tuple(ids.shape)}")
+            if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+                raise TypeError(f"IVF.index: identifiers must be integers, got {ids.dtype}")
+            identifiers = ids.to(torch.int64).contiguous()
+        self._identifiers = identifiers
+        return self
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self) -> dict:
+        if self.centroids is None:
+            raise RuntimeError("IVF: call index() or index_from_trainer() first")
+        return {"nlist": self.nlist, "centroids": self.centroids, "list_offsets": self.list_offsets,
+                "list_vectors": self.list_vectors, "list_ids": self.list_ids}
+
+    def load_state_dict(self, state: dict) -> "IVF":
+        cent = state["centroids"]
+        nlist = int(state["nlist"])
+        if cent.dim() != 2 or cent.shape[0] != nlist or state["list_offsets"].numel() != nlist + 1:
+            raise ValueError(f"IVF.load_state_dict: arrays do not match nlist = {nlist}")
+        if self.nprobe > nlist:
+            raise ValueError(f"IVF.load_state_dict: nprobe = {self.nprobe} exceeds the index's nlist = {nlist}")
+        self.nlist = nlist
+        self.centroids = cent.to(torch.float32).contiguous()
+        self.list_offsets = state["list_offsets"].to(torch.int64).contiguous()
+        self.list_vectors = state["list_vectors"].to(torch.float32).contiguous()
+        self.list_ids = state["list_ids"].to(torch.int32).contiguous()
+        if self.list_ids.numel() != self.list_vectors.shape[0] or self.centroids.shape[1] != self.list_vectors.shape[1]:
+            raise ValueError("IVF.load_state_dict: list_ids / list_vectors / centroids shapes disagree")
+        ops.check_list_offsets(self.list_offsets, self.list_vectors.shape[0], "IVF.load_state_dict")
+        self._candidates = self.list_vectors
+        self._identifiers = None
+        self._ws = None
+        return self
+
+    # ------------------------------------------------------------------ query
+    def _workspace(self, nq: int, k: int) -> torch.Tensor:
+        v = self.list_vectors
+        n = max(ops.ivf_search_workspace_bytes(nq, self.nlist, v.shape[0], v.shape[1], k, self.nprobe), 1)
+        if self._ws is None or self._ws.numel() < n:
+            self._ws = None
+            self._ws = torch.empty(n, dtype=torch.uint8, device=v.device)
+        return self._ws
+
+    def _query(self, queries, exclusions, k):
+        if self.centroids is None:
+            raise RuntimeError("IVF: call index() or index_from_trainer() first")
+        q = self.query_model(queries) if self.query_model is not None else queries
+        q = q.to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        k = self.k if k is None else int(k)
+        scores, idx = ops.ivf_search(q, self.centroids, self.list_offsets, self.list_vectors, self.list_ids, k, self.nprobe,
+                                     exclusions=exclusions, workspace=self._workspace(q.shape[0], k), check_offsets=False)
+        if self._identifiers is None:
+            return scores, idx
+        ids = self._identifiers[idx.clamp(min=0)]
+        return scores, torch.where(idx >= 0, ids, torch.full_like(ids, -1))

@@ -220,6 +220,40 @@ def _(q, c, k, exclusion_offsets, exclusion_indices):
     return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
 
 
+_IVF_WS: dict = {}
+
+
+def _ivf_ws(nq: int, nlist: int, n: int, d: int, k: int, nprobe: int, device) -> Tensor:
+    """Workspace of the IVF op, kept per (device, stream) like the top-k op's (the largest one seen)."""
+    need = max(ops.ivf_search_workspace_bytes(nq, nlist, n, d, k, nprobe), 1)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    hit = _IVF_WS.get(key)
+    if hit is not None and hit.numel() >= need:
+        return hit
+    _IVF_WS.pop(key, None)
+    buf = _IVF_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+@torch.library.custom_op(f"{NS}::ivf_search", mutates_args=(), device_types="cuda")
+def ivf_search(query_embeddings: Tensor, centroids: Tensor, list_offsets: Tensor, list_vectors: Tensor, list_ids: Tensor,
+               k: int, nprobe: int, exclusion_offsets: Optional[Tensor], exclusion_indices: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """IVF approximate top-k (ops.ivf_search): (scores f32 [nq, k], original item ids int64 [nq, k]) over the items of the
+    nprobe best lists, ties by ascending id; optional CSR exclusions of original ids.  Not differentiable (serving)."""
+    q = query_embeddings.contiguous()
+    ex = None if exclusion_offsets is None else (exclusion_offsets.contiguous(), exclusion_indices.contiguous())
+    ws = _ivf_ws(q.shape[0], centroids.shape[0], list_vectors.shape[0], q.shape[1], k, nprobe, q.device)
+    return ops.ivf_search(q, centroids.contiguous(), list_offsets.contiguous(), list_vectors.contiguous(), list_ids.contiguous(),
+                          k, nprobe, exclusions=ex, workspace=ws)
+
+
+@ivf_search.register_fake
+def _(q, centroids, list_offsets, list_vectors, list_ids, k, nprobe, exclusion_offsets, exclusion_indices):
+    return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
+
+
 # --------------------------------------------------------------------------------------------- a2 dense layers
 @torch.library.custom_op(f"{NS}::dense_fwd", mutates_args=(), device_types="cuda")
 def dense_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], relu: bool) -> Tensor:
@@ -286,5 +320,5 @@ def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: T
         ops.sparse_adagrad_(table, accum, grads.contiguous(), plan, lr, eps)
 
 
-OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "dense_fwd", "dense_bwd",
-       "sparse_update_")
+OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "dense_fwd",
+       "dense_bwd", "sparse_update_")
