@@ -1,4 +1,4 @@
-"""Sort-plan microbench: plan of 2 tables x n ids, uniform (U) and Zipf (Z) ids; TT_SORT_GROUPS picks the partition count."""
+"""Sort-plan microbench: plan of 2 tables x n ids, uniform (U) and Zipf (Z) ids."""
 import json
 import os
 import sys
@@ -19,7 +19,7 @@ def main():
             pu, pi = ops.SparsePlan(n, dev), ops.SparsePlan(n, dev)
             t2 = timed(lambda: ops.sparse_plan_batched([pu, pi], [iu, ii], [rows_u, rows_i]), 200)
             t1 = timed(lambda: pu.run(iu, rows_u), 200)
-            print(json.dumps({"groups": os.environ.get("TT_SORT_GROUPS", "auto"), "n": n, "rows": [rows_u, rows_i], "ids": variant,
+            print(json.dumps({"n": n, "rows": [rows_u, rows_i], "ids": variant,
                               "plan_2tables_us": round(t2, 2), "plan_1table_us": round(t1, 2)}), flush=True)
 
 

@@ -1,6 +1,7 @@
 """Soak: N train steps (composite entry) on a small skewed problem; prints a digest of every table / dense parameter at the end.
-Run once with the forward lookup's row-range id lists (default) and once with TT_ID_BUCKETS=0 (the optimizer's own scan): the
-digests must be equal - counters reset, generations, overflow fallbacks and the ranked path's offsets over thousands of steps."""
+It exercises the forward lookup's row-range id lists over thousands of steps - counters reset, generations, overflow fallbacks
+and the ranked path's offsets.  (r04 compared the digest against a run on the optimizer's own id scan, through a library switch
+that has since been removed: they were equal.)"""
 import hashlib
 import os
 import sys
@@ -33,4 +34,4 @@ tr.check_ids()
 h = hashlib.sha256()
 for t in (tr.user_table, tr.item_table, tr.dense_flat) + ((tr.user_accum, tr.item_accum, tr.dense_accum) if opt == "adagrad" else ()):
     h.update(t.cpu().numpy().tobytes())
-print(f"steps {steps} opt {opt} lists {os.environ.get('TT_ID_BUCKETS', '1')} skew_limit {tr.skew_limit} path switches {switches} loss {tr.loss.item():.6f} digest {h.hexdigest()}")
+print(f"steps {steps} opt {opt} skew_limit {tr.skew_limit} path switches {switches} loss {tr.loss.item():.6f} digest {h.hexdigest()}")

@@ -16,31 +16,19 @@
 // The embedding lookup of a tower's first layer is fused into the A loader (fwd and dW): see GemmArgs::a_ids.
 #include "common.h"
 #include "dense_update_body.h"
-#include <cstdlib>
 
 namespace {
 
 using tt::f32x4;
 using tt::f32x16;
 
-#ifndef TT_GEMM_BK
-#define TT_GEMM_BK 32                     // k-tile depth (A/B hook: 64 halves the barrier rounds, doubles LDS and the register ring)
-#endif
-constexpr int BM = 64, BN = 64, BK = TT_GEMM_BK;
+constexpr int BM = 64, BN = 64, BK = 32;   // BK: k-tile depth (64 halves the barrier rounds, doubles LDS and the register ring)
 // k-tiles of global loads in flight per thread.  r02 sweep of the four cfg3 tower launches (us): 1: 96.3, 2: 95.3, 3: 98.8,
 // 4 (3 for the forward orientation, the r01 setting): 98.2 - with four resident workgroups per CU the other waves cover a
 // tile's latency; the smaller ring leaves registers.
-#ifndef TT_GEMM_PF
-#define TT_GEMM_PF 2
-#endif
-#ifndef TT_GEMM_WIDE_STORE
-#define TT_GEMM_WIDE_STORE 1  // the output tile goes through LDS and leaves as 16-byte stores (0: 4-byte stores from the accumulators)
-#endif
-#ifndef TT_GEMM_PF_FWD
-#define TT_GEMM_PF_FWD 2
-#endif
-constexpr int PF_MAX = TT_GEMM_PF;       // k-tiles of global loads kept in flight per thread (register ring); the mixed-orientation
-                                         // forward kernel runs with 3 (it spills 22-48 VGPRs at 4 under the 4-waves/SIMD bound)
+constexpr int PF_MAX = 2;                // k-tiles of global loads kept in flight per thread (register ring); the mixed-orientation
+                                         // forward kernel spills 22-48 VGPRs at 4 under the 4-waves/SIMD bound
+constexpr int PF_FWD = 2;                // ... of the mixed-orientation forward kernel
 constexpr int NST = BM * BK / 4 / 256;   // staged float4 per thread and operand (= 2)
 constexpr int LS_KC = BK + 4;            // [row][k] stride
 constexpr int LS_MC = BM + 4;            // [k][row] stride
@@ -210,23 +198,15 @@ struct GemmBatch {
 // fixed order ((w0 + w2) + (w1 + w3)).  The LDS-tile form this replaces ran a chain of load -> ds_write -> barrier -> 16 MFMAs per
 // 32 batch rows: r04 stamps, layer 1 of cfg3: the dW workgroups' MFMA loops took 11.8-17.6 us for 3.8 us of MFMA time per wave,
 // and the dx workgroups of the same launch finished their second tile only when those had retired.
-// Needs M % 64 == 0 and N % 64 == 0 (every tower layer of the BASELINE configs but cfg1's 32 x 32); TT_DW_DIRECT=0 keeps the tiles.
-#ifndef TT_DW_DIRECT
-#define TT_DW_DIRECT 1
-#endif
-#ifndef TT_DW_PF_DEEP
-#define TT_DW_PF_DEEP 8          // ring depth where no lookup is fused into the rows.  16 fits the registers but ties (towers 87.6-87.8
-#endif                           // vs 87.8-88.1 us, r04) and would give dense and looked-up rows different eligibility (splits of 128 vs 64 rows)
-#ifndef TT_DX_PRIO
-#define TT_DX_PRIO 2
-#endif
-#ifndef TT_DW_PF
-#define TT_DW_PF 8               // iterations (2 batch rows each) of operand loads in flight per wave
-#endif
+// Needs M % 64 == 0 and N % 64 == 0 (every tower layer of the BASELINE configs but cfg1's 32 x 32); other shapes keep the tiles.
+constexpr int kDwPfDeep = 8;     // ring depth where no lookup is fused into the rows.  16 fits the registers but ties (towers 87.6-87.8
+                                 // vs 87.8-88.1 us, r04) and would give dense and looked-up rows different eligibility (splits of 128 vs 64 rows)
+constexpr int kDxPrio = 2;
+constexpr int kDwPf = 8;         // iterations (2 batch rows each) of operand loads in flight per wave
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // TWO: a second table's row is summed into every gathered row (the hashed category feature); its ring is paid for with a
 // shallower one (4 rounds in flight instead of 8: the lookup kernels have no registers to spare at 4 workgroups per CU).
-template <int GK, bool TWO, int PFD = TT_DW_PF>
+template <int GK, bool TWO, int PFD = kDwPf>
 __device__ __forceinline__ void dw_tile_direct(const GemmArgs& p, const int zsplit, const int bx, const int by, float* smem,
                                                int32_t* gids) {
   constexpr bool GATHER = GK != 0;
@@ -389,24 +369,22 @@ __device__ __forceinline__ void dw_tile_direct(const GemmArgs& p, const int zspl
 template <bool A_KC, bool B_KC, bool COLSUM, int GK, bool DROP = false>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& p, const int zsplit, const int bx, const int by, float* smem,
                                           int32_t* gids) {
-#if TT_DW_DIRECT
   if constexpr (!A_KC && !B_KC && COLSUM) {
     // (workgroup-uniform) the direct form takes whole 64 x 64 tiles and 8-byte row pieces
     // (rows straight from a dense activation - GK == 0 -: twice the ring depth, for splits that are whole rounds of it - 4 MFMAs
     // per ring slot are 0.12 us of matrix-pipe time against a 1-2 us load round trip; only ONE depth per kernel: with both
     // instantiated beside the dx tiles the kernel needs more than the 128 VGPRs that 4 workgroups per CU leave)
-    constexpr int RND = 8 * (GK == 0 ? TT_DW_PF_DEEP : TT_DW_PF);       // batch rows of one ring round of the four waves
+    constexpr int RND = 8 * (GK == 0 ? kDwPfDeep : kDwPf);       // batch rows of one ring round of the four waves
     if ((p.M & 63) == 0 && (p.N & 63) == 0 && ((p.lda | p.ldb | p.ldc) & 3) == 0 && p.db_slabs != nullptr &&
         ((p.K | p.k_per_split) & (RND - 1)) == 0 && p.k_per_split * (p.lda > p.ldb ? p.lda : p.ldb) < ((int64_t)1 << 31)) {
       if constexpr (GK != 0) {
         if (p.A2 != nullptr) { dw_tile_direct<GK, true>(p, zsplit, bx, by, smem, gids); return; }
       }
-      dw_tile_direct<GK, false, (GK == 0 ? TT_DW_PF_DEEP : TT_DW_PF)>(p, zsplit, bx, by, smem, gids);
+      dw_tile_direct<GK, false, (GK == 0 ? kDwPfDeep : kDwPf)>(p, zsplit, bx, by, smem, gids);
       return;
     }
   }
-#endif
-  constexpr int PF = (A_KC && !B_KC) ? TT_GEMM_PF_FWD : PF_MAX;
+  constexpr int PF = (A_KC && !B_KC) ? PF_FWD : PF_MAX;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, ln = lane & 31;
@@ -562,7 +540,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, const int zsplit, c
   float* C = p.C + (int64_t)zsplit * p.slab_stride;
   const int64_t n = n0 + wn * 32 + ln;
   uint32_t posbits = 0u;                        // fwd: (C > 0) of this lane's 16 elements
-#if TT_GEMM_WIDE_STORE
   // The output tile leaves through LDS: accumulators -> [64][64 + 4] floats in the (now idle) operand buffers -> 16 bytes
   // per lane, a wave-instruction storing four whole 256-byte row pieces.  Stored straight from the accumulators a wave
   // needs 16 instructions of 4 bytes per lane (two 128-byte pieces each) and the epilogue is store-ISSUE-bound: in the fused
@@ -572,10 +549,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, const int zsplit, c
   // are API requirements - but not for the hard-negative search's [nq][nc] scratch matrix, which keeps the 4-byte stores)
   const bool wide = ((p.ldc | p.N) & 3) == 0 && (reinterpret_cast<uintptr_t>(C) & 15u) == 0;
   if (wide) __syncthreads();                    // every wave has read its last fragments of the operand tiles
-#else
-  constexpr bool wide = false;
-  constexpr int LSO = 1;
-#endif
   if (n < p.N) {
     const float bias = p.bias != nullptr ? p.bias[n] : 0.f;
 #pragma unroll
@@ -600,7 +573,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, const int zsplit, c
       }
     }
   }
-#if TT_GEMM_WIDE_STORE
   if (wide) __syncthreads();
 #pragma unroll
   for (int j = 0; wide && j < BM * BN / 4 / 256; ++j) {
@@ -609,7 +581,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, const int zsplit, c
     const int64_t m = m0 + row, nn = n0 + 4 * c4;
     if (m < p.M && nn < p.N) *reinterpret_cast<f32x4*>(C + m * p.ldc + nn) = *reinterpret_cast<const f32x4*>(smem + row * LSO + 4 * c4);
   }
-#endif
   if constexpr (A_KC && !B_KC) {
     if (p.relu_bits != nullptr) {      // (workgroup-uniform) one ballot per register: low half = tile row acc_row(reg, 0), high = (reg, 1)
       uint32_t myword = 0u;
@@ -691,11 +662,7 @@ constexpr int kDepSpinLimit = 1 << 22;
 __device__ __forceinline__ void dep_release(const DepFlags& d, int prob, int row_block) {
   __syncthreads();                                           // every wave's stores of the tile(s) are issued and counted
   if (threadIdx.x == 0)
-#ifdef TT_DEP_NOREL
-    __hip_atomic_fetch_add(d.ready + prob * d.row_blocks + row_block, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
     __hip_atomic_fetch_add(d.ready + prob * d.row_blocks + row_block, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 
 __device__ __forceinline__ void dep_wait(const DepFlags& d, int prob, int first_block, int count) {
@@ -712,9 +679,7 @@ __device__ __forceinline__ void dep_wait(const DepFlags& d, int prob, int first_
       __hip_atomic_store(d.ready + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-#ifndef TT_DEP_NOACQ
   if (threadIdx.x < 64u) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
   __syncthreads();
 }
 
@@ -756,7 +721,7 @@ __device__ __forceinline__ void bwd_block(const BwdBatch& pb, int b, float* smem
     // the matrix pipe; the dW tiles (since r04 one long barrier-free MFMA stream per wave) fill what they leave.  At equal
     // priority the oldest wave wins: the dW waves, dispatched first, held the pipe and the dx workgroups' second tiles ran
     // alone at the end of the launch, latency-bound (r04 stamps: second dx tiles from 19-24 us to 27-32 us of a 32 us launch).
-    __builtin_amdgcn_s_setprio(TT_DX_PRIO);
+    __builtin_amdgcn_s_setprio(kDxPrio);
     if constexpr (ROLE == 2) dep_wait(dep, prob, b % pb.dx_gm, 1);
     gemm_tile<true, true, false, 0>(pb.ax[prob], 0, b % pb.dx_gm, b / pb.dx_gm, smem, gids);
     if (pb.dx_pair) {
@@ -901,19 +866,15 @@ extern "C" int tt_dense_fwd_dropout_f32(const float* x, const float* w, const fl
   return tt_dense_fwd_batched_f32(&q, 1, m, k, n, relu, drop_rate, seed, counter_offset, stream);
 }
 
-#ifndef TT_DW_MAX_SLABS
-#define TT_DW_MAX_SLABS 32
-#endif
-// Batch rows per dW slab (the slab count is capped at TT_DW_MAX_SLABS).  64: batches below 8192 get more, shorter slabs - the
+constexpr int kDwMaxSlabs = 32;
+// Batch rows per dW slab (the slab count is capped at kDwMaxSlabs).  64: batches below 8192 get more, shorter slabs - the
 // dW tiles' k loop is a chain of load -> barrier -> MFMA rounds, 256 rows of it were 10 of gemm_bwd's 14 us at B = 256
 // (r03 A/B, step time with 256 -> 64: cfg1 51.0 -> 43.8 us, cfg2 124.9 -> 119.6 us, cfg3 / cfg4 unchanged: capped at 32 slabs)
-#ifndef TT_DW_SLAB_ROWS
-#define TT_DW_SLAB_ROWS 64
-#endif
+constexpr int kDwSlabRows = 64;
 extern "C" int32_t tt_dense_bwd_num_slabs(int64_t m) {
-  int64_t s = (m + TT_DW_SLAB_ROWS - 1) / TT_DW_SLAB_ROWS;
+  int64_t s = (m + kDwSlabRows - 1) / kDwSlabRows;
   if (s < 1) s = 1;
-  if (s > TT_DW_MAX_SLABS) s = TT_DW_MAX_SLABS;
+  if (s > kDwMaxSlabs) s = kDwMaxSlabs;
   return (int32_t)s;
 }
 
@@ -999,7 +960,6 @@ void fill_bwd_batch(BwdBatch& pb, const GemmArgs (&ax)[2], const GemmArgs (&aw)[
   // median workgroup end 22.8 us).  Pairing two dx tiles per workgroup makes every workgroup equally long and all resident.
   const int64_t dx_tiles = (int64_t)pb.dx_gm * pb.dx_gn, dw_tiles = (int64_t)pb.dw_gm * pb.dw_gn * splits;
   pb.dx_pair = (n_probs * (dx_tiles + dw_tiles) > 1024 && pb.dx_gn % 2 == 0 && 2 * ax[0].k_per_split <= aw[0].k_per_split) ? 1 : 0;
-  if (const char* e = std::getenv("TT_GEMM_DX_PAIR")) pb.dx_pair = (std::atoi(e) != 0 && pb.dx_gn % 2 == 0) ? 1 : 0;
 }
 int64_t bwd_batch_blocks(const BwdBatch& pb) {
   const int64_t dx_tiles = (int64_t)pb.dx_gm * pb.dx_gn, dw_tiles = (int64_t)pb.dw_gm * pb.dw_gn * pb.splits;
@@ -1086,8 +1046,6 @@ extern "C" int tt_tower_bwd2_batched_f32(const tt_dense_bwd_args* upper, const t
   Bwd2Batch pb{};
   fill_bwd_batch(pb.up, axu, awu, n_probs, su);
   fill_bwd_batch(pb.lo, axl, awl, n_probs, sl);
-  if (const char* e = std::getenv("TT_BWD2_UP_DXFIRST")) { if (std::atoi(e) != 0) pb.up.dw_first = 0; }
-  if (const char* e = std::getenv("TT_BWD2_UP_PAIR")) pb.up.dx_pair = (std::atoi(e) != 0 && pb.up.dx_gn % 2 == 0) ? 1 : 0;
   const int64_t n_up = bwd_batch_blocks(pb.up), n_lo = bwd_batch_blocks(pb.lo);
   TT_REQUIRE(n_up + n_lo <= 0x7fffffff, "tt_tower_bwd2_batched_f32: grid too large");
   pb.n_up = (int)n_up;

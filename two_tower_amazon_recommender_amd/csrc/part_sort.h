@@ -206,7 +206,7 @@ __device__ __forceinline__ uint16_t* part_poss(uint32_t* smem, int cap) {
 }
 
 // The body of one sorting workgroup (1024 threads), group g of table t, in three pieces (part_sort_body composes them; the
-// fused optimizer, csrc/sparse.hip, calls them itself so that it can request rows between the scan and the ranking):
+// fused optimizer, csrc/sparse.hip, calls them itself):
 //   part_scan_append   every id of the table is read and clamped, the keys of the group's row range are appended to the LDS
 //                      list (unordered); returns m = their number (workgroup-uniform), offset = keys sorting before the group
 //   part_rank_small    m <= kPartRankMax: stable rank by counting
@@ -224,15 +224,9 @@ struct PartScan {
 // DROP_OOR: an id outside [0, num_rows) - the exchange's -1 padding, a corrupt id - belongs to NO range (the fused optimizer:
 // such an id has no row to update, and a half-empty fixed-capacity list would otherwise pile its padding onto the last
 // group as one hot "sentinel" range).  !DROP_OOR: it takes the sentinel key and sorts last (the plan's sorted_ids hold all n).
-// on_mine(mask, key, position): called by ALL lanes of a wave for every load j, once every id of the thread has been consumed;
-// mask (wave-uniform) = the lanes whose id j falls in this group's range, key / position = the calling lane's own (the
-// fused optimizer starts the rows' trip from HBM there, two phases before it can consume them).
-struct NoHook {
-  __device__ __forceinline__ void operator()(uint64_t, uint32_t, uint32_t) const {}
-};
-template <int DBITS, int JMAX, bool DROP_OOR = false, typename Hook = NoHook>
+template <int DBITS, int JMAX, bool DROP_OOR = false>
 __device__ __forceinline__ uint32_t part_scan_append(const PartTable& t, const int g, const int cap, uint32_t* smem, PartScan<JMAX>& sc,
-                                                     uint32_t& offset, uint32_t& base_key, Hook on_mine = Hook()) {
+                                                     uint32_t& offset, uint32_t& base_key) {
   constexpr int RADIX = 1 << DBITS;
   constexpr int W = 16, T = 1024;
   uint32_t* keys = smem;                                    // [cap]
@@ -297,12 +291,6 @@ __device__ __forceinline__ uint32_t part_scan_append(const PartTable& t, const i
       if (lane == 0) cjw[j * W + w] = c1;
     }
   }
-  // (the hook runs when EVERY id of the thread has been consumed: its loads are invisible to the compiler's counter model -
-  // inline asm - and the vmcnt(N) it places in front of id j+1 would otherwise wait for the hook's loads of id j too:
-  // memory operations retire in order.  Measured that way: classification 0.8 -> 3 us.)
-#pragma unroll
-  for (int j = 0; j < JMAX; ++j)
-    if (j < J && sc.mm[j] != 0ull) on_mine(sc.mm[j], sc.kj[j], (uint32_t)(j * T + tid));
   SSTAMP(4);
   uint32_t wbase = 0u;
   if (lane == 0) {

@@ -25,13 +25,11 @@
 // XCD's L2 keeps re-serving the same K range); partial results go to per-split slabs that a small
 // kernel sums in split order (bitwise reproducible; no float atomics).
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
 using tt::f32x4;
 using tt::f32x16;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -43,24 +41,6 @@ constexpr float kNegBig = -1.0e30f;   // log2-domain stand-in for -inf (tfrs use
 // MODE_FUSED_S: MODE_FUSED that also writes the raw dot products X[q][c] to ScoreArgs::S; MODE_BWD_S: MODE_BWD that reads
 // them back instead of recomputing GEMM1 (the training entry's pass 2: half the matrix-pipe work)
 enum { MODE_FWD = 0, MODE_BWD = 1, MODE_FUSED = 2, MODE_RANK = 3, MODE_FUSED_S = 4, MODE_BWD_S = 5 };
-#ifndef TT_BX3_ABL
-#define TT_BX3_ABL 0          // timing-only ablation hooks of the bf16x3 kernel (wrong results when non-zero; scratch/abl_bx3.sh)
-#endif
-#ifndef TT_BX3_STAGGER
-// bf16x3, 8 waves: 1 = barrier between GEMM1 and the epilogue + 3-buffer LDS ring (see the tile loop), so that the two waves
-// of a SIMD may drift apart.  r02 measurements at B = 8192, D = 128 (FUSED / BWD pass, us): lock-step (0) 147 / 151;
-// this form 163 / 160; a first form (waves 4-7 run GEMM2 one tile late, coefficients kept across the barrier) 164 / 175 with
-// 24 spilled VGPRs.  The ablation says why lock-step still wins: GEMM1 (69 us) and GEMM2 (39 us) already run at the
-// bf16 matrix pipe's pace at the clock it holds (~1.6 GHz), and what is left (~60 us) is the epilogue + staging VALU,
-// which neither form managed to slide under the partner wave's MFMAs at a 256-VGPR budget.
-#define TT_BX3_STAGGER 0
-#endif
-#ifndef TT_PK_EPILOGUE
-// 1: v_pk_fma_f32 / v_pk_add_f32 pairs in the softmax epilogue; 0: scalar f32 ops.  A/B on one box, alternating runs
-// (profiles/r02_ab_epilogue_pk_vs_scalar.txt): FUSED 273.1 vs 272.4 us, BWD 271.3 vs 271.7 us, step 0.7024 vs 0.7019 ms —
-// a tie; the scalar form is the default (MI355X_MICROARCH.md: packed f32 VALU beside MFMAs is at best neutral).
-#define TT_PK_EPILOGUE 0
-#endif
 constexpr float kRescaleThr = 8.0f;   // FUSED: rescale the accumulators only when a row max grows by > 2^8 (p stays <= 256)
 
 struct ScoreArgs {
@@ -125,29 +105,18 @@ __device__ __forceinline__ Bf3 split3(float x) {
 // reads (ds_read_b128, GEMM1's A operand) and for the transposing reads (ds_read_b64_tr_b16, GEMM2's A operand = K^T).
 __device__ __forceinline__ int img_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
-#ifndef TT_BWDS_WAVES
-#define TT_BWDS_WAVES 2       // min waves per SIMD of the BWD_S pass at D <= 128 (3 = 170 VGPRs)
-#endif
-#ifndef TT_S_PREFETCH
-#define TT_S_PREFETCH 2       // BWD_S: tiles of stored dot products in flight ahead of the one being worked on (1 or 2)
-#endif
-#ifndef TT_ABL_BWDS_NOSTAGE
-#define TT_ABL_BWDS_NOSTAGE 0
-#endif
+constexpr int kBwdSWaves = 2;             // min waves per SIMD of the BWD_S pass at D <= 128 (3 = 170 VGPRs)
+constexpr int kSPrefetch = 2;             // BWD_S: tiles of stored dot products in flight ahead of the one being worked on (1 or 2)
 #ifndef TT_LOOP_LAMBDA
 #define TT_LOOP_LAMBDA 0
 #endif
-#ifndef TT_TILES_PER_BARRIER
-#define TT_TILES_PER_BARRIER 2
-#endif
-#ifndef TT_TILES_PER_BARRIER_BWDS
-#define TT_TILES_PER_BARRIER_BWDS TT_TILES_PER_BARRIER      // the dc pass (one 8-wave workgroup per CU: room for a ring of 8 buffers)
-#endif
+constexpr int kTilesPerBarrier = 2;
+constexpr int kTilesPerBarrierBwdS = kTilesPerBarrier;   // the dc pass (one 8-wave workgroup per CU: room for a ring of 8 buffers)
 template <int D, int MODE, int PREC>
 constexpr int tiles_per_barrier() {
-  if (PREC == 0 && D <= 128 && MODE == MODE_BWD_S) return TT_TILES_PER_BARRIER_BWDS;
+  if (PREC == 0 && D <= 128 && MODE == MODE_BWD_S) return kTilesPerBarrierBwdS;
   return (PREC == 0 && D <= 128 && (MODE == MODE_BWD || MODE == MODE_FUSED || MODE == MODE_FUSED_S))
-             ? TT_TILES_PER_BARRIER : 1;
+             ? kTilesPerBarrier : 1;
 }
 
 // bf16x3 at dim 256, passes with GEMM1 AND GEMM2: a PAIR of waves shares 32 stationary rows and splits the embedding
@@ -174,7 +143,7 @@ template <int D, int MODE, int PREC, int WAVES>
 constexpr int rows_per_wg() { return (split_d<D, MODE, PREC>() ? WAVES / 2 : WAVES) * 32; }
 
 template <int D, int MODE, bool HAS_IDS, bool HAS_HN, int WAVES, int PREC>
-__global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE == MODE_BWD_S && PREC == 0) ? TT_BWDS_WAVES : 2) : 1))) void score_kernel(ScoreArgs p) {   // (min waves per SIMD)
+__global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE == MODE_BWD_S && PREC == 0) ? kBwdSWaves : 2) : 1))) void score_kernel(ScoreArgs p) {   // (min waves per SIMD)
   constexpr bool IS_FUSED = MODE == MODE_FUSED || MODE == MODE_FUSED_S;     // online softmax + dq
   constexpr bool IS_BWD = MODE == MODE_BWD || MODE == MODE_BWD_S;            // gradient pass with given row statistics
   constexpr bool FROM_S = MODE == MODE_BWD_S, TO_S = MODE == MODE_FUSED_S;
@@ -218,7 +187,6 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   // (bf16x3 with 8-wave workgroups: the lo piece — one product per k-step — lives in LDS, [ks][lane] x 16 B per wave,
   // written once: 32 VGPRs less, which is what keeps the gradient kernels free of scratch spills)
   constexpr bool RLO_LDS = PREC == 1 && WAVES == 8;
-  constexpr bool STAG = PREC == 1 && WAVES == 8 && TT_BX3_STAGGER && !FROM_S && !TO_S;     // staggered wave halves + 3-buffer LDS ring (see the tile loop)
   // exact-f32 gradient passes: TPB tiles between workgroup barriers (ring of 2*TPB LDS buffers, the prefetch runs TPB tiles
   // ahead); everything else: one tile per barrier, two buffers
   constexpr int TPB = tiles_per_barrier<D, MODE, PREC>();
@@ -227,7 +195,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   // read, so the next tile's write is only safe behind the per-tile barrier that TPB == 1 gives.
   static_assert(!(SPLIT && RLO_LDS), "wave-pair exchange buffer and the LDS lo fragments share one LDS region");
   static_assert(!SPLIT || TPB == 1, "the wave-pair exchange relies on one workgroup barrier per tile");
-  constexpr int NBUF = STAG ? 3 : 2 * TPB;
+  constexpr int NBUF = 2 * TPB;
   constexpr int RFL = rf_lds_groups<D, MODE, HAS_IDS, HAS_HN, PREC>();      // k-groups of the stationary fragment kept in LDS
   constexpr int RFR = PREC == 0 ? NG - RFL : 1;                             // ... and in registers
   f32x4 rf[RFR];
@@ -323,7 +291,6 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
           bf16x4 q0, q1, q2;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            if constexpr (TT_BX3_ABL & 1) { q0[e] = (__bf16)st[j][e]; q1[e] = q0[e]; q2[e] = q0[e]; continue; }
             const Bf3 u = split3(st[j][e]);
             q0[e] = u.hi; q1[e] = u.mid; q2[e] = u.lo;
           }
@@ -421,7 +388,6 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       // Software-pipelined by hand: the three fragments of k-step ks+1 are in flight under the six MFMAs of k-step ks
       // (left to the compiler the MFMAs sat behind each read's LDS latency: 2.3x the pure MFMA time, r02 ablation).
       const char* img = reinterpret_cast<const char*>(T);
-      constexpr int KSN = (TT_BX3_ABL & 2) ? 1 : KS;
       auto frag = [&](int ks, bf16x8& f_hi, bf16x8& f_mid, bf16x8& f_lo, bf16x8& r_lo) {
         const int off = (SPLIT ? hw : (ks >> 3)) * HALF_B + img_off(ln, 2 * (ks & 7) + h);
         f_hi = *reinterpret_cast<const bf16x8*>(img + off);
@@ -432,9 +398,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       bf16x8 a_hi, a_mid, a_lo, b_lo = {};
       frag(0, a_hi, a_mid, a_lo, b_lo);
 #pragma unroll
-      for (int ks = 0; ks < KSN; ++ks) {
+      for (int ks = 0; ks < KS; ++ks) {
         bf16x8 n_hi = a_hi, n_mid = a_mid, n_lo = a_lo, nb_lo = b_lo;
-        if (ks + 1 < KSN) frag(ks + 1, n_hi, n_mid, n_lo, nb_lo);
+        if (ks + 1 < KS) frag(ks + 1, n_hi, n_mid, n_lo, nb_lo);
         if constexpr (!RLO_LDS) b_lo = rp[2][ks];
         X = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, rp[0][ks], X, 0, 0, 0);     // smallest terms first
         X = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, X, 0, 0, 0);
@@ -547,21 +513,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       run_m = m_new;
     } else {
       if constexpr (IS_BWD) {
-        // the fma and the add as packed f32 pairs (v_pk_fma_f32 / v_pk_add_f32: same roundings, half the VALU
-        // issue slots — VALU cycles are not hidden behind f32 MFMAs)
         float tvs[16];
-        if constexpr (TT_PK_EPILOGUE) {
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const f32x2 x2 = f32x2{X[2 * q], X[2 * q + 1]}, a2 = f32x2{ac[2 * q], ac[2 * q + 1]};
-            const f32x2 t2 = __builtin_elementwise_fma(x2, f32x2{p.c1, p.c1}, a2) + f32x2{ar, ar};
-            tvs[2 * q] = t2[0];
-            tvs[2 * q + 1] = t2[1];
-          }
-        } else {
-#pragma unroll
-          for (int reg = 0; reg < 16; ++reg) tvs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]) + ar;
-        }
+        for (int reg = 0; reg < 16; ++reg) tvs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]) + ar;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const float w = sc[reg] * sr;
@@ -582,18 +536,8 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
         // over both halves' c).  Lazy rescale (threshold kRescaleThr): wave-uniform branch.
         float mx = kNegBig;
         float vs[16];
-        if constexpr (TT_PK_EPILOGUE) {
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {      // packed f32 pairs: v_pk_fma_f32
-            const f32x2 x2 = f32x2{X[2 * q], X[2 * q + 1]}, a2 = f32x2{ac[2 * q], ac[2 * q + 1]};
-            const f32x2 t2 = __builtin_elementwise_fma(x2, f32x2{p.c1, p.c1}, a2);
-            vs[2 * q] = t2[0];
-            vs[2 * q + 1] = t2[1];
-          }
-        } else {
-#pragma unroll
-          for (int reg = 0; reg < 16; ++reg) vs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]);
-        }
+        for (int reg = 0; reg < 16; ++reg) vs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           float v = vs[reg];
@@ -618,30 +562,16 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
             for (int i = 0; i < 16; ++i) G[b][i] *= alpha;
           run_m = m_new;
         }
-        float sum = 0.f;
-        if constexpr (TT_PK_EPILOGUE) {
+        // the sum of the 16 exponentials as two interleaved chains (even / odd registers), then the pair
+        float s0 = 0.f, s1 = 0.f;
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {      // the subtraction as packed pairs (v_pk_add_f32 with negated operand)
-            const f32x2 d2 = f32x2{coef[2 * q], coef[2 * q + 1]} - f32x2{run_m, run_m};
-            coef[2 * q] = __builtin_amdgcn_exp2f(d2[0]);
-            coef[2 * q + 1] = __builtin_amdgcn_exp2f(d2[1]);
-          }
-          f32x2 s2 = f32x2{coef[0], coef[1]};           // 8 packed adds + 1 instead of 16 sequential ones
-#pragma unroll
-          for (int q = 1; q < 8; ++q) s2 += f32x2{coef[2 * q], coef[2 * q + 1]};
-          sum = s2[0] + s2[1];
-        } else {                                        // the same additions (pairs, then the two lanes), scalar ops
-          float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            coef[2 * q] = __builtin_amdgcn_exp2f(coef[2 * q] - run_m);
-            coef[2 * q + 1] = __builtin_amdgcn_exp2f(coef[2 * q + 1] - run_m);
-            s0 = q == 0 ? coef[0] : s0 + coef[2 * q];
-            s1 = q == 0 ? coef[1] : s1 + coef[2 * q + 1];
-          }
-          sum = s0 + s1;
+        for (int q = 0; q < 8; ++q) {
+          coef[2 * q] = __builtin_amdgcn_exp2f(coef[2 * q] - run_m);
+          coef[2 * q + 1] = __builtin_amdgcn_exp2f(coef[2 * q + 1] - run_m);
+          s0 = q == 0 ? coef[0] : s0 + coef[2 * q];
+          s1 = q == 0 ? coef[1] : s1 + coef[2 * q + 1];
         }
-        run_l += sum;
+        run_l += s0 + s1;
       }
     }
   };
@@ -657,12 +587,12 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       for (int i = 0; i < 16; ++i) {
         const __bf16 hi = (__bf16)coef[i];
         c_hi[i >> 3][i & 7] = hi;
-        c_mid[i >> 3][i & 7] = (TT_BX3_ABL & 8) ? hi : (__bf16)(coef[i] - (float)hi);
+        c_mid[i >> 3][i & 7] = (__bf16)(coef[i] - (float)hi);
       }
       const char* img = reinterpret_cast<const char*>(T);
       const int g16 = (lane >> 4) & 1, q = (lane >> 2) & 3, pp = lane & 3;
       // flat step i = 2 b + s; the four transposing reads of step i+1 are in flight under the three MFMAs of step i
-      constexpr int NSTEP = 2 * ((TT_BX3_ABL & 4) ? 1 : NBW);
+      constexpr int NSTEP = 2 * NBW;
       auto frag = [&](int i, bf16x8& k_hi, bf16x8& k_mid) {
         const int b = i >> 1, s = i & 1;
         const int sub = (SPLIT ? hw : ((32 * b) >> 7)) * HALF_B + 8 * (pp & 1);     // (SPLIT: b counts inside the wave's own 128 columns)
@@ -731,26 +661,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
     }
   };
 
-  if constexpr (STAG) {
-    // ---- bf16x3, 8 waves: ONE barrier per tile, placed between [GEMM1(t), LDS store of tile t+1] and [epilogue(t),
-    // GEMM2(t)], with a 3-buffer ring.  A wave that passes barrier t knows tile t+1 is complete, so after its GEMM2(t) it
-    // runs straight into GEMM1(t+1); it only waits at barrier t+1 for the others to finish iteration t.  The two waves of
-    // a SIMD therefore drift up to an epilogue + GEMM2 apart: one wave's softmax VALU runs under the other's MFMAs instead
-    // of both sitting in the same phase (bf16 MFMAs leave 3/4 of the SIMD's issue slots free; MI355X_MICROARCH.md "Two
-    // waves per SIMD").  Buffer t is overwritten by the store of iteration t+2, which is behind barrier t+1, i.e. after
-    // every wave has finished GEMM2(t).  Same code and same arithmetic order for every wave. ----
-    if (ntiles > 1) load_tile(1);
-    for (int t = 0; t < ntiles; ++t) {
-      const float* T = smem + (t % 3) * BUF_F;
-      const f32x16 X = gemm1(T);
-      if (t + 1 < ntiles) store_tile((t + 1) % 3);
-      if (t + 2 < ntiles) load_tile(t + 2);
-      __syncthreads();
-      float coef[16];
-      epilogue(T, t, X, coef);
-      gemm2(T, coef);
-    }
-  } else if constexpr (FROM_S && TT_S_PREFETCH == 2) {
+  if constexpr (FROM_S && kSPrefetch == 2) {
     // ---- BWD_S: epilogue -> GEMM2 per tile on the stored dot products; those of tiles t+1 AND t+2 are in flight while tile
     // t is worked on (two register sets, the body instantiated for each: f32 170 -> 168 us, bf16x3 96 -> 89 us) ----
     f32x16 xa, xb;
@@ -764,16 +675,11 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       const f32x16 X = xs_t;
       float coef[16];
       epilogue(T, t, X, coef);
-#if TT_ABL_BWDS_NOSTAGE      // (timing-only ablation, results wrong: no K-tile staging and no barrier in the dc pass)
-      if (t + 2 < ntiles) load_S(t + 2, xs_t);
-      gemm2(T, coef);
-#else
       if constexpr (PREC == 0) { if (t + TPB < ntiles) load_tile(t + TPB); }
       if (t + 2 < ntiles) load_S(t + 2, xs_t);
       gemm2(T, coef);
       if (t + TPB < ntiles) store_tile((t + TPB) % NBUF);
       if ((t % TPB) == TPB - 1) __syncthreads();
-#endif
     };
     for (int t = 0; t < ntiles; t += 2) {
       tile_step(t, xa);
@@ -1193,17 +1099,11 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const f32x4* __restri
 
 // ---- host side --------------------------------------------------------------------------------
 
-#ifndef TT_SCORE_WAVES
-#define TT_SCORE_WAVES 4      // waves (32-row fragments) per workgroup of the exact-f32 passes
-#endif
-#ifndef TT_SCORE_WGS
-#define TT_SCORE_WGS 512      // workgroups a pass aims for (two 4-wave workgroups per CU)
-#endif
-#ifndef TT_BWDS_WGS
-#define TT_BWDS_WGS 512       // workgroups the BWD_S pass (dc from the stored dot products) aims for
-#endif
-int choose_nsplit_pow2(int64_t n_r, int64_t n_c, int target_wgs = TT_SCORE_WGS) {
-  const int64_t nrb = (n_r + 32 * TT_SCORE_WAVES - 1) / (32 * TT_SCORE_WAVES);
+constexpr int kScoreWaves = 4;            // waves (32-row fragments) per workgroup of the exact-f32 passes
+constexpr int kScoreWgs = 512;            // workgroups a pass aims for (two 4-wave workgroups per CU)
+constexpr int kBwdSWgs = 512;             // workgroups the BWD_S pass (dc from the stored dot products) aims for
+int choose_nsplit_pow2(int64_t n_r, int64_t n_c, int target_wgs = kScoreWgs) {
+  const int64_t nrb = (n_r + 32 * kScoreWaves - 1) / (32 * kScoreWaves);
   int ns = 1;
   // 512 workgroups = two per CU measured best at B = 8192 (256: 291 us, 512: 272 us, 1024: 283 us, 2048: 294 us per launch)
   while (nrb * ns < target_wgs && (int64_t)ns * 2 * 64 <= n_c && ns < 64) ns *= 2;
@@ -1218,7 +1118,7 @@ int choose_nsplit_pow2(int64_t n_r, int64_t n_c, int target_wgs = TT_SCORE_WGS) 
 // columns long, plus the measured price of more, shorter workgroups (1024 instead of 512 at 8192: +4 %).  The minimum over ns =
 // 1..64 is the old choice for every power-of-two shape (checked over n_r, n_c in 64 .. 262144: scratch/r04_nsplit_model.py) and e.g.
 // 15 splits (975 workgroups, two nearly full rounds) for 8200.  Any ns is valid: the columns are cut at multiples of 32.
-int choose_nsplit(int64_t n_r, int64_t n_c, int rows_per_wg = 32 * TT_SCORE_WAVES, int slots = TT_SCORE_WGS) {
+int choose_nsplit(int64_t n_r, int64_t n_c, int rows_per_wg = 32 * kScoreWaves, int slots = kScoreWgs) {
   const int64_t nrb = (n_r + rows_per_wg - 1) / rows_per_wg;
   int best = 1;
   double best_cost = 0.0;
@@ -1241,17 +1141,14 @@ struct WsLayout {
 
 WsLayout ws_layout(int64_t nq, int64_t nc, int32_t dim) {
   WsLayout w{};
-  if (dim <= 128 && std::getenv("TT_NSPLIT_POW2") == nullptr) {
+  if (dim <= 128) {
     w.ns_q = choose_nsplit(nq, nc);
     w.ns_c = choose_nsplit(nc, nq);
     w.ns_cs = choose_nsplit(nc, nq, 256, 256);     // the dc pass from the stored dot products: 8-wave workgroups, one per CU
-    // (experiment hooks: TT_NSPLIT_Q / TT_NSPLIT_CS force the split counts of pass 1 / the dc pass)
-    if (const char* e = std::getenv("TT_NSPLIT_Q")) { const int v = std::atoi(e); if (v >= 1 && v <= 64 && (int64_t)v * 64 <= nc) w.ns_q = v; }
-    if (const char* e = std::getenv("TT_NSPLIT_CS")) { const int v = std::atoi(e); if (v >= 1 && v <= 64 && (int64_t)v * 64 <= nq) w.ns_cs = v; }
   } else {                                         // (dim 256: other workgroup shapes per kernel form; not re-measured - r03's rule)
     w.ns_q = choose_nsplit_pow2(nq, nc);
     w.ns_c = choose_nsplit_pow2(nc, nq);
-    w.ns_cs = choose_nsplit_pow2(nc, nq, TT_BWDS_WGS);
+    w.ns_cs = choose_nsplit_pow2(nc, nq, kBwdSWgs);
   }
   int64_t o = 0;
   w.off_bias = o; o = align_up(o + nc * 4, 256);
@@ -1281,18 +1178,14 @@ WsLayout ws_layout(int64_t nq, int64_t nc, int32_t dim) {
 // slab stores, drain) and ~20 us around the softmax epilogue that the partner wave's MFMAs do not hide (f32-input
 // MFMA runs at the f32 vector rate; a 25 % cut of the epilogue's VALU instructions changed nothing measurable, so the
 // cost is in the GEMM1 -> epilogue -> GEMM2 dependency hand-offs rather than in VALU throughput).
-template <int D, int MODE, int PREC = 0>
 // waves per workgroup of the exact-f32 training passes at D <= 128 (r02 A/B at cfg3: the dc pass with 8 waves = 256 stationary
 // rows per workgroup, one workgroup per CU, half the tile staging per MFMA: 169.0 -> 165.8 us; pass 1 with 8: 276.8 -> 277.6)
-#ifndef TT_BWDS_WG_WAVES
-#define TT_BWDS_WG_WAVES 8
-#endif
-#ifndef TT_FUSEDS_WG_WAVES
-#define TT_FUSEDS_WG_WAVES 4
-#endif
+constexpr int kBwdSWgWaves = 8;
+constexpr int kFusedSWgWaves = 4;
+template <int D, int MODE, int PREC = 0>
 constexpr int waves_for() {
-  return (PREC == 1 && D == 128) ? 8 : (PREC == 1 ? 4 : ((MODE == MODE_BWD_S && D <= 128) ? TT_BWDS_WG_WAVES
-                                                         : ((MODE == MODE_FUSED_S && D <= 128) ? TT_FUSEDS_WG_WAVES : TT_SCORE_WAVES)));
+  return (PREC == 1 && D == 128) ? 8 : (PREC == 1 ? 4 : ((MODE == MODE_BWD_S && D <= 128) ? kBwdSWgWaves
+                                                         : ((MODE == MODE_FUSED_S && D <= 128) ? kFusedSWgWaves : kScoreWaves)));
 }     // bf16x3 at dim 128: 256-row workgroups, one per CU
 
 template <int D, int MODE, int PREC = 0>
@@ -1301,9 +1194,9 @@ int launch_score(const ScoreArgs& a_in, bool has_ids, hipStream_t stream) {
   constexpr int RPW = rows_per_wg<D, MODE, PREC, W>();
   const int64_t nrb = (a_in.n_r + RPW - 1) / RPW;
   const int64_t blocks = nrb * a_in.nsplit;
-  // bf16x3 with 8 waves: a third tile buffer (staggered wave halves) + the R_lo fragments of the 8 waves
+  // bf16x3 with 8 waves: + the R_lo fragments of the 8 waves
   const int lds_base = Geo<D, PREC>::LDS_BYTES * tiles_per_barrier<D, MODE, PREC>() +
-                  ((PREC == 1 && W == 8) ? (TT_BX3_STAGGER ? Geo<D, PREC>::BUF_F * 4 : 0) + W * Geo<D, PREC>::KS * 64 * 16 : 0) +
+                  ((PREC == 1 && W == 8) ? W * Geo<D, PREC>::KS * 64 * 16 : 0) +
                   (split_d<D, MODE, PREC>() ? W * 4096 : 0);          // + the pair's dot-product exchange
   const bool has_hn = (a_in.h_r != nullptr) || (a_in.h_c != nullptr);
   const ScoreArgs& a = a_in;
@@ -1332,13 +1225,6 @@ int dispatch_score_bx3(int32_t dim, const ScoreArgs& a, bool has_ids, hipStream_
     case 256: return launch_score<256, MODE, 1>(a, has_ids, stream);
     default: return tt::fail(TT_ERR_UNSUPPORTED, "retrieval (bf16x3): dim %d not in {128,256}", dim);
   }
-}
-
-// the recomputing bf16x3 gradient passes are reachable at dim 256 only (TT_BX3_RECOMPUTE256, the A/B of keeping the dot products)
-template <int MODE>
-int dispatch_score_bx3_256(int32_t dim, const ScoreArgs& a, bool has_ids, hipStream_t stream) {
-  if (dim != 256) return tt::fail(TT_ERR_UNSUPPORTED, "retrieval (bf16x3, recomputing form): dim %d != 256", dim);
-  return launch_score<256, MODE, 1>(a, has_ids, stream);
 }
 
 template <int MODE>
@@ -1526,18 +1412,16 @@ extern "C" int tt_retrieval_bwd_f32(const float* q, const float* c, int64_t nq, 
 }
 
 // Fused training entry: loss AND both gradients in two passes (8*B^2*D executed FLOPs instead of 10):
-//   pass 1 (R = q, K = c, MODE_FUSED): online softmax + sum_c p*c  -> lse, per-row loss, dq
-//   pass 2 (R = c, K = q, MODE_BWD)  : recompute with the final lse -> dc
+//   pass 1 (R = q, K = c, MODE_FUSED_S): online softmax + sum_c p*c  -> lse, per-row loss, dq; stores the dot products
+//   pass 2 (R = c, K = q, MODE_BWD_S)  : reads them back with the final lse -> dc
 static int retrieval_fwd_bwd(int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
                              int64_t diag_offset, float inv_temperature, const float* sample_weight,
                              const float* cand_prob, const int64_t* cand_ids, const float* hard_thr,
                              float grad_scale, void* workspace, int64_t workspace_bytes, float* lse,
                              float* per_row, float* loss, float* dq, float* dc, tt_stream_t stream_) {
   // Both precisions keep pass 1's dot products for pass 2 (the workspace includes the buffer).  bf16x3 at dim 256 recomputed them
-  // until r03 (TT_BX3_RECOMPUTE256=1 still does, for A/B): with the wave-pair kernels, B 32768: pass 1 / pass 2 = 6.10 / 5.87 ms
-  // recomputing, 6.45 / 3.51 ms keeping them (exact f32: 8.77 / 5.17 ms) - profiles/r03_score_f32_vs_bf16x3.jsonl.
-  static const bool recompute256 = [] { const char* e = getenv("TT_BX3_RECOMPUTE256"); return e != nullptr && e[0] == '1'; }();
-  const bool bx3_keep = prec == 1 && (dim == 128 || !recompute256);
+  // until r03: with the wave-pair kernels, B 32768: pass 1 / pass 2 = 6.10 / 5.87 ms recomputing, 6.45 / 3.51 ms keeping them
+  // (exact f32: 8.77 / 5.17 ms) - profiles/r03_score_f32_vs_bf16x3.jsonl.
   int rc = check_common("tt_retrieval_fwd_bwd_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, true);
   if (rc != TT_OK) return rc;
   TT_REQUIRE(lse && per_row && loss && dq && dc, "tt_retrieval_fwd_bwd_f32: null output pointer");
@@ -1572,8 +1456,7 @@ static int retrieval_fwd_bwd(int prec, const float* q, const float* c, int64_t n
     a.slab = slab;
     // (bf16x3 at dim 128 keeps the dot products too: 134 + 89 us against 123 + 124 us recomputing - with the row-major buffer
     // it had been 200 + 127 us, the blocked layout is what makes it pay.)
-    rc = prec == 1 ? (bx3_keep ? dispatch_score_bx3<MODE_FUSED_S>(dim, a, cand_ids != nullptr, stream)
-                               : dispatch_score_bx3_256<MODE_FUSED>(dim, a, cand_ids != nullptr, stream))
+    rc = prec == 1 ? dispatch_score_bx3<MODE_FUSED_S>(dim, a, cand_ids != nullptr, stream)
                    : dispatch_score<MODE_FUSED_S>(dim, a, cand_ids != nullptr, stream);
     if (rc != TT_OK) return rc;
     {
@@ -1602,12 +1485,11 @@ static int retrieval_fwd_bwd(int prec, const float* q, const float* c, int64_t n
     a.h_c = hq;
     a.id_r = cand_ids;
     a.id_c = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-    a.nsplit = (prec == 1 && !bx3_keep) ? w.ns_c : w.ns_cs;
+    a.nsplit = w.ns_cs;
     a.c_per_split = align_up((nq + a.nsplit - 1) / a.nsplit, 32);
     a.slab = slab;
     a.S = smat; a.ldS = (nq + 31) / 32;
-    rc = prec == 1 ? (bx3_keep ? dispatch_score_bx3<MODE_BWD_S>(dim, a, cand_ids != nullptr, stream)
-                                 : dispatch_score_bx3_256<MODE_BWD>(dim, a, cand_ids != nullptr, stream))
+    rc = prec == 1 ? dispatch_score_bx3<MODE_BWD_S>(dim, a, cand_ids != nullptr, stream)
                    : dispatch_score<MODE_BWD_S>(dim, a, cand_ids != nullptr, stream);
     if (rc != TT_OK) return rc;
     const int64_t n4 = nc * dim / 4;

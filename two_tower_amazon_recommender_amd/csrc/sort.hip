@@ -281,23 +281,13 @@ extern "C" int64_t tt_sparse_plan_workspace_bytes(int64_t n_ids) {
 }
 
 namespace {
-// TT_SORT_GROUPS: 0 = the single-workgroup sort for every list (A/B), k > 0 = force k partitions, unset = n / 128
-// (8192 ids -> 64 workgroups per table).  Measured, 2 tables x 8192 ids: 21-25 us single-workgroup -> 9.5-10 us (of which
-// ~9 us is the host call rate of the microbench), Zipf ids 12-15 us; in the cfg3 step (plan on the main stream) 16 / 32 /
-// 64 / 128 groups: 0.6787 / 0.6780 / 0.6766 / 0.6773 ms.
-int env_sort_groups() {
-  static const int v = [] {
-    const char* e = std::getenv("TT_SORT_GROUPS");
-    return e ? std::atoi(e) : -1;
-  }();
-  return v;
-}
-
+// Key-range partitions of a list that fits one workgroup's LDS: n / 128 of them, at most 128 (8192 ids -> 64 workgroups per
+// table).  Measured, 2 tables x 8192 ids: 21-25 us with the single-workgroup sort -> 9.5-10 us (of which ~9 us is the host call
+// rate of the microbench), Zipf ids 12-15 us; in the cfg3 step (plan on the main stream) 16 / 32 / 64 / 128 groups:
+// 0.6787 / 0.6780 / 0.6766 / 0.6773 ms.
 int part_groups(int n, int64_t num_rows) {
-  const int forced = env_sort_groups();
-  int64_t g = forced > 0 ? forced : (n + 127) / 128;
-  const int64_t cap = forced > 0 ? 256 : 128;
-  if (g > cap) g = cap;
+  int64_t g = (n + 127) / 128;
+  if (g > 128) g = 128;
   if (g > num_rows / 2) g = num_rows / 2;          // a group is at least 2 ids wide (the multiply-high division needs width >= 2)
   return g < 1 ? 1 : (int)g;
 }
@@ -353,7 +343,7 @@ extern "C" int tt_sparse_plan_batched(const tt_sparse_plan_args* tables, int32_t
       if ((rc = plan_rocprim(a, stream)) != TT_OK) return rc;
       continue;
     }
-    if (chunks == 1 && env_sort_groups() != 0) {   // one list that fits a workgroup's LDS: key-range partitions, one launch
+    if (chunks == 1) {                        // one list that fits a workgroup's LDS: key-range partitions, one launch
       tt::PartTable& t = pb.t[npb++];
       t.ids = a.ids; t.sorted_ids = a.sorted_ids; t.order = a.order; t.num_rows = a.num_rows; t.n = (int32_t)a.n_ids;
       t.groups = part_groups(t.n, a.num_rows);

@@ -78,50 +78,30 @@ __device__ __forceinline__ void update_row(f32x4* __restrict__ table, f32x4* __r
 // the producer needs no release fence.  (r02 used plain stores + fence(release, agent) = `buffer_wbl2 sc1`, which writes
 // back EVERY dirty line of the XCD's L2 - in a kernel whose whole job is to dirty L2 with table rows.  One fence per piece
 // of a multi-piece run: ~1,600 of them at 1M uniform ids, ~100x more with power-law ids; the launch went from 350 to 690 us
-// (U) and 634 to 1,992 us (Z) against r01's two-launch form - VERDICT r02.  TT_SPARSE_RELEASE_FENCE=1 rebuilds that form
-// for the A/B in profiles/r03_sparse_apply_ab.jsonl.)
-#ifndef TT_SPARSE_RELEASE_FENCE
-#define TT_SPARSE_RELEASE_FENCE 0
-#endif
+// (U) and 634 to 1,992 us (Z) against r01's two-launch form - VERDICT r02; the A/B is in profiles/r03_sparse_apply_ab.jsonl.)
 __device__ __forceinline__ void store_piece(f32x4* p, const f32x4& v) {
-#if TT_SPARSE_RELEASE_FENCE
-  *p = v;
-#else
   unsigned long long* q = reinterpret_cast<unsigned long long*>(p);
   const unsigned long long lo = ((unsigned long long)__float_as_uint(v[1]) << 32) | __float_as_uint(v[0]);
   const unsigned long long hi = ((unsigned long long)__float_as_uint(v[3]) << 32) | __float_as_uint(v[2]);
   __hip_atomic_store(q, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // global_store_dwordx2 ... sc1
   __hip_atomic_store(q + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 __device__ __forceinline__ f32x4 load_piece(const f32x4* p) {
-#if TT_SPARSE_RELEASE_FENCE
-  return *p;
-#else
   unsigned long long* q = reinterpret_cast<unsigned long long*>(const_cast<f32x4*>(p));
   const unsigned long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // global_load_dwordx2 ... sc1
   const unsigned long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return f32x4{__uint_as_float((uint32_t)lo), __uint_as_float((uint32_t)(lo >> 32)), __uint_as_float((uint32_t)hi),
                __uint_as_float((uint32_t)(hi >> 32))};
-#endif
 }
 
 // A piece of a run that spans several 64-slot blocks (rare): find the run's extent, publish, take a ticket; the last
-// arriver adds the pieces in index order and applies the update.  (TT_SPARSE_TAIL_NOINLINE=1 keeps it out of line - an
-// A/B hook: as a real call it costs the callers 32-76 bytes of scratch for the registers saved around it.)
-#ifndef TT_SPARSE_TAIL_NOINLINE
-#define TT_SPARSE_TAIL_NOINLINE 0
-#endif
-#if TT_SPARSE_TAIL_NOINLINE
-#define TT_TAIL_ATTR __attribute__((noinline))
-#else
-#define TT_TAIL_ATTR __forceinline__
-#endif
+// arriver adds the pieces in index order and applies the update.  (Inlined: as a real call it costs the callers 32-76 bytes of
+// scratch for the registers saved around it.)
 template <int OPT>
-__device__ TT_TAIL_ATTR void finish_run_piece(f32x4* __restrict__ table, f32x4* __restrict__ accum, const int64_t* __restrict__ sid,
-                                              const f32x4* P, const f32x4* S, int32_t* p_flag, const int64_t k, const int64_t e,
-                                              const int64_t pend, const int64_t id, const bool run_head, const bool continues,
-                                              const int dim4, const int lpr_log2, const int64_t n_ids, const float lr, const float eps) {
+__device__ __forceinline__ void finish_run_piece(f32x4* __restrict__ table, f32x4* __restrict__ accum, const int64_t* __restrict__ sid,
+                                                 const f32x4* P, const f32x4* S, int32_t* p_flag, const int64_t k, const int64_t e,
+                                                 const int64_t pend, const int64_t id, const bool run_head, const bool continues,
+                                                 const int dim4, const int lpr_log2, const int64_t n_ids, const float lr, const float eps) {
   const int lpr = 1 << lpr_log2;
   const int l = threadIdx.x & (lpr - 1);
   int64_t first = k;                              // first slot of the run (lower bound of id in the sorted ids)
@@ -145,9 +125,6 @@ __device__ TT_TAIL_ATTR void finish_run_piece(f32x4* __restrict__ table, f32x4* 
   const int64_t jh = first / kPiece, jl = (last - 1) / kPiece;
   const int npieces = (int)(jl - jh + 1);
   // publish: this lane group's write-through stores (all in this wave) have left the CU before the ticket is drawn
-#if TT_SPARSE_RELEASE_FENCE
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int ticket = 0;
   // (the ticket stays a RELAXED add behind the `s_waitcnt vmcnt(0)` above: the piece sums left as write-through sc1 stores and
@@ -282,23 +259,18 @@ __device__ __forceinline__ void sparse_apply_body(const ApplyArgs& a, const int 
                         a.p_flag[t], k, e, pend, id, run_head, continues, dim4, lpr_log2, n_ids, lr, eps);
 }
 
-// TT_OPT_PREFETCH=1: the fused optimizer touches every line of a row the moment the scan finds its id (optimizer_ids_kernel).
+// r03, a prefetch in the fused optimizer (optimizer_ids_kernel) that touched every line of a row the moment the scan found its id.
 // Built, measured three ways on cfg3 and left OFF: the rows do arrive earlier (apply phase 4.9 -> 3.6-3.8 us between the
 // stamps) but issuing the touches costs the scan more than that - a load instruction occupies the address path for a whole
 // wave however few lanes are active, and the per-id broadcast / address arithmetic runs on every wave: launch 12.6 us ->
 // 14.1 (per lane and line, inside the classification loop: its in-order vmcnt waits then also wait for the touches),
-// 13.7 (same, after the loop), 13.25 us (one instruction per id, 12 lanes = the row's lines); =2, one 4-byte touch of the
+// 13.7 (same, after the loop), 13.25 us (one instruction per id, 12 lanes = the row's lines); a fourth form, one 4-byte touch of the
 // table row per id to start its address translation early: 12.8-13.0 -> 13.4 us (the touch returns no sooner than the row
 // loads issued 1 us later: the rows' 4.9 us is a burst of 17 MB of random 512-byte rows draining, not a page walk).
 // profiles/r03_optimizer_ab.txt
-#ifndef TT_OPT_PREFETCH
-#define TT_OPT_PREFETCH 0
-#endif
-#ifndef TT_APPLY_WAVES
-#define TT_APPLY_WAVES 8      // min waves per SIMD of the large-list kernels (8: 64 VGPRs, 6: 80)
-#endif
+constexpr int kApplyWaves = 8;    // min waves per SIMD of the large-list kernels (8: 64 VGPRs, 6: 80)
 template <int OPT>
-__global__ __launch_bounds__(256, TT_APPLY_WAVES) void sparse_apply_kernel(ApplyArgs a, int dim4, int lpr_log2, int64_t n_ids, float lr,
+__global__ __launch_bounds__(256, kApplyWaves) void sparse_apply_kernel(ApplyArgs a, int dim4, int lpr_log2, int64_t n_ids, float lr,
                                                            float eps) {
   sparse_apply_body<OPT>(a, blockIdx.y, blockIdx.x, dim4, lpr_log2, n_ids, lr, eps);
 }
@@ -307,7 +279,7 @@ __global__ __launch_bounds__(256, TT_APPLY_WAVES) void sparse_apply_kernel(Apply
 // else dense segment y - n_tables (csrc/dense_update_body.h).  The two halves are independent and both memory-bound; as
 // two launches they cost 7.5 + 9.0 us plus a launch boundary per step.
 template <int OPT>
-__global__ __launch_bounds__(256, TT_APPLY_WAVES) void optimizer_kernel(ApplyArgs a, int n_tables, int dim4, int lpr_log2, int64_t n_ids,
+__global__ __launch_bounds__(256, kApplyWaves) void optimizer_kernel(ApplyArgs a, int n_tables, int dim4, int lpr_log2, int64_t n_ids,
                                                          int64_t sparse_blocks, tt::SegTable tbl, int dense_blocks, float lr,
                                                          float eps) {
   if ((int)blockIdx.y < n_tables) {
@@ -747,63 +719,11 @@ __global__ __launch_bounds__(1024) void optimizer_ids_kernel(ApplyArgs a, FusedT
       }
     }
     tt::PartScan<JMAX> sc;
-    // (TT_OPT_PREFETCH, off - see the top of the file: the rows' trip from HBM started at the scan.  A wave that finds an id of
-    // this workgroup's range touches every 128-byte line of that id's table (accumulator) row and of its gradient row with a
-    // 4-byte load nobody reads; inline asm, the destination is one scratch VGPR kept reserved until the apply phase has
-    // waited for its own, later loads.)
+    // `sink`: a zeroed VGPR held live to the end of the apply phase, the register of r03's prefetch touches (see the note above
+    // sparse_apply_kernel).  Nothing reads it, but without it the compiler schedules and allocates this kernel differently (8 of
+    // its 12 forms change, two with 3 more SGPR spills), so it stays until that is measured.
     uint32_t sink = 0u;
-#if TT_OPT_PREFETCH == 2
-    // form 4: ONE 4-byte touch per id, by the lane that holds it, of the first line of its TABLE (and accumulator) row only - the
-    // gradient rows are a contiguous [B, D] array, a handful of pages.  What it buys is the address translation: random rows of a
-    // multi-GB table miss the TLBs, and the page walk (several dependent memory reads) is most of the rows' 4.9 us round trip.
-    const char* pf_tab = reinterpret_cast<const char*>(a.table[ti]);
-    const char* pf_acc = reinterpret_cast<const char*>(a.accum[ti]);
-    const int row_bytes = dim4 * 16;
-    const int pf_lane = (int)(threadIdx.x & 63u);
-    auto prefetch = [&](uint64_t mask, uint32_t key, uint32_t) {
-      if ((mask >> pf_lane) & 1ull) {
-        const char* tr = pf_tab + (int64_t)key * row_bytes;
-        asm volatile("global_load_dword %0, %1, off" : "+v"(sink) : "v"(tr) : "memory");
-        if constexpr (OPT != TT_OPT_SGD) {
-          const char* ar = pf_acc + (int64_t)key * row_bytes;
-          asm volatile("global_load_dword %0, %1, off" : "+v"(sink) : "v"(ar) : "memory");
-        }
-      }
-    };
-    const uint32_t m = tt::part_scan_append<DBITS, JMAX, true>(t, g, ft.cap, smem, sc, offset, base_key, prefetch);
-#elif TT_OPT_PREFETCH
-    const char* pf_tab = reinterpret_cast<const char*>(a.table[ti]);
-    const char* pf_acc = reinterpret_cast<const char*>(a.accum[ti]);
-    const char* pf_grd = reinterpret_cast<const char*>(a.grads[ti]);
-    const int row_bytes = dim4 * 16;
-    // ONE load instruction per id of the range: its key and position are broadcast from the lane that holds them, lane 4 s + i
-    // of the wave touches line i of row s (s = 0 table, 1 gradient, 2 accumulator).  (A load instruction occupies the address
-    // path for a whole wave however few lanes are active - one instruction per lane and line, the first form of this
-    // prefetch, cost more than the rows' earlier arrival saved: launch 12.6 -> 13.7 us.)
-    const int lines = row_bytes >> 7;                                   // 128-byte lines per row (dim 128: 4)
-    const int pf_lane = (int)(threadIdx.x & 63u);
-    const int pf_div = lines > 0 ? lines : 1;
-    const int pf_seg = pf_lane / pf_div;
-    // this lane's row base + line offset, chosen once (plain selects: indexed by pf_seg the three pointers became a scratch array)
-    const char* pf_base = pf_tab;
-    if (pf_seg == 1) pf_base = pf_grd;
-    if (pf_seg == 2) pf_base = pf_acc;
-    pf_base += 128 * (pf_lane % pf_div);
-    const bool pf_by_pos = pf_seg == 1;
-    const bool pf_on = lines > 0 && pf_seg < (OPT != TT_OPT_SGD ? 3 : 2);
-    auto prefetch = [&](uint64_t mask, uint32_t key, uint32_t pos) {
-      while (mask != 0ull) {
-        const int b = __builtin_ctzll(mask);
-        mask &= mask - 1ull;
-        const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, b), p = (uint32_t)__builtin_amdgcn_readlane((int)pos, b);
-        const char* addr = pf_base + (int64_t)(pf_by_pos ? p : k) * row_bytes;
-        if (pf_on) asm volatile("global_load_dword %0, %1, off" : "+v"(sink) : "v"(addr) : "memory");
-      }
-    };
-    const uint32_t m = tt::part_scan_append<DBITS, JMAX, true>(t, g, ft.cap, smem, sc, offset, base_key, prefetch);
-#else
     const uint32_t m = tt::part_scan_append<DBITS, JMAX, true>(t, g, ft.cap, smem, sc, offset, base_key);
-#endif
     if (reset_count != nullptr && threadIdx.x == 0) *reset_count = 0u;
     if (m == 0u) return;
     const uint32_t* K = tt::part_keys(smem);
@@ -833,7 +753,7 @@ __global__ __launch_bounds__(1024) void optimizer_ids_kernel(ApplyArgs a, FusedT
       apply_from_lds<OPT, DBITS, false, false>(a, ti, K, P, nullptr, m, offset, base_key, dim4, lpr_log2, lr, eps, &s_multi, none, 0u);
     }
     SSTAMP(6);
-    asm volatile("" :: "v"(sink));                 // (the scratch VGPR of the prefetch loads stays reserved to here)
+    asm volatile("" :: "v"(sink));                 // (sink stays reserved to here)
   } else {
     const int d = (int)blockIdx.x;
     int si = 0;

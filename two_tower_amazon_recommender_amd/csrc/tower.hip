@@ -15,7 +15,6 @@
 // tt_dense_fwd_batched_f32 called twice (tests/test_gpu_parity.py::test_fused_tower_forward_is_bit_identical_to_two_layers).
 // The embedding lookup (a1) is fused into the input tile exactly as there (tt_dense_lookup).
 #include "common.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -63,7 +62,7 @@ __device__ unsigned long long g_tstamps[1024 * 8];
 // floats, one ds_read_b128 per 4 MFMAs.  B (the weights) is NOT shared inside a workgroup - wave w owns output columns
 // [w*H/4, (w+1)*H/4) of layer 0 and [w*N1/4, ...) of layer 1 - so every wave stages ITS OWN weight sub-tiles, 1024 floats
 // each ([16 k][64 cols] for layer 0 at H = 256, [32 k][32 cols] for layer 1 at N1 = 128): four 16-byte global loads per lane
-// (whole 128- / 256-byte row segments), a register ring TT_TOWER_PF tiles deep, a private double buffer in LDS, fragments
+// (whole 128- / 256-byte row segments), a register ring kTowerPf tiles deep, a private double buffer in LDS, fragments
 // read back with ds_read_b32.  A wave's LDS operations execute in order, so write -> read of its private buffer needs no
 // workgroup barrier: two barriers per workgroup in front of the MFMA loops (input tile ready, hidden tile ready) and two
 // around the output tile's trip through LDS.
@@ -74,9 +73,7 @@ __device__ unsigned long long g_tstamps[1024 * 8];
 //     2 or 4 workgroups per CU - 32 B/clk/CU of 4-byte requests is what the vector memory pipe delivers;
 //   this form (private per-wave LDS buffer + register ring, 16-byte output stores from LDS, ids first): 29.6 us - the steps in
 //     between and the stamps are in profiles/r03_tower_forms.txt.
-#ifndef TT_TOWER_PF
-#define TT_TOWER_PF 2             // weight sub-tiles of loads in flight per wave (register ring)
-#endif
+constexpr int kTowerPf = 2;       // weight sub-tiles of loads in flight per wave (register ring)
 constexpr int WT_F = 1024;        // floats per weight sub-tile of a wave
 template <int HB, int NB, bool DROP>
 __global__ __launch_bounds__(256, 2) void tower_fwd2_kernel(Tower2Batch pb) {
@@ -87,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void tower_fwd2_kernel(Tower2Batch pb) {
   constexpr int KT1 = WT_F / C1, KT2 = WT_F / C2;            // k rows per sub-tile (H = 256: 16; N1 = 128: 32)
   constexpr int L1 = C1 + 4, L2 = C2 + 4;                    // sub-tile row strides in LDS
   constexpr int WB_F = (KT1 * L1 > KT2 * L2) ? KT1 * L1 : KT2 * L2;   // floats per private buffer
-  constexpr int PF = TT_TOWER_PF;
+  constexpr int PF = kTowerPf;
   const int K0 = pb.K0;
   const int LX = K0 + 4;                                     // input tile [32][K0]: row stride
   float* XH = smem;                                          // hidden tile [32][H + 4] (later: the output tile on its way out)
@@ -458,11 +455,7 @@ extern "C" int tt_tower_fwd2_batched_f32(const tt_dense_fwd_args* layer0, const 
   const int c1 = h / 4, c2 = n1 / 4;
   const int wb1 = (1024 / c1) * (c1 + 4), wb2 = (1024 / c2) * (c2 + 4);
   // hidden tile + input tile + one private weight buffer per wave (cfg3: 33.3 + 16.9 + 18.4 = 68.6 KB: two workgroups per CU)
-  int lds = (RB * (h + 4) + RB * (k0 + 4) + 4 * (wb1 > wb2 ? wb1 : wb2)) * 4;
-  if (const char* e = std::getenv("TT_TOWER_LDS_KB")) {        // experiment: a larger request caps the workgroups per CU
-    const int want = std::atoi(e) * 1024;
-    if (want > lds && want <= 160 * 1024) lds = want;
-  }
+  const int lds = (RB * (h + 4) + RB * (k0 + 4) + 4 * (wb1 > wb2 ? wb1 : wb2)) * 4;
   hipStream_t stream = tt::as_stream(stream_);
   const unsigned blocks = (unsigned)(pb.blocks_per_prob * n_probs);
   auto go = [&](auto kern) -> int {

@@ -434,10 +434,7 @@ def dense_fwd2(xs, ws, bs, ys, relu: bool, dropout=None, lookups=None, relu_bits
 
 
 def tower_fwd2_supported(m: int, k0: int, h: int, n1: int) -> bool:
-    """Shapes the fused two-layer tower forward takes (csrc/tower.hip).  TT_FUSED_TOWER=0 switches it off (A/B)."""
-    import os
-    if os.environ.get("TT_FUSED_TOWER", "1") == "0":
-        return False
+    """Shapes the fused two-layer tower forward takes (csrc/tower.hip)."""
     return bool(_lib.load().tt_tower_fwd2_supported(m, k0, h, n1))
 
 
