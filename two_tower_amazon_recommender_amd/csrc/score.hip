@@ -239,46 +239,70 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   if constexpr (HAS_IDS) idr = r_ok ? p.id_r[r] : (int64_t)-1;
   const int64_t cpos = p.pos_idx != nullptr ? (r_ok ? p.pos_idx[r] : (int64_t)-1) : r + p.diag;   // positive column
 
-  // ---- staging (global -> regs -> LDS, one tile ahead).  Thread `tid` moves float4 number
-  // tid + 256*j of the tile (row = f / ROW4, col4 = f % ROW4): 32-bit offsets from one running pointer.
+  // ---- staging (global -> regs -> LDS, TPB tiles ahead).  Thread `tid` moves float4 number
+  // tid + THREADS*j of the tile (row = f / ROW4, col4 = f % ROW4).
+  // Every load of the tile loop is UNCONDITIONAL, from a clamped (valid) address, and what a lane must not see is replaced by a
+  // select where the registers are consumed (store_tile, mask_S).  Written as `x = ok ? p[i] : 0`, each load sat in an exec-mask
+  // region of its own, and with one load of the loop under a condition - a lane mask or a uniform `if` alike - the compiler cannot
+  // count the loads YOUNGER than the one it waits for: every wait of the loop was `s_waitcnt vmcnt(0)`, which also drains the
+  // prefetches just issued (tests/isa_audit/audit_score_loads.py).  So the callers clamp the tile index
+  // (past the end a wave reads its last tile again, an L1 / L2 hit nobody consumes) and skip only the store_tile / the use.
   f32x4 st[NV];
   float st_a = 0.f, st_s = 0.f, st_h = -3.0e38f;
   constexpr bool hn = HAS_HN;                                        // hard-negative mining compiled in
   const float hr = (HAS_HN && p.h_r != nullptr && r_ok) ? p.h_r[r] : -3.0e38f;
-  const float* hcp = (HAS_HN && p.h_c != nullptr) ? p.h_c + c_begin + tid : nullptr;
   int64_t st_id = -2;
   constexpr int RPJ = THREADS / ROW4 > 0 ? THREADS / ROW4 : 1;   // tile rows between a thread's consecutive float4s
   const int st_row = tid / ROW4, st_col4 = tid % ROW4;
-  const f32x4* kp = reinterpret_cast<const f32x4*>(p.K) + c_begin * ROW4 + tid;   // tile 0
-  const float* acp = p.a_c != nullptr ? p.a_c + c_begin + tid : nullptr;
-  const float* scp = p.s_c != nullptr ? p.s_c + c_begin + tid : nullptr;
+  const f32x4* kp = reinterpret_cast<const f32x4*>(p.K) + c_begin * ROW4;   // tile 0
+  // the nullable per-column vectors: a null one is read from K instead (n_c * D floats, so [c_begin + 32 t + row] exists) and
+  // its value dropped in store_tile
+  const bool has_ac = p.a_c != nullptr, has_sc = p.s_c != nullptr, has_hc = HAS_HN && p.h_c != nullptr;
+  const float* acp = (has_ac ? p.a_c : p.K) + c_begin;
+  const float* scp = (has_sc ? p.s_c : p.K) + c_begin;
+  const float* hcp = (has_hc ? p.h_c : p.K) + c_begin;
   const int64_t* idp = nullptr;
-  if constexpr (HAS_IDS) idp = p.id_c + c_begin + tid;
+  if constexpr (HAS_IDS) idp = p.id_c + c_begin;
   const int ncols = (int)(c_end - c_begin);         // columns of this split (<= c_per_split)
 
+  // t: a tile that exists (0 <= t < ntiles).  Rows past the tile's last valid row read that row.
   auto load_tile = [&](int t) {
     const int nvalid = ncols - 32 * t;              // valid rows of tile t (may exceed 32)
+    const int last = (nvalid < 32 ? nvalid : 32) - 1;
     const f32x4* src = kp + (int64_t)t * (32 * ROW4);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int row = st_row + j * RPJ;
-      st[j] = (row < 32 && row < nvalid) ? src[THREADS * j] : f32x4{0.f, 0.f, 0.f, 0.f};
+      st[j] = src[(row < last ? row : last) * ROW4 + st_col4];
     }
-    if (tid < 32) {
-      const bool ok = tid < nvalid;
-      st_a = ok ? (acp != nullptr ? acp[32 * t] : 0.f) : kNegBig;
-      if constexpr (HAS_HN) st_h = (ok && hcp != nullptr) ? hcp[32 * t] : -3.0e38f;
-      st_s = ok ? (scp != nullptr ? scp[32 * t] : 1.f) : 0.f;
-      if constexpr (HAS_IDS) st_id = ok ? idp[32 * t] : (int64_t)-2;
-    }
+    const int c = 32 * t + (tid < last ? tid : last);
+    st_a = acp[c];
+    if constexpr (HAS_HN) st_h = hcp[c];
+    if constexpr (IS_BWD) st_s = scp[c];              // (the only passes whose epilogue reads s_c)
+    if constexpr (HAS_IDS) st_id = idp[c];
   };
-  auto store_tile = [&](int buf) {
+  // t: the tile the staging registers were loaded for.  Past the split's end (t >= ntiles: the registers hold the last tile
+  // again) the store is NOT skipped: buffer t % NBUF is free by then, nobody reads what lands in it, and a load that is
+  // consumed on every path is what lets the compiler drop the full waits at the top of the loop (a staging register still
+  // pending there on some path forced `s_waitcnt vmcnt(0)` in front of the first VALU write that reuses one).
+  // The same holds for the lanes: the side values are written by 32 threads only (and at dim 32 with 8 waves half the threads
+  // stage nothing), so every thread "uses" its staging registers in an empty asm statement - no instruction, but the wait for
+  // the load now stands at the store_tile on every path instead of as a vmcnt(0) wherever the register is written next.
+  constexpr bool ST_FULL = NV * THREADS == 32 * ROW4;              // every thread stages NV float4 of every tile
+  auto store_tile = [&](int t, int buf) {
     float* T = smem + buf * BUF_F;
+    const int nvalid = ncols - 32 * t;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) st[j] = (st_row + j * RPJ < nvalid) ? st[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (!ST_FULL) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) asm volatile("" : : "v"(st[j]));
+    }
     if constexpr (PREC == 0) {
       float* dst = T + st_row * LS + st_col4 * 4;
 #pragma unroll
       for (int j = 0; j < NV; ++j)
-        if (st_row + j * RPJ < 32) *reinterpret_cast<f32x4*>(dst + j * RPJ * LS) = st[j];
+        if (ST_FULL || st_row + j * RPJ < 32) *reinterpret_cast<f32x4*>(dst + j * RPJ * LS) = st[j];
     } else {
       // three bf16 images of the tile (hi / mid / lo pieces), each float4 -> 4 bf16 = one ds_write_b64 per piece
       char* img = reinterpret_cast<char*>(T);
@@ -287,7 +311,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
         const int row = st_row + j * RPJ;
-        if (row < 32) {
+        if (ST_FULL || row < 32) {
           bf16x4 q0, q1, q2;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -301,11 +325,16 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
         }
       }
     }
+    asm volatile("" : : "v"(st_a));
+    if constexpr (IS_BWD) asm volatile("" : : "v"(st_s));
+    if constexpr (HAS_HN) asm volatile("" : : "v"(st_h));
+    if constexpr (HAS_IDS) asm volatile("" : : "v"(st_id));
     if (tid < 32) {
-      T[TILE_F + tid] = st_a;
-      T[TILE_F + 32 + tid] = st_s;
-      if constexpr (HAS_HN) T[TILE_F + 128 + tid] = st_h;
-      if constexpr (HAS_IDS) reinterpret_cast<int64_t*>(T + TILE_F + 64)[tid] = st_id;
+      const bool ok = tid < nvalid;
+      T[TILE_F + tid] = ok ? (has_ac ? st_a : 0.f) : kNegBig;
+      T[TILE_F + 32 + tid] = ok ? ((IS_BWD && has_sc) ? st_s : 1.f) : 0.f;
+      if constexpr (HAS_HN) T[TILE_F + 128 + tid] = (ok && has_hc) ? st_h : -3.0e38f;
+      if constexpr (HAS_IDS) reinterpret_cast<int64_t*>(T + TILE_F + 64)[tid] = ok ? st_id : (int64_t)-2;
     }
   };
 
@@ -319,8 +348,11 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   //   consecutive candidates of one query row -> coalesced 4-byte loads.
   // (r02 alternatives, cfg3, pass 1 / pass 2 us against 287 / 174 for row-major: transposed row-major 290 / 170;
   // nontemporal stores 387 / 175 - the pieces of a line are no longer merged in L2; nontemporal loads 287 / 175.)
+  // A fragment with a valid row has its blocks (ws_layout allocates whole blocks), so its rows past n_r are stored too - pass 2
+  // masks them - and the stores sit under no lane mask; a fragment with no valid row at all has none (wave-uniform).
+  const bool frag_ok = __builtin_amdgcn_readfirstlane((int)(r0w < p.n_r)) != 0;
   auto store_S = [&](int t, const f32x16& X) {
-    if (!r_ok) return;
+    if (!frag_ok) return;
     const int64_t ctile = (c_begin >> 5) + t;
     float* blk = p.S + (ctile * p.ldS + (r0w >> 5)) * 1024 + ln * 32 + 4 * h;
 #pragma unroll
@@ -344,16 +376,23 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       for (int i = 0; i < 4; ++i) X[4 * g + i] += o[i];
     }
   };
+  // t: a tile that exists.  16 unconditional loads from a block that exists: S is allocated in whole 32 x 32 blocks, so every
+  // element of the block of a fragment with a valid row may be read; a fragment with none reads row block 0.  What the lanes and
+  // rows past the ends read is uninitialised workspace: mask_S replaces it (a select - it may be NaN) where tile t is consumed.
   auto load_S = [&](int t, f32x16& X) {
     const int64_t q0 = c_begin + 32 * (int64_t)t;
-    const int nq_left = (int)(c_end - q0);            // valid query rows of this tile (may exceed 32)
-    const float* blk = p.S + ((r0w >> 5) * p.ldS + (q0 >> 5)) * 1024 + 4 * h * 32 + ln;
+    const float* blk = p.S + ((frag_ok ? (r0w >> 5) : 0) * p.ldS + (q0 >> 5)) * 1024 + 4 * h * 32 + ln;
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const bool ok = r_ok && (tt::acc_row(reg, 0) + 4 * h) < nq_left;
-      X[reg] = ok ? blk[tt::acc_row(reg, 0) * 32] : 0.f;
-    }
+    for (int reg = 0; reg < 16; ++reg) X[reg] = blk[tt::acc_row(reg, 0) * 32];
   };
+  auto mask_S = [&](int t, const f32x16& Xin) -> f32x16 {
+    const int nq_left = ncols - 32 * t;               // valid query rows of this tile (may exceed 32)
+    f32x16 X;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) X[reg] = (r_ok && (tt::acc_row(reg, 0) + 4 * h) < nq_left) ? Xin[reg] : 0.f;
+    return X;
+  };
+  auto clamp_tile = [&](int t) { return t < ntiles ? t : ntiles - 1; };     // (callers are inside `ntiles > 0`)
 
   // ---- per-lane state ----
   float run_m = kNegBig, run_l = 0.f, pos = 0.f;
@@ -375,7 +414,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   for (int t0 = 0; t0 < TPB; ++t0)
     if (t0 < ntiles) {
       load_tile(t0);
-      store_tile(t0);
+      store_tile(t0, t0);
     }
   __syncthreads();
   // ---- GEMM1: X[c][r] = sum_d K[c][d] R[r][d] ----
@@ -472,6 +511,18 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       const int64_t dd = cpos - c0;
       dloc = (dd >= 0 && dd < 32) ? (int)dd - 4 * h : -100;
     }
+    // The positive pair's fix-ups under the wave-uniform `if (diag_tile)` are selects: an `if` per register was a tree of ~25
+    // nested exec branches per tile step.  Except the capture of the positive logit in the kernels with accidental-hit ids:
+    // there the selects cost 13-18 VGPRs (forward pass with ids 166 -> 179: 3 -> 2 waves per SIMD; bf16x3 with ids and hard
+    // negatives 44 -> 104 B of scratch); with the branches kept those kernels need fewer registers than before (156; 8 B).
+    auto take_pos = [&](bool hit, float v) {
+      if constexpr (HAS_IDS) {
+        if (hit) { pos = v; have_pos = true; }
+      } else {
+        pos = hit ? v : pos;
+        have_pos = have_pos || hit;
+      }
+    };
     bool dup[16];
     if constexpr (HAS_IDS) {
       const int64_t* idc = reinterpret_cast<const int64_t*>(T + TILE_F + 64) + 4 * h;
@@ -502,8 +553,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       }
       if (diag_tile) {
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg)
-          if (tt::acc_row(reg, 0) == dloc) { pos = t2[reg]; have_pos = true; }
+        for (int reg = 0; reg < 16; ++reg) take_pos(tt::acc_row(reg, 0) == dloc, t2[reg]);
       }
       const float m_new = fmaxf(run_m, mx);
       float sum = 0.f;
@@ -525,10 +575,12 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
           if constexpr (HAS_IDS) e = dup[reg] ? 0.f : e;
           coef[reg] = e;
         }
-        if (diag_tile) {
+        if (diag_tile) {                            // (selects: an `if` per register was a tree of exec branches)
 #pragma unroll
-          for (int reg = 0; reg < 16; ++reg)
-            if (tt::acc_row(reg, 0) == dloc) coef[reg] -= sc[reg] * sr;
+          for (int reg = 0; reg < 16; ++reg) {
+            const float d = coef[reg] - sc[reg] * sr;
+            coef[reg] = tt::acc_row(reg, 0) == dloc ? d : coef[reg];
+          }
         }
       } else {
         // FUSED (flash-style): online softmax over c; coef = exp2(t - m_row) un-normalised, the accumulators
@@ -548,8 +600,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
         }
         if (diag_tile) {
 #pragma unroll
-          for (int reg = 0; reg < 16; ++reg)
-            if (tt::acc_row(reg, 0) == dloc) { pos = coef[reg]; have_pos = true; }
+          for (int reg = 0; reg < 16; ++reg) take_pos(tt::acc_row(reg, 0) == dloc, coef[reg]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         if (__any(mx - run_m > kRescaleThr)) {
@@ -667,23 +718,31 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
     f32x16 xa, xb;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { xa[i] = 0.f; xb[i] = 0.f; }
-    if (ntiles > 0) load_S(0, xa);
-    if (ntiles > 1) load_S(1, xb);
+    // Order of issue in a step = order of need: the staged tile (waited for at this step's store_tile, behind GEMM2), then the
+    // dot products of tile t+2 (consumed two steps on) - so the wait in front of the ds_write leaves those 16 loads in flight.
     auto tile_step = [&](int t, f32x16& xs_t) {
-      if constexpr (PREC == 1) { if (t + 1 < ntiles) load_tile(t + 1); }
+      if constexpr (PREC == 1) load_tile(clamp_tile(t + 1));
       const float* T = smem + (t % NBUF) * BUF_F;
-      const f32x16 X = xs_t;
+      const f32x16 X = mask_S(t, xs_t);
       float coef[16];
       epilogue(T, t, X, coef);
-      if constexpr (PREC == 0) { if (t + TPB < ntiles) load_tile(t + TPB); }
-      if (t + 2 < ntiles) load_S(t + 2, xs_t);
+      if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB));
+      load_S(clamp_tile(t + 2), xs_t);
       gemm2(T, coef);
-      if (t + TPB < ntiles) store_tile((t + TPB) % NBUF);
+      store_tile(t + TPB, (t + TPB) % NBUF);
       if ((t % TPB) == TPB - 1) __syncthreads();
     };
-    for (int t = 0; t < ntiles; t += 2) {
-      tile_step(t, xa);
-      if (t + 1 < ntiles) tile_step(t + 1, xb);
+    if (ntiles > 0) {                                  // (an empty split issues nothing at all)
+      load_S(0, xa);
+      load_S(clamp_tile(1), xb);
+      // whole pairs in the loop, an odd last tile behind it: with the second step of a pair under an `if`, the compiler has to
+      // allow for a path on which its loads were never issued, and the wait for tile t at the top of the loop drains tile t+1 too
+      int t = 0;
+      for (; t + 1 < ntiles; t += 2) {
+        tile_step(t, xa);
+        tile_step(t + 1, xb);
+      }
+      if (t < ntiles) tile_step(t, xa);
     }
   } else {
     // ---- every wave runs GEMM1 -> epilogue -> GEMM2 per tile; 2 LDS buffers, one barrier per tile ----
@@ -710,20 +769,20 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
     if constexpr (FROM_S) { if (ntiles > 0) load_S(0, xs); }
 #if TT_LOOP_LAMBDA
     auto tile_step = [&](int t) {
-      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) { if (t + 1 < ntiles) load_tile(t + 1); }
+      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) load_tile(clamp_tile(t + 1));
       const float* T = smem + (t % NBUF) * BUF_F;
       f32x16 X;
-      if constexpr (FROM_S) X = xs; else X = gemm1(T);
+      if constexpr (FROM_S) X = mask_S(t, xs); else X = gemm1(T);
       if constexpr (SPLIT) exchange(X);
       if constexpr (TO_S) store_S(t, X);
       float coef[16];
       epilogue(T, t, X, coef);
       if constexpr (IS_BWD || IS_FUSED) {
-        if constexpr (PREC == 0) { if (t + TPB < ntiles) load_tile(t + TPB); }
-        if constexpr (FROM_S) { if (t + 1 < ntiles) load_S(t + 1, xs); }
+        if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB));
+        if constexpr (FROM_S) load_S(clamp_tile(t + 1), xs);
         gemm2(T, coef);
       }
-      if (t + TPB < ntiles) store_tile((t + TPB) % NBUF);
+      store_tile(t + TPB, (t + TPB) % NBUF);
       if ((t % TPB) == TPB - 1) __syncthreads();
     };
     for (int t = 0; t < ntiles; t += 2) {
@@ -735,20 +794,20 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       // FWD/RANK: prefetch the next tile at the top.  BWD/FUSED: registers are tight (rf + G + X + coef), so the
       // prefetch is issued just before GEMM2, whose 16*NB MFMAs (>= 1.7 us at D=128) cover its latency.
       // bf16x3: a tile is ~1 us of MFMAs, less than a global round trip under load: the prefetch goes to the top too
-      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) { if (t + 1 < ntiles) load_tile(t + 1); }
+      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) load_tile(clamp_tile(t + 1));
       const float* T = smem + (t % NBUF) * BUF_F;
       f32x16 X;
-      if constexpr (FROM_S) X = xs; else X = gemm1(T);
+      if constexpr (FROM_S) X = mask_S(t, xs); else X = gemm1(T);
       if constexpr (SPLIT) exchange(X);
       if constexpr (TO_S) store_S(t, X);
       float coef[16];
       epilogue(T, t, X, coef);
       if constexpr (IS_BWD || IS_FUSED) {
-        if constexpr (PREC == 0) { if (t + TPB < ntiles) load_tile(t + TPB); }
-        if constexpr (FROM_S) { if (t + 1 < ntiles) load_S(t + 1, xs); }     // next tile's dot products, under GEMM2
+        if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB));
+        if constexpr (FROM_S) load_S(clamp_tile(t + 1), xs);                 // next tile's dot products, under GEMM2
         gemm2(T, coef);
       }
-      if (t + TPB < ntiles) store_tile((t + TPB) % NBUF);
+      store_tile(t + TPB, (t + TPB) % NBUF);
       if ((t % TPB) == TPB - 1) __syncthreads();       // (uniform) tiles of the next group are complete, this group's buffers free
     }
 #endif
