@@ -40,7 +40,13 @@ constexpr float kNegBig = -1.0e30f;   // log2-domain stand-in for -inf (tfrs use
 
 // MODE_FUSED_S: MODE_FUSED that also writes the raw dot products X[q][c] to ScoreArgs::S; MODE_BWD_S: MODE_BWD that reads
 // them back instead of recomputing GEMM1 (the training entry's pass 2: half the matrix-pipe work)
-enum { MODE_FWD = 0, MODE_BWD = 1, MODE_FUSED = 2, MODE_RANK = 3, MODE_FUSED_S = 4, MODE_BWD_S = 5 };
+enum { MODE_FWD = 0, MODE_BWD = 1, MODE_FUSED = 2, MODE_RANK = 3, MODE_FUSED_S = 4, MODE_BWD_S = 5,
+       // The plain train step's pair (no sampling probability, ids or hard negatives), chosen on the host in launch_score:
+       // MODE_FUSED_S_NC = MODE_FUSED_S without a column bias (a_c == nullptr), MODE_BWD_S_NR = MODE_BWD_S without a row bias or row
+       // scale (a_r == s_r == nullptr; a_c and s_c given).  Same passes, same arithmetic on every live value; see FAST in score_kernel.
+       MODE_FUSED_S_NC = 6, MODE_BWD_S_NR = 7 };
+constexpr int base_mode(int m) { return m == MODE_FUSED_S_NC ? (int)MODE_FUSED_S : (m == MODE_BWD_S_NR ? (int)MODE_BWD_S : m); }
+template <bool B> struct BoolC { static constexpr bool value = B; };     // compile-time flag of a generic lambda
 constexpr float kRescaleThr = 8.0f;   // FUSED: rescale the accumulators only when a row max grows by > 2^8 (p stays <= 256)
 
 struct ScoreArgs {
@@ -142,8 +148,25 @@ constexpr int rf_lds_groups() {
 template <int D, int MODE, int PREC, int WAVES>
 constexpr int rows_per_wg() { return (split_d<D, MODE, PREC>() ? WAVES / 2 : WAVES) * 32; }
 
-template <int D, int MODE, bool HAS_IDS, bool HAS_HN, int WAVES, int PREC>
-__global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE == MODE_BWD_S && PREC == 0) ? kBwdSWaves : 2) : 1))) void score_kernel(ScoreArgs p) {   // (min waves per SIMD)
+template <int D, int MODE_T, bool HAS_IDS, bool HAS_HN, int WAVES, int PREC>
+__global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mode(MODE_T) == MODE_BWD_S && PREC == 0) ? kBwdSWaves : 2) : 1))) void score_kernel(ScoreArgs p) {   // (min waves per SIMD)
+  // FAST: the two instantiations of the plain train step.  What they leave out is work on values the step's arguments make dead:
+  //  * MODE_BWD_S_NR: `+ a_r` (a zero) and `* s_r` (a one) on every element; a_c / s_c are given, so their staging has no selects.
+  //  * MODE_FUSED_S_NC: the column bias altogether - no staging load, no LDS write, no LDS read; X * c1 instead of fma(X, c1, 0).
+  //  * both: the tile loop is cut in two.  The MAIN loop runs the tiles whose own 32 streamed rows AND those of the tiles it
+  //    prefetches are all valid: no row clamps on the loads, no zeroing selects in store_tile, no mask_S, no tile-index clamp.  The
+  //    TAIL loop (the last 2-4 tiles of the split, the possibly ragged one among them) is the general step with all of these.
+  //    Which lanes need masking for what is stored: a lane whose stationary row r >= n_r feeds only column r of the gradient
+  //    block (the coefficient is the B operand: MFMA output column j depends on B column j alone), and that column is dropped at
+  //    the slab store - no mask needed.  Only an invalid STREAMED row (a register of X, a row of the LDS tile) is summed into
+  //    valid outputs, and invalid streamed rows exist in a split's last tile only.
+  constexpr int MODE = base_mode(MODE_T);
+  constexpr bool FAST = MODE_T != MODE;
+  static_assert(!FAST || (PREC == 0 && !HAS_IDS && !HAS_HN), "the fast forms: exact f32, no ids, no hard negatives");
+  constexpr BoolC<false> GEN{};                            // the general form of a step: every clamp and select
+  constexpr BoolC<true> FULL_TILE{};
+  constexpr bool NO_AC = FAST && MODE == MODE_FUSED_S;      // no column bias: nothing staged for it
+  constexpr bool NO_ROW = FAST && MODE == MODE_BWD_S;       // no row bias / scale; column bias and scale are non-null
   constexpr bool IS_FUSED = MODE == MODE_FUSED || MODE == MODE_FUSED_S;     // online softmax + dq
   constexpr bool IS_BWD = MODE == MODE_BWD || MODE == MODE_BWD_S;            // gradient pass with given row statistics
   constexpr bool FROM_S = MODE == MODE_BWD_S, TO_S = MODE == MODE_FUSED_S;
@@ -161,7 +184,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = tid >> 6;
+  // (FAST: the wave index as a scalar, so that the fragment's first row, the positive-tile test and the block addresses of the
+  // stored dot products are SALU work; the general kernels keep the vector copy they were tuned with)
+  const int wave = FAST ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int h = lane >> 5;
   const int ln = lane & 31;
 
@@ -180,6 +205,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   int64_t c_end = c_begin + p.c_per_split;
   if (c_end > p.n_c) c_end = p.n_c;
   const int ntiles = __builtin_amdgcn_readfirstlane(c_end > c_begin ? (int)((c_end - c_begin + 31) >> 5) : 0);
+  const int nfull = __builtin_amdgcn_readfirstlane(c_end > c_begin ? (int)((c_end - c_begin) >> 5) : 0);   // tiles of 32 valid rows (FAST)
 
   // ---- stationary fragment (B operand of GEMM1), in registers for the whole launch ----
   //   f32:     rf[g][s]     = R[r][8g + 4h + s]
@@ -233,8 +259,8 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       else rp[2][ks] = lo8;
     }
   }
-  const float ar = ((IS_BWD || MODE == MODE_RANK) && p.a_r != nullptr && r_ok) ? p.a_r[r] : 0.f;
-  const float sr = (IS_BWD && p.s_r != nullptr && r_ok) ? p.s_r[r] : 1.f;
+  const float ar = (!NO_ROW && (IS_BWD || MODE == MODE_RANK) && p.a_r != nullptr && r_ok) ? p.a_r[r] : 0.f;
+  const float sr = (!NO_ROW && IS_BWD && p.s_r != nullptr && r_ok) ? p.s_r[r] : 1.f;
   int64_t idr = 0;
   if constexpr (HAS_IDS) idr = r_ok ? p.id_r[r] : (int64_t)-1;
   const int64_t cpos = p.pos_idx != nullptr ? (r_ok ? p.pos_idx[r] : (int64_t)-1) : r + p.diag;   // positive column
@@ -265,18 +291,32 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   if constexpr (HAS_IDS) idp = p.id_c + c_begin;
   const int ncols = (int)(c_end - c_begin);         // columns of this split (<= c_per_split)
 
+  constexpr bool ST_FULL = NV * THREADS == 32 * ROW4;              // every thread stages NV float4 of every tile
   // t: a tile that exists (0 <= t < ntiles).  Rows past the tile's last valid row read that row.
-  auto load_tile = [&](int t) {
+  // full (FAST kernels' main loop): tile t has 32 valid rows - `last` is the constant 31, the clamps are loop-invariant.
+  auto load_tile = [&](int t, auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    const f32x4* src = kp + (int64_t)t * (32 * ROW4);
+    if constexpr (FULL) {
+      // a wave-uniform base per tile and per j (SALU) + one loop-invariant unsigned 32-bit offset per thread: no VALU per tile
+      static_assert(ST_FULL || NV == 1, "threads past row 31 exist only where a thread stages one float4");
+      const unsigned off0 = (unsigned)((ST_FULL ? st_row : (st_row < 31 ? st_row : 31)) * ROW4 + st_col4);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) st[j] = (src + (ST_FULL ? j * RPJ * ROW4 : 0))[off0];
+      const unsigned c31 = (unsigned)(tid < 31 ? tid : 31);
+      if constexpr (!NO_AC) st_a = (acp + 32 * (int64_t)t)[c31];
+      if constexpr (IS_BWD) st_s = (scp + 32 * (int64_t)t)[c31];
+      return;
+    }
     const int nvalid = ncols - 32 * t;              // valid rows of tile t (may exceed 32)
     const int last = (nvalid < 32 ? nvalid : 32) - 1;
-    const f32x4* src = kp + (int64_t)t * (32 * ROW4);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int row = st_row + j * RPJ;
       st[j] = src[(row < last ? row : last) * ROW4 + st_col4];
     }
     const int c = 32 * t + (tid < last ? tid : last);
-    st_a = acp[c];
+    if constexpr (!NO_AC) st_a = acp[c];
     if constexpr (HAS_HN) st_h = hcp[c];
     if constexpr (IS_BWD) st_s = scp[c];              // (the only passes whose epilogue reads s_c)
     if constexpr (HAS_IDS) st_id = idp[c];
@@ -288,12 +328,15 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   // The same holds for the lanes: the side values are written by 32 threads only (and at dim 32 with 8 waves half the threads
   // stage nothing), so every thread "uses" its staging registers in an empty asm statement - no instruction, but the wait for
   // the load now stands at the store_tile on every path instead of as a vmcnt(0) wherever the register is written next.
-  constexpr bool ST_FULL = NV * THREADS == 32 * ROW4;              // every thread stages NV float4 of every tile
-  auto store_tile = [&](int t, int buf) {
+  // full: the staging registers hold a tile of 32 valid rows - nothing to zero (threads past row 31 store nothing, as ever).
+  auto store_tile = [&](int t, int buf, auto full) {
+    constexpr bool FULL = decltype(full)::value;
     float* T = smem + buf * BUF_F;
     const int nvalid = ncols - 32 * t;
+    if constexpr (!FULL) {
 #pragma unroll
-    for (int j = 0; j < NV; ++j) st[j] = (st_row + j * RPJ < nvalid) ? st[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < NV; ++j) st[j] = (st_row + j * RPJ < nvalid) ? st[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     if constexpr (!ST_FULL) {
 #pragma unroll
       for (int j = 0; j < NV; ++j) asm volatile("" : : "v"(st[j]));
@@ -325,6 +368,18 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
         }
       }
     }
+    if constexpr (NO_AC) {
+      return;                                          // no side values at all: the epilogue derives the bias (0 / -big) from t
+    } else if constexpr (NO_ROW) {
+      asm volatile("" : : "v"(st_a));
+      asm volatile("" : : "v"(st_s));
+      if (tid < 32) {                                  // a_c and s_c are given (launch_score checks)
+        const bool ok = FULL || tid < nvalid;
+        T[TILE_F + tid] = ok ? st_a : kNegBig;
+        T[TILE_F + 32 + tid] = ok ? st_s : 0.f;
+      }
+      return;
+    }
     asm volatile("" : : "v"(st_a));
     if constexpr (IS_BWD) asm volatile("" : : "v"(st_s));
     if constexpr (HAS_HN) asm volatile("" : : "v"(st_h));
@@ -354,6 +409,13 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   auto store_S = [&](int t, const f32x16& X) {
     if (!frag_ok) return;
     const int64_t ctile = (c_begin >> 5) + t;
+    if constexpr (FAST) {                              // wave-uniform block address + a loop-invariant 32-bit lane offset
+      float* blk_u = p.S + (ctile * p.ldS + (r0w >> 5)) * 1024;
+      const unsigned lo = (unsigned)(ln * 32 + 4 * h);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(blk_u + (lo + 8u * g)) = f32x4{X[4 * g], X[4 * g + 1], X[4 * g + 2], X[4 * g + 3]};
+      return;
+    }
     float* blk = p.S + (ctile * p.ldS + (r0w >> 5)) * 1024 + ln * 32 + 4 * h;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -381,6 +443,13 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   // rows past the ends read is uninitialised workspace: mask_S replaces it (a select - it may be NaN) where tile t is consumed.
   auto load_S = [&](int t, f32x16& X) {
     const int64_t q0 = c_begin + 32 * (int64_t)t;
+    if constexpr (FAST) {                              // wave-uniform block address + a loop-invariant 32-bit lane offset
+      const float* blk_u = p.S + ((frag_ok ? (r0w >> 5) : 0) * p.ldS + (q0 >> 5)) * 1024;
+      const unsigned lo = (unsigned)(4 * h * 32 + ln);
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) X[reg] = blk_u[lo + (unsigned)(tt::acc_row(reg, 0) * 32)];
+      return;
+    }
     const float* blk = p.S + ((frag_ok ? (r0w >> 5) : 0) * p.ldS + (q0 >> 5)) * 1024 + 4 * h * 32 + ln;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) X[reg] = blk[tt::acc_row(reg, 0) * 32];
@@ -413,8 +482,8 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
 #pragma unroll
   for (int t0 = 0; t0 < TPB; ++t0)
     if (t0 < ntiles) {
-      load_tile(t0);
-      store_tile(t0, t0);
+      load_tile(t0, GEN);
+      store_tile(t0, t0, GEN);
     }
   __syncthreads();
   // ---- GEMM1: X[c][r] = sum_d K[c][d] R[r][d] ----
@@ -473,15 +542,20 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
   };
 
   // ---- per-tile softmax math on the accumulator: statistics (FWD/RANK/FUSED) and the GEMM2 coefficients (BWD/FUSED) ----
-  auto epilogue = [&](const float* T, int t, const f32x16& X, float (&coef)[16]) {
+  auto epilogue = [&](const float* T, int t, const f32x16& X, float (&coef)[16], auto full) {
+    constexpr bool FULL = decltype(full)::value;
     const int64_t c0 = c_begin + 32 * (int64_t)t;
     // ---- per-column terms of this lane's 16 accumulator rows: c = c0 + 8*q + 4*h + i ----
     float ac[16], sc[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4 va = *reinterpret_cast<const f32x4*>(T + TILE_F + 8 * q + 4 * h);
+      if constexpr (NO_AC) {
+        // nothing staged: the bias store_tile would have staged for a null a_c - 0, or -big past the end - is applied below
+      } else {
+        const f32x4 va = *reinterpret_cast<const f32x4*>(T + TILE_F + 8 * q + 4 * h);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) ac[4 * q + i] = va[i];
+        for (int i = 0; i < 4; ++i) ac[4 * q + i] = va[i];
+      }
       if constexpr (IS_BWD) {
         const f32x4 vs = *reinterpret_cast<const f32x4*>(T + TILE_F + 32 + 8 * q + 4 * h);
 #pragma unroll
@@ -565,10 +639,10 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       if constexpr (IS_BWD) {
         float tvs[16];
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) tvs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]) + ar;
+        for (int reg = 0; reg < 16; ++reg) tvs[reg] = NO_ROW ? __builtin_fmaf(X[reg], p.c1, ac[reg]) : __builtin_fmaf(X[reg], p.c1, ac[reg]) + ar;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-          const float w = sc[reg] * sr;
+          const float w = NO_ROW ? sc[reg] : sc[reg] * sr;
           float tv = tvs[reg];
           if constexpr (hn) tv = (tv < hth[reg] && tt::acc_row(reg, 0) != dloc) ? kNegBig : tv;
           float e = __builtin_amdgcn_exp2f(tv) * w;
@@ -578,7 +652,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
         if (diag_tile) {                            // (selects: an `if` per register was a tree of exec branches)
 #pragma unroll
           for (int reg = 0; reg < 16; ++reg) {
-            const float d = coef[reg] - sc[reg] * sr;
+            const float d = coef[reg] - (NO_ROW ? sc[reg] : sc[reg] * sr);
             coef[reg] = tt::acc_row(reg, 0) == dloc ? d : coef[reg];
           }
         }
@@ -589,7 +663,14 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
         float mx = kNegBig;
         float vs[16];
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) vs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]);
+        for (int reg = 0; reg < 16; ++reg) {
+          if constexpr (NO_AC) {                      // fma(X, c1, 0) = X * c1; a row past the end: fma(X, c1, -big), as staged before
+            const float v0 = X[reg] * p.c1;
+            vs[reg] = (FULL || tt::acc_row(reg, 0) + 4 * h < ncols - 32 * t) ? v0 : __builtin_fmaf(X[reg], p.c1, kNegBig);
+          } else {
+            vs[reg] = __builtin_fmaf(X[reg], p.c1, ac[reg]);
+          }
+        }
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           float v = vs[reg];
@@ -721,15 +802,27 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
     // Order of issue in a step = order of need: the staged tile (waited for at this step's store_tile, behind GEMM2), then the
     // dot products of tile t+2 (consumed two steps on) - so the wait in front of the ds_write leaves those 16 loads in flight.
     auto tile_step = [&](int t, f32x16& xs_t) {
-      if constexpr (PREC == 1) load_tile(clamp_tile(t + 1));
+      if constexpr (PREC == 1) load_tile(clamp_tile(t + 1), GEN);
       const float* T = smem + (t % NBUF) * BUF_F;
       const f32x16 X = mask_S(t, xs_t);
       float coef[16];
-      epilogue(T, t, X, coef);
-      if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB));
+      epilogue(T, t, X, coef, GEN);
+      if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB), GEN);
       load_S(clamp_tile(t + 2), xs_t);
       gemm2(T, coef);
-      store_tile(t + TPB, (t + TPB) % NBUF);
+      store_tile(t + TPB, (t + TPB) % NBUF, GEN);
+      if ((t % TPB) == TPB - 1) __syncthreads();
+    };
+    // FAST: tiles t, t + TPB and t + 2 exist and are full (t + 2 < nfull) - the dot products are used as loaded, the loads and
+    // the LDS store of tile t + TPB take no clamp and no select
+    auto full_step = [&](int t, f32x16& xs_t) {
+      const float* T = smem + (t % NBUF) * BUF_F;
+      float coef[16];
+      epilogue(T, t, xs_t, coef, FULL_TILE);
+      load_tile(t + TPB, FULL_TILE);
+      load_S(t + 2, xs_t);
+      gemm2(T, coef);
+      store_tile(t + TPB, (t + TPB) % NBUF, FULL_TILE);
       if ((t % TPB) == TPB - 1) __syncthreads();
     };
     if (ntiles > 0) {                                  // (an empty split issues nothing at all)
@@ -738,6 +831,14 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
       // whole pairs in the loop, an odd last tile behind it: with the second step of a pair under an `if`, the compiler has to
       // allow for a path on which its loads were never issued, and the wait for tile t at the top of the loop drains tile t+1 too
       int t = 0;
+      if constexpr (FAST) {                            // whole pairs of steps whose tiles and prefetches are full tiles
+        static_assert(TPB <= 2, "full_step prefetches at most two tiles ahead");
+        const int nfast = (nfull > 2 ? nfull - 2 : 0) & ~1;
+        for (; t < nfast; t += 2) {
+          full_step(t, xa);
+          full_step(t + 1, xb);
+        }
+      }
       for (; t + 1 < ntiles; t += 2) {
         tile_step(t, xa);
         tile_step(t + 1, xb);
@@ -767,47 +868,65 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((MODE ==
 #pragma unroll
     for (int i = 0; i < 16; ++i) xs[i] = 0.f;
     if constexpr (FROM_S) { if (ntiles > 0) load_S(0, xs); }
+    int t_first = 0;                                   // first tile of the general loop below
+    if constexpr (FAST) {
+      // MODE_FUSED_S_NC's main loop: tile t and the tile t + TPB it prefetches are full tiles (t + TPB < nfull)
+      static_assert(!FROM_S && !SPLIT, "the fast form of pass 1");
+      const int nfast = nfull > TPB ? nfull - TPB : 0;
+      for (int t = 0; t < nfast; ++t) {
+        const float* T = smem + (t % NBUF) * BUF_F;
+        const f32x16 X = gemm1(T);
+        store_S(t, X);
+        float coef[16];
+        epilogue(T, t, X, coef, FULL_TILE);
+        load_tile(t + TPB, FULL_TILE);
+        gemm2(T, coef);
+        store_tile(t + TPB, (t + TPB) % NBUF, FULL_TILE);
+        if ((t % TPB) == TPB - 1) __syncthreads();
+      }
+      t_first = nfast;
+    }
 #if TT_LOOP_LAMBDA
     auto tile_step = [&](int t) {
-      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) load_tile(clamp_tile(t + 1));
+      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) load_tile(clamp_tile(t + 1), GEN);
       const float* T = smem + (t % NBUF) * BUF_F;
       f32x16 X;
       if constexpr (FROM_S) X = mask_S(t, xs); else X = gemm1(T);
       if constexpr (SPLIT) exchange(X);
       if constexpr (TO_S) store_S(t, X);
       float coef[16];
-      epilogue(T, t, X, coef);
+      epilogue(T, t, X, coef, GEN);
       if constexpr (IS_BWD || IS_FUSED) {
-        if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB));
+        if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB), GEN);
         if constexpr (FROM_S) load_S(clamp_tile(t + 1), xs);
         gemm2(T, coef);
       }
-      store_tile(t + TPB, (t + TPB) % NBUF);
+      store_tile(t + TPB, (t + TPB) % NBUF, GEN);
       if ((t % TPB) == TPB - 1) __syncthreads();
     };
-    for (int t = 0; t < ntiles; t += 2) {
+    for (int t = t_first; t < ntiles; t += 2) {
       tile_step(t);
       if (t + 1 < ntiles) tile_step(t + 1);
     }
 #else
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = t_first; t < ntiles; ++t) {
       // FWD/RANK: prefetch the next tile at the top.  BWD/FUSED: registers are tight (rf + G + X + coef), so the
       // prefetch is issued just before GEMM2, whose 16*NB MFMAs (>= 1.7 us at D=128) cover its latency.
       // bf16x3: a tile is ~1 us of MFMAs, less than a global round trip under load: the prefetch goes to the top too
-      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) load_tile(clamp_tile(t + 1));
+      if constexpr (MODE == MODE_FWD || MODE == MODE_RANK || PREC == 1) load_tile(clamp_tile(t + 1), GEN);
       const float* T = smem + (t % NBUF) * BUF_F;
       f32x16 X;
       if constexpr (FROM_S) X = mask_S(t, xs); else X = gemm1(T);
       if constexpr (SPLIT) exchange(X);
       if constexpr (TO_S) store_S(t, X);
       float coef[16];
-      epilogue(T, t, X, coef);
+      epilogue(T, t, X, coef, GEN);
       if constexpr (IS_BWD || IS_FUSED) {
-        if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB));
+        if constexpr (PREC == 0) load_tile(clamp_tile(t + TPB), GEN);
         if constexpr (FROM_S) load_S(clamp_tile(t + 1), xs);                 // next tile's dot products, under GEMM2
         gemm2(T, coef);
       }
-      store_tile(t + TPB, (t + TPB) % NBUF);
+      store_tile(t + TPB, (t + TPB) % NBUF, GEN);
       if ((t % TPB) == TPB - 1) __syncthreads();       // (uniform) tiles of the next group are complete, this group's buffers free
     }
 #endif
@@ -1241,8 +1360,9 @@ WsLayout ws_layout(int64_t nq, int64_t nc, int32_t dim) {
 // rows per workgroup, one workgroup per CU, half the tile staging per MFMA: 169.0 -> 165.8 us; pass 1 with 8: 276.8 -> 277.6)
 constexpr int kBwdSWgWaves = 8;
 constexpr int kFusedSWgWaves = 4;
-template <int D, int MODE, int PREC = 0>
+template <int D, int MODE_T, int PREC = 0>
 constexpr int waves_for() {
+  constexpr int MODE = base_mode(MODE_T);
   return (PREC == 1 && D == 128) ? 8 : (PREC == 1 ? 4 : ((MODE == MODE_BWD_S && D <= 128) ? kBwdSWgWaves
                                                          : ((MODE == MODE_FUSED_S && D <= 128) ? kFusedSWgWaves : kScoreWaves)));
 }     // bf16x3 at dim 128: 256-row workgroups, one per CU
@@ -1270,6 +1390,22 @@ int launch_score(const ScoreArgs& a_in, bool has_ids, hipStream_t stream) {
     tt::launch(tag, kern, dim3((unsigned)blocks), dim3(W * 64), (unsigned)lds, stream, a);
     return tt::check_launch(tag);
   };
+  // the plain train step (exact f32): the instantiations without the arguments it never passes
+  if constexpr (PREC == 0 && (MODE == MODE_FUSED_S || MODE == MODE_BWD_S)) {
+    if (!has_ids && !has_hn && a.pos_idx == nullptr) {
+      if constexpr (MODE == MODE_FUSED_S) {
+        // (dim 256: the general kernel fills the register file - 512 with the accumulators - and a second loop body spilled 300 B;
+        // dim 32: a thread stages ONE float4 per tile, and without the bias that is the only load of the loop - nothing for a
+        // partial wait to keep in flight, and tests/test_isa_score_loads.py takes a loop with fewer than two loads for the wrong loop)
+        if constexpr (D == 64 || D == 128) {
+          if (a.a_c == nullptr) return go(score_kernel<D, MODE_FUSED_S_NC, false, false, W, 0>);
+        }
+      } else {
+        if (a.a_r == nullptr && a.s_r == nullptr && a.a_c != nullptr && a.s_c != nullptr)
+          return go(score_kernel<D, MODE_BWD_S_NR, false, false, W, 0>);
+      }
+    }
+  }
   if (has_ids && has_hn) return go(score_kernel<D, MODE, true, true, W, PREC>, rf_lds_groups<D, MODE, true, true, PREC>());
   if (has_ids) return go(score_kernel<D, MODE, true, false, W, PREC>, rf_lds_groups<D, MODE, true, false, PREC>());
   if (has_hn) return go(score_kernel<D, MODE, false, true, W, PREC>, rf_lds_groups<D, MODE, false, true, PREC>());
