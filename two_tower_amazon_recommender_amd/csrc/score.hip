@@ -1368,7 +1368,7 @@ constexpr int waves_for() {
 }     // bf16x3 at dim 128: 256-row workgroups, one per CU
 
 template <int D, int MODE, int PREC = 0>
-int launch_score(const ScoreArgs& a_in, bool has_ids, hipStream_t stream) {
+int launch_score(const ScoreArgs& a_in, hipStream_t stream) {
   constexpr int W = waves_for<D, MODE, PREC>();
   constexpr int RPW = rows_per_wg<D, MODE, PREC, W>();
   const int64_t nrb = (a_in.n_r + RPW - 1) / RPW;
@@ -1377,6 +1377,7 @@ int launch_score(const ScoreArgs& a_in, bool has_ids, hipStream_t stream) {
   const int lds_base = Geo<D, PREC>::LDS_BYTES * tiles_per_barrier<D, MODE, PREC>() +
                   ((PREC == 1 && W == 8) ? W * Geo<D, PREC>::KS * 64 * 16 : 0) +
                   (split_d<D, MODE, PREC>() ? W * 4096 : 0);          // + the pair's dot-product exchange
+  const bool has_ids = a_in.id_c != nullptr;       // every pass sets the id pair together (pass_args)
   const bool has_hn = (a_in.h_r != nullptr) || (a_in.h_c != nullptr);
   const ScoreArgs& a = a_in;
   auto go = [&](auto kern, int rfl_groups = 0) -> int {
@@ -1412,40 +1413,103 @@ int launch_score(const ScoreArgs& a_in, bool has_ids, hipStream_t stream) {
   return go(score_kernel<D, MODE, false, false, W, PREC>);
 }
 
-// bf16x3 passes at the dims whose tiles are whole [32][128] bf16 images
+// prec 0: exact f32 products; prec 1: bf16x3, at the dims whose tiles are whole [32][128] bf16 images.  MODE_BWD (the separate
+// backward entry) is exact f32 only: no bf16x3 form of it is instantiated.
 template <int MODE>
-int dispatch_score_bx3(int32_t dim, const ScoreArgs& a, bool has_ids, hipStream_t stream) {
-  switch (dim) {
-    case 128: return launch_score<128, MODE, 1>(a, has_ids, stream);
-    case 256: return launch_score<256, MODE, 1>(a, has_ids, stream);
-    default: return tt::fail(TT_ERR_UNSUPPORTED, "retrieval (bf16x3): dim %d not in {128,256}", dim);
+int dispatch_score(int prec, int32_t dim, const ScoreArgs& a, hipStream_t stream) {
+  if (prec == 1) {
+    if constexpr (MODE == MODE_BWD) return tt::fail(TT_ERR_UNSUPPORTED, "retrieval (bf16x3): no separate backward pass");
+    else switch (dim) {
+      case 128: return launch_score<128, MODE, 1>(a, stream);
+      case 256: return launch_score<256, MODE, 1>(a, stream);
+      default: return tt::fail(TT_ERR_UNSUPPORTED, "retrieval (bf16x3): dim %d not in {128,256}", dim);
+    }
   }
-}
-
-template <int MODE>
-int dispatch_score(int32_t dim, const ScoreArgs& a, bool has_ids, hipStream_t stream) {
   switch (dim) {
-    case 32: return launch_score<32, MODE>(a, has_ids, stream);
-    case 64: return launch_score<64, MODE>(a, has_ids, stream);
-    case 128: return launch_score<128, MODE>(a, has_ids, stream);
-    case 256: return launch_score<256, MODE>(a, has_ids, stream);
+    case 32: return launch_score<32, MODE>(a, stream);
+    case 64: return launch_score<64, MODE>(a, stream);
+    case 128: return launch_score<128, MODE>(a, stream);
+    case 256: return launch_score<256, MODE>(a, stream);
     default: return tt::fail(TT_ERR_UNSUPPORTED, "retrieval: dim %d not in {32,64,128,256}", dim);
   }
 }
 
+// How much of the workspace (ws_layout) an entry uses: the rank pass the regions in front of part_l, the forward-only and
+// separate-backward entries everything in front of the stored dot products, the training entry all of it.
+enum WsNeed { WS_RANK, WS_NO_S, WS_FULL };
+
+// The requirements every launching entry shares, reported under the entry's own name `fn`.  has_diag = false: a rank pass with
+// explicit positives has no diagonal, so nq > nc is fine.
 int check_common(const char* fn, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
-                 int64_t diag_offset, const void* ws, int64_t ws_bytes, bool need_S = false) {
+                 int64_t diag_offset, const void* ws, int64_t ws_bytes, WsNeed ws_need, bool has_diag = true) {
   TT_REQUIRE(q && c && ws, "%s: null pointer", fn);
   TT_REQUIRE(nq > 0 && nc > 0, "%s: nq and nc must be positive", fn);
-  TT_REQUIRE(diag_offset >= 0 && nq + diag_offset <= nc, "%s: need 0 <= diag_offset and nq + diag_offset <= nc", fn);
+  TT_REQUIRE(!has_diag || (diag_offset >= 0 && nq + diag_offset <= nc), "%s: need 0 <= diag_offset and nq + diag_offset <= nc", fn);
   TT_REQUIRE(dim == 32 || dim == 64 || dim == 128 || dim == 256, "%s: dim %d not in {32,64,128,256}", fn, dim);
   TT_REQUIRE(tt::aligned16(q) && tt::aligned16(c), "%s: q/c must be 16-byte aligned", fn);
   TT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255u) == 0, "%s: workspace must be 256-byte aligned", fn);
   const WsLayout wl = ws_layout(nq, nc, dim);
-  const int64_t need = need_S ? wl.total : wl.total_no_S;
+  const int64_t need = ws_need == WS_FULL ? wl.total : (ws_need == WS_NO_S ? wl.total_no_S : wl.off_pl);
   if (ws_bytes < need)
     return tt::fail(TT_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes", fn, (long long)ws_bytes, (long long)need);
   return TT_OK;
+}
+
+// The column bias -log2 p_c of the sampling-probability correction: written to the workspace's front when cand_prob is given.
+// *bias = what the passes take as the candidates' additive term (null: none).
+int column_bias(const float* cand_prob, int64_t nc, void* workspace, const WsLayout& w, hipStream_t stream, const float** bias) {
+  *bias = nullptr;
+  if (cand_prob == nullptr) return TT_OK;
+  float* b = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.off_bias);
+  hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, b, nc);
+  *bias = b;
+  return tt::check_launch("prob_bias");
+}
+
+// What every pass derives from the entry's arguments alone: which matrix is stationary (R) and which streamed (K), the diagonal
+// as the stationary rows see it, the split of the streamed side, and the accidental-hit ids of rows and columns.  cand_ids is
+// indexed by candidate, and query i's positive is candidate i + diag_offset: the query side reads it shifted by diag_offset.
+// The caller adds what is particular to the pass: biases, scales, thresholds, outputs, S.
+enum Stationary { STATIONARY_Q, STATIONARY_C };
+ScoreArgs pass_args(Stationary side, const float* q, const float* c, int64_t nq, int64_t nc, int64_t diag_offset,
+                    float inv_temperature, int nsplit, const int64_t* cand_ids) {
+  const int64_t* ids_q = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
+  ScoreArgs a{};
+  if (side == STATIONARY_Q) {
+    a.R = q; a.K = c; a.n_r = nq; a.n_c = nc; a.diag = diag_offset;
+    a.id_r = ids_q; a.id_c = cand_ids;
+  } else {
+    a.R = c; a.K = q; a.n_r = nc; a.n_c = nq; a.diag = -diag_offset;
+    a.id_r = cand_ids; a.id_c = ids_q;
+  }
+  a.c1 = kLog2e * inv_temperature;
+  a.nsplit = nsplit;
+  a.c_per_split = align_up((a.n_c + nsplit - 1) / nsplit, 32);
+  return a;
+}
+
+// dc: stationary c, stream q.  Candidates beyond nq + diag_offset have no positive: diag never matches.
+// smat: the dot products pass 1 stored (MODE_BWD_S); null: the pass recomputes them (MODE_BWD).
+ScoreArgs dc_pass_args(const float* q, const float* c, int64_t nq, int64_t nc, int64_t diag_offset, float inv_temperature,
+                       int nsplit, const int64_t* cand_ids, const float* bias, const float* aq, const float* sq,
+                       const float* hq, float* slab, float* smat) {
+  ScoreArgs a = pass_args(STATIONARY_C, q, c, nq, nc, diag_offset, inv_temperature, nsplit, cand_ids);
+  a.a_r = bias; a.s_r = nullptr; a.a_c = aq; a.s_c = sq;
+  a.h_c = hq;
+  a.slab = slab;
+  if (smat != nullptr) { a.S = smat; a.ldS = (nq + 31) / 32; }
+  return a;
+}
+
+// out [n][dim] = the sum of a pass's nsplit slabs, in split order.  With per_row, one extra workgroup writes
+// loss = sum(per_row[0 .. n_rows)).
+int reduce_slabs(const char* what, const float* slab, float* out, int64_t n, int32_t dim, int nsplit, const float* per_row,
+                 int64_t n_rows, float* loss, hipStream_t stream) {
+  const int64_t n4 = n * dim / 4;
+  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
+  tt::launch("score_aux", reduce_slabs_kernel, dim3((unsigned)blocks + (per_row != nullptr ? 1 : 0)), dim3(256), 0, stream,
+             reinterpret_cast<const f32x4*>(slab), reinterpret_cast<f32x4*>(out), n4, nsplit, per_row, n_rows, loss);
+  return tt::check_launch(what);
 }
 
 }  // namespace
@@ -1475,36 +1539,27 @@ extern "C" int64_t tt_retrieval_rank_workspace_bytes(int64_t nq, int64_t nc, int
   return ws_layout(nq, nc, dim).off_pl;
 }
 
-static int retrieval_fwd(int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
+// (`fn`, here and in the other shared bodies: the entry's own name, for its messages)
+static int retrieval_fwd(const char* fn, int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
                          int64_t diag_offset, float inv_temperature, const float* sample_weight,
                          const float* cand_prob, const int64_t* cand_ids, const float* hard_thr,
                          void* workspace, int64_t workspace_bytes, float* lse, float* per_row, float* loss,
                          tt_stream_t stream_) {
-  int rc = check_common("tt_retrieval_fwd_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes);
+  int rc = check_common(fn, q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, WS_NO_S);
   if (rc != TT_OK) return rc;
-  TT_REQUIRE(lse && per_row && loss, "tt_retrieval_fwd_f32: null output pointer");
+  TT_REQUIRE(lse && per_row && loss, "%s: null output pointer", fn);
   hipStream_t stream = tt::as_stream(stream_);
   const WsLayout w = ws_layout(nq, nc, dim);
   char* ws = static_cast<char*>(workspace);
-  float* bias = reinterpret_cast<float*>(ws + w.off_bias);
-  if (cand_prob != nullptr) {
-    hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, bias, nc);
-    if ((rc = tt::check_launch("prob_bias")) != TT_OK) return rc;
-  }
-  ScoreArgs a{};
-  a.R = q; a.K = c; a.n_r = nq; a.n_c = nc; a.diag = diag_offset;
-  a.c1 = kLog2e * inv_temperature;
-  a.a_c = cand_prob != nullptr ? bias : nullptr;
-  a.id_r = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-  a.id_c = cand_ids;
+  const float* bias;
+  if ((rc = column_bias(cand_prob, nc, workspace, w, stream, &bias)) != TT_OK) return rc;
+  ScoreArgs a = pass_args(STATIONARY_Q, q, c, nq, nc, diag_offset, inv_temperature, w.ns_q, cand_ids);
+  a.a_c = bias;
   a.h_r = hard_thr;
-  a.nsplit = w.ns_q;
-  a.c_per_split = align_up((nc + a.nsplit - 1) / a.nsplit, 32);
   a.part_m = reinterpret_cast<float*>(ws + w.off_pm);
   a.part_l = reinterpret_cast<float*>(ws + w.off_pl);
   a.pos2 = reinterpret_cast<float*>(ws + w.off_pos);
-  rc = prec == 1 ? dispatch_score_bx3<MODE_FWD>(dim, a, cand_ids != nullptr, stream) : dispatch_score<MODE_FWD>(dim, a, cand_ids != nullptr, stream);
-  if (rc != TT_OK) return rc;
+  if ((rc = dispatch_score<MODE_FWD>(prec, dim, a, stream)) != TT_OK) return rc;
   tt::ProfScope prof("score_aux", stream);
   hipLaunchKernelGGL(fwd_combine_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, a.part_m, a.part_l, a.pos2,
                      sample_weight, nq, a.nsplit, lse, per_row);
@@ -1518,8 +1573,8 @@ extern "C" int tt_retrieval_fwd_f32(const float* q, const float* c, int64_t nq, 
                                     const float* cand_prob, const int64_t* cand_ids, const float* hard_thr,
                                     void* workspace, int64_t workspace_bytes, float* lse, float* per_row, float* loss,
                                     tt_stream_t stream) {
-  return retrieval_fwd(0, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob, cand_ids, hard_thr, workspace,
-                       workspace_bytes, lse, per_row, loss, stream);
+  return retrieval_fwd("tt_retrieval_fwd_f32", 0, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob, cand_ids,
+                       hard_thr, workspace, workspace_bytes, lse, per_row, loss, stream);
 }
 
 // The validation pass with the logits' products on the bf16 matrix cores (the 6-product split of GEMM1: 2^-24 relative,
@@ -1530,8 +1585,8 @@ extern "C" int tt_retrieval_fwd_bf16x3_f32(const float* q, const float* c, int64
                                            void* workspace, int64_t workspace_bytes, float* lse, float* per_row, float* loss,
                                            tt_stream_t stream) {
   if (dim != 128 && dim != 256) return tt::fail(TT_ERR_UNSUPPORTED, "tt_retrieval_fwd_bf16x3_f32: dim %d not in {128,256}", dim);
-  return retrieval_fwd(1, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob, cand_ids, hard_thr, workspace,
-                       workspace_bytes, lse, per_row, loss, stream);
+  return retrieval_fwd("tt_retrieval_fwd_bf16x3_f32", 1, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob,
+                       cand_ids, hard_thr, workspace, workspace_bytes, lse, per_row, loss, stream);
 }
 
 extern "C" int tt_retrieval_bwd_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
@@ -1539,25 +1594,21 @@ extern "C" int tt_retrieval_bwd_f32(const float* q, const float* c, int64_t nq, 
                                     const float* cand_prob, const int64_t* cand_ids, const float* hard_thr,
                                     const float* lse, float grad_scale, void* workspace, int64_t workspace_bytes,
                                     float* dq, float* dc, tt_stream_t stream_) {
-  int rc = check_common("tt_retrieval_bwd_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes);
+  int rc = check_common("tt_retrieval_bwd_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, WS_NO_S);
   if (rc != TT_OK) return rc;
   TT_REQUIRE(lse && dq && dc, "tt_retrieval_bwd_f32: null lse/dq/dc");
   TT_REQUIRE(tt::aligned16(dq) && tt::aligned16(dc), "tt_retrieval_bwd_f32: dq/dc must be 16-byte aligned");
   hipStream_t stream = tt::as_stream(stream_);
   const WsLayout w = ws_layout(nq, nc, dim);
   char* ws = static_cast<char*>(workspace);
-  float* bias = reinterpret_cast<float*>(ws + w.off_bias);
   float* aq = reinterpret_cast<float*>(ws + w.off_aq);
   float* sq = reinterpret_cast<float*>(ws + w.off_sq);
   float* slab = reinterpret_cast<float*>(ws + w.off_slab);
-  if (cand_prob != nullptr) {
-    hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, bias, nc);
-    if ((rc = tt::check_launch("prob_bias")) != TT_OK) return rc;
-  }
+  const float* bias;
+  if ((rc = column_bias(cand_prob, nc, workspace, w, stream, &bias)) != TT_OK) return rc;
   hipLaunchKernelGGL(bwd_prep_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, lse, sample_weight, aq,
                      sq, nq, inv_temperature * grad_scale);
   if ((rc = tt::check_launch("bwd_prep")) != TT_OK) return rc;
-  const float* biasp = cand_prob != nullptr ? bias : nullptr;
   float* hq = nullptr;
   if (hard_thr != nullptr) {
     hq = reinterpret_cast<float*>(ws + w.off_hq);
@@ -1567,49 +1618,22 @@ extern "C" int tt_retrieval_bwd_f32(const float* q, const float* c, int64_t nq, 
 
   // dq: stationary q, stream c
   {
-    ScoreArgs a{};
-    a.R = q; a.K = c; a.n_r = nq; a.n_c = nc; a.diag = diag_offset;
-    a.c1 = kLog2e * inv_temperature;
-    a.a_r = aq; a.s_r = sq; a.a_c = biasp; a.s_c = nullptr;
+    ScoreArgs a = pass_args(STATIONARY_Q, q, c, nq, nc, diag_offset, inv_temperature, w.ns_q, cand_ids);
+    a.a_r = aq; a.s_r = sq; a.a_c = bias; a.s_c = nullptr;
     a.h_r = hq;
-    a.id_r = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-    a.id_c = cand_ids;
-    a.nsplit = w.ns_q;
-    a.c_per_split = align_up((nc + a.nsplit - 1) / a.nsplit, 32);
     a.slab = slab;
-    if ((rc = dispatch_score<MODE_BWD>(dim, a, cand_ids != nullptr, stream)) != TT_OK) return rc;
-    const int64_t n4 = nq * dim / 4;
-    const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-    tt::launch("score_aux", reduce_slabs_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
-               reinterpret_cast<const f32x4*>(slab), reinterpret_cast<f32x4*>(dq), n4, a.nsplit, (const float*)nullptr, (int64_t)0, (float*)nullptr);
-    if ((rc = tt::check_launch("reduce_slabs(dq)")) != TT_OK) return rc;
+    if ((rc = dispatch_score<MODE_BWD>(0, dim, a, stream)) != TT_OK) return rc;
+    if ((rc = reduce_slabs("reduce_slabs(dq)", slab, dq, nq, dim, a.nsplit, nullptr, 0, nullptr, stream)) != TT_OK) return rc;
   }
-  // dc: stationary c, stream q.  Candidates beyond nq + diag_offset have no positive: diag never matches.
-  {
-    ScoreArgs a{};
-    a.R = c; a.K = q; a.n_r = nc; a.n_c = nq; a.diag = -diag_offset;
-    a.c1 = kLog2e * inv_temperature;
-    a.a_r = biasp; a.s_r = nullptr; a.a_c = aq; a.s_c = sq;
-    a.h_c = hq;
-    a.id_r = cand_ids;
-    a.id_c = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-    a.nsplit = w.ns_c;
-    a.c_per_split = align_up((nq + a.nsplit - 1) / a.nsplit, 32);
-    a.slab = slab;
-    if ((rc = dispatch_score<MODE_BWD>(dim, a, cand_ids != nullptr, stream)) != TT_OK) return rc;
-    const int64_t n4 = nc * dim / 4;
-    const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-    tt::launch("score_aux", reduce_slabs_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
-               reinterpret_cast<const f32x4*>(slab), reinterpret_cast<f32x4*>(dc), n4, a.nsplit, (const float*)nullptr, (int64_t)0, (float*)nullptr);
-    if ((rc = tt::check_launch("reduce_slabs(dc)")) != TT_OK) return rc;
-  }
-  return TT_OK;
+  const ScoreArgs a = dc_pass_args(q, c, nq, nc, diag_offset, inv_temperature, w.ns_c, cand_ids, bias, aq, sq, hq, slab, nullptr);
+  if ((rc = dispatch_score<MODE_BWD>(0, dim, a, stream)) != TT_OK) return rc;
+  return reduce_slabs("reduce_slabs(dc)", slab, dc, nc, dim, a.nsplit, nullptr, 0, nullptr, stream);
 }
 
 // Fused training entry: loss AND both gradients in two passes (8*B^2*D executed FLOPs instead of 10):
 //   pass 1 (R = q, K = c, MODE_FUSED_S): online softmax + sum_c p*c  -> lse, per-row loss, dq; stores the dot products
 //   pass 2 (R = c, K = q, MODE_BWD_S)  : reads them back with the final lse -> dc
-static int retrieval_fwd_bwd(int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
+static int retrieval_fwd_bwd(const char* fn, int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
                              int64_t diag_offset, float inv_temperature, const float* sample_weight,
                              const float* cand_prob, const int64_t* cand_ids, const float* hard_thr,
                              float grad_scale, void* workspace, int64_t workspace_bytes, float* lse,
@@ -1617,54 +1641,40 @@ static int retrieval_fwd_bwd(int prec, const float* q, const float* c, int64_t n
   // Both precisions keep pass 1's dot products for pass 2 (the workspace includes the buffer).  bf16x3 at dim 256 recomputed them
   // until r03: with the wave-pair kernels, B 32768: pass 1 / pass 2 = 6.10 / 5.87 ms recomputing, 6.45 / 3.51 ms keeping them
   // (exact f32: 8.77 / 5.17 ms) - profiles/r03_score_f32_vs_bf16x3.jsonl.
-  int rc = check_common("tt_retrieval_fwd_bwd_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, true);
+  int rc = check_common(fn, q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, WS_FULL);
   if (rc != TT_OK) return rc;
-  TT_REQUIRE(lse && per_row && loss && dq && dc, "tt_retrieval_fwd_bwd_f32: null output pointer");
-  TT_REQUIRE(tt::aligned16(dq) && tt::aligned16(dc), "tt_retrieval_fwd_bwd_f32: dq/dc must be 16-byte aligned");
+  TT_REQUIRE(lse && per_row && loss && dq && dc, "%s: null output pointer", fn);
+  TT_REQUIRE(tt::aligned16(dq) && tt::aligned16(dc), "%s: dq/dc must be 16-byte aligned", fn);
   hipStream_t stream = tt::as_stream(stream_);
   const WsLayout w = ws_layout(nq, nc, dim);
   char* ws = static_cast<char*>(workspace);
-  float* bias = reinterpret_cast<float*>(ws + w.off_bias);
   float* aq = reinterpret_cast<float*>(ws + w.off_aq);
   float* sq = reinterpret_cast<float*>(ws + w.off_sq);
   float* slab = reinterpret_cast<float*>(ws + w.off_slab);
   float* smat = reinterpret_cast<float*>(ws + w.off_S);       // [nq][nc] raw dot products, pass 1 -> pass 2
-  if (cand_prob != nullptr) {
-    hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, bias, nc);
-    if ((rc = tt::check_launch("prob_bias")) != TT_OK) return rc;
-  }
-  const float* biasp = cand_prob != nullptr ? bias : nullptr;
+  const float* bias;
+  if ((rc = column_bias(cand_prob, nc, workspace, w, stream, &bias)) != TT_OK) return rc;
   {
-    ScoreArgs a{};
-    a.R = q; a.K = c; a.n_r = nq; a.n_c = nc; a.diag = diag_offset;
-    a.c1 = kLog2e * inv_temperature;
-    a.a_c = biasp;
+    ScoreArgs a = pass_args(STATIONARY_Q, q, c, nq, nc, diag_offset, inv_temperature, w.ns_q, cand_ids);
+    a.a_c = bias;
     a.h_r = hard_thr;
     a.S = smat; a.ldS = (nq + 31) / 32;
-    a.id_r = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-    a.id_c = cand_ids;
-    a.nsplit = w.ns_q;
-    a.c_per_split = align_up((nc + a.nsplit - 1) / a.nsplit, 32);
     a.part_m = reinterpret_cast<float*>(ws + w.off_pm);
     a.part_l = reinterpret_cast<float*>(ws + w.off_pl);
     a.pos2 = reinterpret_cast<float*>(ws + w.off_pos);
     a.slab = slab;
     // (bf16x3 at dim 128 keeps the dot products too: 134 + 89 us against 123 + 124 us recomputing - with the row-major buffer
     // it had been 200 + 127 us, the blocked layout is what makes it pay.)
-    rc = prec == 1 ? dispatch_score_bx3<MODE_FUSED_S>(dim, a, cand_ids != nullptr, stream)
-                   : dispatch_score<MODE_FUSED_S>(dim, a, cand_ids != nullptr, stream);
-    if (rc != TT_OK) return rc;
-    {
-      int lpr_log2 = 3;                              // dim/4 lanes per row: 8 (dim 32) .. 64 (dim 256)
-      while ((1 << lpr_log2) < dim / 4) ++lpr_log2;
-      const int rpb = 256 >> lpr_log2;
-      tt::launch("score_aux", fused_combine_kernel, dim3((unsigned)((nq + rpb - 1) / rpb)), dim3(256), 0, stream, a.part_m, a.part_l, a.pos2,
-                         sample_weight, reinterpret_cast<const f32x4*>(slab),
-                         reinterpret_cast<const f32x4*>(c + diag_offset * dim), nq, dim / 4, lpr_log2, a.nsplit,
-                         inv_temperature * grad_scale, lse, per_row, aq, sq, reinterpret_cast<f32x4*>(dq));
-      if ((rc = tt::check_launch("fused_combine")) != TT_OK) return rc;
-      // loss = sum(per_row): by one extra workgroup of the dc slab reduction below
-    }
+    if ((rc = dispatch_score<MODE_FUSED_S>(prec, dim, a, stream)) != TT_OK) return rc;
+    int lpr_log2 = 3;                              // dim/4 lanes per row: 8 (dim 32) .. 64 (dim 256)
+    while ((1 << lpr_log2) < dim / 4) ++lpr_log2;
+    const int rpb = 256 >> lpr_log2;
+    tt::launch("score_aux", fused_combine_kernel, dim3((unsigned)((nq + rpb - 1) / rpb)), dim3(256), 0, stream, a.part_m, a.part_l, a.pos2,
+                       sample_weight, reinterpret_cast<const f32x4*>(slab),
+                       reinterpret_cast<const f32x4*>(c + diag_offset * dim), nq, dim / 4, lpr_log2, a.nsplit,
+                       inv_temperature * grad_scale, lse, per_row, aq, sq, reinterpret_cast<f32x4*>(dq));
+    if ((rc = tt::check_launch("fused_combine")) != TT_OK) return rc;
+    // loss = sum(per_row): by one extra workgroup of the dc slab reduction below
   }
   float* hq = nullptr;
   if (hard_thr != nullptr) {
@@ -1672,28 +1682,9 @@ static int retrieval_fwd_bwd(int prec, const float* q, const float* c, int64_t n
     hipLaunchKernelGGL(hn_shift_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, hard_thr, aq, hq, nq);
     if ((rc = tt::check_launch("hn_shift")) != TT_OK) return rc;
   }
-  {
-    ScoreArgs a{};
-    a.R = c; a.K = q; a.n_r = nc; a.n_c = nq; a.diag = -diag_offset;
-    a.c1 = kLog2e * inv_temperature;
-    a.a_r = biasp; a.s_r = nullptr; a.a_c = aq; a.s_c = sq;
-    a.h_c = hq;
-    a.id_r = cand_ids;
-    a.id_c = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-    a.nsplit = w.ns_cs;
-    a.c_per_split = align_up((nq + a.nsplit - 1) / a.nsplit, 32);
-    a.slab = slab;
-    a.S = smat; a.ldS = (nq + 31) / 32;
-    rc = prec == 1 ? dispatch_score_bx3<MODE_BWD_S>(dim, a, cand_ids != nullptr, stream)
-                   : dispatch_score<MODE_BWD_S>(dim, a, cand_ids != nullptr, stream);
-    if (rc != TT_OK) return rc;
-    const int64_t n4 = nc * dim / 4;
-    const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-    tt::launch("score_aux", reduce_slabs_kernel, dim3((unsigned)blocks + 1), dim3(256), 0, stream,
-                       reinterpret_cast<const f32x4*>(slab), reinterpret_cast<f32x4*>(dc), n4, a.nsplit, per_row, nq, loss);
-    if ((rc = tt::check_launch("reduce_slabs(dc)")) != TT_OK) return rc;
-  }
-  return TT_OK;
+  const ScoreArgs a = dc_pass_args(q, c, nq, nc, diag_offset, inv_temperature, w.ns_cs, cand_ids, bias, aq, sq, hq, slab, smat);
+  if ((rc = dispatch_score<MODE_BWD_S>(prec, dim, a, stream)) != TT_OK) return rc;
+  return reduce_slabs("reduce_slabs(dc)", slab, dc, nc, dim, a.nsplit, per_row, nq, loss, stream);
 }
 
 extern "C" int tt_retrieval_fwd_bwd_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
@@ -1701,8 +1692,8 @@ extern "C" int tt_retrieval_fwd_bwd_f32(const float* q, const float* c, int64_t 
                                         const float* cand_prob, const int64_t* cand_ids, const float* hard_thr,
                                         float grad_scale, void* workspace, int64_t workspace_bytes, float* lse,
                                         float* per_row, float* loss, float* dq, float* dc, tt_stream_t stream) {
-  return retrieval_fwd_bwd(0, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob, cand_ids, hard_thr,
-                           grad_scale, workspace, workspace_bytes, lse, per_row, loss, dq, dc, stream);
+  return retrieval_fwd_bwd("tt_retrieval_fwd_bwd_f32", 0, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob,
+                           cand_ids, hard_thr, grad_scale, workspace, workspace_bytes, lse, per_row, loss, dq, dc, stream);
 }
 
 // The same two passes with every matrix product on bf16 MFMA through the hi/mid/lo split of the f32 operands
@@ -1713,59 +1704,44 @@ extern "C" int tt_retrieval_fwd_bwd_bf16x3_f32(const float* q, const float* c, i
                                                float grad_scale, void* workspace, int64_t workspace_bytes, float* lse,
                                                float* per_row, float* loss, float* dq, float* dc, tt_stream_t stream) {
   if (dim != 128 && dim != 256) return tt::fail(TT_ERR_UNSUPPORTED, "tt_retrieval_fwd_bwd_bf16x3_f32: dim %d not in {128,256}", dim);
-  return retrieval_fwd_bwd(1, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight, cand_prob, cand_ids, hard_thr,
-                           grad_scale, workspace, workspace_bytes, lse, per_row, loss, dq, dc, stream);
+  return retrieval_fwd_bwd("tt_retrieval_fwd_bwd_bf16x3_f32", 1, q, c, nq, nc, dim, diag_offset, inv_temperature, sample_weight,
+                           cand_prob, cand_ids, hard_thr, grad_scale, workspace, workspace_bytes, lse, per_row, loss, dq, dc, stream);
 }
 
 // Retrieval metric support (configs/data_config.yaml:71 top_k_eval): rank of each query's true
 // candidate among ALL nc candidates = number of other candidates with a strictly larger logit.  One fused pass over
 // the [nq, nc] logits (never materialised); Recall@K / NDCG@K follow from rank < K on the host side.
-static int retrieval_rank(int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
-                          float inv_temperature, const float* cand_prob, const int64_t* pos_index,
-                          void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream_) {
-  // (not check_common: a rank pass has no diagonal, so nq > nc is fine, and it needs only the front of the workspace)
-  int rc;
-  TT_REQUIRE(q && c && workspace && pos_index && rank, "tt_retrieval_rank_f32: null pointer");
-  TT_REQUIRE(nq > 0 && nc > 0, "tt_retrieval_rank_f32: nq and nc must be positive");
-  TT_REQUIRE(dim == 32 || dim == 64 || dim == 128 || dim == 256, "tt_retrieval_rank_f32: dim %d not in {32,64,128,256}", dim);
-  TT_REQUIRE(tt::aligned16(q) && tt::aligned16(c), "tt_retrieval_rank_f32: q/c must be 16-byte aligned");
-  TT_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "tt_retrieval_rank_f32: workspace must be 256-byte aligned");
-  const WsLayout w = ws_layout(nq, nc, dim);
-  if (workspace_bytes < w.off_pl)
-    return tt::fail(TT_ERR_WORKSPACE, "tt_retrieval_rank_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                    (long long)w.off_pl);
-  hipStream_t stream = tt::as_stream(stream_);
-  char* ws = static_cast<char*>(workspace);
-  float* bias = reinterpret_cast<float*>(ws + w.off_bias);
-  float* thr = reinterpret_cast<float*>(ws + w.off_aq);
-  int32_t* part_cnt = reinterpret_cast<int32_t*>(ws + w.off_pm);
-  const float c1 = kLog2e * inv_temperature;
-  if (cand_prob != nullptr) {
-    hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, bias, nc);
-    if ((rc = tt::check_launch("prob_bias")) != TT_OK) return rc;
-  }
-  const float* biasp = cand_prob != nullptr ? bias : nullptr;
-  hipLaunchKernelGGL(pos_logit_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(q),
-                     reinterpret_cast<const f32x4*>(c), pos_index, biasp, nq, nc, dim / 4, c1, thr, (int64_t)0);
-  if ((rc = tt::check_launch("pos_logit")) != TT_OK) return rc;
-  ScoreArgs a{};
-  a.R = q; a.K = c; a.n_r = nq; a.n_c = nc; a.diag = 0;
-  a.c1 = c1;
-  a.a_r = thr; a.a_c = biasp;
-  a.pos_idx = pos_index;
-  a.nsplit = w.ns_q;
-  a.c_per_split = align_up((nc + a.nsplit - 1) / a.nsplit, 32);
-  a.part_cnt = part_cnt;
-  rc = prec == 1 ? dispatch_score_bx3<MODE_RANK>(dim, a, false, stream) : dispatch_score<MODE_RANK>(dim, a, false, stream);
+// The positive of query i: candidate pos_index[i], or with pos_index == nullptr (the in-batch form) candidate i + diag_offset.
+static int retrieval_rank(const char* fn, int prec, const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
+                          int64_t diag_offset, float inv_temperature, const float* cand_prob, const int64_t* pos_index,
+                          const int64_t* cand_ids, void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream_) {
+  // (a rank pass with explicit positives has no diagonal, so nq > nc is fine; either form needs only the front of the workspace)
+  int rc = check_common(fn, q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, WS_RANK, pos_index == nullptr);
   if (rc != TT_OK) return rc;
-  hipLaunchKernelGGL(rank_combine_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, part_cnt, nq, a.nsplit, rank);
+  hipStream_t stream = tt::as_stream(stream_);
+  const WsLayout w = ws_layout(nq, nc, dim);
+  char* ws = static_cast<char*>(workspace);
+  float* thr = reinterpret_cast<float*>(ws + w.off_aq);
+  const float* bias;
+  if ((rc = column_bias(cand_prob, nc, workspace, w, stream, &bias)) != TT_OK) return rc;
+  ScoreArgs a = pass_args(STATIONARY_Q, q, c, nq, nc, diag_offset, inv_temperature, w.ns_q, cand_ids);
+  hipLaunchKernelGGL(pos_logit_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(q),
+                     reinterpret_cast<const f32x4*>(c), pos_index, bias, nq, nc, dim / 4, a.c1, thr, diag_offset);
+  if ((rc = tt::check_launch("pos_logit")) != TT_OK) return rc;
+  a.a_r = thr; a.a_c = bias;
+  a.pos_idx = pos_index;
+  a.part_cnt = reinterpret_cast<int32_t*>(ws + w.off_pm);
+  if ((rc = dispatch_score<MODE_RANK>(prec, dim, a, stream)) != TT_OK) return rc;
+  hipLaunchKernelGGL(rank_combine_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, a.part_cnt, nq, a.nsplit, rank);
   return tt::check_launch("rank_combine");
 }
 
 extern "C" int tt_retrieval_rank_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
                                      float inv_temperature, const float* cand_prob, const int64_t* pos_index,
                                      void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream) {
-  return retrieval_rank(0, q, c, nq, nc, dim, inv_temperature, cand_prob, pos_index, workspace, workspace_bytes, rank, stream);
+  TT_REQUIRE(pos_index && rank, "tt_retrieval_rank_f32: null pointer");
+  return retrieval_rank("tt_retrieval_rank_f32", 0, q, c, nq, nc, dim, 0, inv_temperature, cand_prob, pos_index, nullptr, workspace,
+                        workspace_bytes, rank, stream);
 }
 
 // Top-K over a 10M-100M-row corpus is pure GEMM1 as well: the same rank pass with the 6-product bf16 split.  The positive's
@@ -1775,7 +1751,9 @@ extern "C" int tt_retrieval_rank_bf16x3_f32(const float* q, const float* c, int6
                                             float inv_temperature, const float* cand_prob, const int64_t* pos_index,
                                             void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream) {
   if (dim != 128 && dim != 256) return tt::fail(TT_ERR_UNSUPPORTED, "tt_retrieval_rank_bf16x3_f32: dim %d not in {128,256}", dim);
-  return retrieval_rank(1, q, c, nq, nc, dim, inv_temperature, cand_prob, pos_index, workspace, workspace_bytes, rank, stream);
+  TT_REQUIRE(pos_index && rank, "tt_retrieval_rank_bf16x3_f32: null pointer");
+  return retrieval_rank("tt_retrieval_rank_bf16x3_f32", 1, q, c, nq, nc, dim, 0, inv_temperature, cand_prob, pos_index, nullptr,
+                        workspace, workspace_bytes, rank, stream);
 }
 
 // In-batch rank (tfrs.tasks.Retrieval(batch_metrics=...): Keras top-k categorical accuracy over the IN-BATCH score matrix):
@@ -1784,44 +1762,10 @@ extern "C" int tt_retrieval_rank_bf16x3_f32(const float* q, const float* c, int6
 // accuracy = mean(rank < k): no [nq, nc] score matrix is materialised, it is the metric pass above run on the batch.
 extern "C" int tt_retrieval_batch_rank_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim, int64_t diag_offset,
                                            float inv_temperature, const float* cand_prob, const int64_t* cand_ids,
-                                           void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream_) {
-  int rc;
-  TT_REQUIRE(q && c && workspace && rank, "tt_retrieval_batch_rank_f32: null pointer");
-  TT_REQUIRE(nq > 0 && nc > 0, "tt_retrieval_batch_rank_f32: nq and nc must be positive");
-  TT_REQUIRE(diag_offset >= 0 && nq + diag_offset <= nc, "tt_retrieval_batch_rank_f32: need 0 <= diag_offset and nq + diag_offset <= nc");
-  TT_REQUIRE(dim == 32 || dim == 64 || dim == 128 || dim == 256, "tt_retrieval_batch_rank_f32: dim %d not in {32,64,128,256}", dim);
-  TT_REQUIRE(tt::aligned16(q) && tt::aligned16(c), "tt_retrieval_batch_rank_f32: q/c must be 16-byte aligned");
-  TT_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "tt_retrieval_batch_rank_f32: workspace must be 256-byte aligned");
-  const WsLayout w = ws_layout(nq, nc, dim);
-  if (workspace_bytes < w.off_pl)
-    return tt::fail(TT_ERR_WORKSPACE, "tt_retrieval_batch_rank_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                    (long long)w.off_pl);
-  hipStream_t stream = tt::as_stream(stream_);
-  char* ws = static_cast<char*>(workspace);
-  float* bias = reinterpret_cast<float*>(ws + w.off_bias);
-  float* thr = reinterpret_cast<float*>(ws + w.off_aq);
-  int32_t* part_cnt = reinterpret_cast<int32_t*>(ws + w.off_pm);
-  const float c1 = kLog2e * inv_temperature;
-  if (cand_prob != nullptr) {
-    hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, bias, nc);
-    if ((rc = tt::check_launch("prob_bias")) != TT_OK) return rc;
-  }
-  const float* biasp = cand_prob != nullptr ? bias : nullptr;
-  hipLaunchKernelGGL(pos_logit_kernel, dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(q),
-                     reinterpret_cast<const f32x4*>(c), static_cast<const int64_t*>(nullptr), biasp, nq, nc, dim / 4, c1, thr, diag_offset);
-  if ((rc = tt::check_launch("pos_logit")) != TT_OK) return rc;
-  ScoreArgs a{};
-  a.R = q; a.K = c; a.n_r = nq; a.n_c = nc; a.diag = diag_offset;
-  a.c1 = c1;
-  a.a_r = thr; a.a_c = biasp;
-  a.id_r = cand_ids != nullptr ? cand_ids + diag_offset : nullptr;
-  a.id_c = cand_ids;
-  a.nsplit = w.ns_q;
-  a.c_per_split = align_up((nc + a.nsplit - 1) / a.nsplit, 32);
-  a.part_cnt = part_cnt;
-  if ((rc = dispatch_score<MODE_RANK>(dim, a, cand_ids != nullptr, stream)) != TT_OK) return rc;
-  hipLaunchKernelGGL(rank_combine_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, part_cnt, nq, a.nsplit, rank);
-  return tt::check_launch("rank_combine");
+                                           void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream) {
+  TT_REQUIRE(rank, "tt_retrieval_batch_rank_f32: null pointer");
+  return retrieval_rank("tt_retrieval_batch_rank_f32", 0, q, c, nq, nc, dim, diag_offset, inv_temperature, cand_prob, nullptr, cand_ids,
+                        workspace, workspace_bytes, rank, stream);
 }
 
 // Hard-negative thresholds (tfrs.tasks.Retrieval(num_hard_negatives=k)): thr[i] separates the k highest-scoring negatives
@@ -1832,7 +1776,7 @@ extern "C" int tt_retrieval_hard_negative_thresholds_f32(const float* q, const f
                                                          const int64_t* cand_ids, int32_t num_hard_negatives, void* workspace,
                                                          int64_t workspace_bytes, float* scratch, int64_t scratch_bytes,
                                                          float* thr, tt_stream_t stream_) {
-  int rc = check_common("tt_retrieval_hard_negative_thresholds_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes);
+  int rc = check_common("tt_retrieval_hard_negative_thresholds_f32", q, c, nq, nc, dim, diag_offset, workspace, workspace_bytes, WS_NO_S);
   if (rc != TT_OK) return rc;
   TT_REQUIRE(num_hard_negatives >= 1, "tt_retrieval_hard_negative_thresholds_f32: num_hard_negatives must be >= 1");
   TT_REQUIRE(scratch && thr, "tt_retrieval_hard_negative_thresholds_f32: null scratch/thr");
@@ -1840,14 +1784,10 @@ extern "C" int tt_retrieval_hard_negative_thresholds_f32(const float* q, const f
     return tt::fail(TT_ERR_WORKSPACE, "tt_retrieval_hard_negative_thresholds_f32: scratch %lld < %lld bytes",
                     (long long)scratch_bytes, (long long)(nq * nc * 4));
   hipStream_t stream = tt::as_stream(stream_);
-  const WsLayout w = ws_layout(nq, nc, dim);
-  float* bias = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.off_bias);
-  if (cand_prob != nullptr) {
-    hipLaunchKernelGGL(prob_bias_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, cand_prob, bias, nc);
-    if ((rc = tt::check_launch("prob_bias")) != TT_OK) return rc;
-  }
+  const float* bias;
+  if ((rc = column_bias(cand_prob, nc, workspace, ws_layout(nq, nc, dim), stream, &bias)) != TT_OK) return rc;
   if ((rc = tt::gemm_nt(q, c, scratch, nq, nc, dim, stream)) != TT_OK) return rc;
   tt::launch("score_aux", hardneg_select_kernel, dim3((unsigned)nq), dim3(256), 0, stream, scratch, nc, kLog2e * inv_temperature,
-                     cand_prob != nullptr ? bias : nullptr, cand_ids, diag_offset, num_hard_negatives, thr);
+                     bias, cand_ids, diag_offset, num_hard_negatives, thr);
   return tt::check_launch("hardneg_select");
 }

@@ -341,6 +341,12 @@ def _no_lookup():
     return _lib.DenseLookup()
 
 
+def _fwd_args(x, w, b, y, tid, lookup, bits):
+    """One layer's ``tt_dense_fwd_args``; with a lookup the input rows come from the embedding table and x is not passed."""
+    return _lib.DenseFwdArgs(None if lookup is not None else _p(x), _p(w), _p(b), _p(y), tid,
+                             lookup if lookup is not None else _no_lookup(), _p(bits))
+
+
 def _in_shape(x, lookup):
     if lookup is not None:
         return lookup._mk
@@ -381,8 +387,7 @@ def dense_fwd(x, w, b, relu: bool, out=None, dropout=None, lookup=None, relu_bit
         raise RuntimeError(f"dense_fwd: out must be [{m},{n}], got {tuple(out.shape)}")
     rate, seed, tid, off = dropout if dropout is not None else (0.0, 0, 0, 0)
     _chk_bits(relu_bits, m, n, "dense_fwd: relu_bits")
-    arr = (_lib.DenseFwdArgs * 1)(_lib.DenseFwdArgs(None if lookup is not None else _p(x), _p(w), _p(b), _p(out), tid,
-                                                    lookup if lookup is not None else _no_lookup(), _p(relu_bits)))
+    arr = (_lib.DenseFwdArgs * 1)(_fwd_args(x, w, b, out, tid, lookup, relu_bits))
     _lib.check(_lib.load().tt_dense_fwd_batched_f32(arr, 1, m, k, n, int(relu), rate, seed, off, _stream()),
                "tt_dense_fwd_batched_f32")
     return out
@@ -411,9 +416,7 @@ def dense_bwd(x, w, dz, dx, dx_relu_src, dw_slabs, db_slabs, dx_scale: float = 1
         if dw_slabs.numel() < ns * k * n or db_slabs.numel() < ns * n:
             raise RuntimeError("dense_bwd: slab buffers too small")
     _chk_bits(dx_relu_bits, m, k, "dense_bwd: dx_relu_bits")
-    arr = (_lib.DenseBwdArgs * 1)(_lib.DenseBwdArgs(None if lookup is not None else _p(x), _p(w), _p(dz), _p(dx), _p(dx_relu_src),
-                                                    _p(dw_slabs), _p(db_slabs), lookup if lookup is not None else _no_lookup(),
-                                                    _p(dx_relu_bits)))
+    arr = _bwd_args([x], [w], [dz], [dx], [dx_relu_src], [dw_slabs], [db_slabs], None if lookup is None else [lookup], [dx_relu_bits])
     _lib.check(_lib.load().tt_dense_bwd_batched_f32(arr, 1, dx_scale, m, k, n, _stream()), "tt_dense_bwd_batched_f32")
     return ns
 
@@ -426,9 +429,8 @@ def dense_fwd2(xs, ws, bs, ys, relu: bool, dropout=None, lookups=None, relu_bits
     rate, seed, tids, off = dropout if dropout is not None else (0.0, 0, (0, 0), 0)
     for i in range(2):
         _chk_bits(relu_bits[i], m, n, "dense_fwd2: relu_bits")
-    arr = (_lib.DenseFwdArgs * 2)(*[_lib.DenseFwdArgs(None if lookups is not None else _p(xs[i]), _p(ws[i]), _p(bs[i]), _p(ys[i]),
-                                                      tids[i], lookups[i] if lookups is not None else _no_lookup(),
-                                                      _p(relu_bits[i])) for i in range(2)])
+    arr = (_lib.DenseFwdArgs * 2)(*[_fwd_args(xs[i], ws[i], bs[i], ys[i], tids[i], None if lookups is None else lookups[i], relu_bits[i])
+                                    for i in range(2)])
     _lib.check(_lib.load().tt_dense_fwd_batched_f32(arr, 2, m, k, n, int(relu), rate, seed, off, _stream()),
                "tt_dense_fwd_batched_f32")
 
@@ -451,10 +453,9 @@ def tower_fwd2(xs, w0s, b0s, hs, h_bits, w1s, b1s, ys, dropout=None, lookups=Non
         if tuple(w0s[i].shape) != (k0, h) or tuple(w1s[i].shape) != (h, n1) or tuple(hs[i].shape) != (m, h) or tuple(ys[i].shape) != (m, n1):
             raise RuntimeError("tower_fwd2: shape mismatch between the layers' weights and buffers")
         _chk_bits(h_bits[i], m, h, "tower_fwd2: h_bits")
-    l0 = (_lib.DenseFwdArgs * 2)(*[_lib.DenseFwdArgs(None if lookups is not None else _p(xs[i]), _p(w0s[i]), _p(b0s[i]), _p(hs[i]),
-                                                     tids[i], lookups[i] if lookups is not None else _no_lookup(), _p(h_bits[i]))
+    l0 = (_lib.DenseFwdArgs * 2)(*[_fwd_args(xs[i], w0s[i], b0s[i], hs[i], tids[i], None if lookups is None else lookups[i], h_bits[i])
                                    for i in range(2)])
-    l1 = (_lib.DenseFwdArgs * 2)(*[_lib.DenseFwdArgs(_p(hs[i]), _p(w1s[i]), _p(b1s[i]), _p(ys[i]), 0, _no_lookup(), None) for i in range(2)])
+    l1 = (_lib.DenseFwdArgs * 2)(*[_fwd_args(hs[i], w1s[i], b1s[i], ys[i], 0, None, None) for i in range(2)])
     _lib.check(_lib.load().tt_tower_fwd2_batched_f32(l0, l1, 2, m, k0, h, n1, rate, seed, off, _stream()), "tt_tower_fwd2_batched_f32")
 
 
@@ -467,10 +468,7 @@ def dense_bwd2(xs, ws, dzs, dxs, dx_relu_srcs, dw_slabs, db_slabs, dx_scale: flo
     n = ws[0].shape[1]
     for i in range(2):
         _chk_bits(dx_relu_bits[i], m, k, "dense_bwd2: dx_relu_bits")
-    arr = (_lib.DenseBwdArgs * 2)(*[_lib.DenseBwdArgs(None if lookups is not None else _p(xs[i]), _p(ws[i]), _p(dzs[i]), _p(dxs[i]),
-                                                     _p(dx_relu_srcs[i]), _p(dw_slabs[i]), _p(db_slabs[i]),
-                                                     lookups[i] if lookups is not None else _no_lookup(),
-                                                     _p(dx_relu_bits[i])) for i in range(2)])
+    arr = _bwd_args(xs, ws, dzs, dxs, dx_relu_srcs, dw_slabs, db_slabs, lookups, dx_relu_bits)
     if riders is not None:
         segs, opt, lr, eps = riders
         arr_s = (DenseSeg * len(segs))(*segs)
@@ -481,10 +479,12 @@ def dense_bwd2(xs, ws, dzs, dxs, dx_relu_srcs, dw_slabs, db_slabs, dx_scale: flo
 
 
 def _bwd_args(xs, ws, dzs, dxs, dx_relu_srcs, dw_slabs, db_slabs, lookups, dx_relu_bits):
-    return (_lib.DenseBwdArgs * 2)(*[_lib.DenseBwdArgs(None if lookups is not None else _p(xs[i]), _p(ws[i]), _p(dzs[i]), _p(dxs[i]),
+    """The ``tt_dense_bwd_args`` array of one layer: an element per tower (two), or the single layer's one."""
+    n = len(ws)
+    return (_lib.DenseBwdArgs * n)(*[_lib.DenseBwdArgs(None if lookups is not None else _p(xs[i]), _p(ws[i]), _p(dzs[i]), _p(dxs[i]),
                                                       _p(dx_relu_srcs[i]), _p(dw_slabs[i]), _p(db_slabs[i]),
                                                       lookups[i] if lookups is not None else _no_lookup(),
-                                                      _p(dx_relu_bits[i])) for i in range(2)])
+                                                      _p(dx_relu_bits[i])) for i in range(n)])
 
 
 def tower_bwd2_supported(m: int, k0: int, k1: int, n: int) -> bool:
@@ -602,6 +602,14 @@ def make_dense_seg(param, accum, grad_slabs, n_slabs: int, l2: float, grad_out=N
 SCORER_PRECISIONS = ("f32", "bf16x3")
 
 
+def _precision_entry(stem: str, precision: str):
+    """(function, its name) of the scorer entry ``stem`` in the given precision."""
+    if precision not in SCORER_PRECISIONS:
+        raise ValueError(f"precision must be one of {SCORER_PRECISIONS}, got {precision!r}")
+    name = f"tt_retrieval_{stem}_f32" if precision == "f32" else f"tt_retrieval_{stem}_bf16x3_f32"
+    return getattr(_lib.load(), name), name
+
+
 def retrieval_workspace_bytes(nq: int, nc: int, dim: int) -> int:
     """Workspace of the fused training entries (retrieval_fwd_bwd): includes the [nq, nc] f32 logit buffer pass 2 reads back."""
     return int(_lib.load().tt_retrieval_workspace_bytes(nq, nc, dim))
@@ -646,14 +654,11 @@ def retrieval_fwd(q, c, inv_temperature: float, workspace, lse, per_row, loss, s
                   cand_prob=None, cand_ids=None, diag_offset: int = 0, hard_thr=None, precision: str = "f32"):
     """Forward only (validation loss).  precision "bf16x3": the logits' products on the bf16 MFMA (dim 128 / 256)."""
     _chk_retrieval(q, c, sample_weight, cand_prob, cand_ids, hard_thr, lse, per_row)
-    if precision not in SCORER_PRECISIONS:
-        raise ValueError(f"precision must be one of {SCORER_PRECISIONS}, got {precision!r}")
-    lib = _lib.load()
-    fn = lib.tt_retrieval_fwd_f32 if precision == "f32" else lib.tt_retrieval_fwd_bf16x3_f32
+    fn, name = _precision_entry("fwd", precision)
     _lib.check(fn(_p(q), _p(c), q.shape[0], c.shape[0], q.shape[1], diag_offset, inv_temperature,
                   _p(sample_weight), _p(cand_prob), _p(cand_ids), _p(hard_thr), _p(workspace),
                   workspace.numel(), _p(lse), _p(per_row), _p(loss), _stream()),
-               "tt_retrieval_fwd_f32" if precision == "f32" else "tt_retrieval_fwd_bf16x3_f32")
+               name)
     return loss
 
 
@@ -668,30 +673,24 @@ def retrieval_bwd(q, c, inv_temperature: float, workspace, lse, dq, dc, sample_w
     return dq, dc
 
 
-
-
 def retrieval_fwd_bwd(q, c, inv_temperature: float, workspace, lse, per_row, loss, dq, dc, sample_weight=None,
                       cand_prob=None, cand_ids=None, diag_offset: int = 0, grad_scale: float = 1.0, hard_thr=None,
                       precision: str = "f32"):
     """Loss and both gradients in two fused passes (training form).  precision "f32": exact f32 products on the
     f32-input MFMA; "bf16x3": the f32-emulated split-bf16 form on the bf16 MFMA (dim 128 / 256)."""
     _chk_retrieval(q, c, sample_weight, cand_prob, cand_ids, hard_thr, lse, per_row, dq, dc)
-    if precision not in SCORER_PRECISIONS:
-        raise ValueError(f"precision must be one of {SCORER_PRECISIONS}, got {precision!r}")
-    lib = _lib.load()
-    fn = lib.tt_retrieval_fwd_bwd_f32 if precision == "f32" else lib.tt_retrieval_fwd_bwd_bf16x3_f32
+    fn, name = _precision_entry("fwd_bwd", precision)
     _lib.check(fn(_p(q), _p(c), q.shape[0], c.shape[0], q.shape[1], diag_offset, inv_temperature,
-                                            _p(sample_weight), _p(cand_prob), _p(cand_ids), _p(hard_thr), grad_scale, _p(workspace),
-              workspace.numel(), _p(lse), _p(per_row), _p(loss), _p(dq), _p(dc), _stream()),
-               "tt_retrieval_fwd_bwd_f32" if precision == "f32" else "tt_retrieval_fwd_bwd_bf16x3_f32")
+                  _p(sample_weight), _p(cand_prob), _p(cand_ids), _p(hard_thr), grad_scale, _p(workspace),
+                  workspace.numel(), _p(lse), _p(per_row), _p(loss), _p(dq), _p(dc), _stream()),
+               name)
     return loss
 
 
 def retrieval_rank(q, c, inv_temperature: float, pos_index, workspace=None, cand_prob=None, out=None, precision: str = "f32"):
     """rank[i] = #candidates scoring strictly above query i's true candidate ``pos_index[i]`` (int32 [nq]).
     precision "bf16x3": the logits' products on the bf16 MFMA (dim 128 / 256)."""
-    if precision not in SCORER_PRECISIONS:
-        raise ValueError(f"precision must be one of {SCORER_PRECISIONS}, got {precision!r}")
+    fn, name = _precision_entry("rank", precision)
     _chk(q, torch.float32, "query_embeddings", 2)
     _chk(c, torch.float32, "candidate_embeddings", 2)
     _chk(pos_index, torch.int64, "pos_index", 1)
@@ -706,15 +705,29 @@ def retrieval_rank(q, c, inv_temperature: float, pos_index, workspace=None, cand
         workspace = torch.empty(retrieval_rank_workspace_bytes(nq, nc, d), dtype=torch.uint8, device=q.device)
     if out is None:
         out = torch.empty(nq, dtype=torch.int32, device=q.device)
-    lib = _lib.load()
-    fn = lib.tt_retrieval_rank_f32 if precision == "f32" else lib.tt_retrieval_rank_bf16x3_f32
     _lib.check(fn(_p(q), _p(c), nq, nc, d, inv_temperature, _p(cand_prob), _p(pos_index),
                   _p(workspace), workspace.numel(), _p(out), _stream()),
-               "tt_retrieval_rank_f32" if precision == "f32" else "tt_retrieval_rank_bf16x3_f32")
+               name)
     return out
 
 
 TOPK_MAX_K = _lib.TT_TOPK_MAX_K
+
+
+def _topk_buffers(what: str, need: int, nq: int, k: int, device, workspace, out):
+    """(workspace, scores, indices) of a top-k call: allocated where the caller passed none, checked where it did."""
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    else:
+        _chk(workspace, torch.uint8, "workspace", 1)
+    if out is None:
+        out = (torch.empty(nq, k, dtype=torch.float32, device=device), torch.empty(nq, k, dtype=torch.int64, device=device))
+    scores, indices = out
+    _chk(scores, torch.float32, "out scores", 2)
+    _chk(indices, torch.int64, "out indices", 2)
+    if tuple(scores.shape) != (nq, k) or tuple(indices.shape) != (nq, k):
+        raise ValueError(f"{what}: out tensors must be [{nq}, {k}]")
+    return workspace, scores, indices
 
 
 def retrieval_topk_workspace_bytes(nq: int, nc: int, dim: int, k: int) -> int:
@@ -771,18 +784,8 @@ def retrieval_topk(q, c, k: int, exclusions=None, workspace=None, out=None):
     if not 1 <= k <= min(TOPK_MAX_K, nc):
         raise ValueError(f"retrieval_topk: k = {k} must be in [1, min({TOPK_MAX_K}, nc = {nc})]")
     off, idx = exclusions_csr(exclusions, nq)
-    need = retrieval_topk_workspace_bytes(nq, nc, d, k)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
-    else:
-        _chk(workspace, torch.uint8, "workspace", 1)
-    if out is None:
-        out = (torch.empty(nq, k, dtype=torch.float32, device=q.device), torch.empty(nq, k, dtype=torch.int64, device=q.device))
-    scores, indices = out
-    _chk(scores, torch.float32, "out scores", 2)
-    _chk(indices, torch.int64, "out indices", 2)
-    if tuple(scores.shape) != (nq, k) or tuple(indices.shape) != (nq, k):
-        raise ValueError(f"retrieval_topk: out tensors must be [{nq}, {k}]")
+    workspace, scores, indices = _topk_buffers("retrieval_topk", retrieval_topk_workspace_bytes(nq, nc, d, k), nq, k, q.device,
+                                               workspace, out)
     _lib.check(_lib.load().tt_retrieval_topk_f32(_p(q), _p(c), nq, nc, d, k, _p(off), _p(idx), _p(workspace),
                                                  workspace.numel(), _p(scores), _p(indices), _stream()),
                "tt_retrieval_topk_f32")
@@ -831,18 +834,8 @@ def ivf_search(q, centroids, list_offsets, list_vectors, list_ids, k: int, nprob
     if check_offsets:
         check_list_offsets(list_offsets, n, "ivf_search")
     off, idx = exclusions_csr(exclusions, nq)
-    need = ivf_search_workspace_bytes(nq, nlist, n, d, k, nprobe)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
-    else:
-        _chk(workspace, torch.uint8, "workspace", 1)
-    if out is None:
-        out = (torch.empty(nq, k, dtype=torch.float32, device=q.device), torch.empty(nq, k, dtype=torch.int64, device=q.device))
-    scores, indices = out
-    _chk(scores, torch.float32, "out scores", 2)
-    _chk(indices, torch.int64, "out indices", 2)
-    if tuple(scores.shape) != (nq, k) or tuple(indices.shape) != (nq, k):
-        raise ValueError(f"ivf_search: out tensors must be [{nq}, {k}]")
+    workspace, scores, indices = _topk_buffers("ivf_search", ivf_search_workspace_bytes(nq, nlist, n, d, k, nprobe), nq, k, q.device,
+                                               workspace, out)
     _lib.check(_lib.load().tt_ivf_search_f32(_p(q), nq, _p(centroids), nlist, _p(list_offsets), _p(list_vectors), _p(list_ids),
                                              n, d, k, nprobe, _p(off), _p(idx), _p(workspace), workspace.numel(), _p(scores),
                                              _p(indices), _stream()),
