@@ -583,6 +583,29 @@ int tt_ivf_search_f32(const float* q, int64_t nq, const float* centroids, int64_
                       const int64_t* excl_offsets, const int64_t* excl_idx, void* workspace, int64_t workspace_bytes,
                       float* out_scores, int64_t* out_idx, tt_stream_t stream);
 
+/* Int8-quantised top-K retrieval with an exact f32 re-rank (added to v10: new symbols only, the version is unchanged).
+ * tt_quantize_rows_i8: per row of x f32 [n, dim], amax = max|x|, scale = amax / 127.0f (one IEEE f32 division),
+ * code = clamp(rintf(x / scale), -127, 127) (half to even); a row with amax == 0 gets scale 0 and all-zero codes.
+ * codes int8 [n, dim], scales f32 [n]; x and codes 16-byte aligned; dim in {32, 64, 128, 256}.  Inputs must be finite.
+ *
+ * tt_retrieval_topk_i8_f32, stage 1 (scan): the query rows are quantised with the same formula (qc, qscale);
+ * iscore[i][j] = sum_d qc[i][d] * codes[j][d] in int32 (exact in f32); key = float(iscore) * scales[j] (one f32
+ * multiply); the k1 candidates of a query are its best by (key descending, index ascending), also at the cut.  Excluded
+ * ids (CSR as tt_retrieval_topk_f32) never take a candidate slot.
+ * Stage 2 (finish): with c f32 [nc, dim], every candidate gets the f32 score tt_retrieval_topk_f32 gives that pair, bit
+ * for bit, and the best k by (score descending, index ascending) are written.  With c == NULL there is no re-rank, k1 == k
+ * is required, and the output is the stage-1 order with scores key * qscale_i.  Fewer than k candidates left: the tail is
+ * (-inf, -1).  A query's row is bit-identical alone or in any batch.
+ * Limits: dim in {32, 64, 128, 256}, 1 <= k <= k1 <= min(TT_TOPK_MAX_K, nc), nc < 2^31; q, codes and c 16-byte aligned.
+ * Launches only (no synchronisation, no copy to the host).  Every refusal is TT_ERR_INVALID_ARG before any launch.
+ * Workspace (256-byte aligned): tt_retrieval_topk_i8_workspace_bytes(...) (0 for arguments the call refuses). */
+int tt_quantize_rows_i8(const float* x, int64_t n, int32_t dim, int8_t* codes, float* scales, tt_stream_t stream);
+int64_t tt_retrieval_topk_i8_workspace_bytes(int64_t nq, int64_t nc, int32_t dim, int32_t k, int32_t k1);
+int tt_retrieval_topk_i8_f32(const float* q, const int8_t* codes, const float* scales, const float* c, int64_t nq, int64_t nc,
+                             int32_t dim, int32_t k, int32_t k1, const int64_t* excl_offsets, const int64_t* excl_idx,
+                             void* workspace, int64_t workspace_bytes, float* out_scores, int64_t* out_idx,
+                             tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

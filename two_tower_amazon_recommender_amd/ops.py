@@ -792,6 +792,73 @@ def retrieval_topk(q, c, k: int, exclusions=None, workspace=None, out=None):
     return scores, indices
 
 
+def quantize_rows_i8(x, out=None):
+    """Per-row symmetric int8 quantisation (``tt_quantize_rows_i8``): (codes int8 [n, D], scales f32 [n]) with
+    scale = max|row| / 127 and code = clamp(rint(x / scale), -127, 127), half to even; a zero row has scale 0 and zero
+    codes.  ``out``: optional (codes, scales) to write into."""
+    _chk(x, torch.float32, "x", 2)
+    n, d = x.shape
+    if d not in (32, 64, 128, 256):
+        raise ValueError(f"quantize_rows_i8: dim = {d} must be one of 32, 64, 128, 256")
+    if n < 1:
+        raise ValueError("quantize_rows_i8: x must have at least one row")
+    if out is None:
+        out = (torch.empty(n, d, dtype=torch.int8, device=x.device), torch.empty(n, dtype=torch.float32, device=x.device))
+    codes, scales = out
+    _chk(codes, torch.int8, "out codes", 2)
+    _chk(scales, torch.float32, "out scales", 1)
+    if tuple(codes.shape) != (n, d) or scales.numel() != n:
+        raise ValueError(f"quantize_rows_i8: out tensors must be [{n}, {d}] and [{n}]")
+    _lib.check(_lib.load().tt_quantize_rows_i8(_p(x), n, d, _p(codes), _p(scales), _stream()), "tt_quantize_rows_i8")
+    return codes, scales
+
+
+def default_k1(k: int, nc: int, rerank: bool = True, factor: int = 4) -> int:
+    """Stage-1 candidates of ``retrieval_topk_i8``: min(TOPK_MAX_K, nc, max(factor * k, 32)) with a re-rank, k without."""
+    return min(TOPK_MAX_K, nc, max(factor * k, 32)) if rerank else k
+
+
+def retrieval_topk_i8_workspace_bytes(nq: int, nc: int, dim: int, k: int, k1: int) -> int:
+    """Workspace of ``retrieval_topk_i8`` (0 for a shape the call refuses)."""
+    return int(_lib.load().tt_retrieval_topk_i8_workspace_bytes(nq, nc, dim, k, k1))
+
+
+def retrieval_topk_i8(q, codes, scales, k: int, c=None, k1: int | None = None, exclusions=None, workspace=None, out=None):
+    """Int8-quantised top-k: the queries are quantised like the corpus (``quantize_rows_i8``), the int8 scan keeps each
+    query's ``k1`` best candidates by (int32 dot product * row scale, index ascending), and, with the f32 corpus ``c``,
+    those are re-scored exactly (``retrieval_topk``'s score of the pair, bit for bit) and the best k returned.  Without
+    ``c`` the stage-1 order is returned (k1 = k) with scores key * query scale.  ``k1`` defaults to
+    min(TOPK_MAX_K, nc, max(4 k, 32)) with ``c`` and to k without.  Exclusions, padding and outputs as ``retrieval_topk``."""
+    _chk(q, torch.float32, "query_embeddings", 2)
+    _chk(codes, torch.int8, "codes", 2)
+    _chk(scales, torch.float32, "scales", 1)
+    nq, d = q.shape
+    nc = codes.shape[0]
+    if codes.shape[1] != d:
+        raise RuntimeError(f"retrieval_topk_i8: embedding dims differ: q {d}, codes {codes.shape[1]}")
+    if scales.numel() != nc:
+        raise ValueError(f"retrieval_topk_i8: scales needs {nc} entries (one per code row), got {scales.numel()}")
+    if c is not None:
+        _chk(c, torch.float32, "candidate_embeddings", 2)
+        if tuple(c.shape) != (nc, d):
+            raise RuntimeError(f"retrieval_topk_i8: c must be [{nc}, {d}] like codes, got {tuple(c.shape)}")
+    k = int(k)
+    if not 1 <= k <= min(TOPK_MAX_K, nc):
+        raise ValueError(f"retrieval_topk_i8: k = {k} must be in [1, min({TOPK_MAX_K}, nc = {nc})]")
+    k1 = default_k1(k, nc, c is not None) if k1 is None else int(k1)
+    if not k <= k1 <= min(TOPK_MAX_K, nc):
+        raise ValueError(f"retrieval_topk_i8: k1 = {k1} must be in [k = {k}, min({TOPK_MAX_K}, nc = {nc})]")
+    if c is None and k1 != k:
+        raise ValueError(f"retrieval_topk_i8: without c there is no re-rank: k1 = {k1} must equal k = {k}")
+    off, idx = exclusions_csr(exclusions, nq)
+    workspace, scores, indices = _topk_buffers("retrieval_topk_i8", retrieval_topk_i8_workspace_bytes(nq, nc, d, k, k1), nq, k,
+                                               q.device, workspace, out)
+    _lib.check(_lib.load().tt_retrieval_topk_i8_f32(_p(q), _p(codes), _p(scales), _p(c), nq, nc, d, k, k1, _p(off), _p(idx),
+                                                    _p(workspace), workspace.numel(), _p(scores), _p(indices), _stream()),
+               "tt_retrieval_topk_i8_f32")
+    return scores, indices
+
+
 def check_list_offsets(list_offsets, n: int, what: str) -> None:
     """Raise unless list_offsets starts at 0, is non-decreasing and ends at n (checked on the device)."""
     bad = (list_offsets[0] != 0) | (list_offsets[-1] != n) | (list_offsets.diff() < 0).any()

@@ -2,7 +2,9 @@
 written by ``train.py --save``: the model is rebuilt from the checkpoint's ``config``, the whole item corpus goes through
 the item tower once, and users are answered in batches by ``serving.BruteForce`` (one fused score-and-select pass over
 the corpus per batch; no [users x items] score matrix) or, with ``--index ivf``, by the approximate ``serving.IVF``
-(``--nlist`` k-means lists, ``--nprobe`` of them scanned per user; ``--nprobe`` = ``--nlist`` is exact).
+(``--nlist`` k-means lists, ``--nprobe`` of them scanned per user; ``--nprobe`` = ``--nlist`` is exact), or, with
+``--index int8``, by ``serving.Int8BruteForce`` (an int8 scan of the whole corpus, the best ``--rerank`` x k candidates of
+every user re-scored exactly).
 
     python -m two_tower_amazon_recommender_amd.recommend --checkpoint ck.pt --data interactions.parquet \\
         --all-users --exclude-seen --k 10 --out recs.parquet
@@ -39,13 +41,16 @@ def parse(argv=None):
     ap.add_argument("--out", default="recs.parquet", help="output parquet (user_idx, rank, item_idx, score)")
     ap.add_argument("--batch-users", type=int, default=4096, help="users per top-k call (bounds peak device memory)")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--index", choices=("brute", "ivf"), default="brute",
-                    help="brute: exact top-k over the whole corpus; ivf: approximate inverted-file index")
+    ap.add_argument("--index", choices=("brute", "ivf", "int8"), default="brute",
+                    help="brute: exact top-k over the whole corpus; ivf: approximate inverted-file index; int8: quantised "
+                         "scan of the whole corpus with an exact re-rank")
     ap.add_argument("--nlist", type=int, default=None, help="--index ivf: number of k-means lists (default 1024, at most the "
                                                              "number of items)")
     ap.add_argument("--nprobe", type=int, default=None, help=f"--index ivf: lists scanned per user (1..min({MAX_K}, nlist); "
                                                               "default 32)")
     ap.add_argument("--seed", type=int, default=0, help="--index ivf: k-means seed")
+    ap.add_argument("--rerank", type=int, default=None, help="--index int8: candidates re-scored exactly per user, as a multiple "
+                                                              f"of --k (default 4; at least 32 and at most {MAX_K} candidates)")
     args = ap.parse_args(argv)
     if not 1 <= args.k <= MAX_K:
         ap.error(f"--k must be in [1, {MAX_K}], got {args.k}")
@@ -53,6 +58,12 @@ def parse(argv=None):
         ap.error("--batch-users must be positive")
     if args.index != "ivf" and (args.nlist is not None or args.nprobe is not None):
         ap.error("--nlist / --nprobe need --index ivf")
+    if args.index != "int8" and args.rerank is not None:
+        ap.error("--rerank needs --index int8")
+    if args.index == "int8":
+        args.rerank = 4 if args.rerank is None else args.rerank
+        if args.rerank < 1:
+            ap.error(f"--rerank must be positive, got {args.rerank}")
     if args.index == "ivf":
         args.nlist = 1024 if args.nlist is None else args.nlist
         args.nprobe = min(32, args.nlist) if args.nprobe is None else args.nprobe
@@ -98,7 +109,7 @@ def main(argv=None) -> int:
     import pyarrow as pa
     import pyarrow.parquet as pq
     from . import data as datamod
-    from .serving import IVF, BruteForce
+    from .serving import IVF, BruteForce, Int8BruteForce
     from .trainer import TwoTowerConfig, TwoTowerTrainer
 
     dev = torch.device(args.device)
@@ -135,6 +146,8 @@ def main(argv=None) -> int:
         if args.nlist > cfg.n_items:
             raise SystemExit(f"--nlist {args.nlist} exceeds the model's {cfg.n_items} items")
         bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat)
+    elif args.index == "int8":
+        bf = Int8BruteForce(k=k, rerank=args.rerank).index_from_trainer(trainer, item_cat)
     else:
         bf = BruteForce(k=k).index_from_trainer(trainer, item_cat)
     seen = seen_csr(user_idx, item_idx, cfg.n_users) if args.exclude_seen else None

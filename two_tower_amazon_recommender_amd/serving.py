@@ -13,6 +13,12 @@ one ``tt_ivf_search_f32`` per call).  It has the same methods and answers exactl
 items of the probed lists; with ``nprobe = nlist`` the two agree bit for bit.
 
     ivf = IVF(k=10, nlist=1024, nprobe=32).index_from_trainer(trainer)
+
+``Int8BruteForce`` scans the whole corpus as int8 codes (a quarter of the bytes; one ``tt_retrieval_topk_i8_f32`` per
+call) and re-scores the ``rerank * k`` survivors of every query exactly, so the scores it returns are ``BruteForce``'s;
+with ``keep_f32=False`` it serves the quantised order alone, from a quarter of the memory.
+
+    i8 = Int8BruteForce(k=10, rerank=4).index_from_trainer(trainer)
 """
 from __future__ import annotations
 
@@ -223,6 +229,88 @@ class IVF(BruteForce):
         k = self.k if k is None else int(k)
         scores, idx = ops.ivf_search(q, self.centroids, self.list_offsets, self.list_vectors, self.list_ids, k, self.nprobe,
                                      exclusions=exclusions, workspace=self._workspace(q.shape[0], k), check_offsets=False)
+        if self._identifiers is None:
+            return scores, idx
+        ids = self._identifiers[idx.clamp(min=0)]
+        return scores, torch.where(idx >= 0, ids, torch.full_like(ids, -1))
+
+
+class Int8BruteForce(BruteForce):
+    """Quantised exhaustive top-k index: the corpus is held as per-row symmetric int8 codes and f32 scales
+    (``ops.quantize_rows_i8``), every query is quantised the same way inside the scan, and the k1 = min(TOPK_MAX_K, n,
+    max(rerank * k, 32)) best candidates by quantised score are re-scored against the f32 rows (``keep_f32=True``): the
+    returned scores are then exactly ``BruteForce``'s for the returned items, and the answer differs only where a true
+    top-k item fell outside the k1 candidates.  ``keep_f32=False`` drops the f32 rows: no re-rank, k1 = k, scores are the
+    dequantised products.  Exclusions and identifiers as ``BruteForce``."""
+
+    def __init__(self, query_model=None, k: int = 10, rerank: int = 4, keep_f32: bool = True):
+        super().__init__(query_model, k)
+        self.rerank, self.keep_f32 = int(rerank), bool(keep_f32)
+        if self.rerank < 1:
+            raise ValueError(f"Int8BruteForce: rerank must be >= 1, got {self.rerank}")
+        self.codes = self.scales = None
+
+    def index(self, candidates: torch.Tensor, identifiers=None) -> "Int8BruteForce":
+        """candidates: [n, D] f32 device tensor, D in {32, 64, 128, 256}.  identifiers: as ``BruteForce.index``."""
+        super().index(candidates, identifiers)
+        self.codes, self.scales = ops.quantize_rows_i8(self._candidates)
+        if not self.keep_f32:
+            self._candidates = None
+        self._ws = None
+        return self
+
+    def k1(self, k: int) -> int:
+        """Stage-1 candidates per query for a top-k request."""
+        return ops.default_k1(k, self.codes.shape[0], self.keep_f32, self.rerank)
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self) -> dict:
+        if self.codes is None:
+            raise RuntimeError("Int8BruteForce: call index() or index_from_trainer() first")
+        state = {"codes": self.codes, "scales": self.scales}
+        if self.keep_f32:
+            state["candidates"] = self._candidates
+        return state
+
+    def load_state_dict(self, state: dict) -> "Int8BruteForce":
+        codes, scales = state["codes"], state["scales"]
+        if codes.dim() != 2 or codes.dtype != torch.int8 or scales.dim() != 1 or scales.numel() != codes.shape[0]:
+            raise ValueError("Int8BruteForce.load_state_dict: codes must be int8 [n, D] and scales [n]")
+        cand = state.get("candidates")
+        if self.keep_f32:
+            if cand is None:
+                raise ValueError("Int8BruteForce.load_state_dict: keep_f32=True needs the state's f32 'candidates'")
+            if tuple(cand.shape) != tuple(codes.shape):
+                raise ValueError(f"Int8BruteForce.load_state_dict: candidates {tuple(cand.shape)} do not match codes "
+                                 f"{tuple(codes.shape)}")
+            self._candidates = cand.to(torch.float32).contiguous()
+        else:
+            self._candidates = None
+        self.codes = codes.contiguous()
+        self.scales = scales.to(torch.float32).contiguous()
+        self._identifiers = None
+        self._ws = None
+        return self
+
+    # ------------------------------------------------------------------ query
+    def _workspace(self, nq: int, k: int) -> torch.Tensor:
+        n, d = self.codes.shape
+        need = max(ops.retrieval_topk_i8_workspace_bytes(nq, n, d, k, self.k1(k)), 1)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.codes.device)
+        return self._ws
+
+    def _query(self, queries, exclusions, k):
+        if self.codes is None:
+            raise RuntimeError("Int8BruteForce: call index() or index_from_trainer() first")
+        q = self.query_model(queries) if self.query_model is not None else queries
+        q = q.to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        k = self.k if k is None else int(k)
+        scores, idx = ops.retrieval_topk_i8(q, self.codes, self.scales, k, c=self._candidates, k1=self.k1(k),
+                                            exclusions=exclusions, workspace=self._workspace(q.shape[0], k))
         if self._identifiers is None:
             return scores, idx
         ids = self._identifiers[idx.clamp(min=0)]

@@ -254,6 +254,51 @@ def _(q, centroids, list_offsets, list_vectors, list_ids, k, nprobe, exclusion_o
     return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
 
 
+_I8_WS: dict = {}
+
+
+def _i8_ws(nq: int, nc: int, d: int, k: int, k1: int, device) -> Tensor:
+    """Workspace of the int8 top-k op, kept per (device, stream) like the top-k op's (the largest one seen)."""
+    need = max(ops.retrieval_topk_i8_workspace_bytes(nq, nc, d, k, k1), 1)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    hit = _I8_WS.get(key)
+    if hit is not None and hit.numel() >= need:
+        return hit
+    _I8_WS.pop(key, None)
+    buf = _I8_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+@torch.library.custom_op(f"{NS}::quantize_rows_i8", mutates_args=(), device_types="cuda")
+def quantize_rows_i8(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """Per-row symmetric int8 quantisation (ops.quantize_rows_i8): (codes int8 [n, D], scales f32 [n])."""
+    return ops.quantize_rows_i8(x.contiguous())
+
+
+@quantize_rows_i8.register_fake
+def _(x):
+    return x.new_empty(x.shape, dtype=torch.int8), x.new_empty((x.shape[0],))
+
+
+@torch.library.custom_op(f"{NS}::retrieval_topk_i8", mutates_args=(), device_types="cuda")
+def retrieval_topk_i8(query_embeddings: Tensor, codes: Tensor, scales: Tensor, candidate_embeddings: Optional[Tensor], k: int,
+                      k1: int, exclusion_offsets: Optional[Tensor], exclusion_indices: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """Int8-quantised top-k (ops.retrieval_topk_i8): k1 stage-1 candidates per query from the int8 scan, re-scored exactly
+    against candidate_embeddings when given (else k1 must equal k); optional CSR exclusions.  Not differentiable (serving)."""
+    q = query_embeddings.contiguous()
+    c = None if candidate_embeddings is None else candidate_embeddings.contiguous()
+    ex = None if exclusion_offsets is None else (exclusion_offsets.contiguous(), exclusion_indices.contiguous())
+    ws = _i8_ws(q.shape[0], codes.shape[0], q.shape[1], k, k1, q.device)
+    return ops.retrieval_topk_i8(q, codes.contiguous(), scales.contiguous(), k, c=c, k1=k1, exclusions=ex, workspace=ws)
+
+
+@retrieval_topk_i8.register_fake
+def _(q, codes, scales, c, k, k1, exclusion_offsets, exclusion_indices):
+    return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
+
+
 # --------------------------------------------------------------------------------------------- a2 dense layers
 @torch.library.custom_op(f"{NS}::dense_fwd", mutates_args=(), device_types="cuda")
 def dense_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], relu: bool) -> Tensor:
@@ -320,5 +365,5 @@ def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: T
         ops.sparse_adagrad_(table, accum, grads.contiguous(), plan, lr, eps)
 
 
-OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "dense_fwd",
+OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "dense_fwd",
        "dense_bwd", "sparse_update_")
