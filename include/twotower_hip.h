@@ -57,7 +57,10 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * tags: fill, gather, sparse_plan, sparse_apply, dense_fwd, dense_bwd (dx+dw in one launch), dense_bwd_dx, dense_bwd_dw,
  * dense_update, optimizer (sparse + dense in one launch), score_fwd, score_bwd, score_fused, score_rank, score_aux, route, scatter_rows, encode_ids,
  * topk_select, topk_merge (and the scope topk around a whole tt_retrieval_topk_f32 call), ivf_bucket, ivf_select (and
- * the scope ivf around a whole tt_ivf_search_f32 call).
+ * the scope ivf around a whole tt_ivf_search_f32 call), quantize_i8, topk_i8_scan, topk_i8_rerank, topk_i8_scale (and the
+ * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
+ * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
+ * topk_i8_rerank, topk_i8_scale).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -605,6 +608,34 @@ int tt_retrieval_topk_i8_f32(const float* q, const int8_t* codes, const float* s
                              int32_t dim, int32_t k, int32_t k1, const int64_t* excl_offsets, const int64_t* excl_idx,
                              void* workspace, int64_t workspace_bytes, float* out_scores, int64_t* out_idx,
                              tt_stream_t stream);
+
+/* Int8 IVF (added to v10: new symbols only, the version is unchanged): tt_retrieval_topk_i8_f32 restricted to the rows of
+ * the nprobe inverted lists tt_ivf_search_f32 probes.  Index: centroids, list_offsets and list_ids exactly as
+ * tt_ivf_search_f32; list_codes int8 [n, dim] and list_scales f32 [n], the tt_quantize_rows_i8 output of the items in list
+ * order; c (nullable) the f32 corpus [n, dim] in ORIGINAL id order (the row of original id i is c + i * dim: the re-rank
+ * gathers by the ids stage 1 produced).
+ * Probes: the lists tt_retrieval_topk_f32(q, centroids, nprobe) returns (f32 scores; centroids are not quantised).
+ * Stage 1: the query is quantised by tt_quantize_rows_i8's formula; key = float(int32 dot) * list_scales[row] (one f32
+ * multiply); a candidate's id is list_ids[row]; the k1 candidates are the best by (key descending, original id ascending),
+ * also at the cut; excluded original ids (CSR as tt_retrieval_topk_f32) never take a slot.
+ * Stage 2: with c, every candidate gets tt_retrieval_topk_f32's score of that pair, bit for bit, and the best k by (score
+ * descending, id ascending) are written; with c == NULL, k1 == k is required and the output is the stage-1 order with
+ * scores key * qscale.  Fewer than k candidates left: the tail is (-inf, -1).
+ * Hence: with nprobe == nlist the output equals tt_retrieval_topk_i8_f32 over the whole corpus (codes, scales and c in
+ * original order), bit for bit; with fewer probes it equals that call over the union of the probed lists gathered in
+ * ascending original id; a query's row is identical alone, in any batch and on any run.
+ * Limits: dim in {32, 64, 128, 256}, 1 <= k <= k1 <= min(TT_TOPK_MAX_K, n), 1 <= nprobe <= min(nlist, TT_TOPK_MAX_K),
+ * n < 2^31, nq * nprobe <= 2^31 - 1; q, centroids, list_codes and c 16-byte aligned, the others to their element size.
+ * Every refusal is TT_ERR_INVALID_ARG before any launch, except a short workspace: TT_ERR_WORKSPACE, as tt_ivf_search_f32.
+ * Launches only (no synchronisation, no copy to the host).  All row offsets are 64-bit (n * dim may exceed 2^31 bytes).
+ * Workspace (256-byte aligned): tt_ivf_search_i8_workspace_bytes(...) (0 for arguments the call refuses). */
+int64_t tt_ivf_search_i8_workspace_bytes(int64_t nq, int64_t nlist, int64_t n, int32_t dim, int32_t k, int32_t k1,
+                                         int32_t nprobe);
+int tt_ivf_search_i8_f32(const float* q, int64_t nq, const float* centroids, int64_t nlist, const int64_t* list_offsets,
+                         const int8_t* list_codes, const float* list_scales, const int32_t* list_ids, const float* c, int64_t n,
+                         int32_t dim, int32_t k, int32_t k1, int32_t nprobe, const int64_t* excl_offsets,
+                         const int64_t* excl_idx, void* workspace, int64_t workspace_bytes, float* out_scores, int64_t* out_idx,
+                         tt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,9 @@ SIGNATURES = {
     "tt_quantize_rows_i8": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
     "tt_retrieval_topk_i8_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "tt_retrieval_topk_i8_f32": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p]),
+    "tt_ivf_search_i8_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "tt_ivf_search_i8_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p,
+                                       _p, _p]),
     "tt_retrieval_bwd_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _p, _p, _f, _p, _i64, _p, _p, _p]),
 }
 

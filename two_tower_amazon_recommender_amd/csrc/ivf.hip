@@ -31,6 +31,8 @@
 // average list has 64-row pieces and no more than keep the [nq][nprobe * S][k] lists within 1 GiB.  Large batches get
 // S = 1: shorter chunks would let more candidates survive into the selection queues (k of every chunk) for no gain in
 // parallelism.
+// Launches 1 and 2 and the chunk rule are host functions of namespace tt (ivf_probe_plan, ivf_probe_bucket; declared in
+// topk_select.h): ivf_i8.hip's int8 search starts with the same two launches into the same workspace layout.
 #include "topk_select.h"
 
 namespace {
@@ -49,34 +51,18 @@ struct IvfPlan {
   int S;                        // chunks per list
   int nl;                       // lists per query entering the merge: nprobe * S
   int64_t grid;                 // upper bound of the (list, chunk, query tile) work items
-  int64_t coarse_bytes;         // workspace regions (byte offsets)
-  int64_t off_probe_s, off_probe_i, off_cnt, off_pstart, off_tstart, off_pairs, off_as, off_ai, off_bs, off_bi;
+  tt::IvfProbePlan probe;       // the probe + bucket regions (shared with ivf_i8.hip)
+  int64_t off_as, off_ai, off_bs, off_bi;
   int64_t total;
 };
 
 IvfPlan ivf_plan(int64_t nq, int64_t nlist, int64_t n, int dim, int k, int nprobe) {
   IvfPlan p{};
-  const int64_t P = nq * nprobe;
-  int64_t est = P < nlist ? P : nlist;                       // work items before chunking, roughly
-  if (est < (P + 31) / 32) est = (P + 31) / 32;
-  int64_t S = (kTargetWaves + est - 1) / est;
-  const int64_t by_rows = (n / nlist + kMinRowsPerChunk - 1) / kMinRowsPerChunk;
-  if (S > by_rows) S = by_rows;
-  if (S > kMaxChunks) S = kMaxChunks;
-  const int64_t by_ws = kChunkWsCap / (P * (int64_t)k * 8);
-  if (S > by_ws) S = by_ws;
-  if (S < 1) S = 1;
-  p.S = (int)S;
-  p.nl = nprobe * p.S;
-  p.grid = ((P + 31) / 32 + (P < nlist ? P : nlist)) * S;    // sum over lists of ceil(c_l / 32) <= ceil(P / 32) + #lists
-  p.coarse_bytes = align256(tt::topk_workspace_bytes_split(nq, nlist, nprobe, kCoarseMinCols));
-  int64_t o = p.coarse_bytes;
-  p.off_probe_s = o; o += align256(P * 4);
-  p.off_probe_i = o; o += align256(P * 8);
-  p.off_cnt = o; o += align256(nlist * 4);
-  p.off_pstart = o; o += align256((nlist + 1) * 4);
-  p.off_tstart = o; o += align256((nlist + 1) * 4);
-  p.off_pairs = o; o += align256(P * 4);
+  p.probe = tt::ivf_probe_plan(nq, nlist, n, k, nprobe);
+  p.S = p.probe.S;
+  p.nl = p.probe.nl;
+  p.grid = p.probe.grid;
+  int64_t o = p.probe.bytes;
   const int64_t bytes_a = align256(nq * (int64_t)p.nl * k * 4);
   const int64_t bytes_b = tt::topk_merge_b_bytes(nq, p.nl, k);
   p.off_as = o; o += bytes_a;
@@ -253,6 +239,52 @@ bool shape_ok(int64_t nq, int64_t nlist, int64_t n, int32_t dim, int32_t k, int3
 
 }  // namespace
 
+// The chunk rule and the probe + bucket workspace regions, for lists of list_k entries per (query, probe, chunk).
+tt::IvfProbePlan tt::ivf_probe_plan(int64_t nq, int64_t nlist, int64_t n, int list_k, int nprobe) {
+  IvfProbePlan p{};
+  const int64_t P = nq * nprobe;
+  int64_t est = P < nlist ? P : nlist;                       // work items before chunking, roughly
+  if (est < (P + 31) / 32) est = (P + 31) / 32;
+  int64_t S = (kTargetWaves + est - 1) / est;
+  const int64_t by_rows = (n / nlist + kMinRowsPerChunk - 1) / kMinRowsPerChunk;
+  if (S > by_rows) S = by_rows;
+  if (S > kMaxChunks) S = kMaxChunks;
+  const int64_t by_ws = kChunkWsCap / (P * (int64_t)list_k * 8);
+  if (S > by_ws) S = by_ws;
+  if (S < 1) S = 1;
+  p.S = (int)S;
+  p.nl = nprobe * p.S;
+  p.grid = ((P + 31) / 32 + (P < nlist ? P : nlist)) * S;    // sum over lists of ceil(c_l / 32) <= ceil(P / 32) + #lists
+  int64_t o = align256(tt::topk_workspace_bytes_split(nq, nlist, nprobe, kCoarseMinCols));
+  p.off_probe_s = o; o += align256(P * 4);
+  p.off_probe_i = o; o += align256(P * 8);
+  p.off_cnt = o; o += align256(nlist * 4);
+  p.off_pstart = o; o += align256((nlist + 1) * 4);
+  p.off_tstart = o; o += align256((nlist + 1) * 4);
+  p.off_pairs = o; o += align256(P * 4);
+  p.bytes = o;
+  return p;
+}
+
+// Launches 1 and 2: the coarse probe into the workspace, then the bucket kernel (arguments already validated).
+int tt::ivf_probe_bucket(const float* q, const float* centroids, int64_t nq, int64_t nlist, int dim, int nprobe,
+                         const IvfProbePlan& pl, void* workspace, hipStream_t stream) {
+  char* ws = static_cast<char*>(workspace);
+  float* probe_s = reinterpret_cast<float*>(ws + pl.off_probe_s);
+  int64_t* probe_i = reinterpret_cast<int64_t*>(ws + pl.off_probe_i);
+  int rc = tt::topk_run(q, centroids, nq, nlist, dim, nprobe, nullptr, nullptr, ws, probe_s, probe_i, stream, kCoarseMinCols);
+  if (rc != TT_OK) return rc;
+  BucketArgs b{};
+  b.probe = probe_i; b.P = nq * nprobe; b.nlist = nlist; b.S = pl.S;
+  b.cnt = reinterpret_cast<int32_t*>(ws + pl.off_cnt);
+  b.pstart = reinterpret_cast<int32_t*>(ws + pl.off_pstart);
+  b.tstart = reinterpret_cast<int32_t*>(ws + pl.off_tstart);
+  b.pairs = reinterpret_cast<int32_t*>(ws + pl.off_pairs);
+  const unsigned bucket_lds = nlist <= kBucketLdsLists ? (unsigned)(nlist * 4) : 0u;
+  tt::launch("ivf_bucket", ivf_bucket_kernel, dim3(1), dim3(kBucketThreads), bucket_lds, stream, b);
+  return tt::check_launch("ivf_bucket");
+}
+
 extern "C" int64_t tt_ivf_search_workspace_bytes(int64_t nq, int64_t nlist, int64_t n, int32_t dim, int32_t k, int32_t nprobe) {
   if (!shape_ok(nq, nlist, n, dim, k, nprobe)) return 0;
   const IvfPlan pl = ivf_plan(nq, nlist, n, dim, k, nprobe);
@@ -292,24 +324,15 @@ extern "C" int tt_ivf_search_f32(const float* q, int64_t nq, const float* centro
   hipStream_t stream = tt::as_stream(stream_);
   tt::ProfScope scope("ivf", stream);
   char* ws = static_cast<char*>(workspace);
-  float* probe_s = reinterpret_cast<float*>(ws + pl.off_probe_s);
-  int64_t* probe_i = reinterpret_cast<int64_t*>(ws + pl.off_probe_i);
-  int rc = tt::topk_run(q, centroids, nq, nlist, dim, nprobe, nullptr, nullptr, ws, probe_s, probe_i, stream, kCoarseMinCols);
+  int rc = tt::ivf_probe_bucket(q, centroids, nq, nlist, dim, nprobe, pl.probe, workspace, stream);
   if (rc != TT_OK) return rc;
-
-  BucketArgs b{};
-  b.probe = probe_i; b.P = nq * nprobe; b.nlist = nlist; b.S = pl.S;
-  b.cnt = reinterpret_cast<int32_t*>(ws + pl.off_cnt);
-  b.pstart = reinterpret_cast<int32_t*>(ws + pl.off_pstart);
-  b.tstart = reinterpret_cast<int32_t*>(ws + pl.off_tstart);
-  b.pairs = reinterpret_cast<int32_t*>(ws + pl.off_pairs);
-  const unsigned bucket_lds = nlist <= kBucketLdsLists ? (unsigned)(nlist * 4) : 0u;
-  tt::launch("ivf_bucket", ivf_bucket_kernel, dim3(1), dim3(kBucketThreads), bucket_lds, stream, b);
-  if ((rc = tt::check_launch("ivf_bucket")) != TT_OK) return rc;
 
   IvfSelArgs a{};
   a.q = q; a.lv = list_vectors; a.lids = list_ids; a.loff = list_offsets; a.nlist = nlist; a.k = k; a.nprobe = nprobe;
-  a.S = pl.S; a.pstart = b.pstart; a.tstart = b.tstart; a.pairs = b.pairs;
+  a.S = pl.S;
+  a.pstart = reinterpret_cast<const int32_t*>(ws + pl.probe.off_pstart);
+  a.tstart = reinterpret_cast<const int32_t*>(ws + pl.probe.off_tstart);
+  a.pairs = reinterpret_cast<const int32_t*>(ws + pl.probe.off_pairs);
   a.excl_off = excl_offsets; a.excl_idx = excl_idx;
   a.ws_s = reinterpret_cast<float*>(ws + pl.off_as); a.ws_i = reinterpret_cast<int32_t*>(ws + pl.off_ai);
   const int rows = nq < 32 ? (int)nq : 32;                   // a list holds each query at most once

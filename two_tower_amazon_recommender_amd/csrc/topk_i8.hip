@@ -34,7 +34,9 @@
 // candidates per split - about k1 (1 + ln(len / k1)) candidates survive per (query, split), and each split's list of k1
 // goes through the merge rounds, so splits are longer than the exact kernel's 512-row minimum.
 // LDS: scan min(nq, 32) x (k1 + 48) x 8 B; re-rank 2 KB.
+// The quantiser's inline helpers live in quant_i8.h; the finish launch is tt::i8_finish_launch, which ivf_i8.hip ends with too.
 #include "topk_select.h"
+#include "quant_i8.h"
 
 namespace {
 
@@ -44,36 +46,21 @@ using tt::topk::beats;
 using tt::topk::kMaxEntries;
 using tt::topk::kQueue;
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
+using tt::i8::amax4;
+using tt::i8::i32x16;
+using tt::i8::i32x4;
+using tt::i8::kRing;
+using tt::i8::quant4;
+using tt::i8::row_scale;
 
 constexpr int kTargetWaves = 2048;       // 256 CUs x 8
 constexpr int kMinColsPerSplit = 2048;
 constexpr int kMaxSplits = 4096;
-constexpr int kRing = 4;                 // tile buffers: one being scored, three in flight
 constexpr int kQuantThreads = 256;
 
 int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // ---------------------------------------------------------------------------------------------------- quantiser
-__device__ __forceinline__ float row_scale(float amax) { return amax / 127.0f; }
-
-__device__ __forceinline__ int quant1(float x, float scale) {
-  if (scale == 0.f) return 0;
-  float r = rintf(x / scale);
-  r = fminf(fmaxf(r, -127.f), 127.f);
-  return (int)r;
-}
-
-__device__ __forceinline__ int quant4(f32x4 v, float scale) {
-  return (quant1(v[0], scale) & 255) | ((quant1(v[1], scale) & 255) << 8) | ((quant1(v[2], scale) & 255) << 16) |
-         ((quant1(v[3], scale) & 255) << 24);
-}
-
-__device__ __forceinline__ float amax4(float m, f32x4 v) {
-  return fmaxf(fmaxf(fmaxf(m, fabsf(v[0])), fmaxf(fabsf(v[1]), fabsf(v[2]))), fabsf(v[3]));
-}
-
 struct QuantArgs {
   const float* x;
   int64_t n;
@@ -464,6 +451,24 @@ int launch_quantize(const QuantArgs& a, hipStream_t stream) {
 
 }  // namespace
 
+int tt::i8_finish_launch(const float* q, const float* c, const float* cand_s, const int64_t* cand_i, const float* qscale, int64_t nq,
+                         int dim, int k, int k1, float* out_scores, int64_t* out_idx, hipStream_t stream) {
+  FinArgs f{};
+  f.q = q; f.c = c; f.cand_s = cand_s; f.cand_i = cand_i; f.qscale = qscale; f.k = k; f.k1 = k1;
+  f.out_s = out_scores; f.out_i = out_idx;
+  if (c == nullptr) {
+    tt::launch("topk_i8_scale", i8_scale_kernel, dim3((unsigned)nq), dim3(64), 0u, stream, f);
+    return tt::check_launch("topk_i8_scale");
+  }
+  switch (dim) {
+    case 32: tt::launch("topk_i8_rerank", i8_rerank_kernel<32>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
+    case 64: tt::launch("topk_i8_rerank", i8_rerank_kernel<64>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
+    case 128: tt::launch("topk_i8_rerank", i8_rerank_kernel<128>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
+    default: tt::launch("topk_i8_rerank", i8_rerank_kernel<256>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
+  }
+  return tt::check_launch("topk_i8_rerank");
+}
+
 extern "C" int tt_quantize_rows_i8(const float* x, int64_t n, int32_t dim, int8_t* codes, float* scales, tt_stream_t stream_) {
   const char* fn = "tt_quantize_rows_i8";
   TT_REQUIRE(x && codes && scales, "%s: null pointer", fn);
@@ -540,18 +545,5 @@ extern "C" int tt_retrieval_topk_i8_f32(const float* q, const int8_t* codes, con
   rc = tt::topk_merge_launch(nq, pl.nsplit, k1, a_s, a_i, b_s, b_i, cand_s, cand_i, stream);
   if (rc != TT_OK) return rc;
 
-  FinArgs f{};
-  f.q = q; f.c = c; f.cand_s = cand_s; f.cand_i = cand_i; f.qscale = qscale; f.k = k; f.k1 = k1;
-  f.out_s = out_scores; f.out_i = out_idx;
-  if (c == nullptr) {
-    tt::launch("topk_i8_scale", i8_scale_kernel, dim3((unsigned)nq), dim3(64), 0u, stream, f);
-    return tt::check_launch("topk_i8_scale");
-  }
-  switch (dim) {
-    case 32: tt::launch("topk_i8_rerank", i8_rerank_kernel<32>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
-    case 64: tt::launch("topk_i8_rerank", i8_rerank_kernel<64>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
-    case 128: tt::launch("topk_i8_rerank", i8_rerank_kernel<128>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
-    default: tt::launch("topk_i8_rerank", i8_rerank_kernel<256>, dim3((unsigned)nq), dim3(64), 0u, stream, f); break;
-  }
-  return tt::check_launch("topk_i8_rerank");
+  return tt::i8_finish_launch(q, c, cand_s, cand_i, qscale, nq, dim, k, k1, out_scores, out_idx, stream);
 }

@@ -243,4 +243,19 @@ int64_t topk_workspace_bytes_split(int64_t nq, int64_t nc, int k, int min_cols);
 int topk_run(const float* q, const float* c, int64_t nq, int64_t nc, int dim, int k, const int64_t* excl_offsets,
              const int64_t* excl_idx, void* workspace, float* out_scores, int64_t* out_idx, hipStream_t stream, int min_cols);
 
+
+// tt_ivf_search_f32's first two launches (ivf.hip), shared with ivf_i8.hip: the coarse probe over the centroids and
+// ivf_bucket_kernel, into the leading `bytes` of the workspace.  The plan holds the chunk rule too (S chunks per list, chosen
+// for lists of list_k entries per (query, probe, chunk)), so both searches cut lists alike.
+struct IvfProbePlan {
+  int S;                        // chunks per list
+  int nl;                       // lists per query entering the merge: nprobe * S
+  int64_t grid;                 // upper bound of the (list, chunk, query tile) work items
+  int64_t off_probe_s, off_probe_i, off_cnt, off_pstart, off_tstart, off_pairs;   // byte offsets (the coarse top-k's own
+  int64_t bytes;                                                                  // workspace leads); 256-byte multiple
+};
+IvfProbePlan ivf_probe_plan(int64_t nq, int64_t nlist, int64_t n, int list_k, int nprobe);
+int ivf_probe_bucket(const float* q, const float* centroids, int64_t nq, int64_t nlist, int dim, int nprobe,
+                     const IvfProbePlan& pl, void* workspace, hipStream_t stream);
+
 }  // namespace tt

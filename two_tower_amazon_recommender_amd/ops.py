@@ -910,6 +910,63 @@ def ivf_search(q, centroids, list_offsets, list_vectors, list_ids, k: int, nprob
     return scores, indices
 
 
+def ivf_search_i8_workspace_bytes(nq: int, nlist: int, n: int, dim: int, k: int, k1: int, nprobe: int) -> int:
+    """Workspace of ``ivf_search_i8`` (0 for a shape the call refuses)."""
+    return int(_lib.load().tt_ivf_search_i8_workspace_bytes(nq, nlist, n, dim, k, k1, nprobe))
+
+
+def ivf_search_i8(q, centroids, list_offsets, list_codes, list_scales, list_ids, k: int, nprobe: int, c=None,
+                  k1: int | None = None, exclusions=None, workspace=None, out=None, check_offsets: bool = True):
+    """Int8 IVF top-k: ``retrieval_topk_i8`` restricted to the rows of the ``nprobe`` inverted lists ``ivf_search`` probes.
+    Index: centroids f32 [nlist, D], list_offsets int64 [nlist + 1] and list_ids int32 [n] as ``ivf_search``; list_codes int8
+    [n, D] and list_scales f32 [n], the ``quantize_rows_i8`` output of the items in list order.  ``c``: the f32 corpus [n, D]
+    in ORIGINAL id order - the ``k1`` stage-1 candidates (by int32 dot product * row scale, original id ascending) are then
+    re-scored exactly (``retrieval_topk``'s score of the pair, bit for bit) and the best k returned; without ``c`` the
+    stage-1 order is returned (k1 = k) with scores key * query scale.  ``k1`` defaults to ``default_k1(k, n, c is not
+    None)``.  Returns (scores f32 [nq, k], ORIGINAL item ids int64 [nq, k]), tail (-inf, -1) when fewer than k candidates
+    remain.  Exclusions (original ids), outputs and ``check_offsets`` as ``ivf_search``."""
+    _chk(q, torch.float32, "query_embeddings", 2)
+    _chk(centroids, torch.float32, "centroids", 2)
+    _chk(list_offsets, torch.int64, "list_offsets", 1)
+    _chk(list_codes, torch.int8, "list_codes", 2)
+    _chk(list_scales, torch.float32, "list_scales", 1)
+    _chk(list_ids, torch.int32, "list_ids", 1)
+    nq, d = q.shape
+    nlist, n = centroids.shape[0], list_codes.shape[0]
+    if centroids.shape[1] != d or list_codes.shape[1] != d:
+        raise RuntimeError(f"ivf_search_i8: embedding dims differ: q {d}, centroids {centroids.shape[1]}, "
+                           f"list_codes {list_codes.shape[1]}")
+    if list_offsets.numel() != nlist + 1:
+        raise ValueError(f"ivf_search_i8: list_offsets needs nlist + 1 = {nlist + 1} entries, got {list_offsets.numel()}")
+    if list_ids.numel() != n or list_scales.numel() != n:
+        raise ValueError(f"ivf_search_i8: list_ids and list_scales need {n} entries (one per list_codes row), got "
+                         f"{list_ids.numel()} and {list_scales.numel()}")
+    if c is not None:
+        _chk(c, torch.float32, "candidate_embeddings", 2)
+        if tuple(c.shape) != (n, d):
+            raise RuntimeError(f"ivf_search_i8: c must be [{n}, {d}] like list_codes, got {tuple(c.shape)}")
+    k, nprobe = int(k), int(nprobe)
+    if not 1 <= k <= min(TOPK_MAX_K, n):
+        raise ValueError(f"ivf_search_i8: k = {k} must be in [1, min({TOPK_MAX_K}, n = {n})]")
+    k1 = default_k1(k, n, c is not None) if k1 is None else int(k1)
+    if not k <= k1 <= min(TOPK_MAX_K, n):
+        raise ValueError(f"ivf_search_i8: k1 = {k1} must be in [k = {k}, min({TOPK_MAX_K}, n = {n})]")
+    if c is None and k1 != k:
+        raise ValueError(f"ivf_search_i8: without c there is no re-rank: k1 = {k1} must equal k = {k}")
+    if not 1 <= nprobe <= min(TOPK_MAX_K, nlist):
+        raise ValueError(f"ivf_search_i8: nprobe = {nprobe} must be in [1, min({TOPK_MAX_K}, nlist = {nlist})]")
+    if check_offsets:
+        check_list_offsets(list_offsets, n, "ivf_search_i8")
+    off, idx = exclusions_csr(exclusions, nq)
+    workspace, scores, indices = _topk_buffers("ivf_search_i8", ivf_search_i8_workspace_bytes(nq, nlist, n, d, k, k1, nprobe), nq,
+                                               k, q.device, workspace, out)
+    _lib.check(_lib.load().tt_ivf_search_i8_f32(_p(q), nq, _p(centroids), nlist, _p(list_offsets), _p(list_codes),
+                                                _p(list_scales), _p(list_ids), _p(c), n, d, k, k1, nprobe, _p(off), _p(idx),
+                                                _p(workspace), workspace.numel(), _p(scores), _p(indices), _stream()),
+               "tt_ivf_search_i8_f32")
+    return scores, indices
+
+
 def retrieval_batch_rank(q, c, inv_temperature: float, cand_prob=None, cand_ids=None, diag_offset: int = 0, workspace=None, out=None):
     """In-batch rank of every query's positive (candidate i + diag_offset) under the scores the loss sees - temperature,
     sampling-probability correction, accidental hits removed (int32 [nq]); top-k accuracy = mean(rank < k)."""

@@ -4,7 +4,8 @@ the item tower once, and users are answered in batches by ``serving.BruteForce``
 the corpus per batch; no [users x items] score matrix) or, with ``--index ivf``, by the approximate ``serving.IVF``
 (``--nlist`` k-means lists, ``--nprobe`` of them scanned per user; ``--nprobe`` = ``--nlist`` is exact), or, with
 ``--index int8``, by ``serving.Int8BruteForce`` (an int8 scan of the whole corpus, the best ``--rerank`` x k candidates of
-every user re-scored exactly).
+every user re-scored exactly), or, with ``--index ivf-int8``, by ``serving.Int8IVF`` (the int8 scan over the ``--nprobe``
+probed lists only, with the same re-rank).
 
     python -m two_tower_amazon_recommender_amd.recommend --checkpoint ck.pt --data interactions.parquet \\
         --all-users --exclude-seen --k 10 --out recs.parquet
@@ -41,30 +42,31 @@ def parse(argv=None):
     ap.add_argument("--out", default="recs.parquet", help="output parquet (user_idx, rank, item_idx, score)")
     ap.add_argument("--batch-users", type=int, default=4096, help="users per top-k call (bounds peak device memory)")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--index", choices=("brute", "ivf", "int8"), default="brute",
+    ap.add_argument("--index", choices=("brute", "ivf", "int8", "ivf-int8"), default="brute",
                     help="brute: exact top-k over the whole corpus; ivf: approximate inverted-file index; int8: quantised "
-                         "scan of the whole corpus with an exact re-rank")
-    ap.add_argument("--nlist", type=int, default=None, help="--index ivf: number of k-means lists (default 1024, at most the "
+                         "scan of the whole corpus with an exact re-rank; ivf-int8: the quantised scan over the probed lists "
+                         "of an inverted-file index")
+    ap.add_argument("--nlist", type=int, default=None, help="--index ivf / ivf-int8: number of k-means lists (default 1024, at most the "
                                                              "number of items)")
-    ap.add_argument("--nprobe", type=int, default=None, help=f"--index ivf: lists scanned per user (1..min({MAX_K}, nlist); "
+    ap.add_argument("--nprobe", type=int, default=None, help=f"--index ivf / ivf-int8: lists scanned per user (1..min({MAX_K}, nlist); "
                                                               "default 32)")
-    ap.add_argument("--seed", type=int, default=0, help="--index ivf: k-means seed")
-    ap.add_argument("--rerank", type=int, default=None, help="--index int8: candidates re-scored exactly per user, as a multiple "
+    ap.add_argument("--seed", type=int, default=0, help="--index ivf / ivf-int8: k-means seed")
+    ap.add_argument("--rerank", type=int, default=None, help="--index int8 / ivf-int8: candidates re-scored exactly per user, as a multiple "
                                                               f"of --k (default 4; at least 32 and at most {MAX_K} candidates)")
     args = ap.parse_args(argv)
     if not 1 <= args.k <= MAX_K:
         ap.error(f"--k must be in [1, {MAX_K}], got {args.k}")
     if args.batch_users < 1:
         ap.error("--batch-users must be positive")
-    if args.index != "ivf" and (args.nlist is not None or args.nprobe is not None):
-        ap.error("--nlist / --nprobe need --index ivf")
-    if args.index != "int8" and args.rerank is not None:
-        ap.error("--rerank needs --index int8")
-    if args.index == "int8":
+    if args.index not in ("ivf", "ivf-int8") and (args.nlist is not None or args.nprobe is not None):
+        ap.error("--nlist / --nprobe need --index ivf or --index ivf-int8")
+    if args.index not in ("int8", "ivf-int8") and args.rerank is not None:
+        ap.error("--rerank needs --index int8 or --index ivf-int8")
+    if args.index in ("int8", "ivf-int8"):
         args.rerank = 4 if args.rerank is None else args.rerank
         if args.rerank < 1:
             ap.error(f"--rerank must be positive, got {args.rerank}")
-    if args.index == "ivf":
+    if args.index in ("ivf", "ivf-int8"):
         args.nlist = 1024 if args.nlist is None else args.nlist
         args.nprobe = min(32, args.nlist) if args.nprobe is None else args.nprobe
         if args.nlist < 1:
@@ -109,7 +111,7 @@ def main(argv=None) -> int:
     import pyarrow as pa
     import pyarrow.parquet as pq
     from . import data as datamod
-    from .serving import IVF, BruteForce, Int8BruteForce
+    from .serving import IVF, BruteForce, Int8BruteForce, Int8IVF
     from .trainer import TwoTowerConfig, TwoTowerTrainer
 
     dev = torch.device(args.device)
@@ -142,10 +144,14 @@ def main(argv=None) -> int:
         if users.size and (users.min() < 0 or users.max() >= cfg.n_users):
             raise SystemExit(f"{args.users_file}: user ids must be in [0, {cfg.n_users})")
     k = min(args.k, cfg.n_items)
-    if args.index == "ivf":
+    if args.index in ("ivf", "ivf-int8"):
         if args.nlist > cfg.n_items:
             raise SystemExit(f"--nlist {args.nlist} exceeds the model's {cfg.n_items} items")
-        bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat)
+        if args.index == "ivf":
+            bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat)
+        else:
+            bf = Int8IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed,
+                         rerank=args.rerank).index_from_trainer(trainer, item_cat)
     elif args.index == "int8":
         bf = Int8BruteForce(k=k, rerank=args.rerank).index_from_trainer(trainer, item_cat)
     else:

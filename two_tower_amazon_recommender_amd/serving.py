@@ -19,6 +19,11 @@ call) and re-scores the ``rerank * k`` survivors of every query exactly, so the 
 with ``keep_f32=False`` it serves the quantised order alone, from a quarter of the memory.
 
     i8 = Int8BruteForce(k=10, rerank=4).index_from_trainer(trainer)
+
+``Int8IVF`` combines the two: ``IVF``'s lists held as int8 codes (one ``tt_ivf_search_i8_f32`` per call), the same exact
+re-rank; it answers what ``Int8BruteForce`` answers over the items of the probed lists.
+
+    i8ivf = Int8IVF(k=10, nlist=1024, nprobe=32, rerank=4).index_from_trainer(trainer)
 """
 from __future__ import annotations
 
@@ -141,14 +146,16 @@ class IVF(BruteForce):
         csum = torch.cat([xt.new_zeros(x.shape[1], 1), torch.cumsum(xt, 1)], 1)
         return (csum[:, ends] - csum[:, ends - counts]).T, counts
 
-    def index(self, candidates: torch.Tensor, identifiers=None) -> "IVF":
-        """candidates: [n, D] f32 device tensor (n >= nlist).  identifiers: as ``BruteForce.index``."""
+    def _build_lists(self, candidates: torch.Tensor, identifiers):
+        """The list build both IVF classes share: (x f32 [n, D] contiguous, order int64 [n] - the original row of every
+        reordered row -, identifiers int64 or None); sets ``centroids``, ``list_offsets`` and ``list_ids``."""
+        what = type(self).__name__
         if candidates.dim() != 2:
-            raise ValueError(f"IVF.index: candidates must be [n, D], got shape {tuple(candidates.shape)}")
+            raise ValueError(f"{what}.index: candidates must be [n, D], got shape {tuple(candidates.shape)}")
         x = candidates.detach().to(torch.float32).contiguous()
         n, d = x.shape
         if n < self.nlist:
-            raise ValueError(f"IVF.index: nlist = {self.nlist} exceeds the {n} candidates")
+            raise ValueError(f"{what}.index: nlist = {self.nlist} exceeds the {n} candidates")
         dev = x.device
         g = torch.Generator(device=dev).manual_seed(self.seed)
         m = min(n, 256 * self.nlist)
@@ -170,16 +177,21 @@ class IVF(BruteForce):
         counts = torch.bincount(assign, minlength=self.nlist)
         self.centroids = cent
         self.list_offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).contiguous()
-        self.list_vectors = x[order].contiguous()
         self.list_ids = order.to(torch.int32).contiguous()
-        self._candidates = self.list_vectors                # shape / device of the corpus for the base class
         if identifiers is not None:
             ids = torch.as_tensor(identifiers, device=dev)
             if ids.dim() != 1 or ids.numel() != n:
-                raise ValueError(f"IVF.index: identifiers must be [{n}], got {tuple(ids.shape)}")
+                raise ValueError(f"{what}.index: identifiers must be [{n}], got {tuple(ids.shape)}")
             if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
-                raise TypeError(f"IVF.index: identifiers must be integers, got {ids.dtype}")
+                raise TypeError(f"{what}.index: identifiers must be integers, got {ids.dtype}")
             identifiers = ids.to(torch.int64).contiguous()
+        return x, order, identifiers
+
+    def index(self, candidates: torch.Tensor, identifiers=None) -> "IVF":
+        """candidates: [n, D] f32 device tensor (n >= nlist).  identifiers: as ``BruteForce.index``."""
+        x, order, identifiers = self._build_lists(candidates, identifiers)
+        self.list_vectors = x[order].contiguous()
+        self._candidates = self.list_vectors                # shape / device of the corpus for the base class
         self._identifiers = identifiers
         return self
 
@@ -311,6 +323,119 @@ class Int8BruteForce(BruteForce):
         k = self.k if k is None else int(k)
         scores, idx = ops.retrieval_topk_i8(q, self.codes, self.scales, k, c=self._candidates, k1=self.k1(k),
                                             exclusions=exclusions, workspace=self._workspace(q.shape[0], k))
+        if self._identifiers is None:
+            return scores, idx
+        ids = self._identifiers[idx.clamp(min=0)]
+        return scores, torch.where(idx >= 0, ids, torch.full_like(ids, -1))
+
+
+class Int8IVF(IVF):
+    """Quantised inverted-file index: ``IVF``'s lists (with equal arguments, bit-identical ``centroids``, ``list_offsets`` and
+    ``list_ids``) held as ``Int8BruteForce``'s per-row int8 codes and f32 scales in list order (``list_codes``,
+    ``list_scales``; ``list_vectors`` is None).  A query scans the int8 rows of its ``nprobe`` lists (one
+    ``tt_ivf_search_i8_f32`` per call), keeps the k1 = min(TOPK_MAX_K, n, max(rerank * k, 32)) best by quantised score and,
+    with ``keep_f32=True``, re-scores them against the f32 corpus, which is kept in ORIGINAL order (the re-rank gathers by
+    item id): the returned scores are then exactly ``BruteForce``'s for the returned items.  ``keep_f32=False`` drops the
+    f32 rows: no re-rank, k1 = k, scores are the dequantised products.  The answer is ``Int8BruteForce``'s over the items
+    of the probed lists; with ``nprobe = nlist`` the two agree bit for bit.
+
+    Index size: n (D + 8) bytes (codes, scales, ids) plus the centroids, plus 4 n D bytes with the re-rank.
+    Identifiers and exclusions as ``BruteForce`` (exclusions hold original row indices)."""
+
+    QUANT_BATCH = 1 << 20                    # reordered f32 rows alive at a time during the build
+
+    def __init__(self, query_model=None, k: int = 10, nlist: int = 1024, nprobe: int = 32, seed: int = 0, iters: int = 10,
+                 rerank: int = 4, keep_f32: bool = True):
+        super().__init__(query_model, k, nlist, nprobe, seed, iters)
+        self.rerank, self.keep_f32 = int(rerank), bool(keep_f32)
+        if self.rerank < 1:
+            raise ValueError(f"Int8IVF: rerank must be >= 1, got {self.rerank}")
+        self.list_codes = self.list_scales = None
+
+    def index(self, candidates: torch.Tensor, identifiers=None) -> "Int8IVF":
+        """candidates: [n, D] f32 device tensor (n >= nlist, D in {32, 64, 128, 256}).  identifiers: as
+        ``BruteForce.index``."""
+        if candidates.dim() == 2 and candidates.shape[1] not in (32, 64, 128, 256):
+            raise ValueError(f"Int8IVF.index: dim = {candidates.shape[1]} must be one of 32, 64, 128, 256")
+        x, order, identifiers = self._build_lists(candidates, identifiers)
+        n, d = x.shape
+        codes = torch.empty(n, d, dtype=torch.int8, device=x.device)
+        scales = torch.empty(n, dtype=torch.float32, device=x.device)
+        for s in range(0, n, self.QUANT_BATCH):                 # the quantiser is per row: batches change nothing
+            e = min(n, s + self.QUANT_BATCH)
+            ops.quantize_rows_i8(x[order[s:e]], out=(codes[s:e], scales[s:e]))
+        self.list_codes, self.list_scales, self.list_vectors = codes, scales, None
+        self._candidates = x if self.keep_f32 else None         # ORIGINAL order: the re-rank gathers by item id
+        self._identifiers = identifiers
+        self._ws = None
+        return self
+
+    def k1(self, k: int) -> int:
+        """Stage-1 candidates per query for a top-k request."""
+        return ops.default_k1(k, self.list_codes.shape[0], self.keep_f32, self.rerank)
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self) -> dict:
+        if self.centroids is None:
+            raise RuntimeError("Int8IVF: call index() or index_from_trainer() first")
+        state = {"nlist": self.nlist, "centroids": self.centroids, "list_offsets": self.list_offsets,
+                 "list_codes": self.list_codes, "list_scales": self.list_scales, "list_ids": self.list_ids}
+        if self.keep_f32:
+            state["candidates"] = self._candidates
+        return state
+
+    def load_state_dict(self, state: dict) -> "Int8IVF":
+        cent, codes, scales = state["centroids"], state["list_codes"], state["list_scales"]
+        nlist = int(state["nlist"])
+        if cent.dim() != 2 or cent.shape[0] != nlist or state["list_offsets"].numel() != nlist + 1:
+            raise ValueError(f"Int8IVF.load_state_dict: arrays do not match nlist = {nlist}")
+        if self.nprobe > nlist:
+            raise ValueError(f"Int8IVF.load_state_dict: nprobe = {self.nprobe} exceeds the index's nlist = {nlist}")
+        if codes.dim() != 2 or codes.dtype != torch.int8 or scales.dim() != 1 or scales.numel() != codes.shape[0]:
+            raise ValueError("Int8IVF.load_state_dict: list_codes must be int8 [n, D] and list_scales [n]")
+        if state["list_ids"].numel() != codes.shape[0] or cent.shape[1] != codes.shape[1]:
+            raise ValueError("Int8IVF.load_state_dict: list_ids / list_codes / centroids shapes disagree")
+        cand = state.get("candidates")
+        if self.keep_f32:
+            if cand is None:
+                raise ValueError("Int8IVF.load_state_dict: keep_f32=True needs the state's f32 'candidates'")
+            if tuple(cand.shape) != tuple(codes.shape):
+                raise ValueError(f"Int8IVF.load_state_dict: candidates {tuple(cand.shape)} do not match list_codes "
+                                 f"{tuple(codes.shape)}")
+        list_offsets = state["list_offsets"].to(torch.int64).contiguous()
+        ops.check_list_offsets(list_offsets, codes.shape[0], "Int8IVF.load_state_dict")
+        self.nlist = nlist
+        self.centroids = cent.to(torch.float32).contiguous()
+        self.list_offsets = list_offsets
+        self.list_codes = codes.contiguous()
+        self.list_scales = scales.to(torch.float32).contiguous()
+        self.list_ids = state["list_ids"].to(torch.int32).contiguous()
+        self.list_vectors = None
+        self._candidates = cand.to(torch.float32).contiguous() if self.keep_f32 else None
+        self._identifiers = None
+        self._ws = None
+        return self
+
+    # ------------------------------------------------------------------ query
+    def _workspace(self, nq: int, k: int) -> torch.Tensor:
+        n, d = self.list_codes.shape
+        need = max(ops.ivf_search_i8_workspace_bytes(nq, self.nlist, n, d, k, self.k1(k), self.nprobe), 1)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.list_codes.device)
+        return self._ws
+
+    def _query(self, queries, exclusions, k):
+        if self.centroids is None:
+            raise RuntimeError("Int8IVF: call index() or index_from_trainer() first")
+        q = self.query_model(queries) if self.query_model is not None else queries
+        q = q.to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        k = self.k if k is None else int(k)
+        scores, idx = ops.ivf_search_i8(q, self.centroids, self.list_offsets, self.list_codes, self.list_scales, self.list_ids,
+                                        k, self.nprobe, c=self._candidates, k1=self.k1(k), exclusions=exclusions,
+                                        workspace=self._workspace(q.shape[0], k), check_offsets=False)
         if self._identifiers is None:
             return scores, idx
         ids = self._identifiers[idx.clamp(min=0)]

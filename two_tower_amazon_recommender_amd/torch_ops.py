@@ -299,6 +299,43 @@ def _(q, codes, scales, c, k, k1, exclusion_offsets, exclusion_indices):
     return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
 
 
+_IVF_I8_WS: dict = {}
+
+
+def _ivf_i8_ws(nq: int, nlist: int, n: int, d: int, k: int, k1: int, nprobe: int, device) -> Tensor:
+    """Workspace of the int8 IVF op, kept per (device, stream) like the top-k op's (the largest one seen)."""
+    need = max(ops.ivf_search_i8_workspace_bytes(nq, nlist, n, d, k, k1, nprobe), 1)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    hit = _IVF_I8_WS.get(key)
+    if hit is not None and hit.numel() >= need:
+        return hit
+    _IVF_I8_WS.pop(key, None)
+    buf = _IVF_I8_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+@torch.library.custom_op(f"{NS}::ivf_search_i8", mutates_args=(), device_types="cuda")
+def ivf_search_i8(query_embeddings: Tensor, centroids: Tensor, list_offsets: Tensor, list_codes: Tensor, list_scales: Tensor,
+                  list_ids: Tensor, candidate_embeddings: Optional[Tensor], k: int, k1: int, nprobe: int,
+                  exclusion_offsets: Optional[Tensor], exclusion_indices: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """Int8 IVF top-k (ops.ivf_search_i8): the int8 scan of the nprobe best lists keeps k1 candidates per query, re-scored
+    exactly against candidate_embeddings (the f32 corpus in original id order) when given (else k1 must equal k); optional
+    CSR exclusions of original ids.  Not differentiable (serving)."""
+    q = query_embeddings.contiguous()
+    c = None if candidate_embeddings is None else candidate_embeddings.contiguous()
+    ex = None if exclusion_offsets is None else (exclusion_offsets.contiguous(), exclusion_indices.contiguous())
+    ws = _ivf_i8_ws(q.shape[0], centroids.shape[0], list_codes.shape[0], q.shape[1], k, k1, nprobe, q.device)
+    return ops.ivf_search_i8(q, centroids.contiguous(), list_offsets.contiguous(), list_codes.contiguous(),
+                             list_scales.contiguous(), list_ids.contiguous(), k, nprobe, c=c, k1=k1, exclusions=ex, workspace=ws)
+
+
+@ivf_search_i8.register_fake
+def _(q, centroids, list_offsets, list_codes, list_scales, list_ids, c, k, k1, nprobe, exclusion_offsets, exclusion_indices):
+    return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
+
+
 # --------------------------------------------------------------------------------------------- a2 dense layers
 @torch.library.custom_op(f"{NS}::dense_fwd", mutates_args=(), device_types="cuda")
 def dense_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], relu: bool) -> Tensor:
@@ -365,5 +402,5 @@ def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: T
         ops.sparse_adagrad_(table, accum, grads.contiguous(), plan, lr, eps)
 
 
-OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "dense_fwd",
+OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
        "dense_bwd", "sparse_update_")
