@@ -47,7 +47,8 @@ typedef void* tt_stream_t;
 int tt_abi_version(void);
 const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
- * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup; else -1): a binding checks its mirrors with it. */
+ * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args;
+ * else -1): a binding checks its mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
 /* ---------------------------------------------------------------------------------------
@@ -60,7 +61,7 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * the scope ivf around a whole tt_ivf_search_f32 call), quantize_i8, topk_i8_scan, topk_i8_rerank, topk_i8_scale (and the
  * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
- * topk_i8_rerank, topk_i8_scale).
+ * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd.
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -309,6 +310,28 @@ int32_t tt_tower_fwd2_supported(int64_t m, int32_t k0, int32_t h, int32_t n1);
 int tt_tower_fwd2_batched_f32(const tt_dense_fwd_args* layer0, const tt_dense_fwd_args* layer1, int32_t n_probs, int64_t m,
                               int32_t k0, int32_t h, int32_t n1, float drop_rate, uint64_t seed, uint64_t counter_offset,
                               tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * L2-normalised tower outputs (cosine scoring): tf.math.l2_normalize between a tower's last Dense layer and the scorer,
+ * and its backward pass between the scorer's dq / dc and the tower's backward (csrc/normalize.hip).  Per row of x [rows, dim],
+ * with s = sum x^2 (eps clamps the SUM OF SQUARES; TensorFlow's default is 1e-12):
+ *   forward   y  = x * (1 / sqrt(max(s, eps)))                     (correctly rounded division and square root)
+ *   backward  t  = sum x * dy;   s >= eps:  inv = 1 / sqrt(s),  dx = inv * (dy - x * (t * inv * inv))
+ *                                s <  eps:  dx = dy * (1 / sqrt(eps))            (y = x / sqrt(eps) is linear there)
+ * The backward pass takes x and dy and recomputes s and t from the registers it has just loaded: no saved norm, no extra
+ * buffer, the same traffic (x, dy in; dx out) as a form that saves y.  dx MAY ALIAS dy: every lane reads the elements it
+ * owns before it writes them and touches no others; x must not alias either output, y must not alias x.
+ * Up to two problems (both towers) of one shape per launch; `probs` is a HOST array.  n_probs in 1..2; rows >= 0 (0: no
+ * launch, TT_OK); dim % 4 == 0, 4 <= dim <= 1024; eps > 0; all pointers non-NULL and 16-byte aligned.  A group of lanes
+ * sized to the row (8 lanes at dim 32 ... a whole wave from dim 256 on) reduces it with a fixed-order butterfly: no LDS,
+ * no atomics, results bit-reproducible and independent of n_probs and of the grid.  HBM-bound: 8 * rows * dim bytes
+ * per problem forward, 12 * rows * dim backward.                                                                       */
+typedef struct tt_l2norm_fwd_args { const float* x; float* y; } tt_l2norm_fwd_args;
+typedef struct tt_l2norm_bwd_args { const float* x; const float* dy; float* dx; } tt_l2norm_bwd_args;
+int tt_l2_normalize_fwd_f32(const tt_l2norm_fwd_args* probs, int32_t n_probs, int64_t rows, int32_t dim, float eps,
+                            tt_stream_t stream);
+int tt_l2_normalize_bwd_f32(const tt_l2norm_bwd_args* probs, int32_t n_probs, int64_t rows, int32_t dim, float eps,
+                            tt_stream_t stream);
 
 /* Dense parameter update over up to TT_MAX_DENSE_SEGS segments in one launch.
  *   g = sum_s grad_slabs[s*slab_stride + i] (s ascending) + 2*l2*w[i]

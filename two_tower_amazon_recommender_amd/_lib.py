@@ -50,6 +50,16 @@ class DenseBwdArgs(C.Structure):
                 ("dw_slabs", C.c_void_p), ("db_slabs", C.c_void_p), ("lookup", DenseLookup), ("dx_relu_bits", C.c_void_p)]
 
 
+class L2NormFwdArgs(C.Structure):
+    """Mirror of ``tt_l2norm_fwd_args``."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p)]
+
+
+class L2NormBwdArgs(C.Structure):
+    """Mirror of ``tt_l2norm_bwd_args``."""
+    _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("dx", C.c_void_p)]
+
+
 class RouteTable(C.Structure):
     """Mirror of ``tt_route_table`` (include/twotower_hip.h)."""
     _fields_ = [("ids", C.c_void_p), ("num_rows", C.c_int64), ("local_offset", C.c_int64), ("pos_flat", C.c_void_p)]
@@ -141,6 +151,8 @@ SIGNATURES = {
     "tt_tower_fwd2_supported": (_i32, [_i64, _i32, _i32, _i32]),
     "tt_tower_fwd2_batched_f32": (C.c_int, [C.POINTER(DenseFwdArgs), C.POINTER(DenseFwdArgs), _i32, _i64, _i32, _i32, _i32, _f, _u64, _u64, _p]),
     "tt_dense_bwd_num_slabs": (_i32, [_i64]),
+    "tt_l2_normalize_fwd_f32": (C.c_int, [C.POINTER(L2NormFwdArgs), _i32, _i64, _i32, _f, _p]),
+    "tt_l2_normalize_bwd_f32": (C.c_int, [C.POINTER(L2NormBwdArgs), _i32, _i64, _i32, _f, _p]),
     "tt_dense_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     "tt_dense_update_f32": (C.c_int, [C.POINTER(DenseSeg), _i32, _i32, _i32, _f, _f, _p]),
     "tt_optimizer_step_f32": (C.c_int, [_i32, C.POINTER(SparseTable), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, _f, _f, _p]),

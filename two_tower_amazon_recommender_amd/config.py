@@ -29,7 +29,9 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         item_tower_dims=None if item_dims == user_dims else item_dims,
         temperature=float(rt.get("temperature", 1.0)), l2_regularization=float(m.get("l2_regularization", 0.0)),
         learning_rate=float(tr.get("learning_rate", 0.001)), optimizer=optimizer,
-        batch_size=int(tr.get("batch_size", 1024)), dropout_rate=dropout)
+        batch_size=int(tr.get("batch_size", 1024)), dropout_rate=dropout,
+        # not in the reference's schema (left open): an optional key beside retrieval.temperature
+        normalize_embeddings=bool(rt.get("normalize_embeddings", False)))
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),
                 validation_freq=int(tr.get("validation_freq", 1)), top_k_eval=list(rt.get("top_k_eval", [])))
     return cfg, loop

@@ -598,6 +598,54 @@ def make_dense_seg(param, accum, grad_slabs, n_slabs: int, l2: float, grad_out=N
     return DenseSeg(_p(param), _p(accum), _p(grad_slabs), _p(grad_out), count, count, n_slabs, l2)
 
 
+# ----------------------------------------------------------------------------- L2-normalised tower outputs
+L2_NORMALIZE_EPS = 1e-12            # tf.math.l2_normalize's default (a floor of the SUM OF SQUARES)
+
+
+def _l2_shape(groups, what: str):
+    """(rows, dim) shared by every tensor of every problem (1 or 2 problems: the towers of one launch)."""
+    n = len(groups[0])
+    if n not in (1, 2) or any(len(g) != n for g in groups):
+        raise ValueError(f"{what}: one or two problems, every argument a tuple of that length")
+    for g in groups:
+        for t in g:
+            _chk(t, torch.float32, what, 2)
+            if t.shape != groups[0][0].shape:
+                raise RuntimeError(f"{what}: every tensor must be [{groups[0][0].shape[0]}, {groups[0][0].shape[1]}], "
+                                   f"got {tuple(t.shape)}")
+    return n, groups[0][0].shape[0], groups[0][0].shape[1]
+
+
+def l2_normalize2(xs, ys, eps: float = L2_NORMALIZE_EPS):
+    """ys[i] = xs[i] / sqrt(max(sum(xs[i]^2, axis=1), eps)) (tf.math.l2_normalize) for one or two [rows, dim] problems
+    - both towers' outputs - in ONE launch (``tt_l2_normalize_fwd_f32``).  ys[i] must not be xs[i]."""
+    n, rows, dim = _l2_shape((xs, ys), "l2_normalize2")
+    arr = (_lib.L2NormFwdArgs * n)(*[_lib.L2NormFwdArgs(_p(xs[i]), _p(ys[i])) for i in range(n)])
+    _lib.check(_lib.load().tt_l2_normalize_fwd_f32(arr, n, rows, dim, eps, _stream()), "tt_l2_normalize_fwd_f32")
+    return ys
+
+
+def l2_normalize_bwd2(xs, dys, dxs, eps: float = L2_NORMALIZE_EPS):
+    """dxs[i] = gradient of l2_normalize2 at xs[i] given dys[i], for one or two problems in ONE launch
+    (``tt_l2_normalize_bwd_f32``: the row sums are recomputed from xs, nothing is saved by the forward).  dxs[i] may be dys[i]."""
+    n, rows, dim = _l2_shape((xs, dys, dxs), "l2_normalize_bwd2")
+    arr = (_lib.L2NormBwdArgs * n)(*[_lib.L2NormBwdArgs(_p(xs[i]), _p(dys[i]), _p(dxs[i])) for i in range(n)])
+    _lib.check(_lib.load().tt_l2_normalize_bwd_f32(arr, n, rows, dim, eps, _stream()), "tt_l2_normalize_bwd_f32")
+    return dxs
+
+
+def l2_normalize(x, out=None, eps: float = L2_NORMALIZE_EPS):
+    """One-tower form of ``l2_normalize2``."""
+    out = torch.empty_like(x) if out is None else out
+    return l2_normalize2((x,), (out,), eps)[0]
+
+
+def l2_normalize_bwd(x, dy, out=None, eps: float = L2_NORMALIZE_EPS):
+    """One-tower form of ``l2_normalize_bwd2``."""
+    out = torch.empty_like(x) if out is None else out
+    return l2_normalize_bwd2((x,), (dy,), (out,), eps)[0]
+
+
 # ----------------------------------------------------------------------------- a3+a4 retrieval
 SCORER_PRECISIONS = ("f32", "bf16x3")
 

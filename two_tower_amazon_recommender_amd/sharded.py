@@ -413,6 +413,10 @@ class ShardedTwoTowerTrainer:
 
     def __init__(self, cfg, device, group=None, seed: int | None = None, negatives: str = "local",
                  capacity_factor: float = 2.0, force_collectives: bool = False, sync_ops_inline: bool = True):
+        if getattr(cfg, "normalize_embeddings", False):
+            # global negatives must normalise before the all-gather and run the backward after the reduce-scatter
+            raise NotImplementedError("normalize_embeddings is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         from . import ops
         from .trainer import Tower, TID_USER_TABLE, TID_ITEM_TABLE
         cfg.validate()

@@ -385,6 +385,44 @@ def _dense_backward(ctx, dy):
 dense_fwd.register_autograd(_dense_backward, setup_context=_dense_setup)
 
 
+# --------------------------------------------------------------------------------------------- L2-normalised tower outputs
+@torch.library.custom_op(f"{NS}::l2_normalize", mutates_args=(), device_types="cuda")
+def l2_normalize(x: Tensor, eps: float = 1e-12) -> Tensor:
+    """y = x / sqrt(max(sum(x^2, axis=1), eps)) per row of x [rows, dim] (tf.math.l2_normalize): what a model that scores
+    unit-norm embeddings puts between ``dense_fwd`` and ``retrieval_loss``.  Autograd through ``twotower::l2_normalize_bwd``."""
+    return ops.l2_normalize(x.contiguous(), eps=eps)
+
+
+@l2_normalize.register_fake
+def _(x, eps=1e-12):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op(f"{NS}::l2_normalize_bwd", mutates_args=(), device_types="cuda")
+def l2_normalize_bwd(x: Tensor, dy: Tensor, eps: float = 1e-12) -> Tensor:
+    """dx of ``l2_normalize`` at x given dL/dy (the row sums are recomputed from x: the forward saves nothing but x)."""
+    return ops.l2_normalize_bwd(x.contiguous(), dy.contiguous(), eps=eps)
+
+
+@l2_normalize_bwd.register_fake
+def _(x, dy, eps=1e-12):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+def _l2_setup(ctx, inputs, output):
+    x, eps = inputs
+    ctx.save_for_backward(x)
+    ctx.eps = eps
+
+
+def _l2_backward(ctx, dy):
+    (x,) = ctx.saved_tensors
+    return torch.ops.twotower.l2_normalize_bwd(x, dy, ctx.eps), None
+
+
+l2_normalize.register_autograd(_l2_backward, setup_context=_l2_setup)
+
+
 # --------------------------------------------------------------------------------------------- a5 sparse optimizer
 @torch.library.custom_op(f"{NS}::sparse_update_", mutates_args=("table", "accum"), device_types="cuda")
 def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: Tensor, optimizer: str, lr: float,
@@ -403,4 +441,4 @@ def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: T
 
 
 OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "sparse_update_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "sparse_update_")

@@ -66,6 +66,9 @@ def parse(argv=None):
     ap.add_argument("--scorer-precision", default="f32", choices=["f32", "bf16x3"],
                     help="matrix products of the scorer + softmax loss: exact f32 (default) or f32-emulated split-bf16 on the "
                          "bf16 matrix cores (scorer dim 128 / 256; same 1e-4 parity bars, ~2x faster scorer)")
+    ap.add_argument("--normalize-embeddings", action="store_true",
+                    help="L2-normalise both towers' outputs before the scorer (cosine scoring; overrides "
+                         "model.retrieval.normalize_embeddings to true); single-GPU trainer only")
     ap.add_argument("--epochs", type=int, default=None, help="override model.training.epochs")
     ap.add_argument("--batch-size", type=int, default=None, help="override model.training.batch_size")
     ap.add_argument("--val-fraction", type=float, default=0.1)
@@ -89,6 +92,9 @@ def main(argv=None) -> int:
     doc = cfgmod.load_yaml(args.config)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     distributed = args.distributed or world > 1
+    normalize = args.normalize_embeddings or bool(((doc.get("model") or {}).get("retrieval") or {}).get("normalize_embeddings", False))
+    if distributed and normalize:
+        raise NotImplementedError("normalize_embeddings is not implemented for the row-sharded (--distributed) trainer")
     if distributed:
         import torch.distributed as dist
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -126,6 +132,7 @@ def main(argv=None) -> int:
     cfg, loop = cfgmod.model_config_from_dict(doc, n_users, n_items, optimizer=args.optimizer)
     cfg.n_category_buckets = args.category_buckets
     cfg.scorer_precision = args.scorer_precision
+    cfg.normalize_embeddings = normalize
     if args.batch_size:
         cfg.batch_size = args.batch_size
     epochs = args.epochs if args.epochs is not None else loop["epochs"]

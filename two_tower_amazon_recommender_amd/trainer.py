@@ -56,6 +56,11 @@ class TwoTowerConfig:
     # matrix products of the scorer + softmax loss: "f32" (exact f32 products on the f32-input MFMA: the parity-safe default
     # and the headline) or "bf16x3" (f32-emulated through a three-way bf16 split on the bf16 MFMA; scorer dim 128 / 256)
     scorer_precision: str = "f32"
+    # cosine scoring: both towers' outputs are L2-normalised (tf.math.l2_normalize: x / sqrt(max(sum x^2, normalize_eps))) before
+    # the scorer, every metric and every embedding the trainer hands out - what the reference's temperature 0.1 is meant for
+    # (Yi et al. 2019; SURVEY.md lists the choice as left open).  Off = the towers' raw outputs, as before.
+    normalize_embeddings: bool = False
+    normalize_eps: float = 1e-12                   # tf.math.l2_normalize's default (a floor of the SUM OF SQUARES)
 
     @property
     def user_dims(self) -> list:
@@ -88,6 +93,10 @@ class TwoTowerConfig:
             raise ValueError(f"scorer_precision must be one of {ops.SCORER_PRECISIONS}")
         if self.scorer_precision == "bf16x3" and self.tower_dims[-1] not in (128, 256):
             raise ValueError("scorer_precision='bf16x3' needs a scorer dim (last tower dim) of 128 or 256")
+        if not isinstance(self.normalize_embeddings, bool):
+            raise ValueError("normalize_embeddings must be a bool")
+        if not self.normalize_eps > 0:
+            raise ValueError("normalize_eps must be > 0")
 
 
 class Tower:
@@ -114,12 +123,20 @@ class Tower:
         # dz[l]: gradient w.r.t. the pre-activation of layer l; dz[n_layers-1] is the scorer's dq/dc
         self.dz = [torch.empty(b, self.dims[l + 1], device=dev) for l in range(self.n_layers)]
         self.demb = torch.empty(b, self.dims[0], device=dev)
+        # cfg.normalize_embeddings: the L2-normalised output (what the scorer reads as q / c) and the scorer's gradient w.r.t. it
+        self.unit = self.dunit = None
+        if cfg.normalize_embeddings:
+            self.alloc_unit()
         # sign bits of the hidden (ReLU) activations, written by the forward GEMM's epilogue and read by the next layer's dx
         # epilogue as its mask: [b, n/32] words instead of re-reading acts[l] (indexed like acts; None where n % 32 != 0)
         self.bits = [None] + [ops.relu_bits_like(b, self.dims[l + 1], dev) if (l < self.n_layers - 1 and self.dims[l + 1] % 32 == 0)
                               else None for l in range(self.n_layers)]
         self.dw_slabs = [torch.empty(ns, self.dims[l], self.dims[l + 1], device=dev) for l in range(self.n_layers)]
         self.db_slabs = [torch.empty(ns, self.dims[l + 1], device=dev) for l in range(self.n_layers)]
+
+    def alloc_unit(self):
+        if self.unit is None:
+            self.unit, self.dunit = torch.empty_like(self.acts[-1]), torch.empty_like(self.acts[-1])
 
     @staticmethod
     def param_count(cfg: TwoTowerConfig, tower_dims: list) -> int:
@@ -389,6 +406,15 @@ class TwoTowerTrainer:
         if category_ids is not None:
             ops.embedding_gather_add_(it.acts[0], self.cat_table, category_ids, self.oob)
 
+    def _outputs(self, *towers):
+        """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
+        serving: the last layer's output, L2-normalised into ``tower.unit`` (one launch for all of them) when
+        cfg.normalize_embeddings.  The ONE place that decides."""
+        if not self.cfg.normalize_embeddings:
+            return tuple(t.acts[-1] for t in towers)
+        ops.l2_normalize2(tuple(t.acts[-1] for t in towers), tuple(t.unit for t in towers), self.cfg.normalize_eps)
+        return tuple(t.unit for t in towers)
+
     # ------------------------------------------------------------------ the hot path
     def forward_backward(self, user_ids: torch.Tensor, item_ids: torch.Tensor, sample_weight=None,
                          candidate_sampling_probability=None, candidate_ids=None, category_ids=None):
@@ -404,10 +430,15 @@ class TwoTowerTrainer:
         else:
             q = ut.forward((cfg.dropout_rate, self.dropout_seed, 0, row0), lookup=lks[0])
             c = it.forward((cfg.dropout_rate, self.dropout_seed, 1, row0), lookup=lks[1])
+        q, c = self._outputs(ut, it)
+        # normalised: the scorer's gradients are w.r.t. the unit vectors; one launch turns them into the last layer's dz
+        dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
         kw = dict(sample_weight=sample_weight, cand_prob=candidate_sampling_probability, cand_ids=candidate_ids)
         # loss + dq + dc in two fused passes over the logits (probabilities never stored; f32: raw dot products kept in self.ws)
         ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
-                              ut.dz[-1], it.dz[-1], precision=cfg.scorer_precision, **kw)
+                              dq, dc, precision=cfg.scorer_precision, **kw)
+        if cfg.normalize_embeddings:
+            ops.l2_normalize_bwd2((ut.acts[-1], it.acts[-1]), (dq, dc), (ut.dz[-1], it.dz[-1]), cfg.normalize_eps)
         if cfg.symmetric:
             towers_backward(ut, it, cfg.dropout_rate, lookups=lks if lks[0] else None, bwd2_ws=self.bwd2_ws)
         else:
@@ -445,7 +476,10 @@ class TwoTowerTrainer:
                                     cfg.adagrad_epsilon)
 
     def step(self, user_ids: torch.Tensor, item_ids: torch.Tensor, **loss_kw) -> torch.Tensor:
-        """One train step; returns the (device, unsynchronised) retrieval loss (SUM over the batch)."""
+        """One train step; returns the (device, unsynchronised) retrieval loss (SUM over the batch).
+        With cfg.normalize_embeddings the step never takes the composite C call (``tt_train_step_f32`` cannot describe the two
+        normalisation launches): it runs the Python sequence ``forward_backward`` + ``apply_gradients(step_ids=...)`` - the path
+        asymmetric towers take - with one launch after the towers' forward and one in front of their backward."""
         self._check_batch(user_ids, item_ids, loss_kw.get("category_ids"), loss_kw.get("sample_weight"),
                           loss_kw.get("candidate_sampling_probability"), loss_kw.get("candidate_ids"))
         # (never inside a graph capture: the poll queries an event recorded outside it and would bake a D2H copy into every replay)
@@ -464,7 +498,7 @@ class TwoTowerTrainer:
             self._poll_skew(ids, rows)
         fused_sort = shape_ok and not self._skewed()
         if fused_sort:
-            if (self.use_composite and self.fuse_lookup and self.cfg.symmetric
+            if (self.use_composite and self.fuse_lookup and self.cfg.symmetric and not self.cfg.normalize_embeddings
                     and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
                 return self._step_composite(ids, **loss_kw)
             loss = self.forward_backward(user_ids, item_ids, **loss_kw)
@@ -588,6 +622,7 @@ class TwoTowerTrainer:
             q, c = towers_forward(ut, it) if cfg.symmetric else (ut.forward(), it.forward())
         else:
             q, c = towers_forward(ut, it, lookups=lks) if cfg.symmetric else (ut.forward(lookup=lks[0]), it.forward(lookup=lks[1]))
+        q, c = self._outputs(ut, it)
         kw = dict(sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
                   cand_ids=loss_kw.get("candidate_ids"))
         return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
@@ -596,7 +631,8 @@ class TwoTowerTrainer:
     # ------------------------------------------------------------------ retrieval metrics
     @torch.no_grad()
     def item_corpus_embeddings(self, item_category_ids: torch.Tensor | None = None) -> torch.Tensor:
-        """Item-tower output for EVERY item row ([n_items, scorer_dim]), computed batch by batch on the tower's buffers.
+        """Item-tower output for EVERY item row ([n_items, scorer_dim]; unit-norm rows with cfg.normalize_embeddings), computed
+        batch by batch on the tower's buffers.
         item_category_ids [n_items]: the category bucket of every item (required iff the model has the feature)."""
         it, b = self.item_tower, self.cfg.batch_size
         n = self.cfg.n_items
@@ -609,12 +645,13 @@ class TwoTowerTrainer:
             if item_category_ids is not None:
                 ops.embedding_gather_add_(it.acts[0][:e - s], self.cat_table, item_category_ids[s:e], self.oob)
             it.forward()
-            out[s:e].copy_(it.acts[-1][:e - s])
+            out[s:e].copy_(self._outputs(it)[0][:e - s])
         return out
 
     @torch.no_grad()
     def user_embeddings(self, user_ids: torch.Tensor) -> torch.Tensor:
-        """User-tower output (inference: no dropout) for ANY number of user ids ([n, scorer_dim]), computed cfg.batch_size
+        """User-tower output (inference: no dropout; unit-norm rows with cfg.normalize_embeddings) for ANY number of user ids
+        ([n, scorer_dim]), computed cfg.batch_size
         ids at a time on the tower's buffers.  Out-of-range ids give the tower output of a zero row and set the trainer's
         out-of-range flag (``check_ids``)."""
         ut, b = self.user_tower, self.cfg.batch_size
@@ -625,7 +662,7 @@ class TwoTowerTrainer:
             e = min(s + b, n)
             ops.embedding_gather(self.user_table, ids[s:e], out=ut.acts[0][:e - s], oob_flag=self.oob)
             ut.forward()
-            out[s:e].copy_(ut.acts[-1][:e - s])
+            out[s:e].copy_(self._outputs(ut)[0][:e - s])
         return out
 
     @torch.no_grad()
@@ -635,7 +672,8 @@ class TwoTowerTrainer:
         self._check_batch(user_ids, item_ids)
         if corpus is None:
             corpus = self.item_corpus_embeddings()
-        q = self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
+        self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
+        (q,) = self._outputs(self.user_tower)
         return metric.update_state(q, corpus, item_ids)
 
     # ------------------------------------------------------------------ checkpoint
@@ -655,6 +693,12 @@ class TwoTowerTrainer:
             if sd["config"].get(k, 0 if k == "n_category_buckets" else None) != getattr(self.cfg, k):
                 raise ValueError(f"checkpoint {k}={sd['config'].get(k)!r} does not match the trainer's {getattr(self.cfg, k)!r}")
         self.user_table.copy_(sd["user_table"]); self.item_table.copy_(sd["item_table"]); self.dense_flat.copy_(sd["dense"])
+        # whether the embeddings are normalised belongs to the trained model, not to the run that loads it: the checkpoint's
+        # value replaces the trainer's (a checkpoint from before the switch existed: off)
+        self.cfg.normalize_embeddings = bool(sd["config"].get("normalize_embeddings", False))
+        self.cfg.normalize_eps = float(sd["config"].get("normalize_eps", TwoTowerConfig.normalize_eps))
+        if self.cfg.normalize_embeddings:
+            self.user_tower.alloc_unit(); self.item_tower.alloc_unit()
         # the counter-based dropout stream continues where the checkpoint stopped (no replayed masks)
         self.step_index = int(sd.get("step_index", 0))
         self.dropout_seed = int(sd.get("dropout_seed", self.dropout_seed))
