@@ -47,8 +47,9 @@ typedef void* tt_stream_t;
 int tt_abi_version(void);
 const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
- * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args;
- * else -1): a binding checks its mirrors with it. */
+ * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args,
+ * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper; else - 9 included, which stays unassigned - -1): a binding checks its
+ * mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
 /* ---------------------------------------------------------------------------------------
@@ -61,7 +62,7 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * the scope ivf around a whole tt_ivf_search_f32 call), quantize_i8, topk_i8_scan, topk_i8_rerank, topk_i8_scale (and the
  * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
- * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd.
+ * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -420,6 +421,51 @@ int tt_id_range_load(const int64_t* const* ids, const int64_t* table_rows, int32
                      const tt_dense_seg* segs, int32_t n_segs, int32_t* out_max, tt_stream_t stream);
 int tt_optimizer_step_ids_f32(int32_t opt, const tt_sparse_table_ids* tables, int32_t n_tables, int32_t dim, int64_t n_ids,
                               const tt_dense_seg* segs, int32_t n_segs, float lr, float eps, tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Lazy Adam (added to v10: new symbols only, the version is unchanged) - TF-Addons LazyAdam / torch.optim.SparseAdam with
+ * Keras Adam's defaults (configs/data_config.yaml:63 learning_rate 0.001 is Keras Adam's step size): the sparse update of up
+ * to 3 embedding tables AND the dense update of every tower segment in one call (csrc/adam.hip).  Only the rows of this
+ * batch's ids are touched - every other row keeps w, m and v bit for bit; ids outside [0, rows) (the padding id -1
+ * included) are skipped; the bias correction comes from the 1-based global step.
+ * Arithmetic (f32, one rounding per operation, no contraction).  The library computes on the HOST, in f64, each rounded once
+ * to f32:  omb1 = 1 - beta1,  omb2 = 1 - beta2,  alpha_t = lr * sqrt(1 - beta2^step) / (1 - beta1^step)   (lr, beta1, beta2
+ * widened from the f32 values of tt_adam_hyper).  For every distinct id u of a table (every element of a segment):
+ *   m' = m + (g - m) * omb1;    v' = v + (g*g - v) * omb2;    w' = w - (alpha_t * m') / (sqrt(v') + eps)
+ * evaluated in exactly that order.  Sparse g: the sum of the gradient rows of u in the order of tt_sparse_{sgd,adagrad}_f32
+ * (runs cut at global multiples of 64 sorted slots, pieces sequential, pieces added in index order): bit-identical to the g SGD
+ * and Adagrad see.  Dense g = slab 0 + slab 1 + ... (ascending, starting AT slab 0), then + (2*l2)*w, as tt_dense_update_f32.
+ * Consumes tt_sparse_plan / tt_sparse_plan_batched outputs (every table: the same dim and n_ids).  `tables`, `segs` and `h`
+ * are HOST data.  n_tables in 0..3 (0: dense only), n_segs in 0..TT_MAX_DENSE_SEGS (0: sparse only); n_ids == 0 with
+ * n_segs == 0 is a no-op.  dim % 4 == 0; step >= 1; beta1, beta2 in [0, 1); eps > 0; m and v non-NULL; table, m, v, grads
+ * 16-byte aligned: anything else is TT_ERR_INVALID_ARG before any launch.
+ * Two stream-ordered launches and no communication inside either (no tickets, no wait between workgroups): the first sums
+ * every piece and updates the runs that lie inside one 64-slot block; the second finishes the runs that cross a block boundary
+ * from the piece sums the first stored in `workspace` and carries the dense segments as extra workgroups.
+ * workspace: tt_adam_workspace_bytes(n_ids, dim) bytes PER TABLE (0 for n_ids == 0), 256-byte aligned; needs NO
+ * initialisation (the second launch reads only what the first wrote in the same call).                              */
+typedef struct tt_adam_table {
+  float* table; float* m; float* v;      /* [rows, dim] parameters, first and second moment */
+  int64_t rows;
+  const float* grads;                    /* [n_ids, dim] per-position gradient rows */
+  const int64_t* sorted_ids; const int32_t* order;   /* tt_sparse_plan outputs      */
+  void* workspace;                       /* tt_adam_workspace_bytes(n_ids, dim)     */
+} tt_adam_table;
+typedef struct tt_adam_seg {
+  float* param; float* m; float* v;      /* [count]                                 */
+  const float* grad_slabs;               /* [n_slabs][slab_stride]                  */
+  int64_t count;
+  int64_t slab_stride;
+  int32_t n_slabs;
+  float l2;                              /* l2_regularization; 0 for biases         */
+} tt_adam_seg;
+typedef struct tt_adam_hyper {
+  float lr, beta1, beta2, eps;           /* Keras defaults: 0.001, 0.9, 0.999, 1e-7 */
+  int64_t step;                          /* 1-based global step                     */
+} tt_adam_hyper;
+int64_t tt_adam_workspace_bytes(int64_t n_ids, int32_t dim);
+int tt_adam_step_f32(const tt_adam_table* tables, int32_t n_tables, int32_t dim, int64_t n_ids,
+                     const tt_adam_seg* segs, int32_t n_segs, const tt_adam_hyper* h, tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * The WHOLE train step as one call (ABI v8): what `train-model` (pyproject.toml:67, src/training/train.py - declared,

@@ -91,6 +91,27 @@ class DenseSeg(C.Structure):
     ]
 
 
+class AdamTable(C.Structure):
+    """Mirror of ``tt_adam_table`` (one embedding table of ``tt_adam_step_f32``)."""
+    _fields_ = [("table", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("rows", C.c_int64), ("grads", C.c_void_p),
+                ("sorted_ids", C.c_void_p), ("order", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class AdamSeg(C.Structure):
+    """Mirror of ``tt_adam_seg`` (one dense segment of ``tt_adam_step_f32``)."""
+    _fields_ = [("param", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad_slabs", C.c_void_p),
+                ("count", C.c_int64), ("slab_stride", C.c_int64), ("n_slabs", C.c_int32), ("l2", C.c_float)]
+
+
+class AdamHyper(C.Structure):
+    """Mirror of ``tt_adam_hyper``."""
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int64)]
+
+
+# tt_abi_struct_bytes index of each mirror (9 is unassigned: the library answers -1 for it)
+ABI_STRUCT_INDEX = {"AdamTable": 10, "AdamSeg": 11, "AdamHyper": 12}
+
+
 class TrainStep(C.Structure):
     """Mirror of ``tt_train_step``: the whole train step behind one C call (``tt_train_step_f32``)."""
     _fields_ = [
@@ -161,6 +182,8 @@ SIGNATURES = {
                                             C.POINTER(C.c_uint32), C.POINTER(_i32)]),
     "tt_id_buckets_workspace_bytes": (_i64, []),
     "tt_id_range_load": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(_i64), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, _p, _p]),
+    "tt_adam_workspace_bytes": (_i64, [_i64, _i32]),
+    "tt_adam_step_f32": (C.c_int, [C.POINTER(AdamTable), _i32, _i32, _i64, C.POINTER(AdamSeg), _i32, C.POINTER(AdamHyper), _p]),
     "tt_train_step_f32": (C.c_int, [C.POINTER(TrainStep), _p]),
     "tt_retrieval_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "tt_retrieval_num_splits": (_i32, [_i64, _i64, _i32, _i32]),

@@ -215,6 +215,14 @@ class SparsePlan:
         self.sorted_ids = torch.empty(n_ids, dtype=torch.int64, device=device)
         self.order = torch.empty(n_ids, dtype=torch.int32, device=device)
         self._apply_ws = None
+        self._adam_ws = None
+
+    def adam_ws(self, dim: int) -> torch.Tensor:
+        """Piece-sum workspace of ``adam_step_`` for rows of ``dim`` floats (allocated once; never initialised)."""
+        need = max(adam_workspace_bytes(self.n_ids, dim), 256)
+        if self._adam_ws is None or self._adam_ws.numel() < need:
+            self._adam_ws = torch.empty(need, dtype=torch.uint8, device=self.sorted_ids.device)
+        return self._adam_ws
 
     def apply_ws(self, dim: int) -> torch.Tensor:
         """Piece-sum workspace of the apply kernels for rows of ``dim`` floats (allocated once)."""
@@ -596,6 +604,61 @@ def optimizer_step_ids_(opt: str, tables, segs: list[DenseSeg], lr: float, eps: 
 def make_dense_seg(param, accum, grad_slabs, n_slabs: int, l2: float, grad_out=None) -> DenseSeg:
     count = param.numel()
     return DenseSeg(_p(param), _p(accum), _p(grad_slabs), _p(grad_out), count, count, n_slabs, l2)
+
+
+# ----------------------------------------------------------------------------- lazy Adam
+def adam_workspace_bytes(n_ids: int, dim: int) -> int:
+    """Piece-sum workspace of ``adam_step_`` per table: 256-byte aligned, needs no initialisation; 0 for no ids."""
+    return int(_lib.load().tt_adam_workspace_bytes(n_ids, dim))
+
+
+class AdamHyper:
+    """Hyper-parameters of one lazy-Adam step (``tt_adam_hyper``): Keras Adam's defaults and the 1-based global ``step`` the bias
+    correction is taken from.  The library computes 1 - beta1, 1 - beta2 and lr * sqrt(1 - beta2^step) / (1 - beta1^step) on the
+    host in f64 and rounds each once to f32."""
+
+    def __init__(self, lr: float = 0.001, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-7, step: int = 1):
+        self.lr, self.beta1, self.beta2, self.eps, self.step = float(lr), float(beta1), float(beta2), float(eps), int(step)
+
+    def struct(self) -> "_lib.AdamHyper":
+        return _lib.AdamHyper(self.lr, self.beta1, self.beta2, self.eps, self.step)
+
+
+def make_adam_seg(param, m, v, grad_slabs, n_slabs: int, l2: float, slab_stride: int | None = None) -> "_lib.AdamSeg":
+    """One dense segment of ``adam_step_``: ``param``, ``m``, ``v`` [count] and ``grad_slabs`` [n_slabs][slab_stride]."""
+    for t, name in ((param, "param"), (m, "m"), (v, "v"), (grad_slabs, "grad_slabs")):
+        _chk(t, torch.float32, name)
+    count = param.numel()
+    stride = count if slab_stride is None else int(slab_stride)
+    if m.numel() != count or v.numel() != count:
+        raise RuntimeError("make_adam_seg: m and v must have the parameter's size")
+    if n_slabs < 1 or stride < count or grad_slabs.numel() < (n_slabs - 1) * stride + count:
+        raise RuntimeError("make_adam_seg: grad_slabs must hold n_slabs slabs of slab_stride >= count floats")
+    return _lib.AdamSeg(_p(param), _p(m), _p(v), _p(grad_slabs), count, stride, n_slabs, l2)
+
+
+def adam_step_(tables, segs, hyper: AdamHyper):
+    """One lazy-Adam step (``tt_adam_step_f32``: two launches): ``tables`` = [(table, m, v, grads, plan), ...] - up to 3 embedding
+    tables of one width whose plans (``sparse_plan_batched`` / ``SparsePlan.run``) hold the same number of ids - and ``segs`` =
+    ``make_adam_seg`` descriptions of the dense parameters.  Either list may be empty.  Only the rows of the plans' ids change."""
+    for table, m, v, grads, _ in tables:
+        _chk(table, torch.float32, "table", 2)
+        _chk(m, torch.float32, "m", 2)
+        _chk(v, torch.float32, "v", 2)
+        _chk(grads, torch.float32, "grads", 2)
+    dim, n_ids = (tables[0][0].shape[1], tables[0][4].n_ids) if tables else (4, 0)
+    arr_t = (_lib.AdamTable * max(len(tables), 1))()
+    for i, (table, m, v, grads, plan) in enumerate(tables):
+        if m.shape != table.shape or v.shape != table.shape:
+            raise RuntimeError("adam_step_: m and v must have the table's shape")
+        if table.shape[1] != dim or plan.n_ids != n_ids or tuple(grads.shape) != (n_ids, dim):
+            raise RuntimeError("adam_step_: every table needs the same dim, the same number of ids and [n_ids, dim] gradients")
+        arr_t[i] = _lib.AdamTable(_p(table), _p(m), _p(v), table.shape[0], _p(grads), _p(plan.sorted_ids), _p(plan.order),
+                                  _p(plan.adam_ws(dim)))
+    arr_s = (_lib.AdamSeg * max(len(segs), 1))(*segs)
+    h = hyper.struct()
+    _lib.check(_lib.load().tt_adam_step_f32(arr_t, len(tables), dim, n_ids, arr_s, len(segs), C.byref(h), _stream()),
+               "tt_adam_step_f32")
 
 
 # ----------------------------------------------------------------------------- L2-normalised tower outputs

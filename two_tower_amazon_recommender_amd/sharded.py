@@ -417,6 +417,10 @@ class ShardedTwoTowerTrainer:
             # global negatives must normalise before the all-gather and run the backward after the reduce-scatter
             raise NotImplementedError("normalize_embeddings is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "optimizer", None) == "adam":
+            # owner-side lazy Adam (moments sharded with the rows, one global step counter) is not built
+            raise NotImplementedError("optimizer='adam' is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         from . import ops
         from .trainer import Tower, TID_USER_TABLE, TID_ITEM_TABLE
         cfg.validate()

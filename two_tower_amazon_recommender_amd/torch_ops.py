@@ -9,6 +9,7 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
     rows = torch.ops.twotower.embedding_gather(table, ids)
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
+    torch.ops.twotower.sparse_adam_(table, exp_avg, exp_avg_sq, grads, ids, step, lr, 0.9, 0.999, 1e-7)
 
 What the reference would have run through TensorFlow / TFRS for these (``/root/reference/pyproject.toml:22,24``;
 settings ``configs/data_config.yaml:54-71``; the task object's call signature: SURVEY.md Appendix A).
@@ -440,5 +441,14 @@ def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: T
         ops.sparse_adagrad_(table, accum, grads.contiguous(), plan, lr, eps)
 
 
+@torch.library.custom_op(f"{NS}::sparse_adam_", mutates_args=("table", "exp_avg", "exp_avg_sq"), device_types="cuda")
+def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tensor, ids: Tensor, step: int, lr: float,
+                 beta1: float, beta2: float, eps: float) -> None:
+    """Lazy Adam (TF-Addons LazyAdam / torch.optim.SparseAdam, Keras's epsilon placement) on the rows ``ids`` of ``table`` (in
+    place; duplicates summed first; ``step`` is the 1-based global step of the bias correction): one sort launch + two launches."""
+    plan = _plan(ids.numel(), ids.device).run(ids.contiguous(), table.shape[0])
+    ops.adam_step_([(table, exp_avg, exp_avg_sq, grads.contiguous(), plan)], [], ops.AdamHyper(lr, beta1, beta2, eps, step))
+
+
 OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "sparse_update_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "sparse_update_", "sparse_adam_")

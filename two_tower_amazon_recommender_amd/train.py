@@ -56,7 +56,12 @@ def parse(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N synthetic interactions instead of --data")
     ap.add_argument("--synthetic-users", type=int, default=10_000)
     ap.add_argument("--synthetic-items", type=int, default=10_000)
-    ap.add_argument("--optimizer", default="adagrad", choices=["sgd", "adagrad"])
+    ap.add_argument("--optimizer", default="adagrad", choices=["sgd", "adagrad", "adam"],
+                    help="adam = lazy Adam (only the rows of a batch's ids are touched): what model.training.learning_rate 0.001 "
+                         "is the Keras default of; single-GPU trainer only")
+    ap.add_argument("--adam-beta1", type=float, default=0.9)
+    ap.add_argument("--adam-beta2", type=float, default=0.999)
+    ap.add_argument("--adam-epsilon", type=float, default=1e-7)
     ap.add_argument("--category-buckets", type=int, default=0, metavar="N",
                     help="add the hashed category feature: the pair's category (column category / main_category / "
                          "category_encoded) hashed into N buckets, its embedding summed into the item tower input")
@@ -95,6 +100,8 @@ def main(argv=None) -> int:
     normalize = args.normalize_embeddings or bool(((doc.get("model") or {}).get("retrieval") or {}).get("normalize_embeddings", False))
     if distributed and normalize:
         raise NotImplementedError("normalize_embeddings is not implemented for the row-sharded (--distributed) trainer")
+    if distributed and args.optimizer == "adam":
+        raise NotImplementedError("optimizer 'adam' is not implemented for the row-sharded (--distributed) trainer")
     if distributed:
         import torch.distributed as dist
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -133,6 +140,7 @@ def main(argv=None) -> int:
     cfg.n_category_buckets = args.category_buckets
     cfg.scorer_precision = args.scorer_precision
     cfg.normalize_embeddings = normalize
+    cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = args.adam_beta1, args.adam_beta2, args.adam_epsilon
     if args.batch_size:
         cfg.batch_size = args.batch_size
     epochs = args.epochs if args.epochs is not None else loop["epochs"]

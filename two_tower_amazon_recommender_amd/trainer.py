@@ -5,7 +5,8 @@ This is the explicit (no autograd) engine that ``train.py`` and ``bench.py`` dri
     ids ──► tower fwd, the embedding lookup fused into its input tile (both layers of both towers: 1 launch)
         ──► fused scorer + softmax loss (pass 1: loss + dq, combine, pass 2: dc, slab reduction: 4 launches)
         ──► tower bwd (dx + dw + db per layer: 2 launches)
-        ──► optimizer (sort of the ids, duplicate sums, sparse SGD/Adagrad of all tables, dense update: 1 launch)
+        ──► optimizer (sort of the ids, duplicate sums, sparse SGD/Adagrad of all tables, dense update: 1 launch;
+                       lazy Adam: sort plan + two launches, ``ops.adam_step_``)
 
 All buffers are allocated once for a fixed batch size; ``step`` enqueues those 8 launches (cfg3; one more per extra tower
 layer) through ONE C call (``tt_train_step_f32``) on the current stream and never synchronises (it can be captured in a
@@ -45,9 +46,14 @@ class TwoTowerConfig:
     temperature: float = 0.1                       # :70
     l2_regularization: float = 1e-6                # :59
     learning_rate: float = 0.001                   # :63
-    optimizer: str = "sgd"                         # unspecified by the reference; north_star: SGD / Adagrad
+    optimizer: str = "sgd"                         # unspecified by the reference; north_star: SGD / Adagrad; "adam" = lazy Adam
     adagrad_initial_accumulator: float = 0.1       # Keras 2.15 default
     adagrad_epsilon: float = 1e-7                  # Keras 2.15 default
+    # optimizer="adam": lazy Adam (TF-Addons LazyAdam / torch.optim.SparseAdam) - only the rows of the batch's ids are touched,
+    # the bias correction comes from the global step; Keras 2.15 Adam's defaults (its learning_rate default is :63's 0.001)
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.999
+    adam_epsilon: float = 1e-7
     batch_size: int = 1024                         # :62
     dropout_rate: float = 0.0                      # :58 is 0.1; parity/bench runs use 0
     # BASELINE configs[4] "30 categories as hash features": a [n_category_buckets, embedding_dim] table whose row
@@ -75,8 +81,14 @@ class TwoTowerConfig:
         return self.user_dims == self.item_dims
 
     def validate(self):
-        if self.optimizer not in ("sgd", "adagrad"):
-            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {self.optimizer!r}")
+        if self.optimizer not in ("sgd", "adagrad", "adam"):
+            raise ValueError(f"optimizer must be 'sgd', 'adagrad' or 'adam', got {self.optimizer!r}")
+        if not 0.0 <= self.adam_beta1 < 1.0:
+            raise ValueError("adam_beta1 must be in [0, 1)")
+        if not 0.0 <= self.adam_beta2 < 1.0:
+            raise ValueError("adam_beta2 must be in [0, 1)")
+        if not self.adam_epsilon > 0:
+            raise ValueError("adam_epsilon must be > 0")
         if self.embedding_dim % 4 or any(d % 4 for d in self.user_dims + self.item_dims):
             raise ValueError("embedding_dim and tower dims must be multiples of 4")
         if self.user_dims[-1] != self.item_dims[-1]:
@@ -262,7 +274,7 @@ class TwoTowerTrainer:
         if dev.type != "cuda":
             raise RuntimeError("TwoTowerTrainer needs a CUDA/HIP device: there is no CPU fallback")
         b, d = cfg.batch_size, cfg.embedding_dim
-        adagrad = cfg.optimizer == "adagrad"
+        adagrad, adam = cfg.optimizer == "adagrad", cfg.optimizer == "adam"
         self.user_table = torch.empty(cfg.n_users, d, device=dev)
         self.item_table = torch.empty(cfg.n_items, d, device=dev)
         self.user_accum = torch.full_like(self.user_table, cfg.adagrad_initial_accumulator) if adagrad else None
@@ -271,6 +283,13 @@ class TwoTowerTrainer:
         self.dense_flat = torch.zeros(n_user + n_item, device=dev)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
+        # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
+        # global step the bias correction is taken from - part of the optimizer state (checkpointed)
+        self.user_m, self.user_v = (torch.zeros_like(self.user_table), torch.zeros_like(self.user_table)) if adam else (None, None)
+        self.item_m, self.item_v = (torch.zeros_like(self.item_table), torch.zeros_like(self.item_table)) if adam else (None, None)
+        self.dense_m, self.dense_v = (torch.zeros_like(self.dense_flat), torch.zeros_like(self.dense_flat)) if adam else (None, None)
+        self.cat_m = self.cat_v = None
+        self.adam_step = 1
         self.user_tower = Tower(cfg, cfg.user_dims, self.dense_flat, self.dense_accum, 0, dev)
         self.item_tower = Tower(cfg, cfg.item_dims, self.dense_flat, self.dense_accum, n_user, dev)
         sd = cfg.tower_dims[-1]
@@ -286,6 +305,8 @@ class TwoTowerTrainer:
             self.cat_table = torch.empty(cfg.n_category_buckets, d, device=dev)
             self.cat_accum = torch.full_like(self.cat_table, cfg.adagrad_initial_accumulator) if adagrad else None
             self.cat_plan = ops.SparsePlan(b, dev)
+            if adam:
+                self.cat_m, self.cat_v = torch.zeros_like(self.cat_table), torch.zeros_like(self.cat_table)
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -334,6 +355,14 @@ class TwoTowerTrainer:
         self._skew_dev = self._skew_host = self._skew_event = None
         self.dropout_seed = 0 if seed is None else seed
         self._segs = self.user_tower.segments(cfg.l2_regularization) + self.item_tower.segments(cfg.l2_regularization)
+        self._adam_segs = None
+        if adam:        # the same segments (parameter, gradient slabs, l2) with the moments' views of dense_m / dense_v
+            self._adam_segs = []
+            for tower in (self.user_tower, self.item_tower):
+                for l in range(tower.n_layers):
+                    for prm, slabs, reg in ((tower.w[l], tower.dw_slabs[l], cfg.l2_regularization), (tower.b[l], tower.db_slabs[l], 0.0)):
+                        lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
+                        self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, tower.n_slabs, reg))
         if seed is not None:
             self.init_synthetic(seed)
 
@@ -356,6 +385,10 @@ class TwoTowerTrainer:
             for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum):
                 if a is not None:
                     a.fill_(self.cfg.adagrad_initial_accumulator)
+        for a in (self.user_m, self.user_v, self.item_m, self.item_v, self.cat_m, self.cat_v, self.dense_m, self.dense_v):
+            if a is not None:
+                a.zero_()
+        self.adam_step = 1
 
     def synthetic_batch(self, seed: int, step: int, variant: str = "U", out=None):
         b = self.cfg.batch_size
@@ -450,6 +483,15 @@ class TwoTowerTrainer:
     def apply_gradients(self, step_ids=None):
         """``step_ids`` = [user ids, item ids (, category ids)]: the optimizer launch sorts them itself (no plan launch ran)."""
         cfg = self.cfg
+        if cfg.optimizer == "adam":  # every table and every tower segment in ONE call (two launches), from the sort plans
+            tables = [(self.user_table, self.user_m, self.user_v, self.user_tower.demb, self.user_plan),
+                      (self.item_table, self.item_m, self.item_v, self.item_tower.demb, self.item_plan)]
+            if self.cat_table is not None:   # the category row's gradient is the item-tower input gradient itself
+                tables.append((self.cat_table, self.cat_m, self.cat_v, self.item_tower.demb, self.cat_plan))
+            ops.adam_step_(tables, self._adam_segs, ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon,
+                                                                  self.adam_step))
+            self.adam_step += 1
+            return
         if step_ids is not None:     # sort + sparse update of every table + dense update: ONE launch, straight from the raw ids
             tables = [(self.user_table, self.user_accum, self.user_tower.demb, step_ids[0], self.user_plan),
                       (self.item_table, self.item_accum, self.item_tower.demb, step_ids[1], self.item_plan)]
@@ -492,8 +534,9 @@ class TwoTowerTrainer:
             plans.append(self.cat_plan); ids.append(loss_kw["category_ids"]); rows.append(self.cfg.n_category_buckets)
         # fuse_sort: no plan launch at all - the optimizer launch's workgroups sort the ids of their own row range in LDS
         # and update exactly those rows (tt_optimizer_step_ids_f32; lists up to 65536 ids) - unless the batches are skewed
-        shape_ok = (self.fuse_sort and self.fuse_optimizer and user_ids.numel() <= ops.optimizer_ids_max_ids()
-                    and (self.cat_table is None) == (len(ids) == 2))
+        # (lazy Adam always takes the sort plan: it has no composite call, no one-launch form and so no skew probe)
+        shape_ok = (self.cfg.optimizer != "adam" and self.fuse_sort and self.fuse_optimizer
+                    and user_ids.numel() <= ops.optimizer_ids_max_ids() and (self.cat_table is None) == (len(ids) == 2))
         if shape_ok:
             self._poll_skew(ids, rows)
         fused_sort = shape_ok and not self._skewed()
@@ -686,6 +729,11 @@ class TwoTowerTrainer:
             sd.update(user_accum=self.user_accum, item_accum=self.item_accum, dense_accum=self.dense_accum)
             if self.cat_table is not None:
                 sd["cat_accum"] = self.cat_accum
+        if self.cfg.optimizer == "adam":
+            sd.update(user_m=self.user_m, user_v=self.user_v, item_m=self.item_m, item_v=self.item_v, dense_m=self.dense_m,
+                      dense_v=self.dense_v, adam_step=self.adam_step)
+            if self.cat_table is not None:
+                sd.update(cat_m=self.cat_m, cat_v=self.cat_v)
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -709,6 +757,10 @@ class TwoTowerTrainer:
         if self.cfg.optimizer == "adagrad":
             self.user_accum.copy_(sd["user_accum"]); self.item_accum.copy_(sd["item_accum"])
             self.dense_accum.copy_(sd["dense_accum"])
+        if self.cfg.optimizer == "adam":
+            for k in ("user_m", "user_v", "item_m", "item_v", "dense_m", "dense_v") + (("cat_m", "cat_v") if self.cat_table is not None else ()):
+                getattr(self, k).copy_(sd[k])
+            self.adam_step = int(sd["adam_step"])
 
     # ------------------------------------------------------------------ HIP graph replay of the whole step
     def capture_graph(self):
@@ -716,6 +768,9 @@ class TwoTowerTrainer:
         copies the ids into the captured buffers and replays: one host call per step, no launch gaps."""
         if self.cfg.dropout_rate > 0.0:
             raise NotImplementedError("graph replay with dropout: the per-step counter is a kernel argument")
+        if self.cfg.optimizer == "adam":
+            raise NotImplementedError("graph replay with optimizer='adam': the global step, and so the bias-corrected step size, "
+                                      "is a kernel argument")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
