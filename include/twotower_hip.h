@@ -124,6 +124,40 @@ int tt_hash_bucket_u8(const uint8_t* rows_u8, int64_t n, int32_t width, int64_t 
                       int64_t* out, tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Embedding bag (added to v10: new symbols only, the version is unchanged) - a bag of hashed token rows pooled into one
+ * vector: TFRS TextVectorization -> Embedding -> GlobalAveragePooling1D, here the pooled item-title feature summed into the
+ * item tower's input (csrc/bag.hip).
+ * Layout: tokens [n_token_rows, L] int32 row-major, one row per item; the slot value -1 is PADDING and may stand anywhere
+ * in a row.  table [table_rows, dim] f32, dim % 4 == 0, 4 <= dim <= 1024.
+ * Forward.  Bag b pools token row bag_rows[b] (bag_rows [n_bags] int64; NULL = identity, then n_bags must equal
+ * n_token_rows).  bag_rows[b] == -1 is an empty bag; any other value outside [0, n_token_rows) is an empty bag and sets
+ * *oob_flag (device int32, may be NULL).  A slot is VALID when its token lies in [0, table_rows); padding slots are skipped,
+ * any other token out of range is skipped and sets the flag; cnt = the number of valid slots.
+ * Arithmetic (f32, one rounding per operation, no contraction): s = the first valid row, every further valid row added in
+ * ascending slot order;
+ *   pooling 0 (sum):    inv = 1            pooled = s
+ *   pooling 1 (mean):   inv = 1 / cnt      pooled = s * inv          (correctly rounded division)
+ *   pooling 2 (sqrtn):  inv = 1 / sqrt(cnt)  pooled = s * inv        (correctly rounded square root, then division)
+ *   accumulate 1: out[b] = out[b] + pooled;  accumulate 0: out[b] = pooled.
+ * An empty bag (cnt == 0) has inv = 0; with accumulate 1 its out row is not written, with accumulate 0 it is written as +0.
+ * Optional outputs (either may be NULL): batch_ids [n_bags * L] int64 = the token of every slot, -1 for a skipped slot
+ * (the ids tt_sparse_plan sorts); inv [n_bags] f32.
+ * One launch; bit-reproducible, independent of the grid; table and out 16-byte aligned; n_bags * L must fit 31 bits.
+ * n_bags == 0 launches nothing.  Anything else is TT_ERR_INVALID_ARG before any launch.
+ * Backward (one launch, two results): gs[b, :] = dy[b, :] * inv[b] (gs may be NULL for sum pooling - the caller then uses
+ * dy itself; gs may be dy) and order_bags[j] = order[j] / L for the n_ids = n_bags * L positions of a tt_sparse_plan over
+ * batch_ids: the plan's slot positions turned into bag indices.  The table is then updated by tt_sparse_sgd_f32 /
+ * tt_sparse_adagrad_f32 / tt_adam_step_f32 (n_tables = 1, n_segs = 0) with grads = gs and order = order_bags: n_bags * dim
+ * floats of gradient traffic, no per-token gradient rows, and the duplicate sums in the documented order (runs cut at global
+ * multiples of 64 sorted slots, slots in ascending position): bit-identical to an expansion into per-token rows.           */
+int tt_embedding_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim,
+                             const int32_t* tokens, int64_t n_token_rows, int32_t L,
+                             const int64_t* bag_rows, int64_t n_bags, int32_t pooling, int32_t accumulate,
+                             float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag, tt_stream_t stream);
+int tt_embedding_bag_bwd_f32(const float* dy, const float* inv, int64_t n_bags, int32_t dim, int32_t L,
+                             const int32_t* order, int64_t n_ids, float* gs, int32_t* order_bags, tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * a5 — sparse optimizer on embedding rows (Keras SGD / Adagrad on IndexedSlices,
  * duplicates summed before the update; configs/data_config.yaml:63 learning_rate).
  *
@@ -149,7 +183,9 @@ int tt_hash_bucket_u8(const uint8_t* rows_u8, int64_t n, int32_t width, int64_t 
  *        ZERO it once after allocation — the kernels leave it zeroed.
  *   SGD:      w[u] = w[u] - fl(lr*g)
  *   Adagrad:  acc[u] += g*g ; w[u] -= fl(lr*g) / sqrt(acc[u] + eps)      (Keras 2.15)
- * In place.  The `2` forms update the user and the item table in one launch.             */
+ * In place.  The `2` forms update the user and the item table in one launch.
+ * `order` is read only as an index into `grads`: row order[j] of grads is the gradient of sorted slot j; grads need not
+ * have n_ids rows (tt_embedding_bag_bwd_f32 hands in bag indices: many slots share one gradient row).                 */
 typedef struct tt_sparse_plan_args {
   const int64_t* ids;        /* [n_ids] */
   int64_t n_ids;
@@ -435,7 +471,8 @@ int tt_optimizer_step_ids_f32(int32_t opt, const tt_sparse_table_ids* tables, in
  * evaluated in exactly that order.  Sparse g: the sum of the gradient rows of u in the order of tt_sparse_{sgd,adagrad}_f32
  * (runs cut at global multiples of 64 sorted slots, pieces sequential, pieces added in index order): bit-identical to the g SGD
  * and Adagrad see.  Dense g = slab 0 + slab 1 + ... (ascending, starting AT slab 0), then + (2*l2)*w, as tt_dense_update_f32.
- * Consumes tt_sparse_plan / tt_sparse_plan_batched outputs (every table: the same dim and n_ids).  `tables`, `segs` and `h`
+ * Consumes tt_sparse_plan / tt_sparse_plan_batched outputs (every table: the same dim and n_ids).  As for the sparse entries, row
+ * order[j] of grads is the gradient of sorted slot j; grads need not have n_ids rows.  `tables`, `segs` and `h`
  * are HOST data.  n_tables in 0..3 (0: dense only), n_segs in 0..TT_MAX_DENSE_SEGS (0: sparse only); n_ids == 0 with
  * n_segs == 0 is a no-op.  dim % 4 == 0; step >= 1; beta1, beta2 in [0, 1); eps > 0; m and v non-NULL; table, m, v, grads
  * 16-byte aligned: anything else is TT_ERR_INVALID_ARG before any launch.

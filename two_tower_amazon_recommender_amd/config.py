@@ -24,6 +24,8 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     if sampling != "in_batch":
         raise NotImplementedError(f"candidate_sampling {sampling!r}: only 'in_batch' is implemented")
     dropout = float(m.get("dropout_rate", 0.0)) if dropout_override is None else dropout_override
+    # not in the reference's schema: model.features.title {buckets, max_tokens, pooling} - the pooled item-title feature
+    title = (m.get("features") or {}).get("title") or {}
     cfg = TwoTowerConfig(
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
@@ -31,7 +33,9 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         learning_rate=float(tr.get("learning_rate", 0.001)), optimizer=optimizer,
         batch_size=int(tr.get("batch_size", 1024)), dropout_rate=dropout,
         # not in the reference's schema (left open): an optional key beside retrieval.temperature
-        normalize_embeddings=bool(rt.get("normalize_embeddings", False)))
+        normalize_embeddings=bool(rt.get("normalize_embeddings", False)),
+        n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
+        title_pooling=str(title.get("pooling", "mean")))
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),
                 validation_freq=int(tr.get("validation_freq", 1)), top_k_eval=list(rt.get("top_k_eval", [])))
     return cfg, loop

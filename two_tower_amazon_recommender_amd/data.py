@@ -5,6 +5,8 @@
 row counts come from the id columns (max + 1), which is what the sorted-enumerate encoding guarantees."""
 from __future__ import annotations
 
+import re
+
 import numpy as np
 import torch
 
@@ -62,6 +64,53 @@ def item_categories(item_idx: np.ndarray, category_bucket: np.ndarray, n_items: 
     out = np.zeros(n_items, dtype=np.int64)
     first = np.unique(item_idx, return_index=True)
     out[first[0]] = category_bucket[first[1]]
+    return out
+
+
+TITLE_COLUMN = "title"          # prepare_training_data.py:52-62: every interaction carries its item's title
+_TOKEN = re.compile(r"[a-z0-9]+")
+
+
+def read_item_titles(path, item_idx: np.ndarray, n_items: int) -> list:
+    """The title (str) of every item row: the ``title`` column of the item's first interaction; an item never seen, or a
+    missing title, gives ""."""
+    import pyarrow.parquet as pq
+    names = pq.read_schema(path).names
+    if TITLE_COLUMN not in names:
+        raise KeyError(f"{path}: no {TITLE_COLUMN!r} column (columns: {names})")
+    col = pq.read_table(path, columns=[TITLE_COLUMN]).column(TITLE_COLUMN).to_pylist()
+    out = [""] * n_items
+    items, first = np.unique(item_idx, return_index=True)
+    for i, r in zip(items.tolist(), first.tolist()):
+        v = col[r]
+        out[i] = "" if v is None else str(v)
+    return out
+
+
+def title_token_rows(titles, max_tokens: int, width: int = 32):
+    """Pure CPU: (rows uint8 [n, max_tokens, width], valid bool [n, max_tokens]).  A title is lower-cased and cut into its
+    runs of [a-z0-9]; the first ``max_tokens`` tokens are kept, each one's UTF-8 bytes cut to ``width`` and zero-padded (the row
+    format of ``ops.hash_buckets``).  An empty title gives no valid slot."""
+    n = len(titles)
+    rows = np.zeros((n, max_tokens, width), dtype=np.uint8)
+    valid = np.zeros((n, max_tokens), dtype=bool)
+    for i, t in enumerate(titles):
+        for k, tok in enumerate(_TOKEN.findall(str(t).lower())[:max_tokens]):
+            b = tok.encode("utf-8")[:width]
+            rows[i, k, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+            valid[i, k] = True
+    return rows, valid
+
+
+def title_tokens(titles, n_buckets: int, max_tokens: int, device, width: int = 32, chunk: int = 65536) -> torch.Tensor:
+    """int32 [n, max_tokens] token matrix of ``set_item_titles``: every token row hashed on the GPU (``ops.hash_buckets``:
+    FNV-1a-64 mod n_buckets), empty slots -1.  ``chunk`` titles are tokenised and hashed at a time."""
+    from . import ops
+    out = torch.full((len(titles), max_tokens), -1, dtype=torch.int32, device=device)
+    for s in range(0, len(titles), chunk):
+        rows, valid = title_token_rows(titles[s:s + chunk], max_tokens, width)
+        h = ops.hash_buckets(torch.from_numpy(rows.reshape(-1, width)).to(device), n_buckets).view(-1, max_tokens)
+        out[s:s + chunk] = torch.where(torch.from_numpy(valid).to(device), h, -1).to(torch.int32)
     return out
 
 

@@ -161,6 +161,72 @@ def hash_buckets(rows_u8: torch.Tensor, n_buckets: int) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------- embedding bag (pooled item titles)
+POOLINGS = {"sum": _lib.TT_POOL_SUM, "mean": _lib.TT_POOL_MEAN, "sqrtn": _lib.TT_POOL_SQRTN}
+
+
+def embedding_bag(table: torch.Tensor, tokens: torch.Tensor, bag_rows: torch.Tensor | None = None, pooling: str = "mean",
+                  out: torch.Tensor | None = None, accumulate: bool = False, batch_ids: torch.Tensor | None = None,
+                  inv: torch.Tensor | None = None, oob_flag: torch.Tensor | None = None) -> torch.Tensor:
+    """out[b, :] (+)= pool(table[t, :] for the valid tokens t of row bag_rows[b] of ``tokens``) - ``tt_embedding_bag_fwd_f32``.
+    ``tokens`` [n_token_rows, L] int32, -1 = padding (anywhere in a row); ``bag_rows`` [n_bags] int64 (None: bag b is row b;
+    -1: an empty bag); ``pooling`` "sum" | "mean" | "sqrtn"; ``accumulate`` adds into ``out`` (which must then be given).
+    Optional outputs: ``batch_ids`` [n_bags * L] int64 (every slot's token, -1 where skipped: what the sort plan sorts) and
+    ``inv`` [n_bags] f32 (the pooling scale; 0 for an empty bag).  ``oob_flag`` (int32[1]) is set on any token or bag row out
+    of range."""
+    _chk(table, torch.float32, "table", 2)
+    _chk(tokens, torch.int32, "tokens", 2)
+    if pooling not in POOLINGS:
+        raise ValueError(f"embedding_bag: pooling must be one of {tuple(POOLINGS)}, got {pooling!r}")
+    n_rows, L = tokens.shape
+    d = table.shape[1]
+    if bag_rows is not None:
+        _chk(bag_rows, torch.int64, "bag_rows", 1)
+    n_bags = n_rows if bag_rows is None else bag_rows.numel()
+    if out is None:
+        if accumulate:
+            raise ValueError("embedding_bag: accumulate=True adds into `out`, which must be given")
+        out = torch.empty((n_bags, d), dtype=torch.float32, device=table.device)
+    _chk(out, torch.float32, "out", 2)
+    if tuple(out.shape) != (n_bags, d):
+        raise RuntimeError(f"embedding_bag: out must be [{n_bags}, {d}] (n_bags, dim), got {tuple(out.shape)}")
+    if batch_ids is not None:
+        _chk(batch_ids, torch.int64, "batch_ids")
+        if batch_ids.numel() != n_bags * L:
+            raise RuntimeError(f"embedding_bag: batch_ids must hold n_bags * L = {n_bags * L} entries, got {batch_ids.numel()}")
+    if inv is not None:
+        _chk(inv, torch.float32, "inv", 1)
+        if inv.numel() != n_bags:
+            raise RuntimeError(f"embedding_bag: inv must hold n_bags = {n_bags} entries, got {inv.numel()}")
+    if oob_flag is not None:
+        _chk(oob_flag, torch.int32, "oob_flag")
+    _lib.check(_lib.load().tt_embedding_bag_fwd_f32(_p(table), table.shape[0], d, _p(tokens), n_rows, L, _p(bag_rows), n_bags,
+                                                    POOLINGS[pooling], int(bool(accumulate)), _p(out), _p(batch_ids), _p(inv),
+                                                    _p(oob_flag), _stream()), "tt_embedding_bag_fwd_f32")
+    return out
+
+
+def embedding_bag_bwd(dy: torch.Tensor, inv: torch.Tensor | None, order: torch.Tensor, L: int, order_bags: torch.Tensor,
+                      gs: torch.Tensor | None = None):
+    """The backward launch of ``embedding_bag`` (``tt_embedding_bag_bwd_f32``): ``gs[b, :] = dy[b, :] * inv[b]`` (``gs`` None -
+    sum pooling - skips it: the bags' gradient rows are ``dy`` itself) and ``order_bags[j] = order[j] // L``, the bag of every
+    sorted slot of a sort plan over ``batch_ids``.  Returns (the gradient rows to hand to the sparse update, order_bags)."""
+    _chk(dy, torch.float32, "dy", 2)
+    _chk(order, torch.int32, "order", 1)
+    _chk(order_bags, torch.int32, "order_bags", 1)
+    n_bags, d = dy.shape
+    if order.numel() != n_bags * L or order_bags.numel() != n_bags * L:
+        raise RuntimeError(f"embedding_bag_bwd: order and order_bags must hold n_bags * L = {n_bags * L} entries")
+    if gs is not None:
+        _chk(gs, torch.float32, "gs", 2)
+        _chk(inv, torch.float32, "inv", 1)
+        if gs.shape != dy.shape or inv.numel() != n_bags:
+            raise RuntimeError("embedding_bag_bwd: gs must have dy's shape and inv n_bags entries")
+    _lib.check(_lib.load().tt_embedding_bag_bwd_f32(_p(dy), _p(inv), n_bags, d, L, _p(order), n_bags * L, _p(gs), _p(order_bags),
+                                                    _stream()), "tt_embedding_bag_bwd_f32")
+    return (dy if gs is None else gs), order_bags
+
+
 # ----------------------------------------------------------------------------- sharded routing
 def route_by_owner(ids, world: int, num_rows: int, cap: int, send_ids, pos_flat, flags=None):
     _chk(ids, torch.int64, "ids", 1)
@@ -217,6 +283,16 @@ class SparsePlan:
         self._apply_ws = None
         self._adam_ws = None
 
+    @property
+    def grad_order(self) -> torch.Tensor:
+        """What the update kernels index the gradient rows with: row grad_order[j] is the gradient of sorted slot j."""
+        return self.order
+
+    @property
+    def grad_rows(self) -> int:
+        """Rows of the gradient tensor the update kernels read through ``grad_order``."""
+        return self.n_ids
+
     def adam_ws(self, dim: int) -> torch.Tensor:
         """Piece-sum workspace of ``adam_step_`` for rows of ``dim`` floats (allocated once; never initialised)."""
         need = max(adam_workspace_bytes(self.n_ids, dim), 256)
@@ -241,6 +317,30 @@ class SparsePlan:
         return self
 
 
+class BagPlan(SparsePlan):
+    """The sort plan of an ``embedding_bag`` batch: ``run`` sorts the n_bags * L slot tokens (``batch_ids``), ``backward`` turns
+    the sorted slots' positions into bag indices (``order_bags``) - and scales the bags' gradient rows - so that
+    ``sparse_sgd_`` / ``sparse_adagrad_`` / ``adam_step_`` update the bag table from the [n_bags, dim] gradient rows: no
+    per-token gradient row is ever written."""
+
+    def __init__(self, n_bags: int, L: int, device):
+        super().__init__(n_bags * L, device)
+        self.n_bags, self.L = n_bags, L
+        self.order_bags = torch.zeros(n_bags * L, dtype=torch.int32, device=device)
+
+    @property
+    def grad_order(self) -> torch.Tensor:
+        return self.order_bags
+
+    @property
+    def grad_rows(self) -> int:
+        return self.n_bags
+
+    def backward(self, dy: torch.Tensor, inv: torch.Tensor | None = None, gs: torch.Tensor | None = None) -> torch.Tensor:
+        """One launch after ``run``: returns the gradient rows for the update (``gs`` = dy * inv, or ``dy`` when gs is None)."""
+        return embedding_bag_bwd(dy, inv, self.order, self.L, self.order_bags, gs)[0]
+
+
 def sparse_plan_batched(plans, ids_list, num_rows_list):
     """Sort up to 4 id lists (user, item, hashed category, ...) in ONE launch (key-range partitions: csrc/sort.hip)."""
     n = len(plans)
@@ -255,12 +355,20 @@ def sparse_plan_batched(plans, ids_list, num_rows_list):
     _lib.check(_lib.load().tt_sparse_plan_batched(arr, n, _stream()), "tt_sparse_plan_batched")
 
 
+def _chk_plan_grads(grads, plan: SparsePlan, table, what: str):
+    """A BagPlan's positions are bag indices: the gradient tensor must hold exactly one row per bag."""
+    if isinstance(plan, BagPlan) and tuple(grads.shape) != (plan.n_bags, table.shape[1]):
+        raise RuntimeError(f"{what}: grads must be [{plan.n_bags}, {table.shape[1]}] (one row per bag, dim), got {tuple(grads.shape)}")
+
+
 def sparse_sgd_(table, grads, plan: SparsePlan, lr: float):
+    """``plan`` may be a ``BagPlan`` (after its ``backward``): ``grads`` then holds one row per bag."""
     _chk(table, torch.float32, "table", 2)
     _chk(grads, torch.float32, "grads", 2)
+    _chk_plan_grads(grads, plan, table, "sparse_sgd_")
     lib = _lib.load()
     _lib.check(lib.tt_sparse_sgd_f32(_p(table), table.shape[0], table.shape[1], _p(grads), _p(plan.sorted_ids),
-                                     _p(plan.order), plan.n_ids, lr, _p(plan.apply_ws(table.shape[1])), _stream()),
+                                     _p(plan.grad_order), plan.n_ids, lr, _p(plan.apply_ws(table.shape[1])), _stream()),
                "tt_sparse_sgd_f32")
     return table
 
@@ -269,9 +377,10 @@ def sparse_adagrad_(table, accum, grads, plan: SparsePlan, lr: float, eps: float
     _chk(table, torch.float32, "table", 2)
     _chk(accum, torch.float32, "accum", 2)
     _chk(grads, torch.float32, "grads", 2)
+    _chk_plan_grads(grads, plan, table, "sparse_adagrad_")
     lib = _lib.load()
     _lib.check(lib.tt_sparse_adagrad_f32(_p(table), _p(accum), table.shape[0], table.shape[1], _p(grads),
-                                         _p(plan.sorted_ids), _p(plan.order), plan.n_ids, lr, eps,
+                                         _p(plan.sorted_ids), _p(plan.grad_order), plan.n_ids, lr, eps,
                                          _p(plan.apply_ws(table.shape[1])), _stream()), "tt_sparse_adagrad_f32")
     return table
 
@@ -651,9 +760,10 @@ def adam_step_(tables, segs, hyper: AdamHyper):
     for i, (table, m, v, grads, plan) in enumerate(tables):
         if m.shape != table.shape or v.shape != table.shape:
             raise RuntimeError("adam_step_: m and v must have the table's shape")
-        if table.shape[1] != dim or plan.n_ids != n_ids or tuple(grads.shape) != (n_ids, dim):
-            raise RuntimeError("adam_step_: every table needs the same dim, the same number of ids and [n_ids, dim] gradients")
-        arr_t[i] = _lib.AdamTable(_p(table), _p(m), _p(v), table.shape[0], _p(grads), _p(plan.sorted_ids), _p(plan.order),
+        if table.shape[1] != dim or plan.n_ids != n_ids or tuple(grads.shape) != (plan.grad_rows, dim):
+            raise RuntimeError("adam_step_: every table needs the same dim, the same number of ids and [n_ids, dim] gradients "
+                               "([n_bags, dim] with a BagPlan)")
+        arr_t[i] = _lib.AdamTable(_p(table), _p(m), _p(v), table.shape[0], _p(grads), _p(plan.sorted_ids), _p(plan.grad_order),
                                   _p(plan.adam_ws(dim)))
     arr_s = (_lib.AdamSeg * max(len(segs), 1))(*segs)
     h = hyper.struct()

@@ -421,6 +421,10 @@ class ShardedTwoTowerTrainer:
             # owner-side lazy Adam (moments sharded with the rows, one global step counter) is not built
             raise NotImplementedError("optimizer='adam' is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "n_title_buckets", 0):
+            # the bag table would have to be sharded and its pooled rows exchanged like the other tables' rows
+            raise NotImplementedError("the title feature (n_title_buckets > 0) is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         from . import ops
         from .trainer import Tower, TID_USER_TABLE, TID_ITEM_TABLE
         cfg.validate()

@@ -7,6 +7,7 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
 
     loss, per_example, dq, dc = torch.ops.twotower.retrieval_loss(q, c, w, p, ids, inv_t, diag_offset, k)
     rows = torch.ops.twotower.embedding_gather(table, ids)
+    pooled = torch.ops.twotower.embedding_bag(table, tokens, bag_rows, "mean")
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
     torch.ops.twotower.sparse_adam_(table, exp_avg, exp_avg_sq, grads, ids, step, lr, 0.9, 0.999, 1e-7)
@@ -79,6 +80,19 @@ def embedding_gather(table: Tensor, ids: Tensor) -> Tensor:
 @embedding_gather.register_fake
 def _(table, ids):
     return table.new_empty((ids.shape[0], table.shape[1]))
+
+
+@torch.library.custom_op(f"{NS}::embedding_bag", mutates_args=(), device_types="cuda")
+def embedding_bag(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], pooling: str = "mean") -> Tensor:
+    """pooled[b, :] = pool of the rows table[t, :] over the valid tokens t of row bag_rows[b] (None: row b) of ``tokens``
+    [rows, L] int32 (-1 = padding; ``ops.embedding_bag``); ``pooling`` "sum", "mean" or "sqrtn"; an empty bag gives a zero
+    row.  Not differentiable: the table is trained through ``ops.BagPlan`` and the sparse updates on the bags' gradient rows."""
+    return ops.embedding_bag(table.contiguous(), tokens.contiguous(), None if bag_rows is None else bag_rows.contiguous(), pooling)
+
+
+@embedding_bag.register_fake
+def _(table, tokens, bag_rows, pooling="mean"):
+    return table.new_empty(((tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), table.shape[1]))
 
 
 # --------------------------------------------------------------------------------------------- a3 + a4
@@ -450,5 +464,5 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
     ops.adam_step_([(table, exp_avg, exp_avg_sq, grads.contiguous(), plan)], [], ops.AdamHyper(lr, beta1, beta2, eps, step))
 
 
-OPS = ("embedding_gather", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
+OPS = ("embedding_gather", "embedding_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "sparse_update_", "sparse_adam_")

@@ -65,6 +65,12 @@ def parse(argv=None):
     ap.add_argument("--category-buckets", type=int, default=0, metavar="N",
                     help="add the hashed category feature: the pair's category (column category / main_category / "
                          "category_encoded) hashed into N buckets, its embedding summed into the item tower input")
+    ap.add_argument("--title-buckets", type=int, default=None, metavar="N",
+                    help="add the pooled item-title feature: every item's title (column title) is tokenised, its first "
+                         "--title-max-tokens tokens are hashed into N buckets and their embeddings pooled into the item tower "
+                         "input (overrides model.features.title.buckets); single-GPU trainer only")
+    ap.add_argument("--title-max-tokens", type=int, default=None, metavar="L", help="title tokens kept per item (1..64; default 16)")
+    ap.add_argument("--title-pooling", default=None, choices=["sum", "mean", "sqrtn"], help="how the token rows are pooled (default mean)")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -100,6 +106,10 @@ def main(argv=None) -> int:
     normalize = args.normalize_embeddings or bool(((doc.get("model") or {}).get("retrieval") or {}).get("normalize_embeddings", False))
     if distributed and normalize:
         raise NotImplementedError("normalize_embeddings is not implemented for the row-sharded (--distributed) trainer")
+    title_cfg = ((doc.get("model") or {}).get("features") or {}).get("title") or {}
+    title_buckets = int(title_cfg.get("buckets", 0)) if args.title_buckets is None else args.title_buckets
+    if distributed and title_buckets:
+        raise NotImplementedError("the title feature is not implemented for the row-sharded (--distributed) trainer")
     if distributed and args.optimizer == "adam":
         raise NotImplementedError("optimizer 'adam' is not implemented for the row-sharded (--distributed) trainer")
     if distributed:
@@ -141,6 +151,11 @@ def main(argv=None) -> int:
     cfg.scorer_precision = args.scorer_precision
     cfg.normalize_embeddings = normalize
     cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = args.adam_beta1, args.adam_beta2, args.adam_epsilon
+    cfg.n_title_buckets = title_buckets
+    if args.title_max_tokens is not None:
+        cfg.title_max_tokens = args.title_max_tokens
+    if args.title_pooling is not None:
+        cfg.title_pooling = args.title_pooling
     if args.batch_size:
         cfg.batch_size = args.batch_size
     epochs = args.epochs if args.epochs is not None else loop["epochs"]
@@ -165,6 +180,12 @@ def main(argv=None) -> int:
         trainer = ShardedTwoTowerTrainer(cfg, args.device, seed=args.seed, negatives=args.negatives)
     else:
         trainer = TwoTowerTrainer(cfg, args.device, seed=args.seed)
+    if cfg.n_title_buckets:
+        if args.synthetic:                  # tokens from the id generator
+            trainer.set_item_titles(trainer.synthetic_item_titles(args.seed))
+        else:
+            titles = datamod.read_item_titles(args.data, item_idx, n_items)
+            trainer.set_item_titles(datamod.title_tokens(titles, cfg.n_title_buckets, cfg.title_max_tokens, trainer.dev))
 
     def total(x: torch.Tensor) -> float:        # sum over ranks of a device scalar
         if distributed:

@@ -32,6 +32,7 @@ from . import _lib, ops
 # for the tests; the product does not import the oracle)
 TID_USER_TABLE, TID_ITEM_TABLE, TID_USER_IDS, TID_ITEM_IDS = 1, 2, 3, 4
 TID_CATEGORY_TABLE, TID_CATEGORY_IDS = 5, 6
+TID_TITLE_TABLE, TID_TITLE_IDS, TID_TITLE_LENGTHS = 7, 8, 9
 TID_DENSE_BASE = 16
 TID_DROPOUT_BASE = 64
 
@@ -67,6 +68,13 @@ class TwoTowerConfig:
     # (Yi et al. 2019; SURVEY.md lists the choice as left open).  Off = the towers' raw outputs, as before.
     normalize_embeddings: bool = False
     normalize_eps: float = 1e-12                   # tf.math.l2_normalize's default (a floor of the SUM OF SQUARES)
+    # pooled item-title feature (the reference's preprocessing.text_fields: title; TFRS TextVectorization -> Embedding ->
+    # GlobalAveragePooling1D): every item carries up to title_max_tokens hashed title tokens (``set_item_titles``), their rows
+    # of a [n_title_buckets, embedding_dim] table are pooled ("sum" | "mean" | "sqrtn") and ADDED to the item tower's input.
+    # 0 = no such feature.  Single-GPU trainer, materialised tower inputs, no graph capture.
+    n_title_buckets: int = 0
+    title_max_tokens: int = 16
+    title_pooling: str = "mean"
 
     @property
     def user_dims(self) -> list:
@@ -109,6 +117,12 @@ class TwoTowerConfig:
             raise ValueError("normalize_embeddings must be a bool")
         if not self.normalize_eps > 0:
             raise ValueError("normalize_eps must be > 0")
+        if self.n_title_buckets < 0:
+            raise ValueError("n_title_buckets must be >= 0")
+        if not 1 <= self.title_max_tokens <= 64:
+            raise ValueError("title_max_tokens must be in 1..64")
+        if self.title_pooling not in ops.POOLINGS:
+            raise ValueError(f"title_pooling must be one of {tuple(ops.POOLINGS)}")
 
 
 class Tower:
@@ -307,6 +321,22 @@ class TwoTowerTrainer:
             self.cat_plan = ops.SparsePlan(b, dev)
             if adam:
                 self.cat_m, self.cat_v = torch.zeros_like(self.cat_table), torch.zeros_like(self.cat_table)
+        # pooled item-title feature: the bag table with its optimizer state, every item's token row (all padding until
+        # set_item_titles), and the per-step buffers the bag launches fill - the slot tokens the sort plan sorts, the pooling
+        # scales, and (mean / sqrtn) the scaled gradient rows
+        self.title_table = self.title_accum = self.title_m = self.title_v = None
+        self.item_titles = self.title_plan = self.title_ids = self.title_inv = self.title_gs = None
+        if cfg.n_title_buckets:
+            lt = cfg.title_max_tokens
+            self.title_table = torch.empty(cfg.n_title_buckets, d, device=dev)
+            self.title_accum = torch.full_like(self.title_table, cfg.adagrad_initial_accumulator) if adagrad else None
+            if adam:
+                self.title_m, self.title_v = torch.zeros_like(self.title_table), torch.zeros_like(self.title_table)
+            self.item_titles = torch.full((cfg.n_items, lt), -1, dtype=torch.int32, device=dev)
+            self.title_plan = ops.BagPlan(b, lt, dev)
+            self.title_ids = torch.empty(b * lt, dtype=torch.int64, device=dev)
+            self.title_inv = torch.empty(b, device=dev)
+            self.title_gs = torch.empty(b, d, device=dev) if cfg.title_pooling != "sum" else None
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -322,6 +352,8 @@ class TwoTowerTrainer:
         # (r04: at small batches the gather launch's fixed cost decides - the reference's own config, [512, 256, 128] at batch 1024:
         # 0.1631-0.1638 ms fused against 0.1644-0.1654 with the gather launch)
         self.fuse_lookup = os.environ.get("TT_FUSE_LOOKUP", "1" if (cfg.tower_dims[0] < 512 or cfg.batch_size <= 2048) else "0") != "0"
+        if cfg.n_title_buckets:                  # the pooled titles are added to the materialised item-tower input (_item_inputs)
+            self.fuse_lookup = False
         self.fuse_sort = os.environ.get("TT_FUSE_SORT", "1") != "0"   # the optimizer launch sorts the ids itself (no plan launch)
         self.fuse_optimizer = True               # sparse + dense optimizer in one launch (False: dense_update, sparse_update2 [, cat])
         # the whole step behind ONE C call (tt_train_step_f32: the same launches - eight at cfg3 -, enqueued in C - one FFI crossing per step
@@ -374,6 +406,8 @@ class TwoTowerTrainer:
         ops.fill_uniform_(self.item_table, seed, TID_ITEM_TABLE, -0.05, 0.1)
         if self.cat_table is not None:
             ops.fill_uniform_(self.cat_table, seed, TID_CATEGORY_TABLE, -0.05, 0.1)
+        if self.title_table is not None:
+            ops.fill_uniform_(self.title_table, seed, TID_TITLE_TABLE, -0.05, 0.1)
         self.dense_flat.zero_()
         for t, tower in enumerate((self.user_tower, self.item_tower)):
             for l, w in enumerate(tower.w):
@@ -382,10 +416,11 @@ class TwoTowerTrainer:
                 scale32 = (lim + lim).item()
                 ops.fill_uniform_(w, seed, TID_DENSE_BASE + 2 * l + t, -lim32, scale32)
         if self.cfg.optimizer == "adagrad":
-            for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum):
+            for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum):
                 if a is not None:
                     a.fill_(self.cfg.adagrad_initial_accumulator)
-        for a in (self.user_m, self.user_v, self.item_m, self.item_v, self.cat_m, self.cat_v, self.dense_m, self.dense_v):
+        for a in (self.user_m, self.user_v, self.item_m, self.item_v, self.cat_m, self.cat_v, self.title_m, self.title_v,
+                  self.dense_m, self.dense_v):
             if a is not None:
                 a.zero_()
         self.adam_step = 1
@@ -405,6 +440,27 @@ class TwoTowerTrainer:
             out = torch.empty(b, dtype=torch.int64, device=self.dev)
         ops.fill_ids_(out, seed, TID_CATEGORY_IDS, self.cfg.n_category_buckets, variant, start=step * b)
         return out
+
+    def synthetic_item_titles(self, seed: int, variant: str = "Z") -> torch.Tensor:
+        """A synthetic [n_items, title_max_tokens] int32 token matrix from the id generator: power-law tokens (a few frequent
+        words), 1..title_max_tokens of them per item, the rest padding."""
+        n, lt = self.cfg.n_items, self.cfg.title_max_tokens
+        tok = torch.empty(n * lt, dtype=torch.int64, device=self.dev)
+        length = torch.empty(n, dtype=torch.int64, device=self.dev)
+        ops.fill_ids_(tok, seed, TID_TITLE_IDS, self.cfg.n_title_buckets, variant)
+        ops.fill_ids_(length, seed, TID_TITLE_LENGTHS, lt, "U")
+        slot = torch.arange(lt, device=self.dev)
+        return torch.where(slot[None, :] <= length[:, None], tok.view(n, lt), -1).to(torch.int32)
+
+    def set_item_titles(self, tokens: torch.Tensor):
+        """tokens [n_items, title_max_tokens] int32: the hashed title tokens of every item (``data.title_tokens``), -1 = no
+        token in that slot.  Tokens outside [0, n_title_buckets) are skipped by the kernels and raise through ``check_ids``."""
+        if self.item_titles is None:
+            raise ValueError("set_item_titles: the model has no title feature (cfg.n_title_buckets == 0)")
+        if tuple(tokens.shape) != tuple(self.item_titles.shape) or tokens.dtype != torch.int32:
+            raise ValueError(f"set_item_titles: tokens must be int32 {list(self.item_titles.shape)} (n_items, title_max_tokens), "
+                             f"got {tokens.dtype} {list(tokens.shape)}")
+        self.item_titles.copy_(tokens)
 
     def _check_categories(self, category_ids):
         if (category_ids is None) != (self.cat_table is None):
@@ -438,6 +494,9 @@ class TwoTowerTrainer:
         ops.embedding_gather2(self.user_table, user_ids, ut.acts[0], self.item_table, item_ids, it.acts[0], self.oob)
         if category_ids is not None:
             ops.embedding_gather_add_(it.acts[0], self.cat_table, category_ids, self.oob)
+        if self.title_table is not None:     # + the pooled title rows of every pair's item; the slot tokens and scales stay for the update
+            ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=self.cfg.title_pooling, out=it.acts[0],
+                              accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
 
     def _outputs(self, *towers):
         """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
@@ -482,6 +541,27 @@ class TwoTowerTrainer:
 
     def apply_gradients(self, step_ids=None):
         """``step_ids`` = [user ids, item ids (, category ids)]: the optimizer launch sorts them itself (no plan launch ran)."""
+        adam_step = self.adam_step
+        self._apply_table_gradients(step_ids)
+        if self.title_table is not None:
+            self._apply_title_gradients(adam_step)
+
+    def _apply_title_gradients(self, adam_step: int):
+        """The title table's update: sort plan over the step's slot tokens, one launch that scales the item-tower input gradient
+        rows by the bags' pooling scales and turns the plan's slot positions into bag indices, then the configured optimizer on
+        [batch, dim] gradient rows (a slot's gradient is its bag's row: no per-token rows)."""
+        cfg, plan = self.cfg, self.title_plan
+        plan.run(self.title_ids, cfg.n_title_buckets)
+        gs = plan.backward(self.item_tower.demb, self.title_inv, self.title_gs)
+        if cfg.optimizer == "adam":
+            ops.adam_step_([(self.title_table, self.title_m, self.title_v, gs, plan)], [],
+                           ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
+        elif cfg.optimizer == "sgd":
+            ops.sparse_sgd_(self.title_table, gs, plan, cfg.learning_rate)
+        else:
+            ops.sparse_adagrad_(self.title_table, self.title_accum, gs, plan, cfg.learning_rate, cfg.adagrad_epsilon)
+
+    def _apply_table_gradients(self, step_ids=None):
         cfg = self.cfg
         if cfg.optimizer == "adam":  # every table and every tower segment in ONE call (two launches), from the sort plans
             tables = [(self.user_table, self.user_m, self.user_v, self.user_tower.demb, self.user_plan),
@@ -687,6 +767,9 @@ class TwoTowerTrainer:
             it.acts[0][:e - s].copy_(self.item_table[s:e])
             if item_category_ids is not None:
                 ops.embedding_gather_add_(it.acts[0][:e - s], self.cat_table, item_category_ids[s:e], self.oob)
+            if self.title_table is not None:       # bag r of the chunk pools token row s + r
+                ops.embedding_bag(self.title_table, self.item_titles[s:e], pooling=self.cfg.title_pooling, out=it.acts[0][:e - s],
+                                  accumulate=True, oob_flag=self.oob)
             it.forward()
             out[s:e].copy_(self._outputs(it)[0][:e - s])
         return out
@@ -725,6 +808,12 @@ class TwoTowerTrainer:
               "dense": self.dense_flat, "step_index": self.step_index, "dropout_seed": self.dropout_seed}
         if self.cat_table is not None:
             sd["cat_table"] = self.cat_table
+        if self.title_table is not None:
+            sd.update(title_table=self.title_table, item_titles=self.item_titles)
+            if self.cfg.optimizer == "adagrad":
+                sd["title_accum"] = self.title_accum
+            if self.cfg.optimizer == "adam":
+                sd.update(title_m=self.title_m, title_v=self.title_v)
         if self.cfg.optimizer == "adagrad":
             sd.update(user_accum=self.user_accum, item_accum=self.item_accum, dense_accum=self.dense_accum)
             if self.cat_table is not None:
@@ -740,6 +829,19 @@ class TwoTowerTrainer:
         for k in ("n_users", "n_items", "embedding_dim", "tower_dims", "item_tower_dims", "optimizer", "n_category_buckets"):
             if sd["config"].get(k, 0 if k == "n_category_buckets" else None) != getattr(self.cfg, k):
                 raise ValueError(f"checkpoint {k}={sd['config'].get(k)!r} does not match the trainer's {getattr(self.cfg, k)!r}")
+        # a checkpoint from before the title feature existed has none: it loads into a trainer without it, as before
+        if sd["config"].get("n_title_buckets", 0) != self.cfg.n_title_buckets:
+            raise ValueError(f"checkpoint n_title_buckets={sd['config'].get('n_title_buckets', 0)!r} does not match the trainer's "
+                             f"{self.cfg.n_title_buckets!r}")
+        if self.title_table is not None:
+            for k in ("title_max_tokens", "title_pooling"):
+                if sd["config"].get(k) != getattr(self.cfg, k):
+                    raise ValueError(f"checkpoint {k}={sd['config'].get(k)!r} does not match the trainer's {getattr(self.cfg, k)!r}")
+            self.title_table.copy_(sd["title_table"]); self.item_titles.copy_(sd["item_titles"])
+            if self.cfg.optimizer == "adagrad":
+                self.title_accum.copy_(sd["title_accum"])
+            if self.cfg.optimizer == "adam":
+                self.title_m.copy_(sd["title_m"]); self.title_v.copy_(sd["title_v"])
         self.user_table.copy_(sd["user_table"]); self.item_table.copy_(sd["item_table"]); self.dense_flat.copy_(sd["dense"])
         # whether the embeddings are normalised belongs to the trained model, not to the run that loads it: the checkpoint's
         # value replaces the trainer's (a checkpoint from before the switch existed: off)
@@ -771,6 +873,9 @@ class TwoTowerTrainer:
         if self.cfg.optimizer == "adam":
             raise NotImplementedError("graph replay with optimizer='adam': the global step, and so the bias-corrected step size, "
                                       "is a kernel argument")
+        if self.cfg.n_title_buckets:
+            raise NotImplementedError("graph replay with the title feature (n_title_buckets > 0) is not implemented: the warm-up "
+                                      "step's update of the title table is not undone")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
