@@ -62,7 +62,7 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * the scope ivf around a whole tt_ivf_search_f32 call), quantize_i8, topk_i8_scan, topk_i8_rerank, topk_i8_scale (and the
  * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
- * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32).
+ * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -156,6 +156,33 @@ int tt_embedding_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim
                              float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag, tt_stream_t stream);
 int tt_embedding_bag_bwd_f32(const float* dy, const float* inv, int64_t n_bags, int32_t dim, int32_t L,
                              const int32_t* order, int64_t n_ids, float* gs, int32_t* order_bags, tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Mixed negative sampling (added to v10: a new symbol only, the version is unchanged) - Yang et al. 2020: every step
+ * appends n_neg items drawn from the whole corpus to the n_pos in-batch candidates (csrc/sample.hip).  One launch writes
+ *   cand_ids[0 : n_pos]  = pos_ids
+ *   cand_ids[n_pos + i]  = the draw of x = splitmix64 element (start + i) of the stream (seed, tensor_id) - the generator of
+ *                          the synthetic inputs above (oracle/synth.py), the counter taken mod 2^64:
+ *       bucket b = ((x >> 32) * n_items) >> 32                       (the uniform id of tt_fill_ids_i64)
+ *       TT_SAMPLER_UNIFORM: id = b
+ *       TT_SAMPLER_ALIAS:   u = (x & 0xFFFFFF) * 2^-24;  id = u < alias_thr[b] ? b : alias_idx[b]     (Walker's alias table:
+ *                           alias_thr [n_items] f32 and alias_idx [n_items] int32, device pointers; n_items < 2^31)
+ * and, only when item_freq is given (f32 [n_items], the probability of every item as an in-batch candidate),
+ *   cand_prob[j] = ((float)n_pos * item_freq[id] + (float)n_neg * u_id) / (float)(n_pos + n_neg)        id = cand_ids[j]
+ * for EVERY candidate, positive or sampled: the share of the step's expected candidate count that falls on the item, which
+ * the scorer's cand_prob correction takes.  u_id = sampler_prob[id] (f32 [n_items], the item's probability under the
+ * sampler; NULL: 1.0f / (float)n_items, the uniform sampler's).  f32, one rounding per operation, no contraction.
+ * A candidate id outside [0, n_items) - a bad positive id (-1 included), a bad alias_idx entry - sets *oob_flag (device int32,
+ * may be NULL), is written to cand_ids unchanged and gets cand_prob 1.0; the probability vectors are never read for it.
+ * cand_prob is not touched when item_freq is NULL.  Bit-reproducible, independent of the grid.
+ * TT_ERR_INVALID_ARG before any launch: n_items outside 1..2^32; n_pos or n_neg negative (or beyond 31 bits) or both 0; an
+ * unknown sampler; the alias sampler without both arrays or with n_items >= 2^31; sampler_prob without item_freq; a null
+ * pos_ids (n_pos > 0) / cand_ids / cand_prob (with item_freq).                                                             */
+enum { TT_SAMPLER_UNIFORM = 0, TT_SAMPLER_ALIAS = 1 };
+int tt_sample_candidates_i64(const int64_t* pos_ids, int64_t n_pos, int64_t n_items, int64_t n_neg, int32_t sampler,
+                             const float* alias_thr, const int32_t* alias_idx, const float* item_freq,
+                             const float* sampler_prob, uint64_t seed, uint64_t tensor_id, uint64_t start,
+                             int64_t* cand_ids, float* cand_prob, int32_t* oob_flag, tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a5 — sparse optimizer on embedding rows (Keras SGD / Adagrad on IndexedSlices,

@@ -21,6 +21,7 @@ TT_OK, TT_ERR_INVALID_ARG, TT_ERR_LAUNCH, TT_ERR_UNSUPPORTED, TT_ERR_WORKSPACE =
 TT_OPT_SGD, TT_OPT_ADAGRAD = 0, 1
 TT_IDS_UNIFORM, TT_IDS_POWERLAW = 0, 1
 TT_POOL_SUM, TT_POOL_MEAN, TT_POOL_SQRTN = 0, 1, 2
+TT_SAMPLER_UNIFORM, TT_SAMPLER_ALIAS = 0, 1
 TT_MAX_DENSE_SEGS = 16
 TT_MAX_TOWER_LAYERS = 8
 TT_TOPK_MAX_K = 256
@@ -150,6 +151,7 @@ SIGNATURES = {
     "tt_hash_bucket_u8": (C.c_int, [_p, _i64, _i32, _i64, _p, _p]),
     "tt_embedding_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "tt_embedding_bag_bwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "tt_scatter_rows_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _p]),

@@ -21,8 +21,13 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     user_dims, item_dims = list(m["user_tower_dims"]), list(m["item_tower_dims"])
     tr, rt = m.get("training", {}), m.get("retrieval", {})
     sampling = rt.get("candidate_sampling", "in_batch")
-    if sampling != "in_batch":
-        raise NotImplementedError(f"candidate_sampling {sampling!r}: only 'in_batch' is implemented")
+    if sampling not in ("in_batch", "mixed"):
+        raise NotImplementedError(f"candidate_sampling {sampling!r}: only 'in_batch' and 'mixed' (in-batch plus sampled "
+                                  "negatives) are implemented")
+    batch_size = int(tr.get("batch_size", 1024))
+    # mixed negative sampling: num_sampled_negatives (default: as many as the batch), negative_sampler uniform | unigram,
+    # unigram_power - optional keys beside candidate_sampling, not in the reference's schema
+    n_neg = int(rt.get("num_sampled_negatives", batch_size)) if sampling == "mixed" else 0
     dropout = float(m.get("dropout_rate", 0.0)) if dropout_override is None else dropout_override
     # not in the reference's schema: model.features.title {buckets, max_tokens, pooling} - the pooled item-title feature
     title = (m.get("features") or {}).get("title") or {}
@@ -31,7 +36,9 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         item_tower_dims=None if item_dims == user_dims else item_dims,
         temperature=float(rt.get("temperature", 1.0)), l2_regularization=float(m.get("l2_regularization", 0.0)),
         learning_rate=float(tr.get("learning_rate", 0.001)), optimizer=optimizer,
-        batch_size=int(tr.get("batch_size", 1024)), dropout_rate=dropout,
+        batch_size=batch_size, dropout_rate=dropout,
+        candidate_sampling=sampling, n_sampled_negatives=n_neg, negative_sampler=str(rt.get("negative_sampler", "uniform")),
+        unigram_power=float(rt.get("unigram_power", 0.75)),
         # not in the reference's schema (left open): an optional key beside retrieval.temperature
         normalize_embeddings=bool(rt.get("normalize_embeddings", False)),
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),

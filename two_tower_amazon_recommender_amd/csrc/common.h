@@ -91,5 +91,9 @@ inline uint64_t splitmix_host(uint64_t x) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
+// key of the counter-based stream (seed, tensor_id): element i of the stream is splitmix(key + i) (oracle/synth.py stream_key)
+inline uint64_t stream_key(uint64_t seed, uint64_t tensor_id) {
+  return splitmix_host(splitmix_host(seed) ^ (tensor_id * 0xD6E8FEB86659FD93ull));
+}
 
 }  // namespace tt

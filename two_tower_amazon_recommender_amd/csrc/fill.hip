@@ -63,9 +63,7 @@ __global__ __launch_bounds__(256) void fill_ids_kernel(int64_t* __restrict__ dst
   }
 }
 
-uint64_t stream_key(uint64_t seed, uint64_t tensor_id) {
-  return tt::splitmix_host(tt::splitmix_host(seed) ^ (tensor_id * 0xD6E8FEB86659FD93ull));
-}
+using tt::stream_key;
 
 int grid_for(int64_t work_items) {
   int64_t blocks = (work_items + 255) / 256;

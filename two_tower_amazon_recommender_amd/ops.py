@@ -227,6 +227,92 @@ def embedding_bag_bwd(dy: torch.Tensor, inv: torch.Tensor | None, order: torch.T
     return (dy if gs is None else gs), order_bags
 
 
+# ----------------------------------------------------------------------------- mixed negative sampling
+SAMPLERS = {"uniform": _lib.TT_SAMPLER_UNIFORM, "alias": _lib.TT_SAMPLER_ALIAS}
+
+
+def build_alias_table(prob):
+    """Walker's alias table of the distribution ``prob`` (any non-negative weights, normalised here) by Vose's method, in NumPy
+    f64 on the host - once per run, deterministic: ``(thr f32 [n], idx int32 [n])``.  A draw takes a uniform bucket b and
+    u on the 2^-24 grid and returns ``b if u < thr[b] else idx[b]`` (``sample_candidates``, sampler "alias"); the thresholds are
+    rounded to that grid, so the table's implied distribution is exact to 2^-25 / n per bucket."""
+    import numpy as np
+    p = np.asarray(prob, dtype=np.float64).reshape(-1)
+    n = p.size
+    if n == 0 or not np.isfinite(p).all() or (p < 0).any():
+        raise ValueError("build_alias_table: the weights must be finite and non-negative (and there must be some)")
+    total = p.sum()
+    if not total > 0:
+        raise ValueError("build_alias_table: the weights are all zero")
+    if n >= 1 << 31:
+        raise ValueError("build_alias_table: at most 2^31 - 1 items (the alias indices are int32)")
+    scaled = (p / total * n).tolist()
+    thr = [1.0] * n
+    idx = list(range(n))
+    small = [i for i in range(n - 1, -1, -1) if scaled[i] < 1.0]      # (popped from the end: ascending item order)
+    large = [i for i in range(n - 1, -1, -1) if scaled[i] >= 1.0]
+    while small and large:
+        s, g = small.pop(), large[-1]
+        thr[s], idx[s] = scaled[s], g
+        scaled[g] = (scaled[g] + scaled[s]) - 1.0
+        if scaled[g] < 1.0:
+            small.append(large.pop())
+    # what is left on either list is 1 up to rounding: the bucket keeps itself
+    grid = np.rint(np.clip(np.asarray(thr, dtype=np.float64), 0.0, 1.0) * 16777216.0) / 16777216.0
+    return grid.astype(np.float32), np.asarray(idx, dtype=np.int32)
+
+
+def sample_candidates(pos_ids: torch.Tensor, n_items: int, n_neg: int, out_ids: torch.Tensor, out_prob: torch.Tensor | None = None,
+                      *, sampler: str = "uniform", alias=None, item_freq: torch.Tensor | None = None,
+                      sampler_prob: torch.Tensor | None = None, seed: int, tensor_id: int, start: int,
+                      oob_flag: torch.Tensor | None = None):
+    """A step's candidate list in one launch (``tt_sample_candidates_i64``): ``out_ids[:B] = pos_ids`` and ``out_ids[B + i]`` =
+    draw ``start + i`` of the stream (seed, tensor_id) from ``n_items`` items - ``sampler`` "uniform", or "alias" with ``alias`` =
+    (thr f32 [n_items], idx int32 [n_items]) device tensors (``build_alias_table``).  With ``item_freq`` (f32 [n_items], every
+    item's in-batch frequency) ``out_prob[j]`` = (B * item_freq[id] + N * u_id) / (B + N) for every candidate, u_id =
+    ``sampler_prob[id]`` (None: 1 / n_items) - the ``cand_prob`` of the scorer.  ``out_ids`` / ``out_prob`` may be longer than
+    B + N; the rest is not touched.  Returns (out_ids[:B + N], out_prob[:B + N] or None)."""
+    _chk(pos_ids, torch.int64, "pos_ids", 1)
+    _chk(out_ids, torch.int64, "out_ids", 1)
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sample_candidates: sampler must be one of {tuple(SAMPLERS)}, got {sampler!r}")
+    b, n_neg, n_items = pos_ids.numel(), int(n_neg), int(n_items)
+    n = b + max(n_neg, 0)
+    if out_ids.numel() < n:
+        raise RuntimeError(f"sample_candidates: out_ids must hold B + N = {n} entries, got {out_ids.numel()}")
+    thr = idx = None
+    if sampler == "alias":
+        if alias is None:
+            raise ValueError("sample_candidates: sampler 'alias' needs alias=(thr, idx)")
+        thr, idx = alias
+        _chk(thr, torch.float32, "alias thr", 1)
+        _chk(idx, torch.int32, "alias idx", 1)
+        if thr.numel() != n_items or idx.numel() != n_items:
+            raise RuntimeError(f"sample_candidates: the alias table must have n_items = {n_items} entries")
+    elif alias is not None:
+        raise ValueError("sample_candidates: alias is given but the sampler is 'uniform'")
+    for t, name in ((item_freq, "item_freq"), (sampler_prob, "sampler_prob")):
+        if t is not None:
+            _chk(t, torch.float32, name, 1)
+            if t.numel() != n_items:
+                raise RuntimeError(f"sample_candidates: {name} must have n_items = {n_items} entries, got {t.numel()}")
+    if item_freq is not None:
+        if out_prob is None:
+            raise ValueError("sample_candidates: item_freq is given, so out_prob must be too")
+        _chk(out_prob, torch.float32, "out_prob", 1)
+        if out_prob.numel() < n:
+            raise RuntimeError(f"sample_candidates: out_prob must hold B + N = {n} entries, got {out_prob.numel()}")
+    if oob_flag is not None:
+        _chk(oob_flag, torch.int32, "oob_flag")
+    if not (0 <= int(seed) < 1 << 64 and 0 <= int(tensor_id) < 1 << 64 and 0 <= int(start) < 1 << 64):
+        raise ValueError("sample_candidates: seed, tensor_id and start are unsigned 64-bit counters")
+    _lib.check(_lib.load().tt_sample_candidates_i64(_p(pos_ids), b, n_items, n_neg, SAMPLERS[sampler], _p(thr), _p(idx),
+                                                    _p(item_freq), _p(sampler_prob), int(seed), int(tensor_id), int(start),
+                                                    _p(out_ids), _p(out_prob) if item_freq is not None else None, _p(oob_flag),
+                                                    _stream()), "tt_sample_candidates_i64")
+    return out_ids[:n], (out_prob[:n] if item_freq is not None else None)
+
+
 # ----------------------------------------------------------------------------- sharded routing
 def route_by_owner(ids, world: int, num_rows: int, cap: int, send_ids, pos_flat, flags=None):
     _chk(ids, torch.int64, "ids", 1)

@@ -120,6 +120,7 @@ def main(argv=None) -> int:
         raise SystemExit(f"{args.checkpoint}: not a checkpoint written by train.py --save (no 'config')")
     cfg = TwoTowerConfig(**ck["config"])
     cfg.dropout_rate = 0.0
+    cfg.candidate_sampling, cfg.n_sampled_negatives = "in_batch", 0      # serving scores the whole corpus: nothing is sampled
     trainer = TwoTowerTrainer(cfg, dev)
     trainer.load_state_dict(ck)
     del ck

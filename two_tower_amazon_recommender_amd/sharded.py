@@ -425,6 +425,10 @@ class ShardedTwoTowerTrainer:
             # the bag table would have to be sharded and its pooled rows exchanged like the other tables' rows
             raise NotImplementedError("the title feature (n_title_buckets > 0) is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "candidate_sampling", "in_batch") != "in_batch":
+            # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
+            raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         from . import ops
         from .trainer import Tower, TID_USER_TABLE, TID_ITEM_TABLE
         cfg.validate()

@@ -95,6 +95,34 @@ def _(table, tokens, bag_rows, pooling="mean"):
     return table.new_empty(((tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), table.shape[1]))
 
 
+@torch.library.custom_op(f"{NS}::sample_candidates", mutates_args=(), device_types="cuda")
+def sample_candidates(pos_ids: Tensor, n_items: int, n_neg: int, seed: int, tensor_id: int, start: int,
+                      alias_thr: Optional[Tensor], alias_idx: Optional[Tensor], item_freq: Optional[Tensor],
+                      sampler_prob: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """Mixed negative sampling (``ops.sample_candidates``): (candidate_ids [B + n_neg] = ``pos_ids`` followed by draws
+    start .. start + n_neg - 1 of the stream (seed, tensor_id), candidate_sampling_probability).  The alias sampler is used
+    when ``alias_thr`` / ``alias_idx`` are given, the uniform one otherwise; without ``item_freq`` the second result is empty.
+    Both results go to ``retrieval_loss`` as ``candidate_ids`` / ``candidate_sampling_probability``."""
+    if (alias_thr is None) != (alias_idx is None):
+        raise ValueError("sample_candidates: alias_thr and alias_idx go together")
+    n = pos_ids.numel() + n_neg
+    ids = torch.empty(n, dtype=torch.int64, device=pos_ids.device)
+    prob = torch.empty(n if item_freq is not None else 0, dtype=torch.float32, device=pos_ids.device)
+    alias = None if alias_thr is None else (alias_thr.contiguous(), alias_idx.contiguous())
+    ops.sample_candidates(pos_ids.contiguous(), n_items, n_neg, ids, prob if item_freq is not None else None,
+                          sampler="uniform" if alias is None else "alias", alias=alias,
+                          item_freq=None if item_freq is None else item_freq.contiguous(),
+                          sampler_prob=None if sampler_prob is None else sampler_prob.contiguous(),
+                          seed=seed, tensor_id=tensor_id, start=start)
+    return ids, prob
+
+
+@sample_candidates.register_fake
+def _(pos_ids, n_items, n_neg, seed, tensor_id, start, alias_thr, alias_idx, item_freq, sampler_prob):
+    n = pos_ids.shape[0] + n_neg
+    return pos_ids.new_empty((n,)), pos_ids.new_empty((n if item_freq is not None else 0,), dtype=torch.float32)
+
+
 # --------------------------------------------------------------------------------------------- a3 + a4
 @torch.library.custom_op(f"{NS}::retrieval_loss", mutates_args=(), device_types="cuda")
 def retrieval_loss(query_embeddings: Tensor, candidate_embeddings: Tensor, sample_weight: Optional[Tensor],

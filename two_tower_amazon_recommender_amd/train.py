@@ -74,6 +74,16 @@ def parse(argv=None):
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
+    ap.add_argument("--candidate-sampling", default=None, choices=["in_batch", "mixed"],
+                    help="mixed = mixed negative sampling: every step appends --sampled-negatives items drawn from the whole "
+                         "catalogue to the in-batch candidates (overrides model.retrieval.candidate_sampling); with "
+                         "--correct-sampling-bias the correction uses the probability of the mixture; single-GPU trainer only")
+    ap.add_argument("--sampled-negatives", type=int, default=None, metavar="N",
+                    help="sampled negatives per step with mixed sampling (default: model.retrieval.num_sampled_negatives, else the batch size)")
+    ap.add_argument("--negative-sampler", default=None, choices=["uniform", "unigram"],
+                    help="how the sampled negatives are drawn: uniformly, or from the items' training frequency to the power "
+                         "--unigram-power (word2vec's unigram^0.75)")
+    ap.add_argument("--unigram-power", type=float, default=None)
     ap.add_argument("--scorer-precision", default="f32", choices=["f32", "bf16x3"],
                     help="matrix products of the scorer + softmax loss: exact f32 (default) or f32-emulated split-bf16 on the "
                          "bf16 matrix cores (scorer dim 128 / 256; same 1e-4 parity bars, ~2x faster scorer)")
@@ -110,6 +120,9 @@ def main(argv=None) -> int:
     title_buckets = int(title_cfg.get("buckets", 0)) if args.title_buckets is None else args.title_buckets
     if distributed and title_buckets:
         raise NotImplementedError("the title feature is not implemented for the row-sharded (--distributed) trainer")
+    sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
+    if distributed and sampling == "mixed":
+        raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
     if distributed and args.optimizer == "adam":
         raise NotImplementedError("optimizer 'adam' is not implemented for the row-sharded (--distributed) trainer")
     if distributed:
@@ -158,6 +171,21 @@ def main(argv=None) -> int:
         cfg.title_pooling = args.title_pooling
     if args.batch_size:
         cfg.batch_size = args.batch_size
+    if args.candidate_sampling is not None:
+        cfg.candidate_sampling = args.candidate_sampling
+    if cfg.candidate_sampling == "mixed":
+        if args.sampled_negatives is not None:
+            cfg.n_sampled_negatives = args.sampled_negatives
+        elif "num_sampled_negatives" not in ((doc.get("model") or {}).get("retrieval") or {}):   # default: as many as the batch
+            cfg.n_sampled_negatives = cfg.batch_size
+        if args.negative_sampler is not None:
+            cfg.negative_sampler = args.negative_sampler
+        if args.unigram_power is not None:
+            cfg.unigram_power = args.unigram_power
+    else:
+        cfg.n_sampled_negatives = 0
+        if args.sampled_negatives:
+            raise SystemExit("--sampled-negatives needs --candidate-sampling mixed")
     epochs = args.epochs if args.epochs is not None else loop["epochs"]
     n = len(user_idx)
     n_val = int(n * args.val_fraction)
@@ -197,11 +225,17 @@ def main(argv=None) -> int:
                                    category_bucket=None if cat is None else cat[va_idx])
 
     item_prob = None
-    if args.correct_sampling_bias:          # P(item j is drawn as an in-batch candidate) = its share of the training pairs
+    mixed = cfg.candidate_sampling == "mixed"
+    if args.correct_sampling_bias or (mixed and cfg.negative_sampler == "unigram"):
+        # P(item j is drawn as an in-batch candidate) = its share of the training pairs
         counts = torch.from_numpy(np.bincount(item_idx[tr_idx], minlength=n_items).astype(np.float64)).to(trainer.dev)
         if distributed:                     # the candidates' frequencies over ALL ranks' training pairs
             dist.all_reduce(counts)
         item_prob = (counts / counts.sum()).to(torch.float32)
+        if mixed:       # the trainer owns the correction: the sampler launch writes the mixture's probability of every candidate
+            trainer.set_item_frequencies(item_prob)
+        if mixed or not args.correct_sampling_bias:
+            item_prob = None
 
     def kw(batch):
         k = {"category_ids": batch[2]} if len(batch) == 3 else {}

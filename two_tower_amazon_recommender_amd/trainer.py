@@ -33,6 +33,7 @@ from . import _lib, ops
 TID_USER_TABLE, TID_ITEM_TABLE, TID_USER_IDS, TID_ITEM_IDS = 1, 2, 3, 4
 TID_CATEGORY_TABLE, TID_CATEGORY_IDS = 5, 6
 TID_TITLE_TABLE, TID_TITLE_IDS, TID_TITLE_LENGTHS = 7, 8, 9
+TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of step s is element s * n_sampled_negatives + i
 TID_DENSE_BASE = 16
 TID_DROPOUT_BASE = 64
 
@@ -68,6 +69,14 @@ class TwoTowerConfig:
     # (Yi et al. 2019; SURVEY.md lists the choice as left open).  Off = the towers' raw outputs, as before.
     normalize_embeddings: bool = False
     normalize_eps: float = 1e-12                   # tf.math.l2_normalize's default (a floor of the SUM OF SQUARES)
+    # retrieval.candidate_sampling of the reference's schema: "in_batch" (every other pair's item is a negative) or "mixed" - mixed
+    # negative sampling (Yang et al. 2020): every step appends n_sampled_negatives items drawn from the whole corpus to the
+    # batch's candidates, by the "uniform" sampler or the "unigram" one (word2vec's f^unigram_power of the item frequencies,
+    # ``set_item_frequencies``).  Single-GPU trainer, Python sequence of launches, no graph capture.
+    candidate_sampling: str = "in_batch"
+    n_sampled_negatives: int = 0
+    negative_sampler: str = "uniform"
+    unigram_power: float = 0.75
     # pooled item-title feature (the reference's preprocessing.text_fields: title; TFRS TextVectorization -> Embedding ->
     # GlobalAveragePooling1D): every item carries up to title_max_tokens hashed title tokens (``set_item_titles``), their rows
     # of a [n_title_buckets, embedding_dim] table are pooled ("sum" | "mean" | "sqrtn") and ADDED to the item tower's input.
@@ -123,15 +132,33 @@ class TwoTowerConfig:
             raise ValueError("title_max_tokens must be in 1..64")
         if self.title_pooling not in ops.POOLINGS:
             raise ValueError(f"title_pooling must be one of {tuple(ops.POOLINGS)}")
+        if self.candidate_sampling not in ("in_batch", "mixed"):
+            raise ValueError(f"candidate_sampling must be 'in_batch' or 'mixed', got {self.candidate_sampling!r}")
+        if self.negative_sampler not in ("uniform", "unigram"):
+            raise ValueError(f"negative_sampler must be 'uniform' or 'unigram', got {self.negative_sampler!r}")
+        if self.candidate_sampling == "mixed":
+            if self.n_sampled_negatives < 1:
+                raise ValueError("candidate_sampling='mixed' needs n_sampled_negatives >= 1")
+            if self.batch_size + self.n_sampled_negatives > 65536:
+                raise ValueError("batch_size + n_sampled_negatives must be <= 65536")
+            if self.n_category_buckets > 0:
+                raise ValueError("candidate_sampling='mixed' with n_category_buckets > 0: a sampled item has no interaction row "
+                                 "to take a category from")
+        elif self.n_sampled_negatives != 0:
+            raise ValueError("n_sampled_negatives must be 0 with candidate_sampling='in_batch'")
+        if not (self.unigram_power >= 0.0 and math.isfinite(self.unigram_power)):
+            raise ValueError("unigram_power must be a finite number >= 0")
 
 
 class Tower:
     """Dense stack: ReLU on all but the last layer (Keras Dense)."""
 
-    def __init__(self, cfg: TwoTowerConfig, tower_dims: list, flat: torch.Tensor, flat_acc, offset: int, dev):
+    def __init__(self, cfg: TwoTowerConfig, tower_dims: list, flat: torch.Tensor, flat_acc, offset: int, dev, rows: int | None = None):
+        """``rows``: rows of every activation / gradient buffer (default cfg.batch_size; the item tower of mixed negative
+        sampling holds batch_size + n_sampled_negatives)."""
         self.dims = [cfg.embedding_dim] + list(tower_dims)
         self.n_layers = len(tower_dims)
-        b = cfg.batch_size
+        self.rows = b = cfg.batch_size if rows is None else int(rows)
         self.w, self.b, self.w_acc, self.b_acc = [], [], [], []
         for l in range(self.n_layers):
             k, n = self.dims[l], self.dims[l + 1]
@@ -169,10 +196,19 @@ class Tower:
         dims = [cfg.embedding_dim] + list(tower_dims)
         return sum(dims[l] * dims[l + 1] + dims[l + 1] for l in range(len(tower_dims)))
 
-    def forward(self, dropout=None, lookup=None):
+    def forward(self, dropout=None, lookup=None, rows: int | None = None):
         """dropout = (rate, seed, tower_index, first_global_row) in training; None = inference (no dropout).
         Inverted dropout follows every hidden (ReLU) layer, fused in the GEMM epilogue.
-        lookup (ops.make_lookup): layer 0 reads its input rows from the embedding table (acts[0] is not used)."""
+        lookup (ops.make_lookup): layer 0 reads its input rows from the embedding table (acts[0] is not used).
+        rows: only the first ``rows`` rows of the buffers (an in-batch evaluation on the longer item tower of mixed sampling)."""
+        if rows is not None and rows != self.rows:
+            if dropout is not None:
+                raise ValueError("Tower.forward: a partial forward pass is an inference pass (no dropout)")
+            for l in range(self.n_layers):
+                bits = self.bits[l + 1]
+                ops.dense_fwd(self.acts[l][:rows], self.w[l], self.b[l], relu=l < self.n_layers - 1, out=self.acts[l + 1][:rows],
+                              lookup=lookup if l == 0 else None, relu_bits=None if bits is None else bits[:rows])
+            return self.acts[-1][:rows]
         for l in range(self.n_layers):
             hidden = l < self.n_layers - 1
             d = None
@@ -288,6 +324,10 @@ class TwoTowerTrainer:
         if dev.type != "cuda":
             raise RuntimeError("TwoTowerTrainer needs a CUDA/HIP device: there is no CPU fallback")
         b, d = cfg.batch_size, cfg.embedding_dim
+        # mixed negative sampling: the item side of the step - tower buffers, sort plan, title slots, candidate list - holds the
+        # batch's items followed by the sampled ones (bi rows); the user side keeps b
+        self.mixed = cfg.candidate_sampling == "mixed"
+        bi = b + (cfg.n_sampled_negatives if self.mixed else 0)
         adagrad, adam = cfg.optimizer == "adagrad", cfg.optimizer == "adam"
         self.user_table = torch.empty(cfg.n_users, d, device=dev)
         self.item_table = torch.empty(cfg.n_items, d, device=dev)
@@ -305,15 +345,20 @@ class TwoTowerTrainer:
         self.cat_m = self.cat_v = None
         self.adam_step = 1
         self.user_tower = Tower(cfg, cfg.user_dims, self.dense_flat, self.dense_accum, 0, dev)
-        self.item_tower = Tower(cfg, cfg.item_dims, self.dense_flat, self.dense_accum, n_user, dev)
+        self.item_tower = Tower(cfg, cfg.item_dims, self.dense_flat, self.dense_accum, n_user, dev, rows=bi)
         sd = cfg.tower_dims[-1]
-        self.ws = torch.empty(ops.retrieval_workspace_bytes(b, b, sd), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(ops.retrieval_workspace_bytes(b, bi, sd), dtype=torch.uint8, device=dev)
         self.lse = torch.empty(b, device=dev)
         self.per_row = torch.empty(b, device=dev)
         self.loss = torch.empty(1, device=dev)
         self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
         self.user_plan = ops.SparsePlan(b, dev)
-        self.item_plan = ops.SparsePlan(b, dev)
+        self.item_plan = ops.SparsePlan(bi, dev)
+        # mixed: the step's candidate ids and (once set_item_frequencies ran) their probabilities under the mixture of the two
+        # candidate streams, both written by the sampler launch; the frequency vectors and the alias table of the unigram sampler
+        self.cand_ids = torch.empty(bi, dtype=torch.int64, device=dev) if self.mixed else None
+        self.cand_prob = torch.empty(bi, device=dev) if self.mixed else None
+        self.item_freq = self.sampler_prob = self.alias = None
         self.cat_table = self.cat_accum = self.cat_plan = None
         if cfg.n_category_buckets:
             self.cat_table = torch.empty(cfg.n_category_buckets, d, device=dev)
@@ -333,10 +378,10 @@ class TwoTowerTrainer:
             if adam:
                 self.title_m, self.title_v = torch.zeros_like(self.title_table), torch.zeros_like(self.title_table)
             self.item_titles = torch.full((cfg.n_items, lt), -1, dtype=torch.int32, device=dev)
-            self.title_plan = ops.BagPlan(b, lt, dev)
-            self.title_ids = torch.empty(b * lt, dtype=torch.int64, device=dev)
-            self.title_inv = torch.empty(b, device=dev)
-            self.title_gs = torch.empty(b, d, device=dev) if cfg.title_pooling != "sum" else None
+            self.title_plan = ops.BagPlan(bi, lt, dev)
+            self.title_ids = torch.empty(bi * lt, dtype=torch.int64, device=dev)
+            self.title_inv = torch.empty(bi, device=dev)
+            self.title_gs = torch.empty(bi, d, device=dev) if cfg.title_pooling != "sum" else None
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -462,6 +507,29 @@ class TwoTowerTrainer:
                              f"got {tokens.dtype} {list(tokens.shape)}")
         self.item_titles.copy_(tokens)
 
+    def set_item_frequencies(self, freq):
+        """freq [n_items]: every item's probability of being an in-batch candidate (its share of the training pairs; train.py's
+        ``--correct-sampling-bias`` vector).  Mixed negative sampling only: from the next step on the sampler launch writes every
+        candidate's probability under the mixture of the in-batch and the sampled stream and the scorer applies the logQ
+        correction with it.  With negative_sampler="unigram" this also builds the sampler: the distribution freq^unigram_power /
+        sum (NumPy f64), its f32 vector (the kernel's ``sampler_prob``) and Walker's alias table (``ops.build_alias_table``)."""
+        import numpy as np
+        if not self.mixed:
+            raise ValueError("set_item_frequencies: the trainer does not sample negatives (cfg.candidate_sampling == 'in_batch'); "
+                             "pass candidate_sampling_probability to step() instead")
+        f = freq.detach().cpu().numpy() if torch.is_tensor(freq) else np.asarray(freq)
+        f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
+        if f.size != self.cfg.n_items or not np.isfinite(f).all() or (f < 0).any():
+            raise ValueError(f"set_item_frequencies: freq must hold n_items = {self.cfg.n_items} finite, non-negative entries")
+        self.item_freq = torch.from_numpy(f.astype(np.float32)).to(self.dev)
+        if self.cfg.negative_sampler == "unigram":
+            w = f ** self.cfg.unigram_power if self.cfg.unigram_power != 0.0 else np.ones_like(f)
+            if not w.sum() > 0:
+                raise ValueError("set_item_frequencies: the unigram sampler needs some positive frequency")
+            thr, idx = ops.build_alias_table(w)
+            self.sampler_prob = torch.from_numpy((w / w.sum()).astype(np.float32)).to(self.dev)
+            self.alias = (torch.from_numpy(thr).to(self.dev), torch.from_numpy(idx).to(self.dev))
+
     def _check_categories(self, category_ids):
         if (category_ids is None) != (self.cat_table is None):
             raise ValueError("category_ids must be given exactly when cfg.n_category_buckets > 0")
@@ -502,15 +570,35 @@ class TwoTowerTrainer:
         """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
         serving: the last layer's output, L2-normalised into ``tower.unit`` (one launch for all of them) when
         cfg.normalize_embeddings.  The ONE place that decides."""
+        if self.mixed:                       # towers of different row counts (or a partial pass): one launch per tower
+            return self._outputs_rows(towers, [t.rows for t in towers])
         if not self.cfg.normalize_embeddings:
             return tuple(t.acts[-1] for t in towers)
         ops.l2_normalize2(tuple(t.acts[-1] for t in towers), tuple(t.unit for t in towers), self.cfg.normalize_eps)
         return tuple(t.unit for t in towers)
 
+    def _outputs_rows(self, towers, rows):
+        """``_outputs`` over the first rows[i] rows of towers[i]."""
+        xs = tuple(t.acts[-1][:n] for t, n in zip(towers, rows))
+        if not self.cfg.normalize_embeddings:
+            return xs
+        ys = tuple(t.unit[:n] for t, n in zip(towers, rows))
+        if len(set(rows)) == 1:
+            ops.l2_normalize2(xs, ys, self.cfg.normalize_eps)
+        else:
+            for x, y in zip(xs, ys):
+                ops.l2_normalize2((x,), (y,), self.cfg.normalize_eps)
+        return ys
+
     # ------------------------------------------------------------------ the hot path
     def forward_backward(self, user_ids: torch.Tensor, item_ids: torch.Tensor, sample_weight=None,
                          candidate_sampling_probability=None, candidate_ids=None, category_ids=None):
         cfg, ut, it = self.cfg, self.user_tower, self.item_tower
+        if self.mixed:
+            if candidate_sampling_probability is not None or candidate_ids is not None or category_ids is not None:
+                raise ValueError("candidate_sampling='mixed': the trainer draws the candidates itself - candidate_ids, "
+                                 "candidate_sampling_probability (set_item_frequencies) and category_ids cannot be passed")
+            return self._forward_backward_mixed(user_ids, item_ids, sample_weight)
         self._check_categories(category_ids)
         lks = self._lookups(user_ids, item_ids, category_ids)
         if lks is None:
@@ -539,10 +627,102 @@ class TwoTowerTrainer:
         self.step_index += 1
         return self.loss
 
+    # ------------------------------------------------------------------ mixed negative sampling
+    def sample_candidates(self, item_ids: torch.Tensor) -> torch.Tensor:
+        """The sampler launch of the step about to run: ``cand_ids`` = the batch's items followed by draws step_index * N ..
+        step_index * N + N - 1 of the stream (seed, TID_SAMPLED_NEGATIVES) - so a resumed run draws what an uninterrupted one
+        does - and, once the frequencies are set, ``cand_prob``."""
+        cfg = self.cfg
+        unigram = cfg.negative_sampler == "unigram"
+        if unigram and self.alias is None:
+            raise ValueError("negative_sampler='unigram' needs the item frequencies: call set_item_frequencies first")
+        ops.sample_candidates(item_ids, cfg.n_items, cfg.n_sampled_negatives, self.cand_ids, self.cand_prob,
+                              sampler="alias" if unigram else "uniform", alias=self.alias if unigram else None,
+                              item_freq=self.item_freq, sampler_prob=self.sampler_prob if unigram else None,
+                              seed=self.dropout_seed, tensor_id=TID_SAMPLED_NEGATIVES,
+                              start=self.step_index * cfg.n_sampled_negatives, oob_flag=self.oob)
+        return self.cand_ids
+
+    def _forward_backward_mixed(self, user_ids, item_ids, sample_weight=None, sampled: bool = False):
+        """forward_backward with the item side over ``cand_ids`` (B + N rows): one launch sequence per tower, the scorer at
+        [B] x [B + N] with the positive of query i at candidate i.  A sampled id equal to a row's own positive is a false
+        negative: ``cand_ids`` always goes to the scorer, which masks it."""
+        cfg, ut, it = self.cfg, self.user_tower, self.item_tower
+        self._check_batch(user_ids, item_ids, sample_weight)
+        if not sampled:
+            self.sample_candidates(item_ids)
+        cand = self.cand_ids
+        lk_u = lk_i = None
+        if self.fuse_lookup and it.rows <= ops.MAX_FUSED_LOOKUP_ROWS:
+            lk_u = ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob)
+            lk_i = ops.make_lookup(self.item_table, cand, oob_flag=self.oob)
+        else:
+            ops.embedding_gather(self.user_table, user_ids, out=ut.acts[0], oob_flag=self.oob)
+            ops.embedding_gather(self.item_table, cand, out=it.acts[0], oob_flag=self.oob)
+            if self.title_table is not None:
+                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=cand, pooling=cfg.title_pooling, out=it.acts[0],
+                                  accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
+        # the dropout streams count rows per tower: consecutive steps never share a position
+        ut.forward((cfg.dropout_rate, self.dropout_seed, 0, self.step_index * ut.rows), lookup=lk_u)
+        it.forward((cfg.dropout_rate, self.dropout_seed, 1, self.step_index * it.rows), lookup=lk_i)
+        q, c = self._outputs(ut, it)
+        dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
+        ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
+                              sample_weight=sample_weight, cand_prob=self.cand_prob if self.item_freq is not None else None,
+                              cand_ids=cand, precision=cfg.scorer_precision)
+        if cfg.normalize_embeddings:
+            ops.l2_normalize_bwd2((ut.acts[-1],), (dq,), (ut.dz[-1],), cfg.normalize_eps)
+            ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
+        ut.backward(cfg.dropout_rate, lookup=lk_u)
+        it.backward(cfg.dropout_rate, lookup=lk_i)
+        self.step_index += 1
+        return self.loss
+
+    def _run_plans_mixed(self, user_ids):
+        ops.sparse_plan_batched([self.user_plan, self.item_plan], [user_ids, self.cand_ids], [self.cfg.n_users, self.cfg.n_items])
+
+    def _step_mixed(self, user_ids, item_ids, sample_weight=None, **other):
+        bad = [k for k, v in other.items() if v is not None]
+        if bad:
+            raise ValueError(f"candidate_sampling='mixed': the trainer draws the candidates itself - {', '.join(sorted(bad))} cannot "
+                             "be passed to step() (the correction comes from set_item_frequencies)")
+        self._check_batch(user_ids, item_ids, sample_weight)
+        if self.flag_poll_every and self.step_index % self.flag_poll_every == 0:
+            self.poll_ids()
+        self.sample_candidates(item_ids)          # in front of everything else: the plans and both lookups read cand_ids
+        self._run_plans_mixed(user_ids)
+        loss = self._forward_backward_mixed(user_ids, item_ids, sample_weight, sampled=True)
+        self.apply_gradients()
+        return loss
+
+    def _apply_table_gradients_mixed(self):
+        """The two tables' plans hold different id counts (B and B + N): one sparse launch sequence per table.  The sampled
+        items' rows are trained like the positives' (their gradient rows are demb[B:])."""
+        cfg, ut, it = self.cfg, self.user_tower, self.item_tower
+        if cfg.optimizer == "adam":              # the user table with every tower segment, then the item table: the same step t
+            h = ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, self.adam_step)
+            ops.adam_step_([(self.user_table, self.user_m, self.user_v, ut.demb, self.user_plan)], self._adam_segs, h)
+            ops.adam_step_([(self.item_table, self.item_m, self.item_v, it.demb, self.item_plan)], [], h)
+            self.adam_step += 1
+            return
+        ops.dense_update_(self._segs, cfg.optimizer, cfg.learning_rate, cfg.adagrad_epsilon)
+        for table, accum, tower, plan in ((self.user_table, self.user_accum, ut, self.user_plan),
+                                          (self.item_table, self.item_accum, it, self.item_plan)):
+            if cfg.optimizer == "sgd":
+                ops.sparse_sgd_(table, tower.demb, plan, cfg.learning_rate)
+            else:
+                ops.sparse_adagrad_(table, accum, tower.demb, plan, cfg.learning_rate, cfg.adagrad_epsilon)
+
     def apply_gradients(self, step_ids=None):
-        """``step_ids`` = [user ids, item ids (, category ids)]: the optimizer launch sorts them itself (no plan launch ran)."""
+        """``step_ids`` = [user ids, item ids (, category ids)]: the optimizer launch sorts them itself (no plan launch ran).
+        Mixed negative sampling: with ``step_ids`` the sort plans run here (over the user ids and ``cand_ids``)."""
         adam_step = self.adam_step
-        self._apply_table_gradients(step_ids)
+        if self.mixed:
+            if step_ids is not None:
+                self._run_plans_mixed(step_ids[0])
+            self._apply_table_gradients_mixed()
+        else:
+            self._apply_table_gradients(step_ids)
         if self.title_table is not None:
             self._apply_title_gradients(adam_step)
 
@@ -602,6 +782,8 @@ class TwoTowerTrainer:
         With cfg.normalize_embeddings the step never takes the composite C call (``tt_train_step_f32`` cannot describe the two
         normalisation launches): it runs the Python sequence ``forward_backward`` + ``apply_gradients(step_ids=...)`` - the path
         asymmetric towers take - with one launch after the towers' forward and one in front of their backward."""
+        if self.mixed:
+            return self._step_mixed(user_ids, item_ids, **loss_kw)
         self._check_batch(user_ids, item_ids, loss_kw.get("category_ids"), loss_kw.get("sample_weight"),
                           loss_kw.get("candidate_sampling_probability"), loss_kw.get("candidate_ids"))
         # (never inside a graph capture: the poll queries an event recorded outside it and would bake a D2H copy into every replay)
@@ -739,6 +921,20 @@ class TwoTowerTrainer:
         self._check_categories(loss_kw.get("category_ids"))
         self._check_batch(loss_kw.get("sample_weight"), loss_kw.get("candidate_sampling_probability"),
                           loss_kw.get("candidate_ids"))
+        if self.mixed:           # the in-batch loss, as without sampling: the first batch_size rows of the item tower's buffers
+            self._check_batch(user_ids, item_ids)
+            b = cfg.batch_size
+            ops.embedding_gather(self.user_table, user_ids, out=ut.acts[0], oob_flag=self.oob)
+            ops.embedding_gather(self.item_table, item_ids, out=it.acts[0][:b], oob_flag=self.oob)
+            if self.title_table is not None:
+                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=cfg.title_pooling,
+                                  out=it.acts[0][:b], accumulate=True, oob_flag=self.oob)
+            ut.forward()
+            it.forward(rows=b)
+            q, c = self._outputs_rows((ut, it), [b, b])
+            return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
+                                     sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
+                                     cand_ids=loss_kw.get("candidate_ids"), precision=cfg.scorer_precision)
         lks = self._lookups(user_ids, item_ids, loss_kw.get("category_ids"))
         if lks is None:
             self._item_inputs(user_ids, item_ids, loss_kw.get("category_ids"))
@@ -757,7 +953,7 @@ class TwoTowerTrainer:
         """Item-tower output for EVERY item row ([n_items, scorer_dim]; unit-norm rows with cfg.normalize_embeddings), computed
         batch by batch on the tower's buffers.
         item_category_ids [n_items]: the category bucket of every item (required iff the model has the feature)."""
-        it, b = self.item_tower, self.cfg.batch_size
+        it, b = self.item_tower, self.item_tower.rows
         n = self.cfg.n_items
         if (item_category_ids is None) != (self.cat_table is None):
             raise ValueError("item_category_ids must be given exactly when cfg.n_category_buckets > 0")
@@ -806,6 +1002,8 @@ class TwoTowerTrainer:
     def state_dict(self) -> dict:
         sd = {"config": dict(self.cfg.__dict__), "user_table": self.user_table, "item_table": self.item_table,
               "dense": self.dense_flat, "step_index": self.step_index, "dropout_seed": self.dropout_seed}
+        if getattr(self, "item_freq", None) is not None:     # mixed negative sampling: the correction (and the unigram sampler) is rebuilt from it
+            sd["item_freq"] = self.item_freq
         if self.cat_table is not None:
             sd["cat_table"] = self.cat_table
         if self.title_table is not None:
@@ -852,6 +1050,10 @@ class TwoTowerTrainer:
         # the counter-based dropout stream continues where the checkpoint stopped (no replayed masks)
         self.step_index = int(sd.get("step_index", 0))
         self.dropout_seed = int(sd.get("dropout_seed", self.dropout_seed))
+        # how the candidates are drawn belongs to the run, not to the model: the trainer keeps its own sampling settings (a
+        # checkpoint from before they existed, or from an in-batch run, loads as before); a mixed trainer takes the frequencies
+        if self.mixed and sd.get("item_freq") is not None:
+            self.set_item_frequencies(sd["item_freq"])
         if self.cat_table is not None:
             self.cat_table.copy_(sd["cat_table"])
             if self.cfg.optimizer == "adagrad":
@@ -873,6 +1075,9 @@ class TwoTowerTrainer:
         if self.cfg.optimizer == "adam":
             raise NotImplementedError("graph replay with optimizer='adam': the global step, and so the bias-corrected step size, "
                                       "is a kernel argument")
+        if self.mixed:
+            raise NotImplementedError("graph replay with candidate_sampling='mixed' is not implemented: the sampler's counter is a "
+                                      "kernel argument and the step is the Python sequence of per-tower launches")
         if self.cfg.n_title_buckets:
             raise NotImplementedError("graph replay with the title feature (n_title_buckets > 0) is not implemented: the warm-up "
                                       "step's update of the title table is not undone")
