@@ -158,6 +158,32 @@ int tt_embedding_bag_bwd_f32(const float* dy, const float* inv, int64_t n_bags, 
                              const int32_t* order, int64_t n_ids, float* gs, int32_t* order_bags, tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * History bag (added to v10: a new symbol only, the version is unchanged) - the pooled user-history feature: the bag of items
+ * a user interacted with, pooled into the query tower's input (TFRS Embedding -> GlobalAveragePooling1D in the query model).
+ * tt_embedding_bag_fwd_f32 - every argument, rule and rounding above - with two optional extensions, one launch either way:
+ * exclude [n_bags] int64 (may be NULL): LEAVE-ONE-OUT.  Every slot of bag b whose token equals exclude[b] is skipped, on every
+ *   occurrence: it is written to batch_ids as -1 (the sort plan never sees it, it gets no gradient) and does not count towards
+ *   cnt / inv.  The compare is on the slot's raw token in int64, in front of the range check: the result is, bit for bit, what
+ *   tt_embedding_bag_fwd_f32 gives on a token matrix whose matching slots were set to -1.  A value that matches no token
+ *   (-1, any negative, any value >= table_rows) excludes nothing and sets no flag.  A bag whose valid slots are all excluded
+ *   is an empty bag: inv = 0 and nothing is added.
+ * base_table [base_rows, dim] f32 (16-byte aligned) + base_ids [n_bags] int64, both NULL or both given; accumulate must be 0
+ *   with them: out[b] = base_table[base_ids[b]] + pooled - the base row takes the place of the row accumulate 1 reads from
+ *   out, with the same rounding sequence (pooled is scaled first, then one add), so the launch equals
+ *   tt_embedding_gather_f32 into out followed by the accumulating bag launch, bit for bit.  base_ids[b] outside
+ *   [0, base_rows) gives a zero base row and (unless it is -1) sets *oob_flag: tt_embedding_gather_f32's rule.  An empty
+ *   bag's row is written as the base row itself.
+ * With exclude and base both NULL the entry IS tt_embedding_bag_fwd_f32.  The backward launch and the table updates are
+ * tt_embedding_bag_bwd_f32 and the sparse entries, unchanged.  TT_ERR_INVALID_ARG before any launch: everything the bag entry
+ * rejects, a base half given, a base with accumulate 1, base_rows <= 0 or a misaligned base_table with a base.              */
+int tt_history_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim,
+                           const int32_t* tokens, int64_t n_token_rows, int32_t L,
+                           const int64_t* bag_rows, int64_t n_bags, int32_t pooling, int32_t accumulate,
+                           float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag,
+                           const int64_t* exclude, const float* base_table, int64_t base_rows, const int64_t* base_ids,
+                           tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mixed negative sampling (added to v10: a new symbol only, the version is unchanged) - Yang et al. 2020: every step
  * appends n_neg items drawn from the whole corpus to the n_pos in-batch candidates (csrc/sample.hip).  One launch writes
  *   cand_ids[0 : n_pos]  = pos_ids

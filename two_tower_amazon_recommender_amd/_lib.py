@@ -151,6 +151,7 @@ SIGNATURES = {
     "tt_hash_bucket_u8": (C.c_int, [_p, _i64, _i32, _i64, _p, _p]),
     "tt_embedding_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "tt_embedding_bag_bwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    "tt_history_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
     "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),

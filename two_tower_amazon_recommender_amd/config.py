@@ -31,6 +31,8 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     dropout = float(m.get("dropout_rate", 0.0)) if dropout_override is None else dropout_override
     # not in the reference's schema: model.features.title {buckets, max_tokens, pooling} - the pooled item-title feature
     title = (m.get("features") or {}).get("title") or {}
+    # likewise model.features.history {max_items, pooling} - the pooled user-history feature
+    hist = (m.get("features") or {}).get("history") or {}
     cfg = TwoTowerConfig(
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
@@ -41,6 +43,7 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         unigram_power=float(rt.get("unigram_power", 0.75)),
         # not in the reference's schema (left open): an optional key beside retrieval.temperature
         normalize_embeddings=bool(rt.get("normalize_embeddings", False)),
+        user_history_len=int(hist.get("max_items", 0)), history_pooling=str(hist.get("pooling", "mean")),
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
         title_pooling=str(title.get("pooling", "mean")))
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),

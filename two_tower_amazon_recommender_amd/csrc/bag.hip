@@ -9,6 +9,12 @@
 // fixed sequence of f32 adds in ascending slot order inside one lane: no LDS, no atomics (but the out-of-range flag), and the
 // bits of a bag depend on neither the grid nor the other bags.  Lane groups past the last bag load nothing, store nothing and
 // still take part in the ballots and shuffles (a group is wholly inside or wholly outside).
+// The pooled user-history feature (tt_history_bag_fwd_f32) is the same body under two template flags.  EXCL: the bag skips
+// every slot whose token equals exclude[b] (leave-one-out: the pair's own positive must not be pooled into the query it is
+// scored against) - one more 8-byte load per bag, issued with bag_rows[b], one compare per slot, and the slot is written to
+// batch_ids as -1 like any skipped slot, so the sort plan and the update never see it.  BASE: the row the sum is added to is
+// base_table[base_ids[b]] instead of out[b] - the tower input user_table[u] + pool(history rows) in ONE launch, without the
+// gather launch's [n_bags, dim] round trip.  <NV, false, false> is the kernel of tt_embedding_bag_fwd_f32 as it was.
 #include "common.h"
 
 namespace {
@@ -16,12 +22,14 @@ namespace {
 constexpr int kInFlight = 4;
 enum { kPoolSum = 0, kPoolMean = 1, kPoolSqrtN = 2 };
 
-template <int NV>
+template <int NV, bool EXCL, bool BASE>
 __global__ __launch_bounds__(256) void bag_fwd_kernel(const float* __restrict__ table_, int64_t table_rows, int dim4, int lpr_log2,
                                                       const int32_t* __restrict__ tokens, int64_t n_token_rows, int L,
                                                       const int64_t* __restrict__ bag_rows, int64_t n_bags, int pooling,
                                                       int accumulate, float* __restrict__ out_, int64_t* __restrict__ batch_ids,
-                                                      float* __restrict__ inv_out, int32_t* __restrict__ oob_flag) {
+                                                      float* __restrict__ inv_out, int32_t* __restrict__ oob_flag,
+                                                      const int64_t* __restrict__ exclude, const float* __restrict__ base_table_,
+                                                      int64_t base_rows, const int64_t* __restrict__ base_ids) {
   const tt::f32x4* __restrict__ table = reinterpret_cast<const tt::f32x4*>(table_);
   tt::f32x4* __restrict__ out = reinterpret_cast<tt::f32x4*>(out_);
   const int lpr = 1 << lpr_log2;
@@ -33,8 +41,18 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(const float* __restrict__ 
   const bool live = b < n_bags;
 
   int64_t row = -1;                                                  // token row of the bag; -1: empty bag
+  int64_t ex = -1;                                                   // EXCL: the token this bag leaves out
+  int64_t bid = -1;                                                  // BASE: the base row of this bag; -1: a zero row
   if (live) {
     row = bag_rows != nullptr ? bag_rows[b] : b;
+    if constexpr (EXCL) ex = exclude[b];
+    if constexpr (BASE) {
+      bid = base_ids[b];
+      if (bid < 0 || bid >= base_rows) {                             // (tt_embedding_gather's rule: zero row; -1 sets no flag)
+        if (bid != -1 && l == 0 && oob_flag != nullptr) atomicOr(oob_flag, 1);
+        bid = -1;
+      }
+    }
     if (row < 0 || row >= n_token_rows) {
       if (row != -1 && l == 0 && oob_flag != nullptr) atomicOr(oob_flag, 1);
       row = -1;
@@ -46,7 +64,11 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(const float* __restrict__ 
   for (int i = 0; i < NV; ++i) {
     const int c = l + i * lpr;
     o[i] = tt::f32x4{0.f, 0.f, 0.f, 0.f};
-    if (live && accumulate && c < dim4) o[i] = out[b * dim4 + c];
+    if constexpr (BASE) {
+      if (bid >= 0 && c < dim4) o[i] = reinterpret_cast<const tt::f32x4*>(base_table_)[bid * dim4 + c];
+    } else {
+      if (live && accumulate && c < dim4) o[i] = out[b * dim4 + c];
+    }
   }
 
   tt::f32x4 s[NV];
@@ -58,6 +80,9 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(const float* __restrict__ 
     int32_t tok = -1;
     if (row >= 0 && slot < L) {
       tok = tokens[row * L + slot];
+      if constexpr (EXCL) {                                          // the raw token, compared in int64: skipped like padding
+        if ((int64_t)tok == ex) tok = -1;
+      }
       if (tok < 0 || (int64_t)tok >= table_rows) {
         if (tok != -1 && oob_flag != nullptr) atomicOr(oob_flag, 1);
         tok = -1;
@@ -125,7 +150,14 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(const float* __restrict__ 
 #pragma unroll
       for (int q = 0; q < 4; ++q) p[q] = __fmul_rn(p[q], inv);
     }
-    if (accumulate) {
+    if constexpr (BASE) {
+      if (cnt == 0) {                                                // empty bag: the base row itself
+        p = o[i];
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) p[q] = __fadd_rn(o[i][q], p[q]);
+      }
+    } else if (accumulate) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) p[q] = __fadd_rn(o[i][q], p[q]);
     }
@@ -149,13 +181,11 @@ __global__ __launch_bounds__(256) void bag_bwd_kernel(const float* __restrict__ 
   if (i < n_ids) order_bags[i] = order[i] / L;
 }
 
-}  // namespace
-
-extern "C" int tt_embedding_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim, const int32_t* tokens,
-                                        int64_t n_token_rows, int32_t L, const int64_t* bag_rows, int64_t n_bags, int32_t pooling,
-                                        int32_t accumulate, float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag,
-                                        tt_stream_t stream) {
-  const char* what = "tt_embedding_bag_fwd_f32";
+// The argument checks and the launch of both forward entries (``what`` names the entry in the messages).
+int bag_fwd_launch(const char* what, const float* table, int64_t table_rows, int32_t dim, const int32_t* tokens,
+                   int64_t n_token_rows, int32_t L, const int64_t* bag_rows, int64_t n_bags, int32_t pooling, int32_t accumulate,
+                   float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag, const int64_t* exclude, const float* base_table,
+                   int64_t base_rows, const int64_t* base_ids, tt_stream_t stream) {
   TT_REQUIRE(dim >= 4 && dim <= 1024 && dim % 4 == 0, "%s: dim must be a multiple of 4 in 4..1024 (got %d)", what, dim);
   TT_REQUIRE(L >= 1, "%s: L must be >= 1 (got %d)", what, L);
   TT_REQUIRE(pooling >= kPoolSum && pooling <= kPoolSqrtN, "%s: pooling must be 0 (sum), 1 (mean) or 2 (sqrtn) (got %d)", what, pooling);
@@ -165,9 +195,13 @@ extern "C" int tt_embedding_bag_fwd_f32(const float* table, int64_t table_rows, 
              "%s: bag_rows is NULL (identity), so n_bags (%lld) must equal n_token_rows (%lld)", what, (long long)n_bags,
              (long long)n_token_rows);
   TT_REQUIRE(n_bags <= 0x7fffffff / (int64_t)L, "%s: n_bags * L must fit 31 bits (the sort plan's positions are int32)", what);
+  TT_REQUIRE((base_table != nullptr) == (base_ids != nullptr), "%s: base_table and base_ids go together (both NULL or both given)", what);
+  TT_REQUIRE(base_table == nullptr || accumulate == 0, "%s: a base row takes the place of out's: accumulate must be 0 with a base", what);
+  TT_REQUIRE(base_table == nullptr || base_rows > 0, "%s: need base_rows > 0 with a base", what);
   if (n_bags == 0) return TT_OK;
   TT_REQUIRE(table && out && (tokens || n_token_rows == 0), "%s: null pointer", what);
   TT_REQUIRE(tt::aligned16(table) && tt::aligned16(out), "%s: table / out must be 16-byte aligned", what);
+  TT_REQUIRE(base_table == nullptr || tt::aligned16(base_table), "%s: base_table must be 16-byte aligned", what);
   const int dim4 = dim / 4;
   int lg = 0;
   while ((1 << lg) < dim4 && lg < 6) ++lg;
@@ -177,17 +211,48 @@ extern "C" int tt_embedding_bag_fwd_f32(const float* table, int64_t table_rows, 
   TT_REQUIRE(blocks <= 0x7fffffff, "%s: too many bags", what);
   const dim3 grid((unsigned)blocks), block(256);
   hipStream_t s = tt::as_stream(stream);
-#define TT_BAG_LAUNCH(NV)                                                                                                      \
-  tt::launch("bag_fwd", bag_fwd_kernel<NV>, grid, block, 0, s, table, table_rows, dim4, lg, tokens, n_token_rows, (int)L, bag_rows, \
-             n_bags, (int)pooling, (int)accumulate, out, batch_ids, inv, oob_flag)
-  switch (nv) {
-    case 1: TT_BAG_LAUNCH(1); break;
-    case 2: TT_BAG_LAUNCH(2); break;
-    case 3: TT_BAG_LAUNCH(3); break;
-    default: TT_BAG_LAUNCH(4); break;
+#define TT_BAG_LAUNCH(NV, EXCL, BASE)                                                                                          \
+  tt::launch("bag_fwd", bag_fwd_kernel<NV, EXCL, BASE>, grid, block, 0, s, table, table_rows, dim4, lg, tokens, n_token_rows,   \
+             (int)L, bag_rows, n_bags, (int)pooling, (int)accumulate, out, batch_ids, inv, oob_flag, exclude, base_table,       \
+             base_rows, base_ids)
+#define TT_BAG_LAUNCH_NV(EXCL, BASE)                                                                                           \
+  switch (nv) {                                                                                                                \
+    case 1: TT_BAG_LAUNCH(1, EXCL, BASE); break;                                                                               \
+    case 2: TT_BAG_LAUNCH(2, EXCL, BASE); break;                                                                               \
+    case 3: TT_BAG_LAUNCH(3, EXCL, BASE); break;                                                                               \
+    default: TT_BAG_LAUNCH(4, EXCL, BASE); break;                                                                              \
   }
+  if (exclude != nullptr && base_table != nullptr) {
+    TT_BAG_LAUNCH_NV(true, true);
+  } else if (exclude != nullptr) {
+    TT_BAG_LAUNCH_NV(true, false);
+  } else if (base_table != nullptr) {
+    TT_BAG_LAUNCH_NV(false, true);
+  } else {
+    TT_BAG_LAUNCH_NV(false, false);
+  }
+#undef TT_BAG_LAUNCH_NV
 #undef TT_BAG_LAUNCH
   return tt::check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int tt_embedding_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim, const int32_t* tokens,
+                                        int64_t n_token_rows, int32_t L, const int64_t* bag_rows, int64_t n_bags, int32_t pooling,
+                                        int32_t accumulate, float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag,
+                                        tt_stream_t stream) {
+  return bag_fwd_launch("tt_embedding_bag_fwd_f32", table, table_rows, dim, tokens, n_token_rows, L, bag_rows, n_bags, pooling,
+                        accumulate, out, batch_ids, inv, oob_flag, nullptr, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int tt_history_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim, const int32_t* tokens,
+                                      int64_t n_token_rows, int32_t L, const int64_t* bag_rows, int64_t n_bags, int32_t pooling,
+                                      int32_t accumulate, float* out, int64_t* batch_ids, float* inv, int32_t* oob_flag,
+                                      const int64_t* exclude, const float* base_table, int64_t base_rows, const int64_t* base_ids,
+                                      tt_stream_t stream) {
+  return bag_fwd_launch("tt_history_bag_fwd_f32", table, table_rows, dim, tokens, n_token_rows, L, bag_rows, n_bags, pooling,
+                        accumulate, out, batch_ids, inv, oob_flag, exclude, base_table, base_rows, base_ids, stream);
 }
 
 extern "C" int tt_embedding_bag_bwd_f32(const float* dy, const float* inv, int64_t n_bags, int32_t dim, int32_t L,

@@ -67,6 +67,58 @@ def item_categories(item_idx: np.ndarray, category_bucket: np.ndarray, n_items: 
     return out
 
 
+TIMESTAMP_COLUMN = "timestamp"  # prepare_training_data.py:93-94: written as a number
+
+
+def read_timestamps(path):
+    """The ``timestamp`` column of the interaction file as float64 [n_rows] (nulls: -inf, the oldest), or None when the file
+    has no such column."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    import pyarrow.parquet as pq
+    if TIMESTAMP_COLUMN not in pq.read_schema(path).names:
+        return None
+    col = pq.read_table(path, columns=[TIMESTAMP_COLUMN]).column(TIMESTAMP_COLUMN).combine_chunks()
+    ts = pc.fill_null(pc.cast(col, pa.float64()), float("-inf")).to_numpy(zero_copy_only=False).astype(np.float64, copy=False)
+    return np.where(np.isnan(ts), -np.inf, ts)          # (pd.to_numeric(errors="coerce") leaves NaN where it could not parse)
+
+
+def user_histories(user_idx: np.ndarray, item_idx: np.ndarray, n_users: int, max_items: int, timestamp=None) -> np.ndarray:
+    """int32 [n_users, max_items] token matrix of ``set_user_histories``: every user's LAST ``max_items`` interactions in the
+    order of ``timestamp`` (ties, or no timestamps at all: file position), oldest first, left-aligned, padded with -1.  A
+    repeated item is kept as often as it occurs; a user with no pair is all -1.  Vectorised: one lexsort and a rank within
+    the user's group."""
+    user_idx, item_idx = np.asarray(user_idx), np.asarray(item_idx)
+    if len(user_idx) != len(item_idx):
+        raise ValueError("user_idx and item_idx differ in length")
+    if max_items < 1:
+        raise ValueError("max_items must be >= 1")
+    out = np.full((n_users, max_items), -1, dtype=np.int32)
+    n = len(user_idx)
+    if n == 0:
+        return out
+    if user_idx.min() < 0 or user_idx.max() >= n_users:
+        raise ValueError("user_idx outside [0, n_users)")
+    if item_idx.min() < 0 or item_idx.max() >= 2 ** 31:
+        raise ValueError("item_idx outside [0, 2^31): the history tokens are int32")
+    pos = np.arange(n)
+    if timestamp is None:
+        order = np.argsort(user_idx, kind="stable")                       # by user, file position inside
+    else:
+        timestamp = np.asarray(timestamp)
+        if len(timestamp) != n:
+            raise ValueError("timestamp and user_idx differ in length")
+        order = np.lexsort((pos, timestamp, user_idx))                    # by user, then timestamp, then file position
+    u = user_idx[order]
+    cnt = np.bincount(u, minlength=n_users)
+    start = np.cumsum(cnt) - cnt                                          # first sorted position of every user's group
+    rank = pos - start[u]                                                 # 0 = the user's oldest interaction
+    col = rank - np.maximum(cnt[u] - max_items, 0)                        # the last max_items of them, left-aligned
+    keep = col >= 0
+    out[u[keep], col[keep]] = item_idx[order][keep].astype(np.int32)
+    return out
+
+
 TITLE_COLUMN = "title"          # prepare_training_data.py:52-62: every interaction carries its item's title
 _TOKEN = re.compile(r"[a-z0-9]+")
 

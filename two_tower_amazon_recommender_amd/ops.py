@@ -165,6 +165,37 @@ def hash_buckets(rows_u8: torch.Tensor, n_buckets: int) -> torch.Tensor:
 POOLINGS = {"sum": _lib.TT_POOL_SUM, "mean": _lib.TT_POOL_MEAN, "sqrtn": _lib.TT_POOL_SQRTN}
 
 
+def _bag_args(what, table, tokens, bag_rows, pooling, out, accumulate, batch_ids, inv, oob_flag):
+    """The argument checks the two bag forward ops share; returns (n_token_rows, L, dim, n_bags, out)."""
+    _chk(table, torch.float32, "table", 2)
+    _chk(tokens, torch.int32, "tokens", 2)
+    if pooling not in POOLINGS:
+        raise ValueError(f"{what}: pooling must be one of {tuple(POOLINGS)}, got {pooling!r}")
+    n_rows, L = tokens.shape
+    d = table.shape[1]
+    if bag_rows is not None:
+        _chk(bag_rows, torch.int64, "bag_rows", 1)
+    n_bags = n_rows if bag_rows is None else bag_rows.numel()
+    if out is None:
+        if accumulate:
+            raise ValueError(f"{what}: accumulate=True adds into `out`, which must be given")
+        out = torch.empty((n_bags, d), dtype=torch.float32, device=table.device)
+    _chk(out, torch.float32, "out", 2)
+    if tuple(out.shape) != (n_bags, d):
+        raise RuntimeError(f"{what}: out must be [{n_bags}, {d}] (n_bags, dim), got {tuple(out.shape)}")
+    if batch_ids is not None:
+        _chk(batch_ids, torch.int64, "batch_ids")
+        if batch_ids.numel() != n_bags * L:
+            raise RuntimeError(f"{what}: batch_ids must hold n_bags * L = {n_bags * L} entries, got {batch_ids.numel()}")
+    if inv is not None:
+        _chk(inv, torch.float32, "inv", 1)
+        if inv.numel() != n_bags:
+            raise RuntimeError(f"{what}: inv must hold n_bags = {n_bags} entries, got {inv.numel()}")
+    if oob_flag is not None:
+        _chk(oob_flag, torch.int32, "oob_flag")
+    return n_rows, L, d, n_bags, out
+
+
 def embedding_bag(table: torch.Tensor, tokens: torch.Tensor, bag_rows: torch.Tensor | None = None, pooling: str = "mean",
                   out: torch.Tensor | None = None, accumulate: bool = False, batch_ids: torch.Tensor | None = None,
                   inv: torch.Tensor | None = None, oob_flag: torch.Tensor | None = None) -> torch.Tensor:
@@ -174,35 +205,42 @@ def embedding_bag(table: torch.Tensor, tokens: torch.Tensor, bag_rows: torch.Ten
     Optional outputs: ``batch_ids`` [n_bags * L] int64 (every slot's token, -1 where skipped: what the sort plan sorts) and
     ``inv`` [n_bags] f32 (the pooling scale; 0 for an empty bag).  ``oob_flag`` (int32[1]) is set on any token or bag row out
     of range."""
-    _chk(table, torch.float32, "table", 2)
-    _chk(tokens, torch.int32, "tokens", 2)
-    if pooling not in POOLINGS:
-        raise ValueError(f"embedding_bag: pooling must be one of {tuple(POOLINGS)}, got {pooling!r}")
-    n_rows, L = tokens.shape
-    d = table.shape[1]
-    if bag_rows is not None:
-        _chk(bag_rows, torch.int64, "bag_rows", 1)
-    n_bags = n_rows if bag_rows is None else bag_rows.numel()
-    if out is None:
-        if accumulate:
-            raise ValueError("embedding_bag: accumulate=True adds into `out`, which must be given")
-        out = torch.empty((n_bags, d), dtype=torch.float32, device=table.device)
-    _chk(out, torch.float32, "out", 2)
-    if tuple(out.shape) != (n_bags, d):
-        raise RuntimeError(f"embedding_bag: out must be [{n_bags}, {d}] (n_bags, dim), got {tuple(out.shape)}")
-    if batch_ids is not None:
-        _chk(batch_ids, torch.int64, "batch_ids")
-        if batch_ids.numel() != n_bags * L:
-            raise RuntimeError(f"embedding_bag: batch_ids must hold n_bags * L = {n_bags * L} entries, got {batch_ids.numel()}")
-    if inv is not None:
-        _chk(inv, torch.float32, "inv", 1)
-        if inv.numel() != n_bags:
-            raise RuntimeError(f"embedding_bag: inv must hold n_bags = {n_bags} entries, got {inv.numel()}")
-    if oob_flag is not None:
-        _chk(oob_flag, torch.int32, "oob_flag")
+    n_rows, L, d, n_bags, out = _bag_args("embedding_bag", table, tokens, bag_rows, pooling, out, accumulate, batch_ids, inv, oob_flag)
     _lib.check(_lib.load().tt_embedding_bag_fwd_f32(_p(table), table.shape[0], d, _p(tokens), n_rows, L, _p(bag_rows), n_bags,
                                                     POOLINGS[pooling], int(bool(accumulate)), _p(out), _p(batch_ids), _p(inv),
                                                     _p(oob_flag), _stream()), "tt_embedding_bag_fwd_f32")
+    return out
+
+
+def history_bag(table: torch.Tensor, tokens: torch.Tensor, bag_rows: torch.Tensor | None = None,
+                exclude: torch.Tensor | None = None, base=None, pooling: str = "mean", out: torch.Tensor | None = None,
+                accumulate: bool = False, batch_ids: torch.Tensor | None = None, inv: torch.Tensor | None = None,
+                oob_flag: torch.Tensor | None = None) -> torch.Tensor:
+    """``embedding_bag`` with leave-one-out and a base row, in one launch (``tt_history_bag_fwd_f32``): the pooled user-history
+    feature.  ``exclude`` [n_bags] int64: bag b skips every slot whose token equals exclude[b] (written to ``batch_ids`` as -1,
+    not counted).  ``base`` = (base_table [rows, dim] f32, base_ids [n_bags] int64): out[b] = base_table[base_ids[b]] + pooled
+    (an out-of-range base id: a zero row and the flag); it takes the place of ``accumulate``, which must then be False.
+    Every other argument is ``embedding_bag``'s."""
+    if base is not None and accumulate:
+        raise ValueError("history_bag: the base row takes the place of out's row: accumulate must be False with a base")
+    n_rows, L, d, n_bags, out = _bag_args("history_bag", table, tokens, bag_rows, pooling, out, accumulate, batch_ids, inv, oob_flag)
+    if exclude is not None:
+        _chk(exclude, torch.int64, "exclude", 1)
+        if exclude.numel() != n_bags:
+            raise RuntimeError(f"history_bag: exclude must hold n_bags = {n_bags} entries, got {exclude.numel()}")
+    base_table = base_ids = None
+    if base is not None:
+        base_table, base_ids = base
+        _chk(base_table, torch.float32, "base_table", 2)
+        _chk(base_ids, torch.int64, "base_ids", 1)
+        if base_table.shape[1] != d or base_ids.numel() != n_bags:
+            raise RuntimeError(f"history_bag: base must be ([rows, {d}] f32, [{n_bags}] int64), got {tuple(base_table.shape)} "
+                               f"and {tuple(base_ids.shape)}")
+    _lib.check(_lib.load().tt_history_bag_fwd_f32(_p(table), table.shape[0], d, _p(tokens), n_rows, L, _p(bag_rows), n_bags,
+                                                  POOLINGS[pooling], int(bool(accumulate)), _p(out), _p(batch_ids), _p(inv),
+                                                  _p(oob_flag), _p(exclude), _p(base_table),
+                                                  0 if base_table is None else base_table.shape[0], _p(base_ids), _stream()),
+               "tt_history_bag_fwd_f32")
     return out
 
 

@@ -425,6 +425,10 @@ class ShardedTwoTowerTrainer:
             # the bag table would have to be sharded and its pooled rows exchanged like the other tables' rows
             raise NotImplementedError("the title feature (n_title_buckets > 0) is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "user_history_len", 0):
+            # the history table would have to be sharded and every bag's rows fetched from their owners
+            raise NotImplementedError("the user-history feature (user_history_len > 0) is not implemented for the row-sharded "
+                                      "trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "candidate_sampling", "in_batch") != "in_batch":
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "

@@ -8,6 +8,7 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
     loss, per_example, dq, dc = torch.ops.twotower.retrieval_loss(q, c, w, p, ids, inv_t, diag_offset, k)
     rows = torch.ops.twotower.embedding_gather(table, ids)
     pooled = torch.ops.twotower.embedding_bag(table, tokens, bag_rows, "mean")
+    x = torch.ops.twotower.history_bag(hist_table, histories, user_ids, item_ids, user_table, user_ids, "mean")
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
     torch.ops.twotower.sparse_adam_(table, exp_avg, exp_avg_sq, grads, ids, step, lr, 0.9, 0.999, 1e-7)
@@ -92,6 +93,24 @@ def embedding_bag(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], poo
 
 @embedding_bag.register_fake
 def _(table, tokens, bag_rows, pooling="mean"):
+    return table.new_empty(((tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), table.shape[1]))
+
+
+@torch.library.custom_op(f"{NS}::history_bag", mutates_args=(), device_types="cuda")
+def history_bag(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], exclude: Optional[Tensor], base_table: Optional[Tensor],
+                base_ids: Optional[Tensor], pooling: str = "mean") -> Tensor:
+    """``embedding_bag`` with leave-one-out and a base row in one launch (``ops.history_bag``, the pooled user-history feature):
+    bag b skips every slot whose token equals ``exclude[b]``, and out[b] = base_table[base_ids[b]] + pooled when the base pair
+    is given (both or neither).  Not differentiable: the table is trained through ``ops.BagPlan`` and the sparse updates."""
+    if (base_table is None) != (base_ids is None):
+        raise ValueError("history_bag: base_table and base_ids go together")
+    c = lambda t: None if t is None else t.contiguous()
+    return ops.history_bag(table.contiguous(), tokens.contiguous(), c(bag_rows), c(exclude),
+                           None if base_table is None else (c(base_table), c(base_ids)), pooling)
+
+
+@history_bag.register_fake
+def _(table, tokens, bag_rows, exclude, base_table, base_ids, pooling="mean"):
     return table.new_empty(((tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), table.shape[1]))
 
 
@@ -492,5 +511,5 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
     ops.adam_step_([(table, exp_avg, exp_avg_sq, grads.contiguous(), plan)], [], ops.AdamHyper(lr, beta1, beta2, eps, step))
 
 
-OPS = ("embedding_gather", "embedding_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
+OPS = ("embedding_gather", "embedding_bag", "history_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "sparse_update_", "sparse_adam_")

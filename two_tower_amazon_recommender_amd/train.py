@@ -71,6 +71,11 @@ def parse(argv=None):
                          "input (overrides model.features.title.buckets); single-GPU trainer only")
     ap.add_argument("--title-max-tokens", type=int, default=None, metavar="L", help="title tokens kept per item (1..64; default 16)")
     ap.add_argument("--title-pooling", default=None, choices=["sum", "mean", "sqrtn"], help="how the token rows are pooled (default mean)")
+    ap.add_argument("--history-len", type=int, default=None, metavar="L",
+                    help="add the pooled user-history feature: every user's last L training interactions (1..64, by the "
+                         "timestamp column where there is one) are pooled into the user tower input, the pair's own item left "
+                         "out (overrides model.features.history.max_items); single-GPU trainer only")
+    ap.add_argument("--history-pooling", default=None, choices=["sum", "mean", "sqrtn"], help="how the history rows are pooled (default mean)")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -120,6 +125,10 @@ def main(argv=None) -> int:
     title_buckets = int(title_cfg.get("buckets", 0)) if args.title_buckets is None else args.title_buckets
     if distributed and title_buckets:
         raise NotImplementedError("the title feature is not implemented for the row-sharded (--distributed) trainer")
+    hist_cfg = ((doc.get("model") or {}).get("features") or {}).get("history") or {}
+    history_len = int(hist_cfg.get("max_items", 0)) if args.history_len is None else args.history_len
+    if distributed and history_len:
+        raise NotImplementedError("the user-history feature is not implemented for the row-sharded (--distributed) trainer")
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -169,6 +178,9 @@ def main(argv=None) -> int:
         cfg.title_max_tokens = args.title_max_tokens
     if args.title_pooling is not None:
         cfg.title_pooling = args.title_pooling
+    cfg.user_history_len = history_len
+    if args.history_pooling is not None:
+        cfg.history_pooling = args.history_pooling
     if args.batch_size:
         cfg.batch_size = args.batch_size
     if args.candidate_sampling is not None:
@@ -194,6 +206,12 @@ def main(argv=None) -> int:
     tr_idx, va_idx = perm[n_val:], perm[:n_val]
     log.info("users %d items %d interactions %d (train %d, val %d); batch %d; optimizer %s", n_users, n_items, n,
              len(tr_idx), len(va_idx), cfg.batch_size, cfg.optimizer)
+    histories = None
+    if cfg.user_history_len:                # the TRAINING pairs only, in the order of the timestamps (else: of the file)
+        rows = np.sort(tr_idx)
+        ts = None if args.synthetic else datamod.read_timestamps(args.data)
+        histories = datamod.user_histories(user_idx[rows], item_idx[rows], n_users, cfg.user_history_len,
+                                           None if ts is None else ts[rows])
     if distributed:
         # every rank computed the same split; it trains on every world-th pair, cut so all ranks run the same number
         # of (collective) steps
@@ -208,6 +226,8 @@ def main(argv=None) -> int:
         trainer = ShardedTwoTowerTrainer(cfg, args.device, seed=args.seed, negatives=args.negatives)
     else:
         trainer = TwoTowerTrainer(cfg, args.device, seed=args.seed)
+    if histories is not None:
+        trainer.set_user_histories(torch.from_numpy(histories).to(trainer.dev))
     if cfg.n_title_buckets:
         if args.synthetic:                  # tokens from the id generator
             trainer.set_item_titles(trainer.synthetic_item_titles(args.seed))

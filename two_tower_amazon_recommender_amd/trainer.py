@@ -33,6 +33,7 @@ from . import _lib, ops
 TID_USER_TABLE, TID_ITEM_TABLE, TID_USER_IDS, TID_ITEM_IDS = 1, 2, 3, 4
 TID_CATEGORY_TABLE, TID_CATEGORY_IDS = 5, 6
 TID_TITLE_TABLE, TID_TITLE_IDS, TID_TITLE_LENGTHS = 7, 8, 9
+TID_HISTORY_TABLE = 11
 TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of step s is element s * n_sampled_negatives + i
 TID_DENSE_BASE = 16
 TID_DROPOUT_BASE = 64
@@ -77,6 +78,13 @@ class TwoTowerConfig:
     n_sampled_negatives: int = 0
     negative_sampler: str = "uniform"
     unigram_power: float = 0.75
+    # pooled user-history feature (TFRS's context / sequential retrieval shape: Embedding over item ids ->
+    # GlobalAveragePooling1D in the query model): every user carries its last user_history_len training items
+    # (``set_user_histories``), their rows of a [n_items, embedding_dim] table of its own are pooled ("sum" | "mean" | "sqrtn") and
+    # ADDED to the user tower's input - in the train step without the pair's own item (leave-one-out: pooled into the query it is
+    # scored against, the label would leak).  0 = no such feature.  Single-GPU trainer, materialised tower inputs, no graph capture.
+    user_history_len: int = 0
+    history_pooling: str = "mean"
     # pooled item-title feature (the reference's preprocessing.text_fields: title; TFRS TextVectorization -> Embedding ->
     # GlobalAveragePooling1D): every item carries up to title_max_tokens hashed title tokens (``set_item_titles``), their rows
     # of a [n_title_buckets, embedding_dim] table are pooled ("sum" | "mean" | "sqrtn") and ADDED to the item tower's input.
@@ -132,6 +140,15 @@ class TwoTowerConfig:
             raise ValueError("title_max_tokens must be in 1..64")
         if self.title_pooling not in ops.POOLINGS:
             raise ValueError(f"title_pooling must be one of {tuple(ops.POOLINGS)}")
+        if not 0 <= self.user_history_len <= 64:
+            raise ValueError("user_history_len must be 0 (no history feature) or in 1..64")
+        if self.history_pooling not in ops.POOLINGS:
+            raise ValueError(f"history_pooling must be one of {tuple(ops.POOLINGS)}")
+        if self.user_history_len and self.n_items >= 2 ** 31:
+            raise ValueError("user_history_len > 0 needs n_items < 2^31: the history tokens are int32")
+        if self.user_history_len and self.candidate_sampling == "mixed":
+            raise ValueError("user_history_len > 0 with candidate_sampling='mixed' is not implemented: a sampled negative that "
+                             "sits in the query's history is not left out")
         if self.candidate_sampling not in ("in_batch", "mixed"):
             raise ValueError(f"candidate_sampling must be 'in_batch' or 'mixed', got {self.candidate_sampling!r}")
         if self.negative_sampler not in ("uniform", "unigram"):
@@ -382,6 +399,21 @@ class TwoTowerTrainer:
             self.title_ids = torch.empty(bi * lt, dtype=torch.int64, device=dev)
             self.title_inv = torch.empty(bi, device=dev)
             self.title_gs = torch.empty(bi, d, device=dev) if cfg.title_pooling != "sum" else None
+        # pooled user-history feature: the mirror on the user side - a [n_items, dim] table of its own with its optimizer state,
+        # every user's history row (all padding until set_user_histories) and the per-step buffers of the bag launches
+        self.history_table = self.history_accum = self.history_m = self.history_v = None
+        self.user_history = self.history_plan = self.history_ids = self.history_inv = self.history_gs = None
+        if cfg.user_history_len:
+            lh = cfg.user_history_len
+            self.history_table = torch.empty(cfg.n_items, d, device=dev)
+            self.history_accum = torch.full_like(self.history_table, cfg.adagrad_initial_accumulator) if adagrad else None
+            if adam:
+                self.history_m, self.history_v = torch.zeros_like(self.history_table), torch.zeros_like(self.history_table)
+            self.user_history = torch.full((cfg.n_users, lh), -1, dtype=torch.int32, device=dev)
+            self.history_plan = ops.BagPlan(b, lh, dev)
+            self.history_ids = torch.empty(b * lh, dtype=torch.int64, device=dev)
+            self.history_inv = torch.empty(b, device=dev)
+            self.history_gs = torch.empty(b, d, device=dev) if cfg.history_pooling != "sum" else None
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -398,6 +430,8 @@ class TwoTowerTrainer:
         # 0.1631-0.1638 ms fused against 0.1644-0.1654 with the gather launch)
         self.fuse_lookup = os.environ.get("TT_FUSE_LOOKUP", "1" if (cfg.tower_dims[0] < 512 or cfg.batch_size <= 2048) else "0") != "0"
         if cfg.n_title_buckets:                  # the pooled titles are added to the materialised item-tower input (_item_inputs)
+            self.fuse_lookup = False
+        if cfg.user_history_len:                 # the user tower's input is one bag launch: user row + pooled history (_item_inputs)
             self.fuse_lookup = False
         self.fuse_sort = os.environ.get("TT_FUSE_SORT", "1") != "0"   # the optimizer launch sorts the ids itself (no plan launch)
         self.fuse_optimizer = True               # sparse + dense optimizer in one launch (False: dense_update, sparse_update2 [, cat])
@@ -453,6 +487,8 @@ class TwoTowerTrainer:
             ops.fill_uniform_(self.cat_table, seed, TID_CATEGORY_TABLE, -0.05, 0.1)
         if self.title_table is not None:
             ops.fill_uniform_(self.title_table, seed, TID_TITLE_TABLE, -0.05, 0.1)
+        if self.history_table is not None:
+            ops.fill_uniform_(self.history_table, seed, TID_HISTORY_TABLE, -0.05, 0.1)
         self.dense_flat.zero_()
         for t, tower in enumerate((self.user_tower, self.item_tower)):
             for l, w in enumerate(tower.w):
@@ -461,11 +497,11 @@ class TwoTowerTrainer:
                 scale32 = (lim + lim).item()
                 ops.fill_uniform_(w, seed, TID_DENSE_BASE + 2 * l + t, -lim32, scale32)
         if self.cfg.optimizer == "adagrad":
-            for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum):
+            for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum, self.history_accum):
                 if a is not None:
                     a.fill_(self.cfg.adagrad_initial_accumulator)
         for a in (self.user_m, self.user_v, self.item_m, self.item_v, self.cat_m, self.cat_v, self.title_m, self.title_v,
-                  self.dense_m, self.dense_v):
+                  self.history_m, self.history_v, self.dense_m, self.dense_v):
             if a is not None:
                 a.zero_()
         self.adam_step = 1
@@ -506,6 +542,16 @@ class TwoTowerTrainer:
             raise ValueError(f"set_item_titles: tokens must be int32 {list(self.item_titles.shape)} (n_items, title_max_tokens), "
                              f"got {tokens.dtype} {list(tokens.shape)}")
         self.item_titles.copy_(tokens)
+
+    def set_user_histories(self, tokens: torch.Tensor):
+        """tokens [n_users, user_history_len] int32: every user's last training items (``data.user_histories``), -1 = no item in
+        that slot.  Items outside [0, n_items) are skipped by the kernel and raise through ``check_ids``."""
+        if self.user_history is None:
+            raise ValueError("set_user_histories: the model has no history feature (cfg.user_history_len == 0)")
+        if tuple(tokens.shape) != tuple(self.user_history.shape) or tokens.dtype != torch.int32:
+            raise ValueError(f"set_user_histories: tokens must be int32 {list(self.user_history.shape)} (n_users, user_history_len), "
+                             f"got {tokens.dtype} {list(tokens.shape)}")
+        self.user_history.copy_(tokens)
 
     def set_item_frequencies(self, freq):
         """freq [n_items]: every item's probability of being an in-batch candidate (its share of the training pairs; train.py's
@@ -554,12 +600,23 @@ class TwoTowerTrainer:
         return (ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob),
                 ops.make_lookup(self.item_table, item_ids, self.cat_table, category_ids, self.oob))
 
-    def _item_inputs(self, user_ids, item_ids, category_ids):
+    def _user_inputs(self, user_ids, out, exclude=None, keep: bool = False):
+        """The user tower's input rows with the history feature, in ONE launch: user_table[u] + the pooled history rows of u,
+        without the items ``exclude`` (the train step's positives).  ``keep``: the slot tokens and scales stay for the update."""
+        ops.history_bag(self.history_table, self.user_history, bag_rows=user_ids, exclude=exclude, base=(self.user_table, user_ids),
+                        pooling=self.cfg.history_pooling, out=out, batch_ids=self.history_ids if keep else None,
+                        inv=self.history_inv if keep else None, oob_flag=self.oob)
+
+    def _item_inputs(self, user_ids, item_ids, category_ids, train: bool = False):
         """K1 as its own launch (fuse_lookup = False): both towers' input rows; the hashed category's row is summed
-        into the item tower's input."""
+        into the item tower's input.  ``train``: the history bags leave out the pair's own item and keep what the update needs."""
         self._check_batch(user_ids, item_ids, category_ids)
         ut, it = self.user_tower, self.item_tower
-        ops.embedding_gather2(self.user_table, user_ids, ut.acts[0], self.item_table, item_ids, it.acts[0], self.oob)
+        if self.history_table is not None:
+            ops.embedding_gather(self.item_table, item_ids, out=it.acts[0], oob_flag=self.oob)
+            self._user_inputs(user_ids, ut.acts[0], exclude=item_ids if train else None, keep=train)
+        else:
+            ops.embedding_gather2(self.user_table, user_ids, ut.acts[0], self.item_table, item_ids, it.acts[0], self.oob)
         if category_ids is not None:
             ops.embedding_gather_add_(it.acts[0], self.cat_table, category_ids, self.oob)
         if self.title_table is not None:     # + the pooled title rows of every pair's item; the slot tokens and scales stay for the update
@@ -602,7 +659,7 @@ class TwoTowerTrainer:
         self._check_categories(category_ids)
         lks = self._lookups(user_ids, item_ids, category_ids)
         if lks is None:
-            self._item_inputs(user_ids, item_ids, category_ids)
+            self._item_inputs(user_ids, item_ids, category_ids, train=True)
             lks = (None, None)
         row0 = self.step_index * cfg.batch_size
         if cfg.symmetric:        # same shapes: every layer of both towers in one launch
@@ -725,6 +782,22 @@ class TwoTowerTrainer:
             self._apply_table_gradients(step_ids)
         if self.title_table is not None:
             self._apply_title_gradients(adam_step)
+        if self.history_table is not None:
+            self._apply_history_gradients(adam_step)
+
+    def _apply_history_gradients(self, adam_step: int):
+        """The history table's update, the mirror of ``_apply_title_gradients`` on the user side: the sort plan over the step's
+        slot items (an excluded slot is -1 there: no gradient), the bags' scaled user-tower input gradient rows, the optimizer."""
+        cfg, plan = self.cfg, self.history_plan
+        plan.run(self.history_ids, cfg.n_items)
+        gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
+        if cfg.optimizer == "adam":
+            ops.adam_step_([(self.history_table, self.history_m, self.history_v, gs, plan)], [],
+                           ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
+        elif cfg.optimizer == "sgd":
+            ops.sparse_sgd_(self.history_table, gs, plan, cfg.learning_rate)
+        else:
+            ops.sparse_adagrad_(self.history_table, self.history_accum, gs, plan, cfg.learning_rate, cfg.adagrad_epsilon)
 
     def _apply_title_gradients(self, adam_step: int):
         """The title table's update: sort plan over the step's slot tokens, one launch that scales the item-tower input gradient
@@ -982,7 +1055,10 @@ class TwoTowerTrainer:
         out = torch.empty(n, ut.dims[-1], device=self.dev)
         for s in range(0, n, b):
             e = min(s + b, n)
-            ops.embedding_gather(self.user_table, ids[s:e], out=ut.acts[0][:e - s], oob_flag=self.oob)
+            if self.history_table is not None:     # the full stored history: nothing is left out at inference
+                self._user_inputs(ids[s:e], ut.acts[0][:e - s])
+            else:
+                ops.embedding_gather(self.user_table, ids[s:e], out=ut.acts[0][:e - s], oob_flag=self.oob)
             ut.forward()
             out[s:e].copy_(self._outputs(ut)[0][:e - s])
         return out
@@ -994,7 +1070,11 @@ class TwoTowerTrainer:
         self._check_batch(user_ids, item_ids)
         if corpus is None:
             corpus = self.item_corpus_embeddings()
-        self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
+        if self.history_table is not None:
+            self._user_inputs(user_ids, self.user_tower.acts[0])
+            self.user_tower.forward()
+        else:
+            self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
         (q,) = self._outputs(self.user_tower)
         return metric.update_state(q, corpus, item_ids)
 
@@ -1012,6 +1092,12 @@ class TwoTowerTrainer:
                 sd["title_accum"] = self.title_accum
             if self.cfg.optimizer == "adam":
                 sd.update(title_m=self.title_m, title_v=self.title_v)
+        if getattr(self, "history_table", None) is not None:
+            sd.update(history_table=self.history_table, user_history=self.user_history)
+            if self.cfg.optimizer == "adagrad":
+                sd["history_accum"] = self.history_accum
+            if self.cfg.optimizer == "adam":
+                sd.update(history_m=self.history_m, history_v=self.history_v)
         if self.cfg.optimizer == "adagrad":
             sd.update(user_accum=self.user_accum, item_accum=self.item_accum, dense_accum=self.dense_accum)
             if self.cat_table is not None:
@@ -1031,6 +1117,13 @@ class TwoTowerTrainer:
         if sd["config"].get("n_title_buckets", 0) != self.cfg.n_title_buckets:
             raise ValueError(f"checkpoint n_title_buckets={sd['config'].get('n_title_buckets', 0)!r} does not match the trainer's "
                              f"{self.cfg.n_title_buckets!r}")
+        # likewise the history feature: a checkpoint from before it existed has no key and loads into a trainer without it
+        if sd["config"].get("user_history_len", 0) != self.cfg.user_history_len:
+            raise ValueError(f"checkpoint user_history_len={sd['config'].get('user_history_len', 0)!r} does not match the trainer's "
+                             f"{self.cfg.user_history_len!r}")
+        if self.cfg.user_history_len and sd["config"].get("history_pooling", "mean") != self.cfg.history_pooling:
+            raise ValueError(f"checkpoint history_pooling={sd['config'].get('history_pooling')!r} does not match the trainer's "
+                             f"{self.cfg.history_pooling!r}")
         if self.title_table is not None:
             for k in ("title_max_tokens", "title_pooling"):
                 if sd["config"].get(k) != getattr(self.cfg, k):
@@ -1040,6 +1133,12 @@ class TwoTowerTrainer:
                 self.title_accum.copy_(sd["title_accum"])
             if self.cfg.optimizer == "adam":
                 self.title_m.copy_(sd["title_m"]); self.title_v.copy_(sd["title_v"])
+        if self.history_table is not None:
+            self.history_table.copy_(sd["history_table"]); self.user_history.copy_(sd["user_history"])
+            if self.cfg.optimizer == "adagrad":
+                self.history_accum.copy_(sd["history_accum"])
+            if self.cfg.optimizer == "adam":
+                self.history_m.copy_(sd["history_m"]); self.history_v.copy_(sd["history_v"])
         self.user_table.copy_(sd["user_table"]); self.item_table.copy_(sd["item_table"]); self.dense_flat.copy_(sd["dense"])
         # whether the embeddings are normalised belongs to the trained model, not to the run that loads it: the checkpoint's
         # value replaces the trainer's (a checkpoint from before the switch existed: off)
@@ -1081,6 +1180,9 @@ class TwoTowerTrainer:
         if self.cfg.n_title_buckets:
             raise NotImplementedError("graph replay with the title feature (n_title_buckets > 0) is not implemented: the warm-up "
                                       "step's update of the title table is not undone")
+        if self.cfg.user_history_len:
+            raise NotImplementedError("graph replay with the user-history feature (user_history_len > 0) is not implemented: the "
+                                      "warm-up step's update of the history table is not undone")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
