@@ -48,8 +48,8 @@ int tt_abi_version(void);
 const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
  * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args,
- * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper; else - 9 included, which stays unassigned - -1): a binding checks its
- * mirrors with it. */
+ * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args, 15 tt_dense_features_bwd_args; else - 9 and
+ * 13 included, which stay unassigned - -1): a binding checks its mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
 /* ---------------------------------------------------------------------------------------
@@ -62,7 +62,8 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * the scope ivf around a whole tt_ivf_search_f32 call), quantize_i8, topk_i8_scan, topk_i8_rerank, topk_i8_scale (and the
  * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
- * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64).
+ * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
+ * features_fwd, features_bwd (tt_dense_features_*_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -422,6 +423,53 @@ int tt_l2_normalize_fwd_f32(const tt_l2norm_fwd_args* probs, int32_t n_probs, in
                             tt_stream_t stream);
 int tt_l2_normalize_bwd_f32(const tt_l2norm_bwd_args* probs, int32_t n_probs, int64_t rows, int32_t dim, float eps,
                             tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Dense numeric side features (added to v10: new symbols and structs only, the version is unchanged; csrc/features.hip) - the
+ * Normalization -> concat -> Dense branch of a TFRS query / candidate model.  A fixed [feat_rows, F] f32 matrix per tower
+ * (1 <= F <= 32); the row of the pair's id is normalised (Keras Normalization, with an optional clip), projected by a trained
+ * [F, dim] kernel and written to / added into the tower's input rows:
+ *   z_f      = clamp((x_f - mean_f) * inv_std_f, -clip, clip)          (no clamp when clip == 0; z_f = x_f with mean == NULL)
+ *   acc_d    = 0;  for f = 0 .. F-1 ascending:  acc_d = acc_d + z_f * proj[f, d]
+ *   out[b,d] = accumulate ? out[b, d] + acc_d : acc_d
+ * every subtraction, product and sum a separate correctly rounded f32 operation in exactly this order (no fma): a NumPy f32
+ * restatement gives the same bits.  ids[b] == -1: the row contributes z = 0 (z_out row zero) and sets no flag; any other id
+ * outside [0, feat_rows) does the same and sets *oob_flag (may be NULL).  z_out [n, F] (may be NULL) keeps the normalised
+ * values for the backward pass.  Up to two problems (both towers) per launch, every one with its own n and F; `probs` is a
+ * HOST array.  TT_ERR_INVALID_ARG before any launch: n_probs outside 1..2, dim not a multiple of 4 in 4..1024, clip < 0,
+ * F outside 1..32, mean / inv_std given one without the other, a NULL feat / proj / out (ids with n > 0), proj / out not
+ * 16-byte aligned.  n == 0 in every problem: no launch, TT_OK.
+ * The features themselves are not trained; the projection's gradient is the backward entry:
+ *   dp_slabs[s, f, d] = sum of z[b, f] * dy[b, d] over the rows b of slab s = [s * R, min((s + 1) * R, n)), R = ceil(n / n_slabs)
+ * Every slab is written in full - one without rows as zeros - so the caller never pre-zeroes: the [n_slabs][F * dim] form
+ * tt_dense_seg / tt_adam_seg sum (slab_stride = F * dim).  tt_dense_features_num_slabs(n) is a host query for a slab count
+ * that keeps the launch parallel (128-row slabs, at most 64); any n_slabs in 1..65535 is accepted.  No atomics: bits depend
+ * on (n, n_slabs, dim) alone.  dy [n, dim] 16-byte aligned.                                                              */
+typedef struct tt_dense_features_fwd_args {
+  const float* feat;         /* [feat_rows, F]                                         */
+  int64_t feat_rows;
+  int32_t F;
+  int32_t accumulate;        /* 0: out = product; 1: out += product                   */
+  const int64_t* ids;        /* [n]                                                    */
+  int64_t n;
+  const float* mean;         /* [F] or NULL (then inv_std is NULL too)                 */
+  const float* inv_std;      /* [F] or NULL                                            */
+  const float* proj;         /* [F, dim]                                               */
+  float* out;                /* [n, dim]                                               */
+  float* z_out;              /* [n, F] or NULL                                         */
+} tt_dense_features_fwd_args;
+typedef struct tt_dense_features_bwd_args {
+  const float* z;            /* [n, F]: z_out of the forward launch                    */
+  const float* dy;           /* [n, dim]: gradient w.r.t. the tower's input rows       */
+  int64_t n;
+  int32_t F;
+  int32_t n_slabs;
+  float* dp_slabs;           /* [n_slabs, F, dim]                                      */
+} tt_dense_features_bwd_args;
+int tt_dense_features_fwd_f32(const tt_dense_features_fwd_args* probs, int32_t n_probs, int32_t dim, float clip,
+                              int32_t* oob_flag, tt_stream_t stream);
+int tt_dense_features_bwd_f32(const tt_dense_features_bwd_args* probs, int32_t n_probs, int32_t dim, tt_stream_t stream);
+int32_t tt_dense_features_num_slabs(int64_t n);
 
 /* Dense parameter update over up to TT_MAX_DENSE_SEGS segments in one launch.
  *   g = sum_s grad_slabs[s*slab_stride + i] (s ascending) + 2*l2*w[i]

@@ -110,8 +110,22 @@ class AdamHyper(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int64)]
 
 
-# tt_abi_struct_bytes index of each mirror (9 is unassigned: the library answers -1 for it)
+class DenseFeaturesFwdArgs(C.Structure):
+    """Mirror of ``tt_dense_features_fwd_args`` (one problem of ``tt_dense_features_fwd_f32``)."""
+    _fields_ = [("feat", C.c_void_p), ("feat_rows", C.c_int64), ("F", C.c_int32), ("accumulate", C.c_int32),
+                ("ids", C.c_void_p), ("n", C.c_int64), ("mean", C.c_void_p), ("inv_std", C.c_void_p), ("proj", C.c_void_p),
+                ("out", C.c_void_p), ("z_out", C.c_void_p)]
+
+
+class DenseFeaturesBwdArgs(C.Structure):
+    """Mirror of ``tt_dense_features_bwd_args`` (one problem of ``tt_dense_features_bwd_f32``)."""
+    _fields_ = [("z", C.c_void_p), ("dy", C.c_void_p), ("n", C.c_int64), ("F", C.c_int32), ("n_slabs", C.c_int32),
+                ("dp_slabs", C.c_void_p)]
+
+
+# tt_abi_struct_bytes index of each mirror (9 and 13 are unassigned: the library answers -1 for them)
 ABI_STRUCT_INDEX = {"AdamTable": 10, "AdamSeg": 11, "AdamHyper": 12}
+FEATURES_STRUCT_INDEX = {"DenseFeaturesFwdArgs": 14, "DenseFeaturesBwdArgs": 15}
 
 
 class TrainStep(C.Structure):
@@ -152,6 +166,9 @@ SIGNATURES = {
     "tt_embedding_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "tt_embedding_bag_bwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
     "tt_history_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "tt_dense_features_fwd_f32": (C.c_int, [C.POINTER(DenseFeaturesFwdArgs), _i32, _i32, _f, _p, _p]),
+    "tt_dense_features_bwd_f32": (C.c_int, [C.POINTER(DenseFeaturesBwdArgs), _i32, _i32, _p]),
+    "tt_dense_features_num_slabs": (_i32, [_i64]),
     "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),

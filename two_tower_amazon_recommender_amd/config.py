@@ -12,6 +12,23 @@ def load_yaml(path) -> dict:
         return yaml.safe_load(f)
 
 
+NUMERIC_FEATURE_SOURCES = ("none", "rating_stats")
+
+
+def numeric_features_from_dict(doc: dict) -> dict:
+    """{source, clip} of the optional ``model.features.numeric`` block (not in the reference's schema): ``source`` rating_stats -
+    the per-user / per-item rating count, mean, std, min, max of ``data.rating_features`` - or none; ``clip`` >= 0 clamps the
+    normalised values (0: no clipping)."""
+    block = (((doc.get("model") or {}).get("features") or {}).get("numeric")) or {}
+    source = str(block.get("source", "none") or "none").lower()
+    if source not in NUMERIC_FEATURE_SOURCES:
+        raise ValueError(f"model.features.numeric.source must be one of {NUMERIC_FEATURE_SOURCES}, got {source!r}")
+    clip = float(block.get("clip", 0.0))
+    if not clip >= 0.0:
+        raise ValueError("model.features.numeric.clip must be >= 0")
+    return {"source": source, "clip": clip}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -33,6 +50,9 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     title = (m.get("features") or {}).get("title") or {}
     # likewise model.features.history {max_items, pooling} - the pooled user-history feature
     hist = (m.get("features") or {}).get("history") or {}
+    # likewise model.features.numeric {source: rating_stats | none, clip} - the dense numeric side features (the column counts
+    # come from the data: train.py sets n_user_features / n_item_features once it has the matrices)
+    numeric = numeric_features_from_dict(doc)
     cfg = TwoTowerConfig(
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
@@ -44,6 +64,7 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         # not in the reference's schema (left open): an optional key beside retrieval.temperature
         normalize_embeddings=bool(rt.get("normalize_embeddings", False)),
         user_history_len=int(hist.get("max_items", 0)), history_pooling=str(hist.get("pooling", "mean")),
+        feature_clip=numeric["clip"],
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
         title_pooling=str(title.get("pooling", "mean")))
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),

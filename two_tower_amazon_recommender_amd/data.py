@@ -119,6 +119,65 @@ def user_histories(user_idx: np.ndarray, item_idx: np.ndarray, n_users: int, max
     return out
 
 
+RATING_COLUMN = "rating"        # prepare_training_data.py:96-98: every interaction carries its rating
+
+
+def read_ratings(path):
+    """The ``rating`` column of the interaction file as float64 [n_rows] (nulls: NaN), or None when the file has no such column."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    import pyarrow.parquet as pq
+    if RATING_COLUMN not in pq.read_schema(path).names:
+        return None
+    col = pq.read_table(path, columns=[RATING_COLUMN]).column(RATING_COLUMN).combine_chunks()
+    return pc.fill_null(pc.cast(col, pa.float64()), float("nan")).to_numpy(zero_copy_only=False).astype(np.float64, copy=False)
+
+
+def _rating_stats(idx: np.ndarray, rating: np.ndarray, n_rows: int) -> np.ndarray:
+    """f64 [n_rows, 5]: count, mean, std (ddof 1), min, max of ``rating`` per value of ``idx``, rounded to 3 decimals; NaN where
+    the statistic does not exist (no rating: all but the count; one rating: the std).  One lexsort and bincounts."""
+    out = np.full((n_rows, 5), np.nan)
+    cnt = np.bincount(idx, minlength=n_rows)
+    out[:, 0] = cnt
+    has = cnt > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.bincount(idx, weights=rating, minlength=n_rows) / cnt
+        dev = rating - mean[idx]
+        std = np.sqrt(np.bincount(idx, weights=dev * dev, minlength=n_rows) / (cnt - 1))
+    out[:, 1] = mean
+    out[cnt > 1, 2] = std[cnt > 1]
+    order = np.lexsort((rating, idx))                                     # by id, the ratings ascending inside
+    r = rating[order]
+    end = np.cumsum(cnt)
+    out[has, 3] = r[(end - cnt)[has]]
+    out[has, 4] = r[(end - 1)[has]]
+    return np.round(out, 3)
+
+
+def rating_features(user_idx, item_idx, rating, n_users: int, n_items: int) -> tuple[np.ndarray, np.ndarray]:
+    """The reference's engineered rating columns (src/data/preprocessor.py create_user_features / create_item_features:
+    ``groupby(id)["rating"].agg(["count", "mean", "std", "min", "max"]).round(3)``) as the numeric side features of the two
+    towers: (user [n_users, 5], item [n_items, 5]) f32, columns count, mean, std, min, max.  Pass the TRAINING pairs only.  Pairs
+    whose rating is not finite are left out.  An id with no rating has count 0; every entry that does not exist (its other
+    columns, the std of a single rating) takes its column's mean over the entries that do - so its normalised value is 0 -
+    or 0 when the column has none."""
+    user_idx, item_idx, rating = np.asarray(user_idx), np.asarray(item_idx), np.asarray(rating, dtype=np.float64)
+    if not (len(user_idx) == len(item_idx) == len(rating)):
+        raise ValueError("user_idx, item_idx and rating differ in length")
+    keep = np.isfinite(rating)
+    user_idx, item_idx, rating = user_idx[keep], item_idx[keep], rating[keep]
+    outs = []
+    for idx, rows, name in ((user_idx, n_users, "user_idx"), (item_idx, n_items, "item_idx")):
+        if len(idx) and (idx.min() < 0 or idx.max() >= rows):
+            raise ValueError(f"{name} outside [0, {rows})")
+        st = _rating_stats(idx.astype(np.int64), rating, rows)
+        finite = np.isfinite(st)
+        with np.errstate(invalid="ignore"):
+            fill = np.where(finite.any(axis=0), np.where(finite, st, 0.0).sum(axis=0) / np.maximum(finite.sum(axis=0), 1), 0.0)
+        outs.append(np.where(finite, st, fill[None, :]).astype(np.float32))
+    return outs[0], outs[1]
+
+
 TITLE_COLUMN = "title"          # prepare_training_data.py:52-62: every interaction carries its item's title
 _TOKEN = re.compile(r"[a-z0-9]+")
 

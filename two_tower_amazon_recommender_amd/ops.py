@@ -943,6 +943,118 @@ def l2_normalize_bwd(x, dy, out=None, eps: float = L2_NORMALIZE_EPS):
     return l2_normalize_bwd2((x,), (dy,), (out,), eps)[0]
 
 
+# ----------------------------------------------------------------------------- dense numeric side features
+MAX_DENSE_FEATURES = 32
+
+
+def dense_features(*problems, clip: float = 0.0, oob_flag: torch.Tensor | None = None):
+    """The numeric side-feature branch of a tower input (Keras Normalization -> Dense without bias) for one or two problems -
+    both towers - in ONE launch (``tt_dense_features_fwd_f32``).  Every problem is the tuple
+    ``(feat, ids, mean, inv_std, proj, out, accumulate, z_out)``: ``feat`` [rows, F] f32 (1 <= F <= 32), ``ids`` [n] int64,
+    ``mean`` / ``inv_std`` [F] f32 (both None: no normalisation), ``proj`` [F, dim] f32, ``out`` [n, dim] f32 (None: allocated;
+    must be given with ``accumulate``), ``z_out`` [n, F] f32 or None.
+    out[b] (+)= z(feat[ids[b]]) @ proj with z_f = clamp((x_f - mean_f) * inv_std_f, -clip, clip) (``clip`` 0: no clamp), every
+    f32 operation rounded on its own, the sum over f ascending from 0.  An id of -1 contributes z = 0; any other id out of
+    range does too and sets ``oob_flag`` (int32[1]).  Returns the tuple of the problems' ``out``."""
+    if len(problems) not in (1, 2):
+        raise ValueError("dense_features: one or two problems")
+    if oob_flag is not None:
+        _chk(oob_flag, torch.int32, "oob_flag")
+    arr = (_lib.DenseFeaturesFwdArgs * len(problems))()
+    outs, dim = [], None
+    for i, prob in enumerate(problems):
+        if len(prob) != 8:
+            raise ValueError("dense_features: a problem is (feat, ids, mean, inv_std, proj, out, accumulate, z_out)")
+        feat, ids, mean, inv_std, proj, out, accumulate, z_out = prob
+        _chk(feat, torch.float32, "feat", 2)
+        _chk(ids, torch.int64, "ids", 1)
+        _chk(proj, torch.float32, "proj", 2)
+        n, F = ids.numel(), feat.shape[1]
+        if proj.shape[0] != F:
+            raise RuntimeError(f"dense_features: proj must be [{F}, dim] (F = feat.shape[1]), got {tuple(proj.shape)}")
+        if dim is None:
+            dim = proj.shape[1]
+        if proj.shape[1] != dim:
+            raise RuntimeError("dense_features: every problem's proj needs the same dim")
+        if (mean is None) != (inv_std is None):
+            raise ValueError("dense_features: mean and inv_std are given both or neither")
+        for t, name in ((mean, "mean"), (inv_std, "inv_std")):
+            if t is not None:
+                _chk(t, torch.float32, name, 1)
+                if t.numel() != F:
+                    raise RuntimeError(f"dense_features: {name} must hold F = {F} entries, got {t.numel()}")
+        if out is None:
+            if accumulate:
+                raise ValueError("dense_features: accumulate=True adds into `out`, which must be given")
+            out = torch.empty((n, dim), dtype=torch.float32, device=feat.device)
+        _chk(out, torch.float32, "out", 2)
+        if tuple(out.shape) != (n, dim):
+            raise RuntimeError(f"dense_features: out must be [{n}, {dim}] (n, dim), got {tuple(out.shape)}")
+        if z_out is not None:
+            _chk(z_out, torch.float32, "z_out", 2)
+            if tuple(z_out.shape) != (n, F):
+                raise RuntimeError(f"dense_features: z_out must be [{n}, {F}] (n, F), got {tuple(z_out.shape)}")
+        arr[i] = _lib.DenseFeaturesFwdArgs(_p(feat), feat.shape[0], F, int(bool(accumulate)), _p(ids), n, _p(mean), _p(inv_std),
+                                           _p(proj), _p(out), _p(z_out))
+        outs.append(out)
+    _lib.check(_lib.load().tt_dense_features_fwd_f32(arr, len(problems), dim, float(clip), _p(oob_flag), _stream()),
+               "tt_dense_features_fwd_f32")
+    return tuple(outs)
+
+
+def dense_features_num_slabs(n: int) -> int:
+    """Slab count of ``dense_features_bwd`` for ``n`` rows (``tt_dense_features_num_slabs``, a host query)."""
+    return int(_lib.load().tt_dense_features_num_slabs(n))
+
+
+def dense_features_bwd(*problems):
+    """The projection kernels' gradients for one or two problems in ONE launch (``tt_dense_features_bwd_f32``).  Every problem is
+    ``(z, dy, dp_slabs)``: ``z`` [n, F] (the forward's ``z_out``), ``dy`` [n, dim] (the gradient w.r.t. the tower input rows),
+    ``dp_slabs`` [n_slabs, F, dim] (None: allocated with ``dense_features_num_slabs(n)`` slabs).  Slab s is written with the
+    sum of z[b, f] * dy[b, d] over its ceil(n / n_slabs) contiguous rows - every slab in full, an empty one as zeros: the form
+    ``make_dense_seg`` / ``make_adam_seg`` sum.  Returns the tuple of the problems' ``dp_slabs``."""
+    if len(problems) not in (1, 2):
+        raise ValueError("dense_features_bwd: one or two problems")
+    arr = (_lib.DenseFeaturesBwdArgs * len(problems))()
+    outs, dim = [], None
+    for i, prob in enumerate(problems):
+        if len(prob) != 3:
+            raise ValueError("dense_features_bwd: a problem is (z, dy, dp_slabs)")
+        z, dy, dp = prob
+        _chk(z, torch.float32, "z", 2)
+        _chk(dy, torch.float32, "dy", 2)
+        n, F = z.shape
+        if dim is None:
+            dim = dy.shape[1]
+        if tuple(dy.shape) != (n, dim):
+            raise RuntimeError(f"dense_features_bwd: dy must be [{n}, {dim}] (n, dim), got {tuple(dy.shape)}")
+        if dp is None:
+            dp = torch.empty((dense_features_num_slabs(n), F, dim), dtype=torch.float32, device=z.device)
+        _chk(dp, torch.float32, "dp_slabs", 3)
+        if tuple(dp.shape[1:]) != (F, dim) or dp.shape[0] < 1:
+            raise RuntimeError(f"dense_features_bwd: dp_slabs must be [n_slabs, {F}, {dim}], got {tuple(dp.shape)}")
+        arr[i] = _lib.DenseFeaturesBwdArgs(_p(z), _p(dy), n, F, dp.shape[0], _p(dp))
+        outs.append(dp)
+    _lib.check(_lib.load().tt_dense_features_bwd_f32(arr, len(problems), dim, _stream()), "tt_dense_features_bwd_f32")
+    return tuple(outs)
+
+
+def adapt_normalization(x):
+    """Keras ``Normalization.adapt`` over the rows of ``x`` [rows, F]: mean and variance of every column in f64, ``inv_std`` =
+    1 / max(sqrt(var), 1e-7); returns (mean [F], inv_std [F]) as f32 NumPy arrays.  Non-finite input raises."""
+    import numpy as np
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.ndim != 2 or a.shape[0] < 1:
+        raise ValueError(f"adapt_normalization: x must be [rows >= 1, F], got shape {tuple(a.shape)}")
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("adapt_normalization: x holds non-finite values")
+    mean = a.mean(axis=0)
+    var = ((a - mean) ** 2).mean(axis=0)
+    inv_std = 1.0 / np.maximum(np.sqrt(var), 1e-7)
+    return mean.astype(np.float32), inv_std.astype(np.float32)
+
+
 # ----------------------------------------------------------------------------- a3+a4 retrieval
 SCORER_PRECISIONS = ("f32", "bf16x3")
 

@@ -429,6 +429,10 @@ class ShardedTwoTowerTrainer:
             # the history table would have to be sharded and every bag's rows fetched from their owners
             raise NotImplementedError("the user-history feature (user_history_len > 0) is not implemented for the row-sharded "
                                       "trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "n_user_features", 0) or getattr(cfg, "n_item_features", 0):
+            # the projection kernels' gradients would join the dense all-reduce and the feature rows be fetched from their owners
+            raise NotImplementedError("the numeric side features (n_user_features / n_item_features > 0) are not implemented for "
+                                      "the row-sharded trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "candidate_sampling", "in_batch") != "in_batch":
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "

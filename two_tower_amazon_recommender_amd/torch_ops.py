@@ -9,6 +9,7 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
     rows = torch.ops.twotower.embedding_gather(table, ids)
     pooled = torch.ops.twotower.embedding_bag(table, tokens, bag_rows, "mean")
     x = torch.ops.twotower.history_bag(hist_table, histories, user_ids, item_ids, user_table, user_ids, "mean")
+    x = x + torch.ops.twotower.dense_features(feat, ids, mean, inv_std, proj, clip)   # autograd w.r.t. proj
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
     torch.ops.twotower.sparse_adam_(table, exp_avg, exp_avg_sq, grads, ids, step, lr, 0.9, 0.999, 1e-7)
@@ -485,6 +486,55 @@ def _l2_backward(ctx, dy):
 l2_normalize.register_autograd(_l2_backward, setup_context=_l2_setup)
 
 
+# --------------------------------------------------------------------------------------------- dense numeric side features
+@torch.library.custom_op(f"{NS}::dense_features", mutates_args=(), device_types="cuda")
+def dense_features(feat: Tensor, ids: Tensor, mean: Optional[Tensor], inv_std: Optional[Tensor], proj: Tensor,
+                   clip: float = 0.0) -> Tensor:
+    """out[b] = z(feat[ids[b]]) @ proj, z = clamp((x - mean) * inv_std, -clip, clip) (``ops.dense_features``: the numeric side
+    features of a tower input; ``mean`` / ``inv_std`` both None: no normalisation).  Autograd with respect to ``proj`` only,
+    through ``twotower::dense_features_bwd``: the features are data, not parameters."""
+    c = lambda t: None if t is None else t.contiguous()
+    return ops.dense_features((feat.contiguous(), ids.contiguous(), c(mean), c(inv_std), proj.contiguous(), None, False, None),
+                              clip=clip)[0]
+
+
+@dense_features.register_fake
+def _(feat, ids, mean, inv_std, proj, clip=0.0):
+    return proj.new_empty((ids.shape[0], proj.shape[1]))
+
+
+@torch.library.custom_op(f"{NS}::dense_features_bwd", mutates_args=(), device_types="cuda")
+def dense_features_bwd(feat: Tensor, ids: Tensor, mean: Optional[Tensor], inv_std: Optional[Tensor], proj: Tensor, dy: Tensor,
+                       clip: float = 0.0) -> Tensor:
+    """dL/dproj [F, dim] of ``dense_features`` given dL/dout: the normalised features are recomputed by the forward launch (the
+    forward op keeps nothing but its inputs), the backward launch writes the slabs and the slabs are summed here."""
+    c = lambda t: None if t is None else t.contiguous()
+    z = torch.empty((ids.shape[0], feat.shape[1]), dtype=torch.float32, device=feat.device)
+    ops.dense_features((feat.contiguous(), ids.contiguous(), c(mean), c(inv_std), proj.contiguous(), None, False, z), clip=clip)
+    (slabs,) = ops.dense_features_bwd((z, dy.contiguous(), None))
+    return slabs.sum(dim=0)
+
+
+@dense_features_bwd.register_fake
+def _(feat, ids, mean, inv_std, proj, dy, clip=0.0):
+    return torch.empty_like(proj, memory_format=torch.contiguous_format)
+
+
+def _features_setup(ctx, inputs, output):
+    feat, ids, mean, inv_std, proj, clip = inputs
+    ctx.save_for_backward(feat, ids, mean, inv_std, proj)
+    ctx.clip = clip
+
+
+def _features_backward(ctx, dy):
+    feat, ids, mean, inv_std, proj = ctx.saved_tensors
+    dproj = torch.ops.twotower.dense_features_bwd(feat, ids, mean, inv_std, proj, dy, ctx.clip) if ctx.needs_input_grad[4] else None
+    return None, None, None, None, dproj, None
+
+
+dense_features.register_autograd(_features_backward, setup_context=_features_setup)
+
+
 # --------------------------------------------------------------------------------------------- a5 sparse optimizer
 @torch.library.custom_op(f"{NS}::sparse_update_", mutates_args=("table", "accum"), device_types="cuda")
 def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: Tensor, optimizer: str, lr: float,
@@ -512,4 +562,4 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
 
 
 OPS = ("embedding_gather", "embedding_bag", "history_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "sparse_update_", "sparse_adam_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "sparse_update_", "sparse_adam_")

@@ -76,6 +76,16 @@ def parse(argv=None):
                          "timestamp column where there is one) are pooled into the user tower input, the pair's own item left "
                          "out (overrides model.features.history.max_items); single-GPU trainer only")
     ap.add_argument("--history-pooling", default=None, choices=["sum", "mean", "sqrtn"], help="how the history rows are pooled (default mean)")
+    ap.add_argument("--side-features", default=None, choices=["none", "rating_stats"],
+                    help="add the dense numeric side features: rating_stats = every user's and every item's rating count / mean / "
+                         "std / min / max over the training pairs (column rating), normalised, projected by a trained kernel and "
+                         "added to the tower inputs (overrides model.features.numeric.source); single-GPU trainer only")
+    ap.add_argument("--feature-clip", type=float, default=None, metavar="C",
+                    help="clamp the normalised features to [-C, C] (0: no clipping; overrides model.features.numeric.clip)")
+    ap.add_argument("--user-features", default=None, metavar="FILE.npy",
+                    help="an external [n_users, F] f32 matrix (F in 1..32) of numeric user features; takes precedence over "
+                         "rating_stats on the user side")
+    ap.add_argument("--item-features", default=None, metavar="FILE.npy", help="likewise [n_items, F] for the item side")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -129,6 +139,10 @@ def main(argv=None) -> int:
     history_len = int(hist_cfg.get("max_items", 0)) if args.history_len is None else args.history_len
     if distributed and history_len:
         raise NotImplementedError("the user-history feature is not implemented for the row-sharded (--distributed) trainer")
+    numeric = cfgmod.numeric_features_from_dict(doc)
+    side_source = numeric["source"] if args.side_features is None else args.side_features
+    if distributed and (side_source != "none" or args.user_features or args.item_features):
+        raise NotImplementedError("the numeric side features are not implemented for the row-sharded (--distributed) trainer")
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -212,6 +226,27 @@ def main(argv=None) -> int:
         ts = None if args.synthetic else datamod.read_timestamps(args.data)
         histories = datamod.user_histories(user_idx[rows], item_idx[rows], n_users, cfg.user_history_len,
                                            None if ts is None else ts[rows])
+    # numeric side features: an external matrix per side, else the rating statistics of the TRAINING pairs
+    side_features = {"user": None, "item": None}
+    if side_source == "rating_stats" and not (args.user_features and args.item_features):
+        if args.synthetic:                  # synthetic interactions carry no rating: stars 1..5 from the run's seed
+            rating = np.random.default_rng(args.seed + 1).integers(1, 6, size=n).astype(np.float64)
+        else:
+            rating = datamod.read_ratings(args.data)
+            if rating is None:
+                raise SystemExit(f"--side-features rating_stats: {args.data} has no column {datamod.RATING_COLUMN!r}")
+        side_features["user"], side_features["item"] = datamod.rating_features(user_idx[tr_idx], item_idx[tr_idx], rating[tr_idx],
+                                                                               n_users, n_items)
+    for side, path, rows in (("user", args.user_features, n_users), ("item", args.item_features, n_items)):
+        if path:
+            x = np.load(path)
+            if x.ndim != 2 or x.shape[0] != rows or not 1 <= x.shape[1] <= 32:
+                raise SystemExit(f"--{side}-features: {path} must hold a [{rows}, 1..32] matrix, got shape {tuple(x.shape)}")
+            side_features[side] = x.astype(np.float32)
+    cfg.n_user_features = 0 if side_features["user"] is None else side_features["user"].shape[1]
+    cfg.n_item_features = 0 if side_features["item"] is None else side_features["item"].shape[1]
+    if args.feature_clip is not None:
+        cfg.feature_clip = args.feature_clip
     if distributed:
         # every rank computed the same split; it trains on every world-th pair, cut so all ranks run the same number
         # of (collective) steps
@@ -228,6 +263,10 @@ def main(argv=None) -> int:
         trainer = TwoTowerTrainer(cfg, args.device, seed=args.seed)
     if histories is not None:
         trainer.set_user_histories(torch.from_numpy(histories).to(trainer.dev))
+    if side_features["user"] is not None:       # the normalisation is adapted from the matrix (Keras Normalization.adapt)
+        trainer.set_user_features(side_features["user"])
+    if side_features["item"] is not None:
+        trainer.set_item_features(side_features["item"])
     if cfg.n_title_buckets:
         if args.synthetic:                  # tokens from the id generator
             trainer.set_item_titles(trainer.synthetic_item_titles(args.seed))

@@ -34,6 +34,8 @@ TID_USER_TABLE, TID_ITEM_TABLE, TID_USER_IDS, TID_ITEM_IDS = 1, 2, 3, 4
 TID_CATEGORY_TABLE, TID_CATEGORY_IDS = 5, 6
 TID_TITLE_TABLE, TID_TITLE_IDS, TID_TITLE_LENGTHS = 7, 8, 9
 TID_HISTORY_TABLE = 11
+TID_USER_FEATURE_PROJ, TID_ITEM_FEATURE_PROJ = 12, 13       # the projection kernels of the numeric side features
+TID_USER_FEATURES, TID_ITEM_FEATURES = 14, 15               # synthetic_user_features / synthetic_item_features
 TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of step s is element s * n_sampled_negatives + i
 TID_DENSE_BASE = 16
 TID_DROPOUT_BASE = 64
@@ -78,6 +80,15 @@ class TwoTowerConfig:
     n_sampled_negatives: int = 0
     negative_sampler: str = "uniform"
     unigram_power: float = 0.75
+    # dense numeric side features (the reference's create_user_features / create_item_features: per-id rating count / mean / std /
+    # min / max; TFRS Normalization -> concat -> Dense): a fixed [n_users, n_user_features] / [n_items, n_item_features] f32 matrix
+    # (``set_user_features`` / ``set_item_features``; 1..32 columns) whose row is normalised (Keras Normalization; clamped to
+    # [-feature_clip, feature_clip] when feature_clip > 0), projected by a trained [F, embedding_dim] kernel - no bias: the first
+    # Dense layer's plays that part - and ADDED to the tower's input.  0 = no such feature.  Single-GPU trainer, materialised
+    # tower inputs, no graph capture.
+    n_user_features: int = 0
+    n_item_features: int = 0
+    feature_clip: float = 0.0
     # pooled user-history feature (TFRS's context / sequential retrieval shape: Embedding over item ids ->
     # GlobalAveragePooling1D in the query model): every user carries its last user_history_len training items
     # (``set_user_histories``), their rows of a [n_items, embedding_dim] table of its own are pooled ("sum" | "mean" | "sqrtn") and
@@ -149,6 +160,12 @@ class TwoTowerConfig:
         if self.user_history_len and self.candidate_sampling == "mixed":
             raise ValueError("user_history_len > 0 with candidate_sampling='mixed' is not implemented: a sampled negative that "
                              "sits in the query's history is not left out")
+        for name in ("n_user_features", "n_item_features"):
+            f = getattr(self, name)
+            if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= ops.MAX_DENSE_FEATURES:
+                raise ValueError(f"{name} must be 0 (no numeric features) or an int in 1..{ops.MAX_DENSE_FEATURES}")
+        if not (self.feature_clip >= 0.0 and math.isfinite(self.feature_clip)):
+            raise ValueError("feature_clip must be a finite number >= 0 (0: no clipping)")
         if self.candidate_sampling not in ("in_batch", "mixed"):
             raise ValueError(f"candidate_sampling must be 'in_batch' or 'mixed', got {self.candidate_sampling!r}")
         if self.negative_sampler not in ("uniform", "unigram"):
@@ -351,7 +368,9 @@ class TwoTowerTrainer:
         self.user_accum = torch.full_like(self.user_table, cfg.adagrad_initial_accumulator) if adagrad else None
         self.item_accum = torch.full_like(self.item_table, cfg.adagrad_initial_accumulator) if adagrad else None
         n_user, n_item = Tower.param_count(cfg, cfg.user_dims), Tower.param_count(cfg, cfg.item_dims)
-        self.dense_flat = torch.zeros(n_user + n_item, device=dev)
+        # numeric side features: the two projection kernels sit BEHIND both towers' parameters (no existing offset moves)
+        fu, fi = cfg.n_user_features, cfg.n_item_features
+        self.dense_flat = torch.zeros(n_user + n_item + (fu + fi) * d, device=dev)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
         # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
@@ -414,6 +433,25 @@ class TwoTowerTrainer:
             self.history_ids = torch.empty(b * lh, dtype=torch.int64, device=dev)
             self.history_inv = torch.empty(b, device=dev)
             self.history_gs = torch.empty(b, d, device=dev) if cfg.history_pooling != "sum" else None
+        # numeric side features, per side: the fixed feature matrix with its normalisation (zeros / mean 0 / inv_std 1 until the
+        # setter ran: z = 0, nothing is added), the projection kernel (a view of dense_flat), the step's normalised rows (kept for
+        # the backward launch) and the gradient slabs the dense optimizer segment sums
+        self.user_features = self.user_feature_mean = self.user_feature_inv_std = self.P_user = self._fz_user = self._fslabs_user = None
+        self.item_features = self.item_feature_mean = self.item_feature_inv_std = self.P_item = self._fz_item = self._fslabs_item = None
+        self._feature_sides = []                 # (side, projection kernel, gradient slabs, slab count)
+        off = n_user + n_item
+        for side, f, rows, nb in (("user", fu, cfg.n_users, b), ("item", fi, cfg.n_items, bi)):
+            if not f:
+                continue
+            ns = ops.dense_features_num_slabs(nb)
+            setattr(self, f"{side}_features", torch.zeros(rows, f, device=dev))
+            setattr(self, f"{side}_feature_mean", torch.zeros(f, device=dev))
+            setattr(self, f"{side}_feature_inv_std", torch.ones(f, device=dev))
+            setattr(self, f"P_{side}", self.dense_flat[off:off + f * d].view(f, d))
+            setattr(self, f"_fz_{side}", torch.empty(nb, f, device=dev))
+            setattr(self, f"_fslabs_{side}", torch.empty(ns, f, d, device=dev))
+            self._feature_sides.append((side, getattr(self, f"P_{side}"), getattr(self, f"_fslabs_{side}"), ns))
+            off += f * d
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -432,6 +470,8 @@ class TwoTowerTrainer:
         if cfg.n_title_buckets:                  # the pooled titles are added to the materialised item-tower input (_item_inputs)
             self.fuse_lookup = False
         if cfg.user_history_len:                 # the user tower's input is one bag launch: user row + pooled history (_item_inputs)
+            self.fuse_lookup = False
+        if self._feature_sides:                  # the projected features are added to the materialised tower inputs (_add_features)
             self.fuse_lookup = False
         self.fuse_sort = os.environ.get("TT_FUSE_SORT", "1") != "0"   # the optimizer launch sorts the ids itself (no plan launch)
         self.fuse_optimizer = True               # sparse + dense optimizer in one launch (False: dense_update, sparse_update2 [, cat])
@@ -474,6 +514,15 @@ class TwoTowerTrainer:
                     for prm, slabs, reg in ((tower.w[l], tower.dw_slabs[l], cfg.l2_regularization), (tower.b[l], tower.db_slabs[l], 0.0)):
                         lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
                         self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, tower.n_slabs, reg))
+        for _, prm, slabs, ns in self._feature_sides:      # the projection kernels: Dense kernels like any other (l2 included)
+            lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
+            self._segs.append(ops.make_dense_seg(prm, None if self.dense_accum is None else self.dense_accum[lo:hi], slabs, ns,
+                                                 cfg.l2_regularization))
+            if adam:
+                self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, ns, cfg.l2_regularization))
+        if len(self._segs) > _lib.TT_MAX_DENSE_SEGS:
+            raise NotImplementedError(f"the numeric side features add one dense segment per side to the towers' {len(self._segs) - len(self._feature_sides)}: "
+                                      f"the optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
         if seed is not None:
             self.init_synthetic(seed)
 
@@ -496,6 +545,9 @@ class TwoTowerTrainer:
                 lim32 = lim.item()
                 scale32 = (lim + lim).item()
                 ops.fill_uniform_(w, seed, TID_DENSE_BASE + 2 * l + t, -lim32, scale32)
+        for side, w, _, _ in self._feature_sides:            # Glorot-uniform, like the Dense kernels
+            lim = torch.tensor(math.sqrt(6.0 / (w.shape[0] + w.shape[1])), dtype=torch.float64).to(torch.float32)
+            ops.fill_uniform_(w, seed, TID_USER_FEATURE_PROJ if side == "user" else TID_ITEM_FEATURE_PROJ, -lim.item(), (lim + lim).item())
         if self.cfg.optimizer == "adagrad":
             for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum, self.history_accum):
                 if a is not None:
@@ -553,6 +605,55 @@ class TwoTowerTrainer:
                              f"got {tokens.dtype} {list(tokens.shape)}")
         self.user_history.copy_(tokens)
 
+    def _synthetic_features(self, seed: int, tid: int, rows: int, f: int) -> torch.Tensor:
+        out = torch.empty(rows, f, device=self.dev)
+        if f:
+            ops.fill_uniform_(out, seed, tid, 0.0, 5.0)
+        return out
+
+    def synthetic_user_features(self, seed: int) -> torch.Tensor:
+        """A synthetic [n_users, n_user_features] f32 matrix, U(0, 5) from the counter-based generator (tensor id 14)."""
+        return self._synthetic_features(seed, TID_USER_FEATURES, self.cfg.n_users, self.cfg.n_user_features)
+
+    def synthetic_item_features(self, seed: int) -> torch.Tensor:
+        """A synthetic [n_items, n_item_features] f32 matrix, U(0, 5) from the counter-based generator (tensor id 15)."""
+        return self._synthetic_features(seed, TID_ITEM_FEATURES, self.cfg.n_items, self.cfg.n_item_features)
+
+    def _set_features(self, side: str, x, mean, inv_std):
+        import numpy as np
+        what = f"set_{side}_features"
+        dst = getattr(self, f"{side}_features")
+        if dst is None:
+            raise ValueError(f"{what}: the model has no numeric {side} features (cfg.n_{side}_features == 0)")
+        a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        if tuple(a.shape) != tuple(dst.shape):
+            raise ValueError(f"{what}: x must be {list(dst.shape)} (rows, n_{side}_features), got {list(a.shape)}")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError(f"{what}: x holds non-finite values")
+        if (mean is None) != (inv_std is None):
+            raise ValueError(f"{what}: mean and inv_std are given both or neither")
+        if mean is None:
+            mean, inv_std = ops.adapt_normalization(a)
+        stats = []
+        for t, name in ((mean, "mean"), (inv_std, "inv_std")):
+            t = np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t), dtype=np.float32).reshape(-1)
+            if t.size != a.shape[1] or not np.isfinite(t).all():
+                raise ValueError(f"{what}: {name} must hold {a.shape[1]} finite entries")
+            stats.append(t)
+        dst.copy_(torch.from_numpy(a))
+        getattr(self, f"{side}_feature_mean").copy_(torch.from_numpy(stats[0]))
+        getattr(self, f"{side}_feature_inv_std").copy_(torch.from_numpy(stats[1]))
+
+    def set_user_features(self, x, mean=None, inv_std=None):
+        """x [n_users, n_user_features]: every user's numeric features (finite; ``data.rating_features``).  ``mean`` / ``inv_std``
+        [F]: the normalisation's statistics; both None: adapted from x (``ops.adapt_normalization``, Keras Normalization.adapt)."""
+        self._set_features("user", x, mean, inv_std)
+
+    def set_item_features(self, x, mean=None, inv_std=None):
+        """x [n_items, n_item_features]: every item's numeric features; see ``set_user_features``."""
+        self._set_features("item", x, mean, inv_std)
+
     def set_item_frequencies(self, freq):
         """freq [n_items]: every item's probability of being an in-batch candidate (its share of the training pairs; train.py's
         ``--correct-sampling-bias`` vector).  Mixed negative sampling only: from the next step on the sampler launch writes every
@@ -607,6 +708,28 @@ class TwoTowerTrainer:
                         pooling=self.cfg.history_pooling, out=out, batch_ids=self.history_ids if keep else None,
                         inv=self.history_inv if keep else None, oob_flag=self.oob)
 
+    def _add_features(self, user=None, item=None, keep: bool = False):
+        """+ the projected numeric features, into materialised tower-input rows: ``user`` / ``item`` = (ids, rows) or None.  ONE
+        launch for the sides that have the feature; ``keep``: the normalised rows stay for the backward launch (train step)."""
+        probs = []
+        for side, arg in (("user", user), ("item", item)):
+            feat = getattr(self, f"{side}_features")
+            if feat is None or arg is None:
+                continue
+            ids, out = arg
+            z = getattr(self, f"_fz_{side}") if keep else None
+            probs.append((feat, ids, getattr(self, f"{side}_feature_mean"), getattr(self, f"{side}_feature_inv_std"),
+                          getattr(self, f"P_{side}"), out, True, z))
+        if probs:
+            ops.dense_features(*probs, clip=self.cfg.feature_clip, oob_flag=self.oob)
+
+    def _features_backward(self):
+        """The projection kernels' gradient slabs from the towers' input gradients (demb) and the kept normalised rows: one
+        launch for both sides, after the towers' backward."""
+        if self._feature_sides:
+            towers = {"user": self.user_tower, "item": self.item_tower}
+            ops.dense_features_bwd(*[(getattr(self, f"_fz_{side}"), towers[side].demb, slabs) for side, _, slabs, _ in self._feature_sides])
+
     def _item_inputs(self, user_ids, item_ids, category_ids, train: bool = False):
         """K1 as its own launch (fuse_lookup = False): both towers' input rows; the hashed category's row is summed
         into the item tower's input.  ``train``: the history bags leave out the pair's own item and keep what the update needs."""
@@ -622,6 +745,7 @@ class TwoTowerTrainer:
         if self.title_table is not None:     # + the pooled title rows of every pair's item; the slot tokens and scales stay for the update
             ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=self.cfg.title_pooling, out=it.acts[0],
                               accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
+        self._add_features((user_ids, ut.acts[0]), (item_ids, it.acts[0]), keep=train)
 
     def _outputs(self, *towers):
         """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
@@ -681,6 +805,7 @@ class TwoTowerTrainer:
         else:
             ut.backward(cfg.dropout_rate, lookup=lks[0])
             it.backward(cfg.dropout_rate, lookup=lks[1])
+        self._features_backward()
         self.step_index += 1
         return self.loss
 
@@ -719,6 +844,7 @@ class TwoTowerTrainer:
             if self.title_table is not None:
                 ops.embedding_bag(self.title_table, self.item_titles, bag_rows=cand, pooling=cfg.title_pooling, out=it.acts[0],
                                   accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
+            self._add_features((user_ids, ut.acts[0]), (cand, it.acts[0]), keep=True)   # cand_ids: the sampled rows too
         # the dropout streams count rows per tower: consecutive steps never share a position
         ut.forward((cfg.dropout_rate, self.dropout_seed, 0, self.step_index * ut.rows), lookup=lk_u)
         it.forward((cfg.dropout_rate, self.dropout_seed, 1, self.step_index * it.rows), lookup=lk_i)
@@ -732,6 +858,7 @@ class TwoTowerTrainer:
             ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
         ut.backward(cfg.dropout_rate, lookup=lk_u)
         it.backward(cfg.dropout_rate, lookup=lk_i)
+        self._features_backward()
         self.step_index += 1
         return self.loss
 
@@ -1002,6 +1129,7 @@ class TwoTowerTrainer:
             if self.title_table is not None:
                 ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=cfg.title_pooling,
                                   out=it.acts[0][:b], accumulate=True, oob_flag=self.oob)
+            self._add_features((user_ids, ut.acts[0]), (item_ids, it.acts[0][:b]))
             ut.forward()
             it.forward(rows=b)
             q, c = self._outputs_rows((ut, it), [b, b])
@@ -1039,6 +1167,8 @@ class TwoTowerTrainer:
             if self.title_table is not None:       # bag r of the chunk pools token row s + r
                 ops.embedding_bag(self.title_table, self.item_titles[s:e], pooling=self.cfg.title_pooling, out=it.acts[0][:e - s],
                                   accumulate=True, oob_flag=self.oob)
+            if self.item_features is not None:
+                self._add_features(item=(torch.arange(s, e, dtype=torch.int64, device=self.dev), it.acts[0][:e - s]))
             it.forward()
             out[s:e].copy_(self._outputs(it)[0][:e - s])
         return out
@@ -1059,6 +1189,7 @@ class TwoTowerTrainer:
                 self._user_inputs(ids[s:e], ut.acts[0][:e - s])
             else:
                 ops.embedding_gather(self.user_table, ids[s:e], out=ut.acts[0][:e - s], oob_flag=self.oob)
+            self._add_features(user=(ids[s:e], ut.acts[0][:e - s]))
             ut.forward()
             out[s:e].copy_(self._outputs(ut)[0][:e - s])
         return out
@@ -1070,8 +1201,12 @@ class TwoTowerTrainer:
         self._check_batch(user_ids, item_ids)
         if corpus is None:
             corpus = self.item_corpus_embeddings()
-        if self.history_table is not None:
-            self._user_inputs(user_ids, self.user_tower.acts[0])
+        if self.history_table is not None or self.user_features is not None:
+            if self.history_table is not None:
+                self._user_inputs(user_ids, self.user_tower.acts[0])
+            else:
+                ops.embedding_gather(self.user_table, user_ids, out=self.user_tower.acts[0], oob_flag=self.oob)
+            self._add_features(user=(user_ids, self.user_tower.acts[0]))
             self.user_tower.forward()
         else:
             self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
@@ -1098,6 +1233,9 @@ class TwoTowerTrainer:
                 sd["history_accum"] = self.history_accum
             if self.cfg.optimizer == "adam":
                 sd.update(history_m=self.history_m, history_v=self.history_v)
+        for side, _, _, _ in getattr(self, "_feature_sides", ()):    # the projection kernels are part of "dense" (and its state)
+            for k in (f"{side}_features", f"{side}_feature_mean", f"{side}_feature_inv_std"):
+                sd[k] = getattr(self, k)
         if self.cfg.optimizer == "adagrad":
             sd.update(user_accum=self.user_accum, item_accum=self.item_accum, dense_accum=self.dense_accum)
             if self.cat_table is not None:
@@ -1113,6 +1251,11 @@ class TwoTowerTrainer:
         for k in ("n_users", "n_items", "embedding_dim", "tower_dims", "item_tower_dims", "optimizer", "n_category_buckets"):
             if sd["config"].get(k, 0 if k == "n_category_buckets" else None) != getattr(self.cfg, k):
                 raise ValueError(f"checkpoint {k}={sd['config'].get(k)!r} does not match the trainer's {getattr(self.cfg, k)!r}")
+        # the numeric side features: a checkpoint from before they existed has no key and loads into a trainer without them
+        for k in ("n_user_features", "n_item_features"):
+            if sd["config"].get(k, 0) != getattr(self.cfg, k):
+                raise ValueError(f"checkpoint {k}={sd['config'].get(k, 0)!r} does not match the trainer's {getattr(self.cfg, k)!r}: "
+                                 "the numeric side features (and their projection kernels in 'dense') belong to the trained model")
         # a checkpoint from before the title feature existed has none: it loads into a trainer without it, as before
         if sd["config"].get("n_title_buckets", 0) != self.cfg.n_title_buckets:
             raise ValueError(f"checkpoint n_title_buckets={sd['config'].get('n_title_buckets', 0)!r} does not match the trainer's "
@@ -1140,6 +1283,11 @@ class TwoTowerTrainer:
             if self.cfg.optimizer == "adam":
                 self.history_m.copy_(sd["history_m"]); self.history_v.copy_(sd["history_v"])
         self.user_table.copy_(sd["user_table"]); self.item_table.copy_(sd["item_table"]); self.dense_flat.copy_(sd["dense"])
+        for side, _, _, _ in self._feature_sides:
+            for k in (f"{side}_features", f"{side}_feature_mean", f"{side}_feature_inv_std"):
+                getattr(self, k).copy_(sd[k])
+        if self._feature_sides:                  # the clip belongs to the trained model, like the normalisation switch below
+            self.cfg.feature_clip = float(sd["config"].get("feature_clip", 0.0))
         # whether the embeddings are normalised belongs to the trained model, not to the run that loads it: the checkpoint's
         # value replaces the trainer's (a checkpoint from before the switch existed: off)
         self.cfg.normalize_embeddings = bool(sd["config"].get("normalize_embeddings", False))
@@ -1183,6 +1331,9 @@ class TwoTowerTrainer:
         if self.cfg.user_history_len:
             raise NotImplementedError("graph replay with the user-history feature (user_history_len > 0) is not implemented: the "
                                       "warm-up step's update of the history table is not undone")
+        if self.cfg.n_user_features or self.cfg.n_item_features:
+            raise NotImplementedError("graph replay with the numeric side features (n_user_features / n_item_features > 0) is not "
+                                      "implemented: the step is the Python sequence of launches over materialised tower inputs")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
@@ -1309,4 +1460,6 @@ class TwoTowerTrainer:
         for tower in (self.user_tower, self.item_tower):
             for w in tower.w:
                 tot += (w.double() ** 2).sum()
+        for _, w, _, _ in self._feature_sides:
+            tot += (w.double() ** 2).sum()
         return self.cfg.l2_regularization * tot
