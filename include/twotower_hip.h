@@ -63,7 +63,7 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
  * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
- * features_fwd, features_bwd (tt_dense_features_*_f32).
+ * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -470,6 +470,40 @@ int tt_dense_features_fwd_f32(const tt_dense_features_fwd_args* probs, int32_t n
                               int32_t* oob_flag, tt_stream_t stream);
 int tt_dense_features_bwd_f32(const tt_dense_features_bwd_args* probs, int32_t n_probs, int32_t dim, tt_stream_t stream);
 int32_t tt_dense_features_num_slabs(int64_t n);
+
+/* ---------------------------------------------------------------------------------------
+ * Rating-prediction head (added to v10: new symbols only, the version is unchanged; csrc/rating.hip) - the tfrs.tasks.Ranking
+ * side of a joint retrieval + ranking model: one hidden ReLU layer over the pair's two tower outputs and a scalar output.
+ * D = the scorer dim (32, 64, 128 or 256), H = the hidden width (a multiple of 32 in 32..256), n pairs:
+ *   a[b,j]  = b1[j] + sum_i q[b,i] W1[i,j] + sum_i c[b,i] W1[D+i,j]      W1 [2D, H] row-major, b1 [H]
+ *   h[b,j]  = max(a[b,j], 0)                                             h [n, H] is kept for the backward launch
+ *   pred[b] = b2[0] + sum_j h[b,j] w2[j]                                 w2 [H], b2 [1]
+ * One launch, no labels (train step, validation and serving share it): exact f32 products on the f32-input MFMA, the A
+ * operand read straight from q and c (no [n, 2D] concat buffer), W1 streamed from global memory; a workgroup owns 32 rows
+ * and neither reads nor writes past row n.
+ * Backward, one launch, for the MSE loss L = (1/n) sum_valid w_b e_b^2 scaled by the caller (grad_scale = 2 rating_weight / n):
+ *   e_b = pred[b] - rating[b];  valid_b = isfinite(rating[b]) (NaN: a missing label);  w_b = sample_weight[b] (NULL: 1)
+ *   g_b = valid_b ? grad_scale w_b e_b : 0;      dh[b,j] = g_b w2[j] (h[b,j] > 0)     (built on the fly: never in HBM)
+ *   dq[b,:] (+)= sum_j dh[b,j] W1[0:D, j];       dc[b,:] (+)= sum_j dh[b,j] W1[D:2D, j]   (accumulate: 1 adds, 0 overwrites)
+ *   kslabs [n_slabs][2D H + H]:  dW1[i,j] = sum_b x[b,i] dh[b,j] (x = [q ; c], row-major), then dw2[j] = sum_b g_b h[b,j]
+ *   bslabs [n_slabs][H + 1]:     db1[j] = sum_b dh[b,j], then db2 = sum_b g_b
+ *   se_slabs [n_slabs]:          sum of w_b e_b^2 over the slab's valid rows (the caller forms the loss from these)
+ * Slab s owns the rows [s * R, min((s + 1) * R, n)), R = ceil(n / n_slabs); every slab is written in full - one without rows
+ * as zeros - so nothing is pre-zeroed: the form tt_dense_seg / tt_adam_seg sum (slab_stride = 2D H + H and H + 1).  Every row
+ * of dq / dc is touched by exactly one workgroup per 32-column block; no atomics: bits depend on (n, n_slabs, D, H) alone.
+ * An arbitrary upstream gradient g is expressed as pred = g, rating = 0, sample_weight = NULL, grad_scale = 1 (h is read
+ * separately).  tt_rating_head_num_slabs(n) is a host query for a slab count that keeps the launch parallel (128-row slabs,
+ * at most 64; the launch has n_slabs * 2D / 32 workgroups).
+ * TT_ERR_INVALID_ARG before any launch: D not in {32, 64, 128, 256}, H not a multiple of 32 in 32..256, n < 0, n_slabs outside
+ * 1..65535, and with n > 0 a NULL pointer (sample_weight excepted) or q / c / h / W1 / w2 / dq / dc not 16-byte aligned.
+ * n == 0: no launch, TT_OK.                                                                                              */
+int tt_rating_head_fwd_f32(const float* q, const float* c, int64_t n, int32_t D, int32_t H, const float* w1,
+                           const float* b1, const float* w2, const float* b2, float* pred, float* h, tt_stream_t stream);
+int tt_rating_head_bwd_f32(const float* q, const float* c, const float* h, const float* pred, const float* rating,
+                           const float* sample_weight, float grad_scale, int64_t n, int32_t D, int32_t H,
+                           const float* w1, const float* w2, float* dq, float* dc, int32_t accumulate,
+                           float* kslabs, float* bslabs, float* se_slabs, int32_t n_slabs, tt_stream_t stream);
+int32_t tt_rating_head_num_slabs(int64_t n);
 
 /* Dense parameter update over up to TT_MAX_DENSE_SEGS segments in one launch.
  *   g = sum_s grad_slabs[s*slab_stride + i] (s ascending) + 2*l2*w[i]

@@ -169,6 +169,9 @@ SIGNATURES = {
     "tt_dense_features_fwd_f32": (C.c_int, [C.POINTER(DenseFeaturesFwdArgs), _i32, _i32, _f, _p, _p]),
     "tt_dense_features_bwd_f32": (C.c_int, [C.POINTER(DenseFeaturesBwdArgs), _i32, _i32, _p]),
     "tt_dense_features_num_slabs": (_i32, [_i64]),
+    "tt_rating_head_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "tt_rating_head_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _f, _i64, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _p]),
+    "tt_rating_head_num_slabs": (_i32, [_i64]),
     "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),

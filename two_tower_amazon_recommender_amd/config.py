@@ -29,6 +29,22 @@ def numeric_features_from_dict(doc: dict) -> dict:
     return {"source": source, "clip": clip}
 
 
+def ranking_from_dict(doc: dict) -> dict:
+    """{weight, hidden_dim} of the optional ``model.ranking`` block (not in the reference's schema): the rating-prediction head -
+    ``weight`` > 0 trains it beside the retrieval task (total = retrieval + weight * MSE on the rating), ``hidden_dim`` is its
+    hidden width (a multiple of 32 in 32..256).  Without the block: no head."""
+    import math
+    block = (doc.get("model") or {}).get("ranking") or {}
+    if not isinstance(block, dict):
+        raise ValueError("model.ranking must be a mapping {weight, hidden_dim}")
+    weight, hidden = block.get("weight", 0.0), block.get("hidden_dim", 128)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not (weight >= 0.0 and math.isfinite(weight)):
+        raise ValueError(f"model.ranking.weight must be a finite number >= 0, got {weight!r}")
+    if isinstance(hidden, bool) or not isinstance(hidden, int) or not (32 <= hidden <= 256 and hidden % 32 == 0):
+        raise ValueError(f"model.ranking.hidden_dim must be a multiple of 32 in 32..256, got {hidden!r}")
+    return {"weight": float(weight), "hidden_dim": hidden}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -53,6 +69,8 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     # likewise model.features.numeric {source: rating_stats | none, clip} - the dense numeric side features (the column counts
     # come from the data: train.py sets n_user_features / n_item_features once it has the matrices)
     numeric = numeric_features_from_dict(doc)
+    # likewise model.ranking {weight, hidden_dim} - the rating-prediction head beside the retrieval task
+    ranking = ranking_from_dict(doc)
     cfg = TwoTowerConfig(
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
@@ -64,7 +82,7 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         # not in the reference's schema (left open): an optional key beside retrieval.temperature
         normalize_embeddings=bool(rt.get("normalize_embeddings", False)),
         user_history_len=int(hist.get("max_items", 0)), history_pooling=str(hist.get("pooling", "mean")),
-        feature_clip=numeric["clip"],
+        feature_clip=numeric["clip"], rating_weight=ranking["weight"], rating_hidden=ranking["hidden_dim"],
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
         title_pooling=str(title.get("pooling", "mean")))
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),

@@ -230,7 +230,7 @@ class BatchIterator:
     of an epoch is dropped (the kernels' buffers are sized for one batch size)."""
 
     def __init__(self, user_idx: np.ndarray, item_idx: np.ndarray, batch_size: int, device, seed: int = 42, shuffle=True,
-                 category_bucket: np.ndarray | None = None):
+                 category_bucket: np.ndarray | None = None, ratings: np.ndarray | None = None):
         if len(user_idx) != len(item_idx):
             raise ValueError("user_idx and item_idx differ in length")
         if category_bucket is not None and len(category_bucket) != len(user_idx):
@@ -239,6 +239,10 @@ class BatchIterator:
         self.i = torch.from_numpy(np.ascontiguousarray(item_idx)).to(device)
         # with a category column the iterator yields (user, item, category bucket) triples
         self.c = None if category_bucket is None else torch.from_numpy(np.ascontiguousarray(category_bucket)).to(device)
+        # with ratings (the rating head's labels; NaN = none) every batch carries a trailing f32 [batch] entry
+        if ratings is not None and len(ratings) != len(user_idx):
+            raise ValueError("ratings and user_idx differ in length")
+        self.r = None if ratings is None else torch.from_numpy(np.ascontiguousarray(ratings, dtype=np.float32)).to(device)
         self.batch_size, self.shuffle = batch_size, shuffle
         # the epoch's permutation is drawn ON THE DEVICE (r04): torch.randperm of 5.9 M indices on the host took ~0.1 s of a
         # 0.53 s epoch of 720 cfg3-sized steps - the CLI reported 11.2 M pairs/s for a step loop that runs at 14.0 M
@@ -250,14 +254,16 @@ class BatchIterator:
 
     def __iter__(self):
         n = self.u.numel()
-        c = self.c
+        c, r = self.c, self.r
         if self.shuffle:
             perm = torch.randperm(n, generator=self.gen, device=self.u.device)
             u, i = self.u[perm], self.i[perm]
             c = None if c is None else c[perm]
+            r = None if r is None else r[perm]
         else:
             u, i = self.u, self.i
         b = self.batch_size
         for k in range(self.n_batches):
             sl = slice(k * b, (k + 1) * b)
-            yield (u[sl], i[sl]) if c is None else (u[sl], i[sl], c[sl])
+            batch = (u[sl], i[sl]) if c is None else (u[sl], i[sl], c[sl])
+            yield batch if r is None else batch + (r[sl],)

@@ -1039,6 +1039,90 @@ def dense_features_bwd(*problems):
     return tuple(outs)
 
 
+# ----------------------------------------------------------------------------- rating-prediction head
+RATING_DIMS = (32, 64, 128, 256)
+
+
+def _chk_rating_head(what: str, q, c, w1, w2):
+    _chk(q, torch.float32, "q", 2)
+    _chk(c, torch.float32, "c", 2)
+    _chk(w1, torch.float32, "W1", 2)
+    _chk(w2, torch.float32, "w2", 1)
+    n, d = q.shape
+    h = w2.numel()
+    if tuple(c.shape) != (n, d):
+        raise RuntimeError(f"{what}: q and c must have one shape [n, D], got {tuple(q.shape)} and {tuple(c.shape)}")
+    if tuple(w1.shape) != (2 * d, h):
+        raise RuntimeError(f"{what}: W1 must be [2 D, H] = [{2 * d}, {h}], got {tuple(w1.shape)}")
+    return n, d, h
+
+
+def rating_head(q, c, w1, b1, w2, b2, pred=None, h=None):
+    """The rating head's forward pass in ONE launch (``tt_rating_head_fwd_f32``): ``q``, ``c`` [n, D] (D in 32 / 64 / 128 / 256),
+    ``w1`` [2 D, H] (rows 0..D-1 multiply q, rows D..2D-1 multiply c; H a multiple of 32 in 32..256), ``b1`` [H], ``w2`` [H],
+    ``b2`` [1]:  h = relu(b1 + q @ w1[:D] + c @ w1[D:]),  pred = b2 + h @ w2.  Returns (pred [n], h [n, H]); both may be
+    given (views of longer buffers are fine: nothing past row n is touched)."""
+    n, d, hd = _chk_rating_head("rating_head", q, c, w1, w2)
+    _chk(b1, torch.float32, "b1", 1)
+    _chk(b2, torch.float32, "b2", 1)
+    if b1.numel() != hd or b2.numel() != 1:
+        raise RuntimeError(f"rating_head: b1 must hold H = {hd} entries and b2 one, got {b1.numel()} and {b2.numel()}")
+    pred = torch.empty(n, dtype=torch.float32, device=q.device) if pred is None else pred
+    h = torch.empty((n, hd), dtype=torch.float32, device=q.device) if h is None else h
+    _chk(pred, torch.float32, "pred", 1)
+    _chk(h, torch.float32, "h", 2)
+    if pred.numel() != n or tuple(h.shape) != (n, hd):
+        raise RuntimeError(f"rating_head: pred must be [{n}] and h [{n}, {hd}], got {tuple(pred.shape)} and {tuple(h.shape)}")
+    _lib.check(_lib.load().tt_rating_head_fwd_f32(_p(q), _p(c), n, d, hd, _p(w1), _p(b1), _p(w2), _p(b2), _p(pred), _p(h), _stream()),
+               "tt_rating_head_fwd_f32")
+    return pred, h
+
+
+def rating_head_num_slabs(n: int) -> int:
+    """Slab count of ``rating_head_bwd`` for ``n`` pairs (``tt_rating_head_num_slabs``, a host query)."""
+    return int(_lib.load().tt_rating_head_num_slabs(n))
+
+
+def rating_head_bwd(q, c, h, pred, rating, w1, w2, grad_scale: float, dq, dc, kslabs=None, bslabs=None, se_slabs=None,
+                    sample_weight=None, accumulate: bool = False, n_slabs: int | None = None):
+    """The rating head's backward pass for the MSE loss in ONE launch (``tt_rating_head_bwd_f32``).  With e = pred - rating
+    (a non-finite rating: a missing label, no gradient), w = sample_weight (None: 1) and g = grad_scale * w * e:
+    dq / dc [n, D] receive (``accumulate``: are added) the gradient w.r.t. q / c; ``kslabs`` [n_slabs, 2 D H + H] the slabs of
+    dW1 (row-major) followed by dw2, ``bslabs`` [n_slabs, H + 1] those of db1 followed by db2, ``se_slabs`` [n_slabs] the
+    slabs' sums of w e^2.  Slab s covers ceil(n / n_slabs) contiguous rows; every slab is written in full (an empty one as
+    zeros).  Buffers not given are allocated with ``n_slabs`` (default ``rating_head_num_slabs(n)``) slabs.
+    Returns (dq, dc, kslabs, bslabs, se_slabs)."""
+    n, d, hd = _chk_rating_head("rating_head_bwd", q, c, w1, w2)
+    _chk(h, torch.float32, "h", 2)
+    _chk(pred, torch.float32, "pred", 1)
+    _chk(rating, torch.float32, "rating", 1)
+    _chk(dq, torch.float32, "dq", 2)
+    _chk(dc, torch.float32, "dc", 2)
+    if tuple(h.shape) != (n, hd) or pred.numel() != n or rating.numel() != n:
+        raise RuntimeError(f"rating_head_bwd: h must be [{n}, {hd}], pred and rating [{n}]")
+    if tuple(dq.shape) != (n, d) or tuple(dc.shape) != (n, d):
+        raise RuntimeError(f"rating_head_bwd: dq and dc must be [{n}, {d}], got {tuple(dq.shape)} and {tuple(dc.shape)}")
+    if sample_weight is not None:
+        _chk(sample_weight, torch.float32, "sample_weight", 1)
+        if sample_weight.numel() != n:
+            raise RuntimeError(f"rating_head_bwd: sample_weight must hold n = {n} entries")
+    if n_slabs is None:
+        n_slabs = kslabs.shape[0] if kslabs is not None else rating_head_num_slabs(n)
+    ks = 2 * d * hd + hd
+    kslabs = torch.empty((n_slabs, ks), dtype=torch.float32, device=q.device) if kslabs is None else kslabs
+    bslabs = torch.empty((n_slabs, hd + 1), dtype=torch.float32, device=q.device) if bslabs is None else bslabs
+    se_slabs = torch.empty(n_slabs, dtype=torch.float32, device=q.device) if se_slabs is None else se_slabs
+    for t, name, shape in ((kslabs, "kslabs", (n_slabs, ks)), (bslabs, "bslabs", (n_slabs, hd + 1)), (se_slabs, "se_slabs", (n_slabs,))):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"rating_head_bwd: {name} must be {list(shape)}, got {list(t.shape)}")
+    _lib.check(_lib.load().tt_rating_head_bwd_f32(_p(q), _p(c), _p(h), _p(pred), _p(rating), _p(sample_weight), float(grad_scale),
+                                                  n, d, hd, _p(w1), _p(w2), _p(dq), _p(dc), int(bool(accumulate)),
+                                                  _p(kslabs), _p(bslabs), _p(se_slabs), int(n_slabs), _stream()),
+               "tt_rating_head_bwd_f32")
+    return dq, dc, kslabs, bslabs, se_slabs
+
+
 def adapt_normalization(x):
     """Keras ``Normalization.adapt`` over the rows of ``x`` [rows, F]: mean and variance of every column in f64, ``inv_std`` =
     1 / max(sqrt(var), 1e-7); returns (mean [F], inv_std [F]) as f32 NumPy arrays.  Non-finite input raises."""

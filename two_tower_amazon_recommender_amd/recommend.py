@@ -11,7 +11,9 @@ probed lists only, with the same re-rank).
         --all-users --exclude-seen --k 10 --out recs.parquet
 
 Output parquet: one row per (user, rank) with columns user_idx, rank (0 = best), item_idx, score.  A user with fewer
-than k unexcluded items gets fewer rows.
+than k unexcluded items gets fewer rows.  For a model trained with the rating head (``train.py --rating-weight``),
+``--predict-ratings`` adds the column predicted_rating - the head's prediction for every returned (user, item) - and
+``--rank-by rating`` re-orders each user's k retrieved items by it (retrieve, then rank; the item set is the retrieval's).
 """
 from __future__ import annotations
 
@@ -53,7 +55,14 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="--index ivf / ivf-int8: k-means seed")
     ap.add_argument("--rerank", type=int, default=None, help="--index int8 / ivf-int8: candidates re-scored exactly per user, as a multiple "
                                                               f"of --k (default 4; at least 32 and at most {MAX_K} candidates)")
+    ap.add_argument("--predict-ratings", action="store_true",
+                    help="add a predicted_rating column: the rating head's prediction for every returned (user, item); needs a "
+                         "checkpoint trained with --rating-weight")
+    ap.add_argument("--rank-by", choices=("score", "rating"), default="score",
+                    help="score: the retrieval order (default); rating: each user's k retrieved items re-ordered by the "
+                         "predicted rating, best first (implies --predict-ratings)")
     args = ap.parse_args(argv)
+    args.predict_ratings = args.predict_ratings or args.rank_by == "rating"
     if not 1 <= args.k <= MAX_K:
         ap.error(f"--k must be in [1, {MAX_K}], got {args.k}")
     if args.batch_users < 1:
@@ -119,6 +128,9 @@ def main(argv=None) -> int:
     if not isinstance(ck, dict) or "config" not in ck:
         raise SystemExit(f"{args.checkpoint}: not a checkpoint written by train.py --save (no 'config')")
     cfg = TwoTowerConfig(**ck["config"])
+    if args.predict_ratings and not cfg.rating_weight > 0:
+        raise SystemExit(f"{args.checkpoint}: the model has no rating head (trained without --rating-weight): "
+                         "--predict-ratings / --rank-by rating cannot be answered")
     cfg.dropout_rate = 0.0
     cfg.candidate_sampling, cfg.n_sampled_negatives = "in_batch", 0      # serving scores the whole corpus: nothing is sampled
     trainer = TwoTowerTrainer(cfg, dev)
@@ -160,6 +172,7 @@ def main(argv=None) -> int:
     seen = seen_csr(user_idx, item_idx, cfg.n_users) if args.exclude_seen else None
 
     cols = {"user_idx": [], "rank": [], "item_idx": [], "score": []}
+    group = []                          # the request position of every row's user (a user may be asked for twice)
     for s in range(0, len(users), args.batch_users):
         ub = users[s:s + args.batch_users]
         ut = torch.from_numpy(ub).to(dev)
@@ -174,8 +187,23 @@ def main(argv=None) -> int:
         cols["rank"].append(np.tile(np.arange(k, dtype=np.int32), (len(ub), 1))[keep])
         cols["item_idx"].append(items[keep])
         cols["score"].append(scores[keep])
+        group.append(np.repeat(np.arange(s, s + len(ub), dtype=np.int64), k).reshape(-1, k)[keep])
+    out = {name: np.concatenate(v) if v else np.zeros(0) for name, v in cols.items()}
+    if args.predict_ratings and len(out["user_idx"]):
+        ui, ii = torch.from_numpy(out["user_idx"]).to(dev), torch.from_numpy(out["item_idx"].astype(np.int64)).to(dev)
+        pred = trainer.predict_ratings(ui, ii, None if item_cat is None else item_cat[ii]).cpu().numpy()
+        out["predicted_rating"] = pred
+        if args.rank_by == "rating":    # inside every user's rows: best predicted rating first, ties in retrieval order
+            grp = np.concatenate(group)
+            order = np.lexsort((out["rank"], -pred.astype(np.float64), grp))
+            out = {name: v[order] for name, v in out.items()}
+            grp = grp[order]
+            first = np.flatnonzero(np.r_[True, grp[1:] != grp[:-1]])
+            out["rank"] = (np.arange(len(grp)) - np.repeat(first, np.diff(np.r_[first, len(grp)]))).astype(np.int32)
+    elif args.predict_ratings:
+        out["predicted_rating"] = np.zeros(0, dtype=np.float32)
     trainer.check_ids()
-    table = pa.table({name: np.concatenate(v) if v else np.zeros(0) for name, v in cols.items()})
+    table = pa.table(out)
     pq.write_table(table, args.out)
     log.info("wrote %d recommendations for %d users to %s", table.num_rows, len(users), args.out)
     return 0

@@ -433,6 +433,10 @@ class ShardedTwoTowerTrainer:
             # the projection kernels' gradients would join the dense all-reduce and the feature rows be fetched from their owners
             raise NotImplementedError("the numeric side features (n_user_features / n_item_features > 0) are not implemented for "
                                       "the row-sharded trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "rating_weight", 0.0) > 0:
+            # the head would have to run on the all-gathered candidates' owners and its gradients join the dense all-reduce
+            raise NotImplementedError("the rating head (rating_weight > 0) is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "candidate_sampling", "in_batch") != "in_batch":
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "

@@ -128,3 +128,43 @@ class Retrieval:
         return self._batch_metrics
 
     call = __call__
+
+
+class MeanSquaredError:
+    """Marker for ``tf.keras.losses.MeanSquaredError()`` (reduction SUM_OVER_BATCH_SIZE), the one loss ``Ranking`` implements."""
+
+
+class Ranking:
+    """A ranking task with the call signature of ``tfrs.tasks.Ranking``: ``task(labels, predictions, sample_weight=None)``
+    returns the scalar loss, here the mean squared error - mean over ALL n pairs (Keras SUM_OVER_BATCH_SIZE: the divisor is n)
+    of w (prediction - label)^2.  (Extension) a NaN label is a missing one: the pair contributes nothing, the divisor stays n.
+    The predictions come from ``torch.ops.twotower.rating_head`` (the HIP rating head, with autograd); the loss itself is
+    n elementwise operations in torch.  ``metrics`` takes objects with ``update_state(labels, predictions)``."""
+
+    def __init__(self, loss=None, metrics=None, name="ranking_task"):
+        if loss is not None and not isinstance(loss, MeanSquaredError):
+            raise NotImplementedError("Ranking(loss=...): only tasks.MeanSquaredError() is implemented")
+        self._metrics = list(metrics) if metrics is not None else []
+        for m in self._metrics:
+            if not hasattr(m, "update_state"):
+                raise TypeError("Ranking(metrics=...): every entry needs update_state(labels, predictions)")
+        self.name = name
+
+    def __call__(self, labels, predictions, sample_weight=None, compute_metrics=True):
+        labels = labels.to(predictions.dtype).reshape(-1)
+        predictions = predictions.reshape(-1)
+        if labels.numel() != predictions.numel():
+            raise RuntimeError(f"Ranking: {labels.numel()} labels for {predictions.numel()} predictions")
+        valid = torch.isfinite(labels)
+        e = torch.where(valid, predictions - torch.nan_to_num(labels), torch.zeros_like(predictions))
+        e2 = e * e
+        if sample_weight is not None:
+            e2 = e2 * sample_weight.to(predictions.dtype).reshape(-1)
+        loss = e2.sum() / max(predictions.numel(), 1)
+        if compute_metrics:
+            with torch.no_grad():
+                for m in self._metrics:
+                    m.update_state(labels, predictions.detach())
+        return loss
+
+    call = __call__

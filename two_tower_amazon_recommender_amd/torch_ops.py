@@ -535,6 +535,56 @@ def _features_backward(ctx, dy):
 dense_features.register_autograd(_features_backward, setup_context=_features_setup)
 
 
+# --------------------------------------------------------------------------------------------- rating-prediction head
+@torch.library.custom_op(f"{NS}::rating_head", mutates_args=(), device_types="cuda")
+def rating_head(q: Tensor, c: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor) -> Tensor:
+    """pred [n] = b2 + relu(b1 + q @ w1[:D] + c @ w1[D:]) @ w2 (``ops.rating_head``: one launch).  Autograd with respect to all
+    six inputs through ``twotower::rating_head_bwd``."""
+    return ops.rating_head(q.contiguous(), c.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous())[0]
+
+
+@rating_head.register_fake
+def _(q, c, w1, b1, w2, b2):
+    return q.new_empty((q.shape[0],))
+
+
+@torch.library.custom_op(f"{NS}::rating_head_bwd", mutates_args=(), device_types="cuda")
+def rating_head_bwd(q: Tensor, c: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor,
+                    grad_pred: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The six input gradients of ``rating_head`` given dL/dpred: h is recomputed by the forward launch (the forward op keeps
+    nothing but its inputs); the ONE backward launch takes the upstream gradient in the place of the error (pred = grad_pred,
+    rating = 0, grad_scale = 1: g = grad_pred exactly), and its slabs are summed here."""
+    q, c, w1, w2 = q.contiguous(), c.contiguous(), w1.contiguous(), w2.contiguous()
+    n, d = q.shape
+    hd = w2.numel()
+    _, h = ops.rating_head(q, c, w1, b1.contiguous(), w2, b2.contiguous())
+    dq, dc = torch.empty_like(q), torch.empty_like(c)
+    if n == 0:
+        z = lambda t: torch.zeros_like(t, memory_format=torch.contiguous_format)
+        return dq, dc, z(w1), z(b1), z(w2), z(b2)
+    _, _, ks, bs, _ = ops.rating_head_bwd(q, c, h, grad_pred.to(torch.float32).contiguous(), torch.zeros(n, device=q.device), w1, w2,
+                                          1.0, dq, dc)
+    ks, bs = ks.sum(dim=0), bs.sum(dim=0)
+    return dq, dc, ks[:2 * d * hd].view(2 * d, hd).clone(), bs[:hd].clone(), ks[2 * d * hd:].clone(), bs[hd:].clone()
+
+
+@rating_head_bwd.register_fake
+def _(q, c, w1, b1, w2, b2, grad_pred):
+    e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
+    return e(q), e(c), e(w1), e(b1), e(w2), e(b2)
+
+
+def _rating_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _rating_backward(ctx, grad_pred):
+    return torch.ops.twotower.rating_head_bwd(*ctx.saved_tensors, grad_pred)
+
+
+rating_head.register_autograd(_rating_backward, setup_context=_rating_setup)
+
+
 # --------------------------------------------------------------------------------------------- a5 sparse optimizer
 @torch.library.custom_op(f"{NS}::sparse_update_", mutates_args=("table", "accum"), device_types="cuda")
 def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: Tensor, optimizer: str, lr: float,
@@ -562,4 +612,4 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
 
 
 OPS = ("embedding_gather", "embedding_bag", "history_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "sparse_update_", "sparse_adam_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "sparse_update_", "sparse_adam_")

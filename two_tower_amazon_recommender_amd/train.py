@@ -86,6 +86,12 @@ def parse(argv=None):
                     help="an external [n_users, F] f32 matrix (F in 1..32) of numeric user features; takes precedence over "
                          "rating_stats on the user side")
     ap.add_argument("--item-features", default=None, metavar="FILE.npy", help="likewise [n_items, F] for the item side")
+    ap.add_argument("--rating-weight", type=float, default=None, metavar="W",
+                    help="add the rating-prediction head (joint retrieval + ranking): one hidden ReLU layer over the pair's two "
+                         "tower outputs trained with MSE on the rating column, total loss = retrieval + W * MSE (overrides "
+                         "model.ranking.weight; 0: no head); single-GPU trainer only")
+    ap.add_argument("--rating-hidden", type=int, default=None, metavar="H",
+                    help="hidden width of the rating head (a multiple of 32 in 32..256; default model.ranking.hidden_dim, else 128)")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -143,6 +149,17 @@ def main(argv=None) -> int:
     side_source = numeric["source"] if args.side_features is None else args.side_features
     if distributed and (side_source != "none" or args.user_features or args.item_features):
         raise NotImplementedError("the numeric side features are not implemented for the row-sharded (--distributed) trainer")
+    ranking = cfgmod.ranking_from_dict(doc)
+    rating_weight = ranking["weight"] if args.rating_weight is None else args.rating_weight
+    rating_hidden = ranking["hidden_dim"] if args.rating_hidden is None else args.rating_hidden
+    if not (rating_weight >= 0.0 and np.isfinite(rating_weight)):
+        raise SystemExit("--rating-weight must be a finite number >= 0")
+    if not (32 <= rating_hidden <= 256 and rating_hidden % 32 == 0):
+        raise SystemExit("--rating-hidden must be a multiple of 32 in 32..256")
+    if args.rating_hidden is not None and not rating_weight > 0:
+        raise SystemExit("--rating-hidden needs a rating head: --rating-weight W > 0 (or model.ranking.weight)")
+    if distributed and rating_weight > 0:
+        raise NotImplementedError("the rating head is not implemented for the row-sharded (--distributed) trainer")
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -188,6 +205,7 @@ def main(argv=None) -> int:
     cfg.normalize_embeddings = normalize
     cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = args.adam_beta1, args.adam_beta2, args.adam_epsilon
     cfg.n_title_buckets = title_buckets
+    cfg.rating_weight, cfg.rating_hidden = float(rating_weight), int(rating_hidden)
     if args.title_max_tokens is not None:
         cfg.title_max_tokens = args.title_max_tokens
     if args.title_pooling is not None:
@@ -228,13 +246,17 @@ def main(argv=None) -> int:
                                            None if ts is None else ts[rows])
     # numeric side features: an external matrix per side, else the rating statistics of the TRAINING pairs
     side_features = {"user": None, "item": None}
-    if side_source == "rating_stats" and not (args.user_features and args.item_features):
+    need_stats = side_source == "rating_stats" and not (args.user_features and args.item_features)
+    rating = None
+    if need_stats or cfg.rating_weight > 0:
         if args.synthetic:                  # synthetic interactions carry no rating: stars 1..5 from the run's seed
             rating = np.random.default_rng(args.seed + 1).integers(1, 6, size=n).astype(np.float64)
         else:
             rating = datamod.read_ratings(args.data)
             if rating is None:
-                raise SystemExit(f"--side-features rating_stats: {args.data} has no column {datamod.RATING_COLUMN!r}")
+                raise SystemExit(f"{'--rating-weight' if cfg.rating_weight > 0 else '--side-features rating_stats'}: {args.data} "
+                                 f"has no column {datamod.RATING_COLUMN!r}")
+    if need_stats:
         side_features["user"], side_features["item"] = datamod.rating_features(user_idx[tr_idx], item_idx[tr_idx], rating[tr_idx],
                                                                                n_users, n_items)
     for side, path, rows in (("user", args.user_features, n_users), ("item", args.item_features, n_items)):
@@ -279,9 +301,11 @@ def main(argv=None) -> int:
             dist.all_reduce(x)
         return x.item()
     train_it = datamod.BatchIterator(user_idx[tr_idx], item_idx[tr_idx], cfg.batch_size, trainer.dev, args.seed,
-                                     category_bucket=None if cat is None else cat[tr_idx])
+                                     category_bucket=None if cat is None else cat[tr_idx],
+                                     ratings=rating[tr_idx] if cfg.rating_weight > 0 else None)
     val_it = datamod.BatchIterator(user_idx[va_idx], item_idx[va_idx], cfg.batch_size, trainer.dev, args.seed, shuffle=False,
-                                   category_bucket=None if cat is None else cat[va_idx])
+                                   category_bucket=None if cat is None else cat[va_idx],
+                                   ratings=rating[va_idx] if cfg.rating_weight > 0 else None)
 
     item_prob = None
     mixed = cfg.candidate_sampling == "mixed"
@@ -297,7 +321,9 @@ def main(argv=None) -> int:
             item_prob = None
 
     def kw(batch):
-        k = {"category_ids": batch[2]} if len(batch) == 3 else {}
+        k = {"category_ids": batch[2]} if cat is not None else {}
+        if cfg.rating_weight > 0:           # the pairs' ratings ride behind the ids (NaN: no label)
+            k["ratings"] = batch[-1]
         if item_prob is not None:
             k["candidate_sampling_probability"] = item_prob[batch[1]]
         return k
@@ -310,6 +336,10 @@ def main(argv=None) -> int:
         if "early_stopping" in ck:
             stopper.load_state_dict(ck["early_stopping"])
         log.info("resumed from %s (epoch %d, step %d)", path, first_epoch, trainer.step_index)
+    if cfg.rating_weight > 0 and not args.resume:        # a fresh head starts from the constant predictor: the mean training rating
+        finite = rating[tr_idx][np.isfinite(rating[tr_idx])]
+        if finite.size:
+            trainer.init_rating_bias(float(finite.mean()))
     for epoch in range(first_epoch, epochs):
         t0 = time.perf_counter()
         tot = torch.zeros((), device=trainer.dev, dtype=torch.float64)
@@ -322,9 +352,15 @@ def main(argv=None) -> int:
                "pairs_per_sec": len(train_it) * cfg.batch_size * world / dt}
         if len(val_it) and (epoch + 1) % loop["validation_freq"] == 0:
             vt = torch.zeros((), device=trainer.dev, dtype=torch.float64)
+            vse = torch.zeros((), device=trainer.dev, dtype=torch.float64)
+            vcount = torch.zeros((), device=trainer.dev, dtype=torch.float64)
             for batch in val_it:
                 vt.add_(trainer.evaluate(batch[0], batch[1], **kw(batch)).view(()))
+                if cfg.rating_weight > 0:
+                    vse.add_(trainer.eval_rating_se); vcount.add_(trainer.eval_rating_count)
             rec["val_loss_per_pair"] = total(vt) / (len(val_it) * cfg.batch_size * world)
+            if cfg.rating_weight > 0:       # RMSE over the held-out pairs with a finite rating (early stopping stays on the loss above)
+                rec["val_rating_rmse"] = float(np.sqrt(vse.item() / max(vcount.item(), 1.0)))
             stop = stopper.update(rec["val_loss_per_pair"])
         else:
             stop = False

@@ -38,6 +38,7 @@ TID_USER_FEATURE_PROJ, TID_ITEM_FEATURE_PROJ = 12, 13       # the projection ker
 TID_USER_FEATURES, TID_ITEM_FEATURES = 14, 15               # synthetic_user_features / synthetic_item_features
 TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of step s is element s * n_sampled_negatives + i
 TID_DENSE_BASE = 16
+TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
 TID_DROPOUT_BASE = 64
 
 
@@ -80,6 +81,13 @@ class TwoTowerConfig:
     n_sampled_negatives: int = 0
     negative_sampler: str = "uniform"
     unigram_power: float = 0.75
+    # rating-prediction head (tfrs.tasks.Ranking beside tfrs.tasks.Retrieval): rating_weight > 0 adds one hidden ReLU layer of
+    # rating_hidden units (a multiple of 32 in 32..256) over the pair's two tower outputs - the vectors the scorer reads - and a
+    # scalar output trained with MSE on the interaction's rating: total = retrieval + rating_weight * L_r, L_r = mean over the
+    # batch of w (pred - rating)^2 (a NaN rating: no label).  0 = no head.  Single-GPU trainer, Python sequence of launches, no
+    # graph capture.
+    rating_weight: float = 0.0
+    rating_hidden: int = 128
     # dense numeric side features (the reference's create_user_features / create_item_features: per-id rating count / mean / std /
     # min / max; TFRS Normalization -> concat -> Dense): a fixed [n_users, n_user_features] / [n_items, n_item_features] f32 matrix
     # (``set_user_features`` / ``set_item_features``; 1..32 columns) whose row is normalised (Keras Normalization; clamped to
@@ -182,6 +190,12 @@ class TwoTowerConfig:
             raise ValueError("n_sampled_negatives must be 0 with candidate_sampling='in_batch'")
         if not (self.unigram_power >= 0.0 and math.isfinite(self.unigram_power)):
             raise ValueError("unigram_power must be a finite number >= 0")
+        if isinstance(self.rating_weight, bool) or not isinstance(self.rating_weight, (int, float)) \
+                or not (self.rating_weight >= 0.0 and math.isfinite(self.rating_weight)):
+            raise ValueError("rating_weight must be a finite number >= 0 (0: no rating head)")
+        h = self.rating_hidden
+        if isinstance(h, bool) or not isinstance(h, int) or not (32 <= h <= 256 and h % 32 == 0):
+            raise ValueError("rating_hidden must be a multiple of 32 in 32..256")
 
 
 class Tower:
@@ -370,7 +384,11 @@ class TwoTowerTrainer:
         n_user, n_item = Tower.param_count(cfg, cfg.user_dims), Tower.param_count(cfg, cfg.item_dims)
         # numeric side features: the two projection kernels sit BEHIND both towers' parameters (no existing offset moves)
         fu, fi = cfg.n_user_features, cfg.n_item_features
-        self.dense_flat = torch.zeros(n_user + n_item + (fu + fi) * d, device=dev)
+        # the rating head sits behind those again, W1 | w2 | b1 | b2 (the head-off layout is unchanged)
+        self.rating_on = cfg.rating_weight > 0
+        sd, rh = cfg.tower_dims[-1], cfg.rating_hidden
+        n_head = (2 * sd * rh + rh + rh + 1) if self.rating_on else 0
+        self.dense_flat = torch.zeros(n_user + n_item + (fu + fi) * d + n_head, device=dev)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
         # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
@@ -382,7 +400,6 @@ class TwoTowerTrainer:
         self.adam_step = 1
         self.user_tower = Tower(cfg, cfg.user_dims, self.dense_flat, self.dense_accum, 0, dev)
         self.item_tower = Tower(cfg, cfg.item_dims, self.dense_flat, self.dense_accum, n_user, dev, rows=bi)
-        sd = cfg.tower_dims[-1]
         self.ws = torch.empty(ops.retrieval_workspace_bytes(b, bi, sd), dtype=torch.uint8, device=dev)
         self.lse = torch.empty(b, device=dev)
         self.per_row = torch.empty(b, device=dev)
@@ -452,6 +469,25 @@ class TwoTowerTrainer:
             setattr(self, f"_fslabs_{side}", torch.empty(ns, f, d, device=dev))
             self._feature_sides.append((side, getattr(self, f"P_{side}"), getattr(self, f"_fslabs_{side}"), ns))
             off += f * d
+        # rating head: the four parameters (views of dense_flat), the step's predictions and hidden activations (kept for the
+        # backward launch) and the gradient slabs of the two dense segments (W1 | w2 with l2, b1 | b2 without)
+        self.W1_rating = self.w2_rating = self.b1_rating = self.b2_rating = None
+        self.rating_pred = self._r_h = self._r_kslabs = self._r_bslabs = self._r_se = None
+        self._r_slabs = 0
+        self.eval_rating_se = self.eval_rating_count = None
+        if self.rating_on:
+            nk = 2 * sd * rh
+            self.W1_rating = self.dense_flat[off:off + nk].view(2 * sd, rh)
+            self.w2_rating = self.dense_flat[off + nk:off + nk + rh]
+            self.b1_rating = self.dense_flat[off + nk + rh:off + nk + 2 * rh]
+            self.b2_rating = self.dense_flat[off + nk + 2 * rh:off + nk + 2 * rh + 1]
+            self._r_off = off
+            self._r_slabs = ns = ops.rating_head_num_slabs(b)
+            self.rating_pred = torch.zeros(b, device=dev)
+            self._r_h = torch.empty(b, rh, device=dev)
+            self._r_kslabs = torch.empty(ns, nk + rh, device=dev)
+            self._r_bslabs = torch.empty(ns, rh + 1, device=dev)
+            self._r_se = torch.zeros(ns, device=dev)
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -520,8 +556,21 @@ class TwoTowerTrainer:
                                                  cfg.l2_regularization))
             if adam:
                 self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, ns, cfg.l2_regularization))
+        n_tower_segs = len(self._segs) - len(self._feature_sides)
+        if self.rating_on:                       # two more Dense segments: the kernels W1 | w2 (l2 like any kernel) and the biases b1 | b2
+            nk = 2 * sd * rh + rh
+            for lo, hi, slabs, reg in ((self._r_off, self._r_off + nk, self._r_kslabs, cfg.l2_regularization),
+                                       (self._r_off + nk, self._r_off + nk + rh + 1, self._r_bslabs, 0.0)):
+                self._segs.append(ops.make_dense_seg(self.dense_flat[lo:hi], None if self.dense_accum is None else self.dense_accum[lo:hi],
+                                                     slabs, self._r_slabs, reg))
+                if adam:
+                    self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs,
+                                                             self._r_slabs, reg))
+        if len(self._segs) > _lib.TT_MAX_DENSE_SEGS and not self._feature_sides:
+            raise NotImplementedError(f"the rating head adds two dense segments to the towers' {n_tower_segs}: the optimizer launches "
+                                      f"take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
         if len(self._segs) > _lib.TT_MAX_DENSE_SEGS:
-            raise NotImplementedError(f"the numeric side features add one dense segment per side to the towers' {len(self._segs) - len(self._feature_sides)}: "
+            raise NotImplementedError(f"the numeric side features add one dense segment per side to the towers' {n_tower_segs}: "
                                       f"the optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
         if seed is not None:
             self.init_synthetic(seed)
@@ -548,6 +597,10 @@ class TwoTowerTrainer:
         for side, w, _, _ in self._feature_sides:            # Glorot-uniform, like the Dense kernels
             lim = torch.tensor(math.sqrt(6.0 / (w.shape[0] + w.shape[1])), dtype=torch.float64).to(torch.float32)
             ops.fill_uniform_(w, seed, TID_USER_FEATURE_PROJ if side == "user" else TID_ITEM_FEATURE_PROJ, -lim.item(), (lim + lim).item())
+        if self.rating_on:                                   # Glorot-uniform kernels (w2 as the [H, 1] kernel it is), zero biases
+            for w, tid, fan in ((self.W1_rating, TID_RATING_W1, sum(self.W1_rating.shape)), (self.w2_rating, TID_RATING_W2, self.w2_rating.numel() + 1)):
+                lim = torch.tensor(math.sqrt(6.0 / fan), dtype=torch.float64).to(torch.float32)
+                ops.fill_uniform_(w, seed, tid, -lim.item(), (lim + lim).item())
         if self.cfg.optimizer == "adagrad":
             for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum, self.history_accum):
                 if a is not None:
@@ -557,6 +610,15 @@ class TwoTowerTrainer:
             if a is not None:
                 a.zero_()
         self.adam_step = 1
+
+    def init_rating_bias(self, x: float):
+        """Sets the head's output bias b2 (train.py: the mean finite training rating, so that the head starts from the constant
+        predictor instead of 0)."""
+        if not self.rating_on:
+            raise ValueError("init_rating_bias: the model has no rating head (cfg.rating_weight == 0)")
+        if not math.isfinite(float(x)):
+            raise ValueError("init_rating_bias: x must be finite")
+        self.b2_rating.fill_(float(x))
 
     def synthetic_batch(self, seed: int, step: int, variant: str = "U", out=None):
         b = self.cfg.batch_size
@@ -772,14 +834,48 @@ class TwoTowerTrainer:
         return ys
 
     # ------------------------------------------------------------------ the hot path
+    def _check_ratings(self, ratings):
+        if self.rating_on and ratings is None:
+            raise ValueError("the model has a rating head (cfg.rating_weight > 0): pass ratings=<f32 [batch], NaN = no label>")
+        if not self.rating_on and ratings is not None:
+            raise ValueError("ratings were passed but the model has no rating head (cfg.rating_weight == 0)")
+        if ratings is not None:
+            ops._chk(ratings, torch.float32, "ratings", 1)
+            self._check_batch(ratings)
+
+    def _rating_forward(self, q, c, rows: int | None = None, pred=None):
+        """The head's forward launch over the first ``rows`` pairs of q / c (default: the batch); fills ``rating_pred`` / the kept h."""
+        n = self.cfg.batch_size if rows is None else rows
+        ops.rating_head(q[:n], c[:n], self.W1_rating, self.b1_rating, self.w2_rating, self.b2_rating,
+                        pred=self.rating_pred[:n] if pred is None else pred, h=self._r_h[:n])
+
+    def _rating_forward_backward(self, q, c, dq, dc, ratings, sample_weight):
+        """The head's two launches of the train step, right behind the scorer's: the forward over the vectors the scorer has
+        just read, the backward ADDING the head's gradient into the scorer's dq / dc (the first batch_size candidate rows) and
+        writing the slabs of the two dense segments and of the squared error."""
+        b = self.cfg.batch_size
+        self._rating_forward(q, c)
+        ops.rating_head_bwd(q[:b], c[:b], self._r_h, self.rating_pred, ratings, self.W1_rating, self.w2_rating,
+                            2.0 * self.cfg.rating_weight / b, dq[:b], dc[:b], self._r_kslabs, self._r_bslabs, self._r_se,
+                            sample_weight=sample_weight, accumulate=True)
+
+    @property
+    def rating_loss(self) -> torch.Tensor:
+        """L_r of the last train step: the mean over the batch (the divisor is batch_size, not the number of labels) of
+        w (pred - rating)^2 over the pairs with a finite rating; device scalar, unsynchronised, formed from the slabs on demand."""
+        if not self.rating_on:
+            raise ValueError("rating_loss: the model has no rating head (cfg.rating_weight == 0)")
+        return self._r_se.sum() / self.cfg.batch_size
+
     def forward_backward(self, user_ids: torch.Tensor, item_ids: torch.Tensor, sample_weight=None,
-                         candidate_sampling_probability=None, candidate_ids=None, category_ids=None):
+                         candidate_sampling_probability=None, candidate_ids=None, category_ids=None, ratings=None):
         cfg, ut, it = self.cfg, self.user_tower, self.item_tower
+        self._check_ratings(ratings)
         if self.mixed:
             if candidate_sampling_probability is not None or candidate_ids is not None or category_ids is not None:
                 raise ValueError("candidate_sampling='mixed': the trainer draws the candidates itself - candidate_ids, "
                                  "candidate_sampling_probability (set_item_frequencies) and category_ids cannot be passed")
-            return self._forward_backward_mixed(user_ids, item_ids, sample_weight)
+            return self._forward_backward_mixed(user_ids, item_ids, sample_weight, ratings=ratings)
         self._check_categories(category_ids)
         lks = self._lookups(user_ids, item_ids, category_ids)
         if lks is None:
@@ -798,6 +894,8 @@ class TwoTowerTrainer:
         # loss + dq + dc in two fused passes over the logits (probabilities never stored; f32: raw dot products kept in self.ws)
         ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
                               dq, dc, precision=cfg.scorer_precision, **kw)
+        if self.rating_on:
+            self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
         if cfg.normalize_embeddings:
             ops.l2_normalize_bwd2((ut.acts[-1], it.acts[-1]), (dq, dc), (ut.dz[-1], it.dz[-1]), cfg.normalize_eps)
         if cfg.symmetric:
@@ -825,7 +923,7 @@ class TwoTowerTrainer:
                               start=self.step_index * cfg.n_sampled_negatives, oob_flag=self.oob)
         return self.cand_ids
 
-    def _forward_backward_mixed(self, user_ids, item_ids, sample_weight=None, sampled: bool = False):
+    def _forward_backward_mixed(self, user_ids, item_ids, sample_weight=None, sampled: bool = False, ratings=None):
         """forward_backward with the item side over ``cand_ids`` (B + N rows): one launch sequence per tower, the scorer at
         [B] x [B + N] with the positive of query i at candidate i.  A sampled id equal to a row's own positive is a false
         negative: ``cand_ids`` always goes to the scorer, which masks it."""
@@ -853,6 +951,8 @@ class TwoTowerTrainer:
         ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
                               sample_weight=sample_weight, cand_prob=self.cand_prob if self.item_freq is not None else None,
                               cand_ids=cand, precision=cfg.scorer_precision)
+        if self.rating_on:                       # the pairs are the first batch_size candidate rows; the sampled rows get no head gradient
+            self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
         if cfg.normalize_embeddings:
             ops.l2_normalize_bwd2((ut.acts[-1],), (dq,), (ut.dz[-1],), cfg.normalize_eps)
             ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
@@ -865,7 +965,8 @@ class TwoTowerTrainer:
     def _run_plans_mixed(self, user_ids):
         ops.sparse_plan_batched([self.user_plan, self.item_plan], [user_ids, self.cand_ids], [self.cfg.n_users, self.cfg.n_items])
 
-    def _step_mixed(self, user_ids, item_ids, sample_weight=None, **other):
+    def _step_mixed(self, user_ids, item_ids, sample_weight=None, ratings=None, **other):
+        self._check_ratings(ratings)
         bad = [k for k, v in other.items() if v is not None]
         if bad:
             raise ValueError(f"candidate_sampling='mixed': the trainer draws the candidates itself - {', '.join(sorted(bad))} cannot "
@@ -875,7 +976,7 @@ class TwoTowerTrainer:
             self.poll_ids()
         self.sample_candidates(item_ids)          # in front of everything else: the plans and both lookups read cand_ids
         self._run_plans_mixed(user_ids)
-        loss = self._forward_backward_mixed(user_ids, item_ids, sample_weight, sampled=True)
+        loss = self._forward_backward_mixed(user_ids, item_ids, sample_weight, sampled=True, ratings=ratings)
         self.apply_gradients()
         return loss
 
@@ -984,6 +1085,9 @@ class TwoTowerTrainer:
         asymmetric towers take - with one launch after the towers' forward and one in front of their backward."""
         if self.mixed:
             return self._step_mixed(user_ids, item_ids, **loss_kw)
+        self._check_ratings(loss_kw.get("ratings"))
+        if not self.rating_on:
+            loss_kw.pop("ratings", None)
         self._check_batch(user_ids, item_ids, loss_kw.get("category_ids"), loss_kw.get("sample_weight"),
                           loss_kw.get("candidate_sampling_probability"), loss_kw.get("candidate_ids"))
         # (never inside a graph capture: the poll queries an event recorded outside it and would bake a D2H copy into every replay)
@@ -1004,7 +1108,7 @@ class TwoTowerTrainer:
         fused_sort = shape_ok and not self._skewed()
         if fused_sort:
             if (self.use_composite and self.fuse_lookup and self.cfg.symmetric and not self.cfg.normalize_embeddings
-                    and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
+                    and not self.rating_on and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
                 return self._step_composite(ids, **loss_kw)
             loss = self.forward_backward(user_ids, item_ids, **loss_kw)
             self.apply_gradients(step_ids=ids)
@@ -1118,6 +1222,8 @@ class TwoTowerTrainer:
     def evaluate(self, user_ids: torch.Tensor, item_ids: torch.Tensor, **loss_kw) -> torch.Tensor:
         """Forward only (validation loss, SUM over the batch); device tensor, unsynchronised."""
         cfg, ut, it = self.cfg, self.user_tower, self.item_tower
+        ratings = loss_kw.get("ratings")
+        self._check_ratings(ratings)
         self._check_categories(loss_kw.get("category_ids"))
         self._check_batch(loss_kw.get("sample_weight"), loss_kw.get("candidate_sampling_probability"),
                           loss_kw.get("candidate_ids"))
@@ -1133,6 +1239,8 @@ class TwoTowerTrainer:
             ut.forward()
             it.forward(rows=b)
             q, c = self._outputs_rows((ut, it), [b, b])
+            if self.rating_on:
+                self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
             return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
                                      sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
                                      cand_ids=loss_kw.get("candidate_ids"), precision=cfg.scorer_precision)
@@ -1143,10 +1251,58 @@ class TwoTowerTrainer:
         else:
             q, c = towers_forward(ut, it, lookups=lks) if cfg.symmetric else (ut.forward(lookup=lks[0]), it.forward(lookup=lks[1]))
         q, c = self._outputs(ut, it)
+        if self.rating_on:
+            self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
         kw = dict(sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
                   cand_ids=loss_kw.get("candidate_ids"))
         return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
                                  precision=cfg.scorer_precision, **kw)
+
+    def _rating_evaluate(self, q, c, ratings, sample_weight=None):
+        """The head's forward launch on a validation batch; leaves ``rating_pred`` and two device scalars for the caller's
+        metric - ``eval_rating_se`` (sum of w (pred - rating)^2 over the finite ratings) and ``eval_rating_count`` (their
+        number) - formed with torch ops (reporting, not the train step)."""
+        self._rating_forward(q, c)
+        ok = torch.isfinite(ratings)
+        e2 = torch.where(ok, (self.rating_pred - torch.nan_to_num(ratings)) ** 2, torch.zeros_like(ratings))
+        self.eval_rating_se = (e2 if sample_weight is None else e2 * sample_weight).sum()
+        self.eval_rating_count = ok.sum()
+
+    @torch.no_grad()
+    def predict_ratings(self, user_ids: torch.Tensor, item_ids: torch.Tensor, category_ids: torch.Tensor | None = None) -> torch.Tensor:
+        """The head's prediction for ANY number of (user, item) pairs ([n] f32), computed cfg.batch_size pairs at a time on the
+        towers' buffers (inference: no dropout, the stored histories in full).  ``category_ids`` [n]: the pairs' category
+        buckets (required iff the model has the feature)."""
+        if not self.rating_on:
+            raise ValueError("predict_ratings: the model has no rating head (cfg.rating_weight == 0)")
+        if (category_ids is None) != (self.cat_table is None):
+            raise ValueError("category_ids must be given exactly when cfg.n_category_buckets > 0")
+        ut, it, b = self.user_tower, self.item_tower, self.cfg.batch_size
+        uid = user_ids.to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
+        iid = item_ids.to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
+        n = uid.numel()
+        if iid.numel() != n or (category_ids is not None and category_ids.numel() != n):
+            raise ValueError(f"predict_ratings: user_ids, item_ids (and category_ids) must have one length, got {n} and {iid.numel()}")
+        out = torch.empty(n, device=self.dev)
+        for s in range(0, n, b):
+            e = min(s + b, n)
+            m = e - s
+            if self.history_table is not None:
+                self._user_inputs(uid[s:e], ut.acts[0][:m])
+            else:
+                ops.embedding_gather(self.user_table, uid[s:e], out=ut.acts[0][:m], oob_flag=self.oob)
+            ops.embedding_gather(self.item_table, iid[s:e], out=it.acts[0][:m], oob_flag=self.oob)
+            if category_ids is not None:
+                ops.embedding_gather_add_(it.acts[0][:m], self.cat_table, category_ids[s:e].to(self.dev).contiguous(), self.oob)
+            if self.title_table is not None:
+                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=iid[s:e], pooling=self.cfg.title_pooling,
+                                  out=it.acts[0][:m], accumulate=True, oob_flag=self.oob)
+            self._add_features(user=(uid[s:e], ut.acts[0][:m]), item=(iid[s:e], it.acts[0][:m]))
+            ut.forward()
+            it.forward()
+            q, c = self._outputs(ut, it)
+            self._rating_forward(q, c, rows=m, pred=out[s:e])
+        return out
 
     # ------------------------------------------------------------------ retrieval metrics (SURVEY.md §8f row 2)
     @torch.no_grad()
@@ -1256,6 +1412,13 @@ class TwoTowerTrainer:
             if sd["config"].get(k, 0) != getattr(self.cfg, k):
                 raise ValueError(f"checkpoint {k}={sd['config'].get(k, 0)!r} does not match the trainer's {getattr(self.cfg, k)!r}: "
                                  "the numeric side features (and their projection kernels in 'dense') belong to the trained model")
+        # the rating head: a checkpoint from before it existed has no field and loads with the head off
+        ck_w, ck_h = float(sd["config"].get("rating_weight", 0.0)), int(sd["config"].get("rating_hidden", TwoTowerConfig.rating_hidden))
+        if (ck_w > 0) != self.rating_on:
+            raise ValueError(f"checkpoint rating_weight={ck_w!r} ({'with' if ck_w > 0 else 'without'} a rating head) does not match the "
+                             f"trainer's {self.cfg.rating_weight!r}: the head's parameters in 'dense' belong to the trained model")
+        if self.rating_on and ck_h != self.cfg.rating_hidden:
+            raise ValueError(f"checkpoint rating_hidden={ck_h!r} does not match the trainer's {self.cfg.rating_hidden!r}")
         # a checkpoint from before the title feature existed has none: it loads into a trainer without it, as before
         if sd["config"].get("n_title_buckets", 0) != self.cfg.n_title_buckets:
             raise ValueError(f"checkpoint n_title_buckets={sd['config'].get('n_title_buckets', 0)!r} does not match the trainer's "
@@ -1334,6 +1497,9 @@ class TwoTowerTrainer:
         if self.cfg.n_user_features or self.cfg.n_item_features:
             raise NotImplementedError("graph replay with the numeric side features (n_user_features / n_item_features > 0) is not "
                                       "implemented: the step is the Python sequence of launches over materialised tower inputs")
+        if self.rating_on:
+            raise NotImplementedError("graph replay with the rating head (rating_weight > 0) is not implemented: the step is the "
+                                      "Python sequence of launches")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
@@ -1462,4 +1628,6 @@ class TwoTowerTrainer:
                 tot += (w.double() ** 2).sum()
         for _, w, _, _ in self._feature_sides:
             tot += (w.double() ** 2).sum()
+        if getattr(self, "rating_on", False):
+            tot += (self.W1_rating.double() ** 2).sum() + (self.w2_rating.double() ** 2).sum()
         return self.cfg.l2_regularization * tot
