@@ -48,8 +48,9 @@ int tt_abi_version(void);
 const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
  * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args,
- * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args, 15 tt_dense_features_bwd_args; else - 9 and
- * 13 included, which stay unassigned - -1): a binding checks its mirrors with it. */
+ * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args, 15 tt_dense_features_bwd_args,
+ * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args; else - 9, 13 and 16 included, which stay unassigned - -1): a binding checks its
+ * mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
 /* ---------------------------------------------------------------------------------------
@@ -63,7 +64,8 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * scope topk_i8 around a whole tt_retrieval_topk_i8_f32 call), ivf_i8_select (and the scope ivf_i8 around a whole
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
  * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
- * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32).
+ * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32), cross_fwd, cross_bwd
+ * (tt_cross_*_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -504,6 +506,60 @@ int tt_rating_head_bwd_f32(const float* q, const float* c, const float* h, const
                            const float* w1, const float* w2, float* dq, float* dc, int32_t accumulate,
                            float* kslabs, float* bslabs, float* se_slabs, int32_t n_slabs, tt_stream_t stream);
 int32_t tt_rating_head_num_slabs(int64_t n);
+
+/* ---------------------------------------------------------------------------------------
+ * DCN-v2 cross layer (added to v10: new symbols and structs only, the version is unchanged; csrc/cross.hip) - tfrs.layers.dcn.Cross
+ * (Wang et al. 2021) between a tower's summed input rows x0 and its Dense stack.  D = the embedding dim (a multiple of 32 in
+ * 32..256), n rows, W [D, D] row-major as Keras stores a kernel ([in, out]), b [D]:
+ *   u[r,j] = b[j] + sum_i x[r,i] W[i,j]                                  exact f32 products on the f32-input MFMA
+ *   y[r,j] = x0[r,j] * u[r,j] + x[r,j]                                   product and sum two separately rounded f32 operations
+ * One forward launch covers up to two problems (both towers), every one with its own n; `probs` is a HOST array.  A workgroup
+ * owns 32 rows and neither reads nor writes past row n.  u_out (may be NULL: inference) keeps u for the backward launch.  x may
+ * be x0 (layer 0).  y and u_out must not alias x, x0 or each other (pointer-equal aliases are refused).
+ * Backward, ONE launch for up to two problems, for the upstream gradient g = dL/dy, with t = g * x0:
+ *   x_is_x0 == 0 (upper layers):  dx = g + t W^T;   dx0 = accumulate_dx0 ? dx0 + g * u : g * u
+ *   x_is_x0 == 1 (layer 0, x == x0):  dx = ((g + t W^T) + g * u) [+ dx0 when dx0 != NULL: read only]
+ *   dw_slabs[s * slab_stride + i * D + j] = sum of x[r,i] t[r,j],   db_slabs[s * slab_stride + j] = sum of t[r,j]
+ * over the rows r of slab s = [s * R, min((s + 1) * R, n)), R = ceil(n / n_slabs).  Every slab is written in full - one without
+ * rows as zeros - so nothing is pre-zeroed; dw_slabs and db_slabs are the addresses of slab 0 and share slab_stride, so all
+ * layers and both towers can write into one [n_slabs][slab_stride] array that tt_dense_seg / tt_adam_seg sum.  A problem with
+ * n == 0 beside one with rows still writes its (zero) slabs.  No atomics: bits depend on (n, n_slabs, D) alone.
+ * The launch holds the dW tiles and the dx tiles side by side: the dW tiles read g, x0 and x while dx is written, so dx MUST NOT
+ * alias g, x0, x or u, and dx0 none of those nor dx (pointer-equal aliases are refused).
+ * tt_cross_num_slabs(n) is a host query for a slab count that keeps the launch parallel (128-row slabs, at most 64; the launch
+ * has n_slabs * D / 32 + ceil(n / 32) workgroups per problem); any n_slabs in 1..65535 is accepted.
+ * TT_ERR_INVALID_ARG before any launch: n_probs outside 1..2, D not a multiple of 32 in 32..256, n < 0, n_slabs outside
+ * 1..65535, slab_stride < D * D with more than one slab, and with n > 0 a NULL pointer (u_out; dx0 with x_is_x0 excepted), a
+ * pointer that is not 16-byte aligned, x_is_x0 with x != x0, or one of the aliases above.  n == 0 in every problem: no launch,
+ * TT_OK.                                                                                                                    */
+typedef struct tt_cross_fwd_args {
+  const float* x0;           /* [n, D]: the summed input rows                          */
+  const float* x;            /* [n, D]: x_l (== x0 at layer 0)                         */
+  const float* w;            /* [D, D]                                                 */
+  const float* b;            /* [D]                                                    */
+  float* u_out;              /* [n, D] or NULL                                         */
+  float* y;                  /* [n, D]: x_{l+1}                                        */
+  int64_t n;
+} tt_cross_fwd_args;
+typedef struct tt_cross_bwd_args {
+  const float* x0;           /* [n, D]                                                 */
+  const float* x;            /* [n, D]: x_l (== x0 with x_is_x0)                       */
+  const float* u;            /* [n, D]: u_out of the forward launch                    */
+  const float* w;            /* [D, D]                                                 */
+  const float* g;            /* [n, D]: gradient w.r.t. y                              */
+  float* dx;                 /* [n, D]: gradient w.r.t. x (x_is_x0: w.r.t. x0, whole)  */
+  float* dx0;                /* [n, D]: written / accumulated; x_is_x0: read only, may be NULL */
+  float* dw_slabs;           /* slab s: D * D floats at dw_slabs + s * slab_stride     */
+  float* db_slabs;           /* slab s: D floats at db_slabs + s * slab_stride         */
+  int64_t n;
+  int64_t slab_stride;
+  int32_t n_slabs;
+  int32_t x_is_x0;
+  int32_t accumulate_dx0;    /* x_is_x0 == 0 only                                      */
+} tt_cross_bwd_args;
+int tt_cross_fwd_f32(const tt_cross_fwd_args* probs, int32_t n_probs, int32_t D, tt_stream_t stream);
+int tt_cross_bwd_f32(const tt_cross_bwd_args* probs, int32_t n_probs, int32_t D, tt_stream_t stream);
+int32_t tt_cross_num_slabs(int64_t n);
 
 /* Dense parameter update over up to TT_MAX_DENSE_SEGS segments in one launch.
  *   g = sum_s grad_slabs[s*slab_stride + i] (s ascending) + 2*l2*w[i]

@@ -123,9 +123,24 @@ class DenseFeaturesBwdArgs(C.Structure):
                 ("dp_slabs", C.c_void_p)]
 
 
-# tt_abi_struct_bytes index of each mirror (9 and 13 are unassigned: the library answers -1 for them)
+class CrossFwdArgs(C.Structure):
+    """Mirror of ``tt_cross_fwd_args`` (one problem of ``tt_cross_fwd_f32``)."""
+    _fields_ = [("x0", C.c_void_p), ("x", C.c_void_p), ("w", C.c_void_p), ("b", C.c_void_p), ("u_out", C.c_void_p),
+                ("y", C.c_void_p), ("n", C.c_int64)]
+
+
+class CrossBwdArgs(C.Structure):
+    """Mirror of ``tt_cross_bwd_args`` (one problem of ``tt_cross_bwd_f32``)."""
+    _fields_ = [("x0", C.c_void_p), ("x", C.c_void_p), ("u", C.c_void_p), ("w", C.c_void_p), ("g", C.c_void_p),
+                ("dx", C.c_void_p), ("dx0", C.c_void_p), ("dw_slabs", C.c_void_p), ("db_slabs", C.c_void_p),
+                ("n", C.c_int64), ("slab_stride", C.c_int64), ("n_slabs", C.c_int32), ("x_is_x0", C.c_int32),
+                ("accumulate_dx0", C.c_int32)]
+
+
+# tt_abi_struct_bytes index of each mirror (9, 13 and 16 are unassigned: the library answers -1 for them)
 ABI_STRUCT_INDEX = {"AdamTable": 10, "AdamSeg": 11, "AdamHyper": 12}
 FEATURES_STRUCT_INDEX = {"DenseFeaturesFwdArgs": 14, "DenseFeaturesBwdArgs": 15}
+CROSS_STRUCT_INDEX = {"CrossFwdArgs": 17, "CrossBwdArgs": 18}
 
 
 class TrainStep(C.Structure):
@@ -172,6 +187,9 @@ SIGNATURES = {
     "tt_rating_head_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "tt_rating_head_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _f, _i64, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _p]),
     "tt_rating_head_num_slabs": (_i32, [_i64]),
+    "tt_cross_fwd_f32": (C.c_int, [C.POINTER(CrossFwdArgs), _i32, _i32, _p]),
+    "tt_cross_bwd_f32": (C.c_int, [C.POINTER(CrossBwdArgs), _i32, _i32, _p]),
+    "tt_cross_num_slabs": (_i32, [_i64]),
     "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),

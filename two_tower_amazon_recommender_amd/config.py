@@ -45,6 +45,23 @@ def ranking_from_dict(doc: dict) -> dict:
     return {"weight": float(weight), "hidden_dim": hidden}
 
 
+def cross_from_dict(doc: dict) -> dict:
+    """{layers} of the optional ``model.cross`` block (not in the reference's schema): ``layers`` DCN-v2 cross layers (0..3) in
+    both towers, between the summed input features and the Dense stack.  Without the block: none."""
+    block = (doc.get("model") or {}).get("cross")
+    if block is None:
+        return {"layers": 0}
+    if not isinstance(block, dict):
+        raise ValueError("model.cross must be a mapping {layers}")
+    unknown = sorted(set(block) - {"layers"})
+    if unknown:
+        raise ValueError(f"model.cross: unknown keys {unknown} (low-rank, diag_scale and preactivation forms are not implemented)")
+    layers = block.get("layers", 0)
+    if isinstance(layers, bool) or not isinstance(layers, int) or not 0 <= layers <= 3:
+        raise ValueError(f"model.cross.layers must be an int in 0..3, got {layers!r}")
+    return {"layers": layers}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -71,6 +88,8 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     numeric = numeric_features_from_dict(doc)
     # likewise model.ranking {weight, hidden_dim} - the rating-prediction head beside the retrieval task
     ranking = ranking_from_dict(doc)
+    # likewise model.cross {layers} - DCN-v2 cross layers in both towers
+    cross = cross_from_dict(doc)
     cfg = TwoTowerConfig(
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
@@ -84,7 +103,7 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         user_history_len=int(hist.get("max_items", 0)), history_pooling=str(hist.get("pooling", "mean")),
         feature_clip=numeric["clip"], rating_weight=ranking["weight"], rating_hidden=ranking["hidden_dim"],
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
-        title_pooling=str(title.get("pooling", "mean")))
+        title_pooling=str(title.get("pooling", "mean")), cross_layers=cross["layers"])
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),
                 validation_freq=int(tr.get("validation_freq", 1)), top_k_eval=list(rt.get("top_k_eval", [])))
     return cfg, loop

@@ -834,9 +834,11 @@ def optimizer_step_ids_(opt: str, tables, segs: list[DenseSeg], lr: float, eps: 
                "tt_optimizer_step_ids_f32")
 
 
-def make_dense_seg(param, accum, grad_slabs, n_slabs: int, l2: float, grad_out=None) -> DenseSeg:
+def make_dense_seg(param, accum, grad_slabs, n_slabs: int, l2: float, grad_out=None, slab_stride: int | None = None) -> DenseSeg:
+    """``slab_stride`` (default: the parameter's size): floats between two slabs of ``grad_slabs``."""
     count = param.numel()
-    return DenseSeg(_p(param), _p(accum), _p(grad_slabs), _p(grad_out), count, count, n_slabs, l2)
+    return DenseSeg(_p(param), _p(accum), _p(grad_slabs), _p(grad_out), count, count if slab_stride is None else int(slab_stride),
+                    n_slabs, l2)
 
 
 # ----------------------------------------------------------------------------- lazy Adam
@@ -1121,6 +1123,119 @@ def rating_head_bwd(q, c, h, pred, rating, w1, w2, grad_scale: float, dq, dc, ks
                                                   _p(kslabs), _p(bslabs), _p(se_slabs), int(n_slabs), _stream()),
                "tt_rating_head_bwd_f32")
     return dq, dc, kslabs, bslabs, se_slabs
+
+
+# ----------------------------------------------------------------------------- DCN-v2 cross layer
+def _chk_cross(what: str, x0, x, w):
+    _chk(x0, torch.float32, "x0", 2)
+    _chk(x, torch.float32, "x", 2)
+    _chk(w, torch.float32, "w", 2)
+    n, d = x0.shape
+    if tuple(x.shape) != (n, d) or tuple(w.shape) != (d, d):
+        raise RuntimeError(f"{what}: x0 and x must be [n, D] and w [D, D], got {tuple(x0.shape)}, {tuple(x.shape)} and {tuple(w.shape)}")
+    return n, d
+
+
+def cross_layer(*problems, u=None):
+    """One DCN-v2 cross layer (tfrs.layers.dcn.Cross) for one or two problems - both towers - in ONE launch
+    (``tt_cross_fwd_f32``).  Every problem is ``(x0, x, w, b, y)``: ``x0`` [n, D] the summed input rows, ``x`` [n, D] the layer's
+    input (``x0`` itself at layer 0), ``w`` [D, D] ([in, out]), ``b`` [D], ``y`` [n, D] or None (allocated); D a multiple of 32
+    in 32..256, every problem with its own n.  y = x0 * (x @ w + b) + x, the product and the sum rounded separately.
+    ``u``: None (inference) or one [n, D] buffer per problem that receives u = x @ w + b for ``cross_layer_bwd``.  ``y`` and
+    ``u`` must not alias ``x`` / ``x0``.  Returns the tuple of the problems' ``y``."""
+    if len(problems) not in (1, 2):
+        raise ValueError("cross_layer: one or two problems")
+    us = (None,) * len(problems) if u is None else ((u,) if isinstance(u, torch.Tensor) else tuple(u))
+    if len(us) != len(problems):
+        raise ValueError("cross_layer: u holds one buffer per problem")
+    arr = (_lib.CrossFwdArgs * len(problems))()
+    outs, dim = [], None
+    for i, prob in enumerate(problems):
+        if len(prob) != 5:
+            raise ValueError("cross_layer: a problem is (x0, x, w, b, y)")
+        x0, x, w, b, y = prob
+        n, d = _chk_cross("cross_layer", x0, x, w)
+        _chk(b, torch.float32, "b", 1)
+        if dim is None:
+            dim = d
+        if d != dim or b.numel() != d:
+            raise RuntimeError("cross_layer: every problem needs the same D, and b must hold D entries")
+        y = torch.empty((n, d), dtype=torch.float32, device=x.device) if y is None else y
+        _chk(y, torch.float32, "y", 2)
+        if tuple(y.shape) != (n, d):
+            raise RuntimeError(f"cross_layer: y must be [{n}, {d}], got {tuple(y.shape)}")
+        if us[i] is not None:
+            _chk(us[i], torch.float32, "u", 2)
+            if tuple(us[i].shape) != (n, d):
+                raise RuntimeError(f"cross_layer: u must be [{n}, {d}], got {tuple(us[i].shape)}")
+        arr[i] = _lib.CrossFwdArgs(_p(x0), _p(x), _p(w), _p(b), _p(us[i]), _p(y), n)
+        outs.append(y)
+    _lib.check(_lib.load().tt_cross_fwd_f32(arr, len(problems), dim, _stream()), "tt_cross_fwd_f32")
+    return tuple(outs)
+
+
+def cross_num_slabs(n: int) -> int:
+    """Slab count of ``cross_layer_bwd`` for ``n`` rows (``tt_cross_num_slabs``, a host query)."""
+    return int(_lib.load().tt_cross_num_slabs(n))
+
+
+def cross_layer_bwd(*problems, x_is_x0: bool = False, accumulate_dx0: bool = False, n_slabs: int | None = None,
+                    slab_stride: int | None = None):
+    """The backward pass of one cross layer for one or two problems in ONE launch (``tt_cross_bwd_f32``).  Every problem is
+    ``(x0, x, u, w, g, dx, dx0, dw_slabs, db_slabs)``: ``u`` the forward launch's ``u``, ``g`` [n, D] the gradient w.r.t. y.
+    With t = g * x0:  upper layers (``x_is_x0`` False): dx = g + t @ w.T and dx0 = g * u (``accumulate_dx0``: dx0 += g * u);
+    layer 0 (``x_is_x0``: x is x0): dx = ((g + t @ w.T) + g * u) [+ dx0, read only, may be None].  ``dx`` (None: allocated)
+    must not alias g, x0, x or u.  ``dw_slabs`` / ``db_slabs``: flat f32 tensors that START at slab 0 of dW = x.T @ t and of
+    db = t.sum(0); slab s sits ``slab_stride`` floats further on, so several layers and both towers can share one
+    [n_slabs, slab_stride] array (both None: an [n_slabs, D D + D] array of the problem's own, ``n_slabs`` default
+    ``cross_num_slabs(n)``).  Slab s covers ceil(n / n_slabs) contiguous rows; every slab is written in full (an empty one as
+    zeros).  Returns one ``(dx, dx0, dw_slabs [n_slabs, D, D], db_slabs [n_slabs, D])`` per problem (views)."""
+    if len(problems) not in (1, 2):
+        raise ValueError("cross_layer_bwd: one or two problems")
+    arr = (_lib.CrossBwdArgs * len(problems))()
+    outs, dim = [], None
+    for i, prob in enumerate(problems):
+        if len(prob) != 9:
+            raise ValueError("cross_layer_bwd: a problem is (x0, x, u, w, g, dx, dx0, dw_slabs, db_slabs)")
+        x0, x, u, w, g, dx, dx0, dws, dbs = prob
+        n, d = _chk_cross("cross_layer_bwd", x0, x, w)
+        if dim is None:
+            dim = d
+        if d != dim:
+            raise RuntimeError("cross_layer_bwd: every problem needs the same D")
+        if x_is_x0 and x.data_ptr() != x0.data_ptr():
+            raise ValueError("cross_layer_bwd: x_is_x0 needs x to be x0")
+        dx = torch.empty((n, d), dtype=torch.float32, device=x.device) if dx is None else dx
+        if dx0 is None and not x_is_x0:
+            if accumulate_dx0:
+                raise ValueError("cross_layer_bwd: accumulate_dx0=True adds into `dx0`, which must be given")
+            dx0 = torch.empty((n, d), dtype=torch.float32, device=x.device)
+        for t, name in ((u, "u"), (g, "g"), (dx, "dx"), (dx0, "dx0")):
+            if t is not None:
+                _chk(t, torch.float32, name, 2)
+                if tuple(t.shape) != (n, d):
+                    raise RuntimeError(f"cross_layer_bwd: {name} must be [{n}, {d}], got {tuple(t.shape)}")
+        if (dws is None) != (dbs is None):
+            raise ValueError("cross_layer_bwd: dw_slabs and db_slabs are given both or neither")
+        if dws is None:
+            ns = cross_num_slabs(n) if n_slabs is None else int(n_slabs)
+            stride = d * d + d
+            slabs = torch.empty(max(ns, 1) * stride, dtype=torch.float32, device=x.device)
+            dws, dbs = slabs, slabs[d * d:]
+        else:
+            if n_slabs is None or slab_stride is None:
+                raise ValueError("cross_layer_bwd: dw_slabs / db_slabs need n_slabs and slab_stride")
+            ns, stride = int(n_slabs), int(slab_stride)
+            _chk(dws, torch.float32, "dw_slabs", 1)
+            _chk(dbs, torch.float32, "db_slabs", 1)
+            if ns >= 1 and (dws.numel() < (ns - 1) * stride + d * d or dbs.numel() < (ns - 1) * stride + d):
+                raise RuntimeError("cross_layer_bwd: dw_slabs / db_slabs must reach n_slabs slabs of slab_stride floats")
+        arr[i] = _lib.CrossBwdArgs(_p(x0), _p(x), _p(u), _p(w), _p(g), _p(dx), _p(dx0), _p(dws), _p(dbs), n, stride, ns,
+                                   int(bool(x_is_x0)), int(bool(accumulate_dx0)))
+        outs.append((dx, dx0, dws, dbs, ns, stride, d))
+    _lib.check(_lib.load().tt_cross_bwd_f32(arr, len(problems), dim, _stream()), "tt_cross_bwd_f32")
+    return tuple((dx, dx0, torch.as_strided(dws, (ns, d, d), (stride, d, 1)), torch.as_strided(dbs, (ns, d), (stride, 1)))
+                 for dx, dx0, dws, dbs, ns, stride, d in outs)
 
 
 def adapt_normalization(x):

@@ -437,6 +437,10 @@ class ShardedTwoTowerTrainer:
             # the head would have to run on the all-gathered candidates' owners and its gradients join the dense all-reduce
             raise NotImplementedError("the rating head (rating_weight > 0) is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "cross_layers", 0):
+            # the cross kernels' gradients would join the dense all-reduce and the chain run behind the exchanged input rows
+            raise NotImplementedError("cross layers (cross_layers > 0) are not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "candidate_sampling", "in_batch") != "in_batch":
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "

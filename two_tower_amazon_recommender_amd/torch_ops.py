@@ -585,6 +585,52 @@ def _rating_backward(ctx, grad_pred):
 rating_head.register_autograd(_rating_backward, setup_context=_rating_setup)
 
 
+# --------------------------------------------------------------------------------------------- DCN-v2 cross layer
+@torch.library.custom_op(f"{NS}::cross_layer", mutates_args=(), device_types="cuda")
+def cross_layer(x0: Tensor, x: Tensor, w: Tensor, b: Tensor) -> Tensor:
+    """y [n, D] = x0 * (x @ w + b) + x (``ops.cross_layer``: one launch; tfrs.layers.dcn.Cross with x0 the stack's input).
+    Autograd with respect to all four inputs through ``twotower::cross_layer_bwd``."""
+    return ops.cross_layer((x0.contiguous(), x.contiguous(), w.contiguous(), b.contiguous(), None))[0]
+
+
+@cross_layer.register_fake
+def _(x0, x, w, b):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op(f"{NS}::cross_layer_bwd", mutates_args=(), device_types="cuda")
+def cross_layer_bwd(x0: Tensor, x: Tensor, w: Tensor, b: Tensor, grad_y: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The four input gradients of ``cross_layer`` given dL/dy: u is recomputed by the forward launch (the forward op keeps
+    nothing but its inputs), the ONE backward launch runs in its upper-layer form (x0 and x are separate inputs) and its slabs
+    are summed here."""
+    x0, x, w, b = x0.contiguous(), x.contiguous(), w.contiguous(), b.contiguous()
+    n = x.shape[0]
+    if n == 0:
+        z = lambda t: torch.zeros_like(t, memory_format=torch.contiguous_format)
+        return z(x0), z(x), z(w), z(b)
+    u = torch.empty_like(x)
+    ops.cross_layer((x0, x, w, b, None), u=(u,))
+    ((dx, dx0, dws, dbs),) = ops.cross_layer_bwd((x0, x, u, w, grad_y.to(torch.float32).contiguous(), None, None, None, None))
+    return dx0, dx, dws.sum(dim=0), dbs.sum(dim=0)
+
+
+@cross_layer_bwd.register_fake
+def _(x0, x, w, b, grad_y):
+    e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
+    return e(x0), e(x), e(w), e(b)
+
+
+def _cross_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _cross_backward(ctx, grad_y):
+    return torch.ops.twotower.cross_layer_bwd(*ctx.saved_tensors, grad_y)
+
+
+cross_layer.register_autograd(_cross_backward, setup_context=_cross_setup)
+
+
 # --------------------------------------------------------------------------------------------- a5 sparse optimizer
 @torch.library.custom_op(f"{NS}::sparse_update_", mutates_args=("table", "accum"), device_types="cuda")
 def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: Tensor, optimizer: str, lr: float,
@@ -612,4 +658,4 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
 
 
 OPS = ("embedding_gather", "embedding_bag", "history_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "sparse_update_", "sparse_adam_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "sparse_update_", "sparse_adam_")

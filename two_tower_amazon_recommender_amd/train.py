@@ -92,6 +92,10 @@ def parse(argv=None):
                          "model.ranking.weight; 0: no head); single-GPU trainer only")
     ap.add_argument("--rating-hidden", type=int, default=None, metavar="H",
                     help="hidden width of the rating head (a multiple of 32 in 32..256; default model.ranking.hidden_dim, else 128)")
+    ap.add_argument("--cross-layers", type=int, default=None, metavar="L",
+                    help="DCN-v2 cross layers (0..3) in both towers, between the summed input features and the Dense stack: "
+                         "x_{l+1} = x_0 * (x_l W_l + b_l) + x_l (overrides model.cross.layers; 0: none; embedding_dim must be a "
+                         "multiple of 32 in 32..256); single-GPU trainer only")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -160,6 +164,11 @@ def main(argv=None) -> int:
         raise SystemExit("--rating-hidden needs a rating head: --rating-weight W > 0 (or model.ranking.weight)")
     if distributed and rating_weight > 0:
         raise NotImplementedError("the rating head is not implemented for the row-sharded (--distributed) trainer")
+    cross_layers = cfgmod.cross_from_dict(doc)["layers"] if args.cross_layers is None else args.cross_layers
+    if not 0 <= cross_layers <= 3:
+        raise SystemExit("--cross-layers must be in 0..3")
+    if distributed and cross_layers:
+        raise NotImplementedError("the cross layers are not implemented for the row-sharded (--distributed) trainer")
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -206,6 +215,7 @@ def main(argv=None) -> int:
     cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = args.adam_beta1, args.adam_beta2, args.adam_epsilon
     cfg.n_title_buckets = title_buckets
     cfg.rating_weight, cfg.rating_hidden = float(rating_weight), int(rating_hidden)
+    cfg.cross_layers = int(cross_layers)
     if args.title_max_tokens is not None:
         cfg.title_max_tokens = args.title_max_tokens
     if args.title_pooling is not None:

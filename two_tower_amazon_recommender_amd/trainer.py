@@ -39,6 +39,8 @@ TID_USER_FEATURES, TID_ITEM_FEATURES = 14, 15               # synthetic_user_fea
 TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of step s is element s * n_sampled_negatives + i
 TID_DENSE_BASE = 16
 TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
+TID_CROSS_BASE = 48                          # the cross kernels: layer l of tower t is 48 + 2 l + t (48..53)
+MAX_CROSS_LAYERS = 3
 TID_DROPOUT_BASE = 64
 
 
@@ -88,6 +90,11 @@ class TwoTowerConfig:
     # graph capture.
     rating_weight: float = 0.0
     rating_hidden: int = 128
+    # DCN-v2 cross layers (tfrs.layers.dcn.Cross, Wang et al. 2021) in BOTH towers, between the summed input rows x_0 and the
+    # Dense stack: x_{l+1} = x_0 * (x_l W_l + b_l) + x_l, W_l [embedding_dim, embedding_dim] - explicit bilinear interactions of
+    # the features summed into x_0.  0..3 layers; 0 = none.  embedding_dim must be a multiple of 32 in 32..256.  Single-GPU
+    # trainer, materialised tower inputs, no graph capture.
+    cross_layers: int = 0
     # dense numeric side features (the reference's create_user_features / create_item_features: per-id rating count / mean / std /
     # min / max; TFRS Normalization -> concat -> Dense): a fixed [n_users, n_user_features] / [n_items, n_item_features] f32 matrix
     # (``set_user_features`` / ``set_item_features``; 1..32 columns) whose row is normalised (Keras Normalization; clamped to
@@ -123,6 +130,12 @@ class TwoTowerConfig:
     @property
     def symmetric(self) -> bool:
         return self.user_dims == self.item_dims
+
+    def dense_segment_count(self, cross: bool = True) -> int:
+        """Segments of the dense optimizer launches: a kernel and a bias per Dense layer, a projection kernel per side with
+        numeric features, two for the rating head, two for the cross layers (``cross=False``: without those)."""
+        return (2 * (len(self.user_dims) + len(self.item_dims)) + (self.n_user_features > 0) + (self.n_item_features > 0)
+                + 2 * (self.rating_weight > 0) + 2 * (bool(cross) and self.cross_layers > 0))
 
     def validate(self):
         if self.optimizer not in ("sgd", "adagrad", "adam"):
@@ -196,6 +209,14 @@ class TwoTowerConfig:
         h = self.rating_hidden
         if isinstance(h, bool) or not isinstance(h, int) or not (32 <= h <= 256 and h % 32 == 0):
             raise ValueError("rating_hidden must be a multiple of 32 in 32..256")
+        cl = self.cross_layers
+        if isinstance(cl, bool) or not isinstance(cl, int) or not 0 <= cl <= MAX_CROSS_LAYERS:
+            raise ValueError(f"cross_layers must be an int in 0..{MAX_CROSS_LAYERS} (0: no cross layers)")
+        if cl and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
+            raise ValueError(f"cross_layers > 0 needs an embedding_dim that is a multiple of 32 in 32..256 (got {self.embedding_dim})")
+        if cl and self.dense_segment_count(False) <= _lib.TT_MAX_DENSE_SEGS < self.dense_segment_count():
+            raise NotImplementedError(f"the cross layers add two dense segments to the model's {self.dense_segment_count(False)}: the "
+                                      f"optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
 
 
 class Tower:
@@ -234,6 +255,45 @@ class Tower:
                               else None for l in range(self.n_layers)]
         self.dw_slabs = [torch.empty(ns, self.dims[l], self.dims[l + 1], device=dev) for l in range(self.n_layers)]
         self.db_slabs = [torch.empty(ns, self.dims[l + 1], device=dev) for l in range(self.n_layers)]
+        # cfg.cross_layers: the cross stack between acts[0] (x_0) and layer 0.  xc[l] = x_{l+1} (layer 0 reads xc[-1]) and
+        # cu[l] = u_l stay for the backward chain; layer 0 writes its input gradient G_L into cg[0], the chain alternates
+        # between cg[0] and cg[1] (a launch never writes the buffer it reads) and ends in demb; ca collects the gradient that
+        # reaches x_0 through the Hadamard factors of layers 1 .. L-1.  The parameters (views of dense_flat) and the gradient
+        # slabs belong to the trainer: ``set_cross``.
+        self.n_cross = nc = cfg.cross_layers
+        self.cross_w, self.cross_b, self.cross_dw_slabs, self.cross_db_slabs = [], [], [], []
+        self.cross_n_slabs = self.cross_slab_stride = 0
+        d0 = self.dims[0]
+        self.xc = [torch.empty(b, d0, device=dev) for _ in range(nc)]
+        self.cu = [torch.empty(b, d0, device=dev) for _ in range(nc)]
+        self.cg = [torch.empty(b, d0, device=dev) for _ in range(min(nc, 2))]
+        self.ca = torch.empty(b, d0, device=dev) if nc > 1 else None
+
+    def set_cross(self, ws, bs, dw_slabs, db_slabs, n_slabs: int, slab_stride: int):
+        """The cross stack's parameters [D, D] / [D] per layer and, per layer, the flat views that start at slab 0 of its dW /
+        db in the trainer's shared [n_slabs, slab_stride] gradient-slab array."""
+        self.cross_w, self.cross_b, self.cross_dw_slabs, self.cross_db_slabs = list(ws), list(bs), list(dw_slabs), list(db_slabs)
+        self.cross_n_slabs, self.cross_slab_stride = int(n_slabs), int(slab_stride)
+
+    def layer_input(self, l: int, rows: int | None = None):
+        """What Dense layer ``l`` reads: acts[l] - for layer 0 under cross layers the crossed rows x_L."""
+        x = self.xc[-1] if (l == 0 and self.n_cross) else self.acts[l]
+        return x if rows is None else x[:rows]
+
+    def input_grad(self):
+        """Where Dense layer 0 writes its input gradient: demb - under cross layers G_L, which the cross chain turns into demb."""
+        return self.cg[0] if self.n_cross else self.demb
+
+    def cross_fwd_problem(self, l: int, keep_u: bool, rows: int | None = None):
+        n = self.rows if rows is None else rows
+        x0 = self.acts[0][:n]
+        return (x0, x0 if l == 0 else self.xc[l - 1][:n], self.cross_w[l], self.cross_b[l], self.xc[l][:n]), \
+            (self.cu[l][:n] if keep_u else None)
+
+    def cross_bwd_problem(self, l: int):
+        L = self.n_cross
+        return (self.acts[0], self.acts[0] if l == 0 else self.xc[l - 1], self.cu[l], self.cross_w[l], self.cg[(L - 1 - l) % 2],
+                self.demb if l == 0 else self.cg[(L - l) % 2], self.ca, self.cross_dw_slabs[l], self.cross_db_slabs[l])
 
     def alloc_unit(self):
         if self.unit is None:
@@ -249,21 +309,25 @@ class Tower:
         Inverted dropout follows every hidden (ReLU) layer, fused in the GEMM epilogue.
         lookup (ops.make_lookup): layer 0 reads its input rows from the embedding table (acts[0] is not used).
         rows: only the first ``rows`` rows of the buffers (an in-batch evaluation on the longer item tower of mixed sampling)."""
+        if self.n_cross and lookup is not None:
+            raise ValueError("Tower.forward: the cross layers read materialised input rows (acts[0]), not a fused lookup")
         if rows is not None and rows != self.rows:
             if dropout is not None:
                 raise ValueError("Tower.forward: a partial forward pass is an inference pass (no dropout)")
+            cross_forward((self,), keep_u=False, rows=(rows,))
             for l in range(self.n_layers):
                 bits = self.bits[l + 1]
-                ops.dense_fwd(self.acts[l][:rows], self.w[l], self.b[l], relu=l < self.n_layers - 1, out=self.acts[l + 1][:rows],
+                ops.dense_fwd(self.layer_input(l, rows), self.w[l], self.b[l], relu=l < self.n_layers - 1, out=self.acts[l + 1][:rows],
                               lookup=lookup if l == 0 else None, relu_bits=None if bits is None else bits[:rows])
             return self.acts[-1][:rows]
+        cross_forward((self,), keep_u=dropout is not None)       # (training passes a dropout tuple even at rate 0)
         for l in range(self.n_layers):
             hidden = l < self.n_layers - 1
             d = None
             if dropout is not None and hidden and dropout[0] > 0.0:
                 rate, seed, tower, row0 = dropout
                 d = (rate, seed, TID_DROPOUT_BASE + 2 * l + tower, row0 * self.dims[l + 1])
-            ops.dense_fwd(self.acts[l], self.w[l], self.b[l], relu=hidden, out=self.acts[l + 1], dropout=d,
+            ops.dense_fwd(self.layer_input(l), self.w[l], self.b[l], relu=hidden, out=self.acts[l + 1], dropout=d,
                           lookup=lookup if l == 0 else None, relu_bits=self.bits[l + 1])
         return self.acts[-1]
 
@@ -275,12 +339,16 @@ class Tower:
             one = torch.ones((), dtype=torch.float32)
             scale = (one / (one - torch.tensor(dropout_rate, dtype=torch.float32))).item()
         for l in range(self.n_layers - 1, -1, -1):
-            dxo = (self.dz[l - 1] if l > 0 else self.demb) if dx else None
+            dxo = (self.dz[l - 1] if l > 0 else self.input_grad()) if dx else None
             bits = self.bits[l] if (l > 0 and dx) else None
             mask_src = self.acts[l] if (l > 0 and dx and bits is None) else None   # acts[l] = (dropped-out) ReLU output of layer l-1
-            ops.dense_bwd(self.acts[l], self.w[l], self.dz[l], dxo, mask_src, self.dw_slabs[l] if dw else None,
+            ops.dense_bwd(self.layer_input(l), self.w[l], self.dz[l], dxo, mask_src, self.dw_slabs[l] if dw else None,
                           self.db_slabs[l] if dw else None, dx_scale=scale if l > 0 else 1.0,
                           lookup=lookup if l == 0 else None, dx_relu_bits=bits)
+        if self.n_cross:
+            if not (dx and dw):
+                raise NotImplementedError("Tower.backward: the cross layers' backward launch computes dx and dW together")
+            cross_backward((self,))
 
     def segments(self, l2: float, grad_flat=None, grad_offset: int = 0):
         segs = []
@@ -294,11 +362,32 @@ class Tower:
         return segs
 
 
+def cross_forward(towers, keep_u: bool, rows=None):
+    """The cross stacks of ``towers`` (one or both), one launch per layer for all of them: xc[l] = x_0 * (x_l W_l + b_l) + x_l.
+    ``keep_u``: u_l stays in cu[l] for the backward chain (train step).  ``rows``: rows per tower (default: all)."""
+    for l in range(towers[0].n_cross):
+        probs, us = zip(*[t.cross_fwd_problem(l, keep_u, None if rows is None else rows[i]) for i, t in enumerate(towers)])
+        ops.cross_layer(*probs, u=us if keep_u else None)
+
+
+def cross_backward(towers):
+    """The cross stacks' backward chain, one launch per layer for all ``towers``: from G_L (cg[0], written by Dense layer 0)
+    down to demb, the parameter gradients into the trainer's shared slab array."""
+    L = towers[0].n_cross
+    for l in range(L - 1, -1, -1):
+        ops.cross_layer_bwd(*[t.cross_bwd_problem(l) for t in towers], x_is_x0=l == 0, accumulate_dx0=0 < l < L - 1,
+                            n_slabs=towers[0].cross_n_slabs, slab_stride=towers[0].cross_slab_stride)
+
+
 def towers_forward(ut: "Tower", it: "Tower", dropout=None, lookups=None):
     """Both towers layer by layer, one launch per layer (the towers have identical shapes).
     dropout = (rate, seed, first_global_row) in training, None at inference.
     lookups = (user lookup, item lookup): layer 0 gathers its input rows from the embedding tables itself."""
     L = ut.n_layers
+    if ut.n_cross:
+        if lookups is not None:
+            raise ValueError("towers_forward: the cross layers read materialised input rows (acts[0]), not a fused lookup")
+        cross_forward((ut, it), keep_u=dropout is not None)
     # the last two layers (ReLU hidden + linear output) of both towers in ONE launch when their shapes allow it: the hidden tile
     # never leaves the CU between them (csrc/tower.hip); two-layer towers are that launch alone (with the lookup inside), deeper
     # ones - the reference's [512, 256, 128] - run the layers below one by one first
@@ -309,7 +398,7 @@ def towers_forward(ut: "Tower", it: "Tower", dropout=None, lookups=None):
         if dropout is not None and hidden and dropout[0] > 0.0:
             rate, seed, row0 = dropout
             d = (rate, seed, (TID_DROPOUT_BASE + 2 * l, TID_DROPOUT_BASE + 2 * l + 1), row0 * ut.dims[l + 1])
-        ops.dense_fwd2((ut.acts[l], it.acts[l]), (ut.w[l], it.w[l]), (ut.b[l], it.b[l]), (ut.acts[l + 1], it.acts[l + 1]),
+        ops.dense_fwd2((ut.layer_input(l), it.layer_input(l)), (ut.w[l], it.w[l]), (ut.b[l], it.b[l]), (ut.acts[l + 1], it.acts[l + 1]),
                        relu=hidden, dropout=d, lookups=lookups if l == 0 else None, relu_bits=(ut.bits[l + 1], it.bits[l + 1]))
     if fused:
         a = L - 2
@@ -317,7 +406,7 @@ def towers_forward(ut: "Tower", it: "Tower", dropout=None, lookups=None):
         if dropout is not None and dropout[0] > 0.0:
             rate, seed, row0 = dropout
             d = (rate, seed, (TID_DROPOUT_BASE + 2 * a, TID_DROPOUT_BASE + 2 * a + 1), row0 * ut.dims[a + 1])
-        ops.tower_fwd2((ut.acts[a], it.acts[a]), (ut.w[a], it.w[a]), (ut.b[a], it.b[a]), (ut.acts[a + 1], it.acts[a + 1]),
+        ops.tower_fwd2((ut.layer_input(a), it.layer_input(a)), (ut.w[a], it.w[a]), (ut.b[a], it.b[a]), (ut.acts[a + 1], it.acts[a + 1]),
                        (ut.bits[a + 1], it.bits[a + 1]), (ut.w[a + 1], it.w[a + 1]), (ut.b[a + 1], it.b[a + 1]),
                        (ut.acts[a + 2], it.acts[a + 2]), dropout=d, lookups=lookups if a == 0 else None)
     return ut.acts[-1], it.acts[-1]
@@ -335,10 +424,10 @@ def towers_backward(ut: "Tower", it: "Tower", dropout_rate: float = 0.0, on_embe
     none2 = (None, None)
 
     def layer_args(l, dx: bool, dw: bool):
-        dxs = ((ut.dz[l - 1], it.dz[l - 1]) if l > 0 else (ut.demb, it.demb)) if dx else none2
+        dxs = ((ut.dz[l - 1], it.dz[l - 1]) if l > 0 else (ut.input_grad(), it.input_grad())) if dx else none2
         bits = (ut.bits[l], it.bits[l]) if (l > 0 and dx and ut.bits[l] is not None) else none2
         masks = (ut.acts[l], it.acts[l]) if (l > 0 and dx and bits[0] is None) else none2
-        return dict(xs=(ut.acts[l], it.acts[l]), ws=(ut.w[l], it.w[l]), dzs=(ut.dz[l], it.dz[l]), dxs=dxs, dx_relu_srcs=masks,
+        return dict(xs=(ut.layer_input(l), it.layer_input(l)), ws=(ut.w[l], it.w[l]), dzs=(ut.dz[l], it.dz[l]), dxs=dxs, dx_relu_srcs=masks,
                     dw_slabs=(ut.dw_slabs[l], it.dw_slabs[l]) if dw else none2, db_slabs=(ut.db_slabs[l], it.db_slabs[l]) if dw else none2,
                     lookups=lookups if l == 0 else None, dx_relu_bits=bits)
 
@@ -356,7 +445,11 @@ def towers_backward(ut: "Tower", it: "Tower", dropout_rate: float = 0.0, on_embe
             layer(l, True, True)
         if last == 1:
             ops.tower_bwd2(layer_args(1, True, True), layer_args(0, True, True), bwd2_ws, dx_scale_upper=scale, dx_scale_lower=1.0)
+        if ut.n_cross:
+            cross_backward((ut, it))
         return
+    if ut.n_cross:
+        raise NotImplementedError("towers_backward: on_embedding_grads with cross layers is not implemented")
     for l in range(ut.n_layers - 1, -1, -1):
         layer(l, True, False)
     on_embedding_grads()
@@ -388,7 +481,13 @@ class TwoTowerTrainer:
         self.rating_on = cfg.rating_weight > 0
         sd, rh = cfg.tower_dims[-1], cfg.rating_hidden
         n_head = (2 * sd * rh + rh + rh + 1) if self.rating_on else 0
-        self.dense_flat = torch.zeros(n_user + n_item + (fu + fi) * d + n_head, device=dev)
+        # the cross layers sit behind the head: [user W_0 .. W_{L-1} | item W_0 .. | user b_0 .. | item b_0 ..]
+        # (from a 16-byte boundary: the head's parameter count is odd, the cross launches load float4s - up to 3 idle floats)
+        ncl = cfg.cross_layers
+        n_cross = 2 * ncl * (d * d + d)
+        n_front = n_user + n_item + (fu + fi) * d + n_head
+        c_off = (n_front + 3) // 4 * 4 if ncl else n_front
+        self.dense_flat = torch.zeros(c_off + n_cross, device=dev)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
         # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
@@ -488,6 +587,21 @@ class TwoTowerTrainer:
             self._r_kslabs = torch.empty(ns, nk + rh, device=dev)
             self._r_bslabs = torch.empty(ns, rh + 1, device=dev)
             self._r_se = torch.zeros(ns, device=dev)
+        # cross layers: the parameters (views of dense_flat) and ONE gradient-slab array for all layers of both towers, laid out
+        # like the parameters, so that two dense segments - every kernel (l2 like any kernel), every bias - sum it
+        self._c_off = c_off
+        self._c_slabs = None
+        self._c_nslabs = 0
+        if ncl:
+            nk, stride = 2 * ncl * d * d, n_cross
+            self._c_nslabs = ns = ops.cross_num_slabs(bi)
+            self._c_slabs = torch.empty(ns * stride, device=dev)
+            for ti, tower in enumerate((self.user_tower, self.item_tower)):
+                ko = [(ti * ncl + l) * d * d for l in range(ncl)]
+                bo = [nk + (ti * ncl + l) * d for l in range(ncl)]
+                tower.set_cross([self.dense_flat[self._c_off + o:self._c_off + o + d * d].view(d, d) for o in ko],
+                                [self.dense_flat[self._c_off + o:self._c_off + o + d] for o in bo],
+                                [self._c_slabs[o:] for o in ko], [self._c_slabs[o:] for o in bo], ns, stride)
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -508,6 +622,8 @@ class TwoTowerTrainer:
         if cfg.user_history_len:                 # the user tower's input is one bag launch: user row + pooled history (_item_inputs)
             self.fuse_lookup = False
         if self._feature_sides:                  # the projected features are added to the materialised tower inputs (_add_features)
+            self.fuse_lookup = False
+        if cfg.cross_layers:                     # the cross layers read the materialised tower inputs (Tower.forward)
             self.fuse_lookup = False
         self.fuse_sort = os.environ.get("TT_FUSE_SORT", "1") != "0"   # the optimizer launch sorts the ids itself (no plan launch)
         self.fuse_optimizer = True               # sparse + dense optimizer in one launch (False: dense_update, sparse_update2 [, cat])
@@ -566,6 +682,19 @@ class TwoTowerTrainer:
                 if adam:
                     self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs,
                                                              self._r_slabs, reg))
+        n_before_cross = len(self._segs)
+        if ncl:                                  # two more Dense segments: every cross kernel (l2 like any kernel), every cross bias
+            nk = 2 * ncl * d * d
+            for lo, hi, slabs, reg in ((self._c_off, self._c_off + nk, self._c_slabs, cfg.l2_regularization),
+                                       (self._c_off + nk, self._c_off + n_cross, self._c_slabs[nk:], 0.0)):
+                self._segs.append(ops.make_dense_seg(self.dense_flat[lo:hi], None if self.dense_accum is None else self.dense_accum[lo:hi],
+                                                     slabs, self._c_nslabs, reg, slab_stride=n_cross))
+                if adam:
+                    self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs,
+                                                             self._c_nslabs, reg, slab_stride=n_cross))
+        if len(self._segs) > _lib.TT_MAX_DENSE_SEGS and n_before_cross <= _lib.TT_MAX_DENSE_SEGS:
+            raise NotImplementedError(f"the cross layers add two dense segments to the model's {n_before_cross}: the optimizer launches "
+                                      f"take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
         if len(self._segs) > _lib.TT_MAX_DENSE_SEGS and not self._feature_sides:
             raise NotImplementedError(f"the rating head adds two dense segments to the towers' {n_tower_segs}: the optimizer launches "
                                       f"take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
@@ -601,6 +730,10 @@ class TwoTowerTrainer:
             for w, tid, fan in ((self.W1_rating, TID_RATING_W1, sum(self.W1_rating.shape)), (self.w2_rating, TID_RATING_W2, self.w2_rating.numel() + 1)):
                 lim = torch.tensor(math.sqrt(6.0 / fan), dtype=torch.float64).to(torch.float32)
                 ops.fill_uniform_(w, seed, tid, -lim.item(), (lim + lim).item())
+        for t, tower in enumerate((self.user_tower, self.item_tower)):     # Glorot-uniform [D, D] kernels, zero biases
+            for l, w in enumerate(tower.cross_w):
+                lim = torch.tensor(math.sqrt(6.0 / (w.shape[0] + w.shape[1])), dtype=torch.float64).to(torch.float32)
+                ops.fill_uniform_(w, seed, TID_CROSS_BASE + 2 * l + t, -lim.item(), (lim + lim).item())
         if self.cfg.optimizer == "adagrad":
             for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum, self.history_accum):
                 if a is not None:
@@ -1357,7 +1490,7 @@ class TwoTowerTrainer:
         self._check_batch(user_ids, item_ids)
         if corpus is None:
             corpus = self.item_corpus_embeddings()
-        if self.history_table is not None or self.user_features is not None:
+        if self.history_table is not None or self.user_features is not None or self.cfg.cross_layers:
             if self.history_table is not None:
                 self._user_inputs(user_ids, self.user_tower.acts[0])
             else:
@@ -1419,6 +1552,10 @@ class TwoTowerTrainer:
                              f"trainer's {self.cfg.rating_weight!r}: the head's parameters in 'dense' belong to the trained model")
         if self.rating_on and ck_h != self.cfg.rating_hidden:
             raise ValueError(f"checkpoint rating_hidden={ck_h!r} does not match the trainer's {self.cfg.rating_hidden!r}")
+        # the cross layers: a checkpoint from before they existed has no field and loads as 0
+        if int(sd["config"].get("cross_layers", 0)) != self.cfg.cross_layers:
+            raise ValueError(f"checkpoint cross_layers={sd['config'].get('cross_layers', 0)!r} does not match the trainer's "
+                             f"{self.cfg.cross_layers!r}: the cross kernels in 'dense' belong to the trained model")
         # a checkpoint from before the title feature existed has none: it loads into a trainer without it, as before
         if sd["config"].get("n_title_buckets", 0) != self.cfg.n_title_buckets:
             raise ValueError(f"checkpoint n_title_buckets={sd['config'].get('n_title_buckets', 0)!r} does not match the trainer's "
@@ -1500,6 +1637,9 @@ class TwoTowerTrainer:
         if self.rating_on:
             raise NotImplementedError("graph replay with the rating head (rating_weight > 0) is not implemented: the step is the "
                                       "Python sequence of launches")
+        if self.cfg.cross_layers:
+            raise NotImplementedError("graph replay with cross layers (cross_layers > 0) is not implemented: the step is the "
+                                      "Python sequence of launches over materialised tower inputs")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
@@ -1630,4 +1770,7 @@ class TwoTowerTrainer:
             tot += (w.double() ** 2).sum()
         if getattr(self, "rating_on", False):
             tot += (self.W1_rating.double() ** 2).sum() + (self.w2_rating.double() ** 2).sum()
+        for tower in (self.user_tower, self.item_tower):
+            for w in tower.cross_w:
+                tot += (w.double() ** 2).sum()
         return self.cfg.l2_regularization * tot
