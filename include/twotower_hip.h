@@ -187,6 +187,44 @@ int tt_history_bag_fwd_f32(const float* table, int64_t table_rows, int32_t dim,
                            tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * History attention (added to v10: new symbols only, the version is unchanged) - the history bag pooled by a learned query
+ * with a recency bias instead of a fixed scale (csrc/history_attn.hip).  attn [dim + L] f32 (16-byte aligned) = [a | p].
+ * Forward, one launch.  table, tokens, bag_rows, n_bags, batch_ids, oob_flag, exclude and base_table / base_rows / base_ids are
+ * tt_history_bag_fwd_f32's, rule for rule (-1 padding anywhere, out-of-range tokens skipped with the flag, leave-one-out on
+ * the raw token, a -1 or out-of-range bag row or base id, empty bags); dim a multiple of 4 in 4..1024, L in 1..64.  For the
+ * valid slots j of bag b, in ascending slot order:
+ *   r_j = number of valid slots behind j (0: the newest kept item - counted after the exclusion, so the ranks stay contiguous)
+ *   e_j = <table[token_j], a> * (1 / sqrt(dim)) + p[r_j]
+ *   w   = softmax(e) over the valid slots (max-subtracted, hardware exponential);  pooled = sum_j w_j table[token_j]
+ *   out[b] = base row + pooled (no base: pooled; an empty bag: the base row itself, or +0)
+ * weights [n_bags, L] f32 (may be NULL): the normalised weights, exactly 0 in a skipped slot; a bag with one valid slot has
+ * weight exactly 1 and pooled = that row.  pooled [n_bags, dim] f32 (may be NULL, 16-byte aligned): the pooled term without
+ * the base row - what the backward launch takes G from.  A bag's bits depend on that bag alone: not on the grid, not on its
+ * neighbours.  n_bags == 0 launches nothing; anything else is TT_ERR_INVALID_ARG before any launch (dim, L, n_bags * L beyond
+ * 31 bits, a base half given, null or misaligned table / out / attn / pooled / base_table).
+ * Backward, one launch, given dy = d out [n_bags, dim] and the forward's batch_ids, weights and pooled:
+ *   G = <dy[b], pooled[b]>    t_j = <dy[b], h_j>    de_j = w_j (t_j - G)
+ *   slot_grads[b * L + j, :] = w_j dy[b] + de_j a / sqrt(dim)        one gradient row PER SLOT; a skipped slot's row is untouched
+ *   dattn_slabs [n_slabs][dim + L]: slab s = [sum de_j table[token_j] / sqrt(dim) | dp, dp[r_j] += de_j] over the bags
+ *   [s * ceil(n_bags / n_slabs), ...) - every slab written in full (an empty one as zeros), no atomics, no pre-zeroing: the
+ *   form tt_dense_seg / tt_adam_seg sum (slab_stride = dim + L).  tt_history_attention_num_slabs(n_bags) is a host query for a
+ *   slab count that fills the chip (8 bags per slab, at most 1024); any n_slabs in 1..65536 is accepted.
+ * The table is then updated by tt_sparse_plan over batch_ids (n_ids = n_bags * L; a skipped slot's id is -1) and
+ * tt_sparse_sgd_f32 / tt_sparse_adagrad_f32 / tt_adam_step_f32 with grads = slot_grads and order = the plan's order;
+ * d base_table[base_ids[b]] = dy[b].  Bit-reproducible for one (n_bags, n_slabs).                                            */
+int tt_history_attention_fwd_f32(const float* table, int64_t table_rows, int32_t dim,
+                                 const int32_t* tokens, int64_t n_token_rows, int32_t L,
+                                 const int64_t* bag_rows, int64_t n_bags, const float* attn,
+                                 float* out, int64_t* batch_ids, float* weights, float* pooled, int32_t* oob_flag,
+                                 const int64_t* exclude, const float* base_table, int64_t base_rows, const int64_t* base_ids,
+                                 tt_stream_t stream);
+int tt_history_attention_bwd_f32(const float* table, int64_t table_rows, int32_t dim, int32_t L,
+                                 const int64_t* batch_ids, const float* weights, const float* pooled, const float* dy,
+                                 int64_t n_bags, const float* attn, float* slot_grads, float* dattn_slabs, int32_t n_slabs,
+                                 tt_stream_t stream);
+int32_t tt_history_attention_num_slabs(int64_t n_bags);
+
+/* ---------------------------------------------------------------------------------------
  * Mixed negative sampling (added to v10: a new symbol only, the version is unchanged) - Yang et al. 2020: every step
  * appends n_neg items drawn from the whole corpus to the n_pos in-batch candidates (csrc/sample.hip).  One launch writes
  *   cand_ids[0 : n_pos]  = pos_ids

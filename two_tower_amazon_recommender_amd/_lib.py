@@ -181,6 +181,9 @@ SIGNATURES = {
     "tt_embedding_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "tt_embedding_bag_bwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
     "tt_history_bag_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "tt_history_attention_fwd_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "tt_history_attention_bwd_f32": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p]),
+    "tt_history_attention_num_slabs": (_i32, [_i64]),
     "tt_dense_features_fwd_f32": (C.c_int, [C.POINTER(DenseFeaturesFwdArgs), _i32, _i32, _f, _p, _p]),
     "tt_dense_features_bwd_f32": (C.c_int, [C.POINTER(DenseFeaturesBwdArgs), _i32, _i32, _p]),
     "tt_dense_features_num_slabs": (_i32, [_i64]),

@@ -244,6 +244,97 @@ def history_bag(table: torch.Tensor, tokens: torch.Tensor, bag_rows: torch.Tenso
     return out
 
 
+def history_attention(table: torch.Tensor, tokens: torch.Tensor, attn: torch.Tensor, bag_rows: torch.Tensor | None = None,
+                      exclude: torch.Tensor | None = None, base=None, out: torch.Tensor | None = None,
+                      batch_ids: torch.Tensor | None = None, weights: torch.Tensor | None = None,
+                      pooled: torch.Tensor | None = None, oob_flag: torch.Tensor | None = None):
+    """The history bag pooled by a learned query with a recency bias, in one launch (``tt_history_attention_fwd_f32``):
+    ``attn`` [dim + L] f32 = [a | p]; for the valid slots j of a bag (``history_bag``'s rules: padding, out-of-range tokens and
+    ``exclude`` skipped) r_j = valid slots behind j, e_j = <table[t_j], a> / sqrt(dim) + p[r_j], w = softmax(e),
+    out[b] = base row + sum_j w_j table[t_j].  ``tokens``, ``bag_rows``, ``exclude``, ``base``, ``batch_ids`` and ``oob_flag``
+    are ``history_bag``'s; ``weights`` [n_bags, L] (0 in a skipped slot) and ``pooled`` [n_bags, dim] (the pooled term without
+    the base row) are allocated when None.  dim a multiple of 4 in 4..1024, L in 1..64.  Returns (out, weights, pooled)."""
+    n_rows, L, d, n_bags, out = _bag_args("history_attention", table, tokens, bag_rows, "sum", out, False, batch_ids, None, oob_flag)
+    _chk(attn, torch.float32, "attn", 1)
+    if attn.numel() != d + L:
+        raise RuntimeError(f"history_attention: attn must hold dim + L = {d + L} entries ([a | p]), got {attn.numel()}")
+    if exclude is not None:
+        _chk(exclude, torch.int64, "exclude", 1)
+        if exclude.numel() != n_bags:
+            raise RuntimeError(f"history_attention: exclude must hold n_bags = {n_bags} entries, got {exclude.numel()}")
+    base_table = base_ids = None
+    if base is not None:
+        base_table, base_ids = base
+        _chk(base_table, torch.float32, "base_table", 2)
+        _chk(base_ids, torch.int64, "base_ids", 1)
+        if base_table.shape[1] != d or base_ids.numel() != n_bags:
+            raise RuntimeError(f"history_attention: base must be ([rows, {d}] f32, [{n_bags}] int64), got "
+                               f"{tuple(base_table.shape)} and {tuple(base_ids.shape)}")
+    if weights is None:
+        weights = torch.empty((n_bags, L), dtype=torch.float32, device=table.device)
+    _chk(weights, torch.float32, "weights", 2)
+    if tuple(weights.shape) != (n_bags, L):
+        raise RuntimeError(f"history_attention: weights must be [{n_bags}, {L}] (n_bags, L), got {tuple(weights.shape)}")
+    if pooled is None:
+        pooled = torch.empty((n_bags, d), dtype=torch.float32, device=table.device)
+    _chk(pooled, torch.float32, "pooled", 2)
+    if tuple(pooled.shape) != (n_bags, d):
+        raise RuntimeError(f"history_attention: pooled must be [{n_bags}, {d}] (n_bags, dim), got {tuple(pooled.shape)}")
+    _lib.check(_lib.load().tt_history_attention_fwd_f32(_p(table), table.shape[0], d, _p(tokens), n_rows, L, _p(bag_rows), n_bags,
+                                                        _p(attn), _p(out), _p(batch_ids), _p(weights), _p(pooled), _p(oob_flag),
+                                                        _p(exclude), _p(base_table),
+                                                        0 if base_table is None else base_table.shape[0], _p(base_ids), _stream()),
+               "tt_history_attention_fwd_f32")
+    return out, weights, pooled
+
+
+def history_attention_num_slabs(n: int) -> int:
+    """Slab count of ``history_attention_bwd`` for ``n`` bags (``tt_history_attention_num_slabs``, a host query)."""
+    return int(_lib.load().tt_history_attention_num_slabs(n))
+
+
+def history_attention_bwd(table: torch.Tensor, batch_ids: torch.Tensor, weights: torch.Tensor, pooled: torch.Tensor,
+                          dy: torch.Tensor, attn: torch.Tensor, L: int, slot_grads: torch.Tensor | None = None,
+                          dattn_slabs: torch.Tensor | None = None):
+    """The backward launch of ``history_attention`` (``tt_history_attention_bwd_f32``) from the forward's ``batch_ids``,
+    ``weights`` and ``pooled`` and ``dy`` [n_bags, dim]: ``slot_grads`` [n_bags * L, dim] gets ONE gradient row per kept slot
+    (w_j dy[b] + de_j a / sqrt(dim), de_j = w_j (<dy[b], h_j> - <dy[b], pooled[b]>); a skipped slot's row is left untouched) -
+    what ``sparse_sgd_`` / ``sparse_adagrad_`` / ``adam_step_`` take with a plain ``SparsePlan(n_bags * L)`` run over
+    ``batch_ids`` - and ``dattn_slabs`` [n_slabs, dim + L] the gradient of ``attn`` as slabs over contiguous bags, every slab
+    written in full: the form ``make_dense_seg`` / ``make_adam_seg`` sum.  Both are allocated when None (the slot rows
+    uninitialised, ``history_attention_num_slabs(n_bags)`` slabs).  Returns (slot_grads, dattn_slabs)."""
+    _chk(table, torch.float32, "table", 2)
+    _chk(batch_ids, torch.int64, "batch_ids")
+    _chk(weights, torch.float32, "weights", 2)
+    _chk(pooled, torch.float32, "pooled", 2)
+    _chk(dy, torch.float32, "dy", 2)
+    _chk(attn, torch.float32, "attn", 1)
+    n_bags, d = dy.shape
+    L = int(L)
+    if table.shape[1] != d or tuple(pooled.shape) != (n_bags, d):
+        raise RuntimeError(f"history_attention_bwd: dy and pooled must be [n_bags, dim] with the table's dim {table.shape[1]}, got "
+                           f"{tuple(dy.shape)} and {tuple(pooled.shape)}")
+    if tuple(weights.shape) != (n_bags, L) or batch_ids.numel() != n_bags * L:
+        raise RuntimeError(f"history_attention_bwd: weights must be [{n_bags}, {L}] and batch_ids hold {n_bags * L} entries, got "
+                           f"{tuple(weights.shape)} and {batch_ids.numel()}")
+    if attn.numel() != d + L:
+        raise RuntimeError(f"history_attention_bwd: attn must hold dim + L = {d + L} entries, got {attn.numel()}")
+    if slot_grads is None:
+        slot_grads = torch.empty((n_bags * L, d), dtype=torch.float32, device=table.device)
+    _chk(slot_grads, torch.float32, "slot_grads", 2)
+    if tuple(slot_grads.shape) != (n_bags * L, d):
+        raise RuntimeError(f"history_attention_bwd: slot_grads must be [{n_bags * L}, {d}] (n_bags * L, dim), got {tuple(slot_grads.shape)}")
+    if dattn_slabs is None:
+        dattn_slabs = torch.empty((history_attention_num_slabs(n_bags), d + L), dtype=torch.float32, device=table.device)
+    _chk(dattn_slabs, torch.float32, "dattn_slabs", 2)
+    if dattn_slabs.shape[0] < 1 or dattn_slabs.shape[1] != d + L:
+        raise RuntimeError(f"history_attention_bwd: dattn_slabs must be [n_slabs, {d + L}] (dim + L), got {tuple(dattn_slabs.shape)}")
+    _lib.check(_lib.load().tt_history_attention_bwd_f32(_p(table), table.shape[0], d, L, _p(batch_ids), _p(weights), _p(pooled),
+                                                        _p(dy), n_bags, _p(attn), _p(slot_grads), _p(dattn_slabs),
+                                                        dattn_slabs.shape[0], _stream()), "tt_history_attention_bwd_f32")
+    return slot_grads, dattn_slabs
+
+
 def embedding_bag_bwd(dy: torch.Tensor, inv: torch.Tensor | None, order: torch.Tensor, L: int, order_bags: torch.Tensor,
                       gs: torch.Tensor | None = None):
     """The backward launch of ``embedding_bag`` (``tt_embedding_bag_bwd_f32``): ``gs[b, :] = dy[b, :] * inv[b]`` (``gs`` None -

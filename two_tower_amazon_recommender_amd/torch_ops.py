@@ -9,6 +9,8 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
     rows = torch.ops.twotower.embedding_gather(table, ids)
     pooled = torch.ops.twotower.embedding_bag(table, tokens, bag_rows, "mean")
     x = torch.ops.twotower.history_bag(hist_table, histories, user_ids, item_ids, user_table, user_ids, "mean")
+    x, w, pooled, slot_ids = torch.ops.twotower.history_attention(hist_table, histories, user_ids, item_ids, user_table, user_ids,
+                                                                  attn)        # autograd w.r.t. attn = [query | recency bias]
     x = x + torch.ops.twotower.dense_features(feat, ids, mean, inv_std, proj, clip)   # autograd w.r.t. proj
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
@@ -113,6 +115,68 @@ def history_bag(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], exclu
 @history_bag.register_fake
 def _(table, tokens, bag_rows, exclude, base_table, base_ids, pooling="mean"):
     return table.new_empty(((tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), table.shape[1]))
+
+
+@torch.library.custom_op(f"{NS}::history_attention", mutates_args=(), device_types="cuda")
+def history_attention(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], exclude: Optional[Tensor],
+                      base_table: Optional[Tensor], base_ids: Optional[Tensor], attn: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The history bag pooled by a learned query with a recency bias (``ops.history_attention``; ``attn`` [dim + L] = [a | p]):
+    (out [n_bags, dim] = base row + sum_j w_j table[t_j], weights [n_bags, L], pooled [n_bags, dim], batch_ids [n_bags * L]
+    int64 - the slots' tokens, -1 where skipped).  Autograd with respect to ``attn`` only (from the gradients of ``out`` and
+    ``pooled``), through ``twotower::history_attention_bwd``.  The table's gradient is sparse - one row per kept slot, the first
+    result of ``history_attention_bwd`` - and goes through ``sparse_update_`` / ``sparse_adam_`` with ``batch_ids`` as the ids;
+    the base table's gradient rows are the gradient of ``out`` itself."""
+    if (base_table is None) != (base_ids is None):
+        raise ValueError("history_attention: base_table and base_ids go together")
+    c = lambda t: None if t is None else t.contiguous()
+    n_bags = tokens.shape[0] if bag_rows is None else bag_rows.shape[0]
+    ids = torch.empty(n_bags * tokens.shape[1], dtype=torch.int64, device=table.device)
+    out, weights, pooled = ops.history_attention(table.contiguous(), tokens.contiguous(), attn.contiguous(), c(bag_rows), c(exclude),
+                                                 None if base_table is None else (c(base_table), c(base_ids)), batch_ids=ids)
+    return out, weights, pooled, ids
+
+
+@history_attention.register_fake
+def _(table, tokens, bag_rows, exclude, base_table, base_ids, attn):
+    n_bags, L = (tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), tokens.shape[1]
+    return (table.new_empty((n_bags, table.shape[1])), table.new_empty((n_bags, L)), table.new_empty((n_bags, table.shape[1])),
+            tokens.new_empty((n_bags * L,), dtype=torch.int64))
+
+
+@torch.library.custom_op(f"{NS}::history_attention_bwd", mutates_args=(), device_types="cuda")
+def history_attention_bwd(table: Tensor, batch_ids: Tensor, weights: Tensor, pooled: Tensor, dy: Tensor,
+                          attn: Tensor) -> Tuple[Tensor, Tensor]:
+    """(slot_grads [n_bags * L, dim], dattn [dim + L]) of ``history_attention`` given dL/dout and what the forward returned: one
+    gradient row per kept slot (a skipped slot's row is zero here) for ``sparse_update_`` / ``sparse_adam_`` with ``batch_ids``
+    as the ids, and the gradient of ``attn``, the backward launch's slabs summed."""
+    n_bags, L = weights.shape
+    slot_grads = torch.zeros((n_bags * L, table.shape[1]), dtype=torch.float32, device=table.device)
+    _, slabs = ops.history_attention_bwd(table.contiguous(), batch_ids.contiguous(), weights.contiguous(), pooled.contiguous(),
+                                         dy.contiguous(), attn.contiguous(), L, slot_grads=slot_grads)
+    return slot_grads, slabs.sum(dim=0)
+
+
+@history_attention_bwd.register_fake
+def _(table, batch_ids, weights, pooled, dy, attn):
+    return table.new_empty((weights.shape[0] * weights.shape[1], table.shape[1])), torch.empty_like(attn, memory_format=torch.contiguous_format)
+
+
+def _attention_setup(ctx, inputs, output):
+    table, attn = inputs[0], inputs[6]
+    _, weights, pooled, batch_ids = output
+    ctx.save_for_backward(table, batch_ids, weights, pooled, attn)
+
+
+def _attention_backward(ctx, d_out, d_weights, d_pooled, d_ids):
+    table, batch_ids, weights, pooled, attn = ctx.saved_tensors
+    dy = d_out if d_pooled is None else (d_pooled if d_out is None else d_out + d_pooled)
+    dattn = None
+    if ctx.needs_input_grad[6] and dy is not None:
+        dattn = torch.ops.twotower.history_attention_bwd(table, batch_ids, weights, pooled, dy, attn)[1]
+    return None, None, None, None, None, None, dattn
+
+
+history_attention.register_autograd(_attention_backward, setup_context=_attention_setup)
 
 
 @torch.library.custom_op(f"{NS}::sample_candidates", mutates_args=(), device_types="cuda")
@@ -657,5 +721,5 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
     ops.adam_step_([(table, exp_avg, exp_avg_sq, grads.contiguous(), plan)], [], ops.AdamHyper(lr, beta1, beta2, eps, step))
 
 
-OPS = ("embedding_gather", "embedding_bag", "history_bag", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
+OPS = ("embedding_gather", "embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "sparse_update_", "sparse_adam_")

@@ -41,6 +41,8 @@ TID_DENSE_BASE = 16
 TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
 TID_CROSS_BASE = 48                          # the cross kernels: layer l of tower t is 48 + 2 l + t (48..53)
 MAX_CROSS_LAYERS = 3
+# poolings of the user-history feature: the bag launch's three and the attention pool (csrc/history_attn.hip), history only
+HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention",)
 TID_DROPOUT_BASE = 64
 
 
@@ -109,6 +111,9 @@ class TwoTowerConfig:
     # (``set_user_histories``), their rows of a [n_items, embedding_dim] table of its own are pooled ("sum" | "mean" | "sqrtn") and
     # ADDED to the user tower's input - in the train step without the pair's own item (leave-one-out: pooled into the query it is
     # scored against, the label would leak).  0 = no such feature.  Single-GPU trainer, materialised tower inputs, no graph capture.
+    # history_pooling "attention": a softmax over the kept slots of e_j = <row_j, a> / sqrt(embedding_dim) + p[recency rank of j]
+    # with one trained vector [a | p] (embedding_dim + user_history_len floats, zero-initialised: a fresh model pools by the
+    # mean; no l2 penalty) - the histories are stored oldest first, and the rank counts the kept slots behind j.
     user_history_len: int = 0
     history_pooling: str = "mean"
     # pooled item-title feature (the reference's preprocessing.text_fields: title; TFRS TextVectorization -> Embedding ->
@@ -131,11 +136,18 @@ class TwoTowerConfig:
     def symmetric(self) -> bool:
         return self.user_dims == self.item_dims
 
-    def dense_segment_count(self, cross: bool = True) -> int:
+    @property
+    def history_attention(self) -> bool:
+        """The history feature is on and pooled by attention."""
+        return self.user_history_len > 0 and self.history_pooling == "attention"
+
+    def dense_segment_count(self, cross: bool = True, attention: bool = True) -> int:
         """Segments of the dense optimizer launches: a kernel and a bias per Dense layer, a projection kernel per side with
-        numeric features, two for the rating head, two for the cross layers (``cross=False``: without those)."""
+        numeric features, two for the rating head, two for the cross layers (``cross=False``: without those), one for the
+        history attention's vector (``attention=False``: without it)."""
         return (2 * (len(self.user_dims) + len(self.item_dims)) + (self.n_user_features > 0) + (self.n_item_features > 0)
-                + 2 * (self.rating_weight > 0) + 2 * (bool(cross) and self.cross_layers > 0))
+                + 2 * (self.rating_weight > 0) + 2 * (bool(cross) and self.cross_layers > 0)
+                + (bool(attention) and self.history_attention))
 
     def validate(self):
         if self.optimizer not in ("sgd", "adagrad", "adam"):
@@ -174,8 +186,8 @@ class TwoTowerConfig:
             raise ValueError(f"title_pooling must be one of {tuple(ops.POOLINGS)}")
         if not 0 <= self.user_history_len <= 64:
             raise ValueError("user_history_len must be 0 (no history feature) or in 1..64")
-        if self.history_pooling not in ops.POOLINGS:
-            raise ValueError(f"history_pooling must be one of {tuple(ops.POOLINGS)}")
+        if self.history_pooling not in HISTORY_POOLINGS:
+            raise ValueError(f"history_pooling must be one of {HISTORY_POOLINGS}")
         if self.user_history_len and self.n_items >= 2 ** 31:
             raise ValueError("user_history_len > 0 needs n_items < 2^31: the history tokens are int32")
         if self.user_history_len and self.candidate_sampling == "mixed":
@@ -214,6 +226,10 @@ class TwoTowerConfig:
             raise ValueError(f"cross_layers must be an int in 0..{MAX_CROSS_LAYERS} (0: no cross layers)")
         if cl and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
             raise ValueError(f"cross_layers > 0 needs an embedding_dim that is a multiple of 32 in 32..256 (got {self.embedding_dim})")
+        if self.history_attention and self.dense_segment_count(attention=False) <= _lib.TT_MAX_DENSE_SEGS < self.dense_segment_count():
+            raise NotImplementedError(f"the history attention adds one dense segment to the model's "
+                                      f"{self.dense_segment_count(attention=False)}: the optimizer launches take at most "
+                                      f"{_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers, or drop a feature)")
         if cl and self.dense_segment_count(False) <= _lib.TT_MAX_DENSE_SEGS < self.dense_segment_count():
             raise NotImplementedError(f"the cross layers add two dense segments to the model's {self.dense_segment_count(False)}: the "
                                       f"optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
@@ -487,7 +503,11 @@ class TwoTowerTrainer:
         n_cross = 2 * ncl * (d * d + d)
         n_front = n_user + n_item + (fu + fi) * d + n_head
         c_off = (n_front + 3) // 4 * 4 if ncl else n_front
-        self.dense_flat = torch.zeros(c_off + n_cross, device=dev)
+        # the history attention's vector [a | p] sits behind the cross parameters, from a 16-byte boundary (the launches load a
+        # as float4s); with any other pooling dense_flat keeps its size
+        self._attn_on = cfg.history_attention
+        a_off = (c_off + n_cross + 3) // 4 * 4
+        self.dense_flat = torch.zeros(a_off + d + cfg.user_history_len if self._attn_on else c_off + n_cross, device=dev)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
         # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
@@ -538,6 +558,7 @@ class TwoTowerTrainer:
         # every user's history row (all padding until set_user_histories) and the per-step buffers of the bag launches
         self.history_table = self.history_accum = self.history_m = self.history_v = None
         self.user_history = self.history_plan = self.history_ids = self.history_inv = self.history_gs = None
+        self.history_attn = self.history_weights = self.history_pooled = self.history_slot_grads = self._ha_slabs = None
         if cfg.user_history_len:
             lh = cfg.user_history_len
             self.history_table = torch.empty(cfg.n_items, d, device=dev)
@@ -545,10 +566,22 @@ class TwoTowerTrainer:
             if adam:
                 self.history_m, self.history_v = torch.zeros_like(self.history_table), torch.zeros_like(self.history_table)
             self.user_history = torch.full((cfg.n_users, lh), -1, dtype=torch.int32, device=dev)
-            self.history_plan = ops.BagPlan(b, lh, dev)
             self.history_ids = torch.empty(b * lh, dtype=torch.int64, device=dev)
-            self.history_inv = torch.empty(b, device=dev)
-            self.history_gs = torch.empty(b, d, device=dev) if cfg.history_pooling != "sum" else None
+            if self._attn_on:
+                # attention pooling: the slots' gradient rows differ, so the update takes one row per slot through a plain sort
+                # plan; the step keeps the weights and the pooled rows for the backward launch, which also writes the slabs of
+                # the attention vector's dense segment
+                self.history_plan = ops.SparsePlan(b * lh, dev)
+                self.history_attn = self.dense_flat[a_off:a_off + d + lh]
+                self.history_weights = torch.empty(b, lh, device=dev)
+                self.history_pooled = torch.empty(b, d, device=dev)
+                self.history_slot_grads = torch.zeros(b * lh, d, device=dev)
+                self._ha_nslabs = ops.history_attention_num_slabs(b)
+                self._ha_slabs = torch.empty(self._ha_nslabs, d + lh, device=dev)
+            else:
+                self.history_plan = ops.BagPlan(b, lh, dev)
+                self.history_inv = torch.empty(b, device=dev)
+                self.history_gs = torch.empty(b, d, device=dev) if cfg.history_pooling != "sum" else None
         # numeric side features, per side: the fixed feature matrix with its normalisation (zeros / mean 0 / inv_std 1 until the
         # setter ran: z = 0, nothing is added), the projection kernel (a view of dense_flat), the step's normalised rows (kept for
         # the backward launch) and the gradient slabs the dense optimizer segment sums
@@ -692,6 +725,18 @@ class TwoTowerTrainer:
                 if adam:
                     self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs,
                                                              self._c_nslabs, reg, slab_stride=n_cross))
+        if self._attn_on:                        # one more segment: the attention vector [a | p], no l2
+            prm = self.history_attn
+            lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
+            if len(self._segs) == _lib.TT_MAX_DENSE_SEGS:
+                raise NotImplementedError(f"the history attention adds one dense segment to the model's {len(self._segs)}: the "
+                                          f"optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 "
+                                          "layers, or drop a feature)")
+            self._segs.append(ops.make_dense_seg(prm, None if self.dense_accum is None else self.dense_accum[lo:hi], self._ha_slabs,
+                                                 self._ha_nslabs, 0.0))
+            if adam:
+                self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], self._ha_slabs,
+                                                         self._ha_nslabs, 0.0))
         if len(self._segs) > _lib.TT_MAX_DENSE_SEGS and n_before_cross <= _lib.TT_MAX_DENSE_SEGS:
             raise NotImplementedError(f"the cross layers add two dense segments to the model's {n_before_cross}: the optimizer launches "
                                       f"take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
@@ -899,6 +944,12 @@ class TwoTowerTrainer:
     def _user_inputs(self, user_ids, out, exclude=None, keep: bool = False):
         """The user tower's input rows with the history feature, in ONE launch: user_table[u] + the pooled history rows of u,
         without the items ``exclude`` (the train step's positives).  ``keep``: the slot tokens and scales stay for the update."""
+        if self._attn_on:                        # (the weights and pooled rows of an inference pass are never read)
+            n = user_ids.numel()
+            ops.history_attention(self.history_table, self.user_history, self.history_attn, bag_rows=user_ids, exclude=exclude,
+                                  base=(self.user_table, user_ids), out=out, batch_ids=self.history_ids if keep else None,
+                                  weights=self.history_weights[:n], pooled=self.history_pooled[:n], oob_flag=self.oob)
+            return
         ops.history_bag(self.history_table, self.user_history, bag_rows=user_ids, exclude=exclude, base=(self.user_table, user_ids),
                         pooling=self.cfg.history_pooling, out=out, batch_ids=self.history_ids if keep else None,
                         inv=self.history_inv if keep else None, oob_flag=self.oob)
@@ -924,6 +975,14 @@ class TwoTowerTrainer:
         if self._feature_sides:
             towers = {"user": self.user_tower, "item": self.item_tower}
             ops.dense_features_bwd(*[(getattr(self, f"_fz_{side}"), towers[side].demb, slabs) for side, _, slabs, _ in self._feature_sides])
+
+    def _history_backward(self):
+        """Attention pooling: the slots' gradient rows and the attention vector's gradient slabs from the user tower's input
+        gradient (demb), one launch after the towers' backward - in front of the optimizer launches, which update the vector."""
+        if self._attn_on:
+            ops.history_attention_bwd(self.history_table, self.history_ids, self.history_weights, self.history_pooled,
+                                      self.user_tower.demb, self.history_attn, self.cfg.user_history_len,
+                                      slot_grads=self.history_slot_grads, dattn_slabs=self._ha_slabs)
 
     def _item_inputs(self, user_ids, item_ids, category_ids, train: bool = False):
         """K1 as its own launch (fuse_lookup = False): both towers' input rows; the hashed category's row is summed
@@ -1037,6 +1096,7 @@ class TwoTowerTrainer:
             ut.backward(cfg.dropout_rate, lookup=lks[0])
             it.backward(cfg.dropout_rate, lookup=lks[1])
         self._features_backward()
+        self._history_backward()
         self.step_index += 1
         return self.loss
 
@@ -1148,10 +1208,14 @@ class TwoTowerTrainer:
 
     def _apply_history_gradients(self, adam_step: int):
         """The history table's update, the mirror of ``_apply_title_gradients`` on the user side: the sort plan over the step's
-        slot items (an excluded slot is -1 there: no gradient), the bags' scaled user-tower input gradient rows, the optimizer."""
+        slot items (an excluded slot is -1 there: no gradient), the bags' scaled user-tower input gradient rows, the optimizer.
+        Attention pooling: the slots' own gradient rows (``_history_backward`` wrote them) through the plain sort plan."""
         cfg, plan = self.cfg, self.history_plan
         plan.run(self.history_ids, cfg.n_items)
-        gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
+        if self._attn_on:                        # one gradient row per kept slot, written by the step's backward launch
+            gs = self.history_slot_grads
+        else:
+            gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
         if cfg.optimizer == "adam":
             ops.adam_step_([(self.history_table, self.history_m, self.history_v, gs, plan)], [],
                            ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
