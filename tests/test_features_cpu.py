@@ -12,7 +12,7 @@ import torch
 
 import features_check as fc
 from two_tower_amazon_recommender_amd import _lib, data, ops
-from two_tower_amazon_recommender_amd.trainer import TwoTowerConfig, TwoTowerTrainer
+from two_tower_amazon_recommender_amd.trainer import EmbeddingTable, FeatureSide, TwoTowerConfig, TwoTowerTrainer
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
@@ -228,14 +228,11 @@ def test_feature_off_keeps_the_fields_in_front_of_the_history_block_and_the_chec
         s = Stub()
         s.cfg = TwoTowerConfig(n_users=10, n_items=10, optimizer="adagrad", n_user_features=5 if "user" in sides else 0,
                                n_item_features=5 if "item" in sides else 0)
-        for name in ("user_table", "item_table", "dense_flat", "user_accum", "item_accum", "dense_accum"):
-            setattr(s, name, name)
-        for side in sides:
-            for k in (f"{side}_features", f"{side}_feature_mean", f"{side}_feature_inv_std"):
-                setattr(s, k, k)
-        s.cat_table = s.title_table = s.history_table = None
+        s.dense_flat, s.dense_accum = "dense_flat", "dense_accum"
+        s.tables = {p: EmbeddingTable.new(s.cfg, "cpu", p, 0, 10, None) for p in ("user", "item")}     # (the records: CPU tensors)
+        s.sides = {side: FeatureSide(side, f"{side}_features", f"{side}_feature_mean", f"{side}_feature_inv_std", None, None, None, 1)
+                   for side in sides}
         s.step_index, s.dropout_seed, s.adam_step = 0, 0, 1
-        s._feature_sides = [(side, None, None, 1) for side in sides]
         more = {f"{side}{k}" for side in sides for k in ("_features", "_feature_mean", "_feature_inv_std")}
         assert set(TwoTowerTrainer.state_dict(s)) == {"config", "user_table", "item_table", "dense", "step_index", "dropout_seed",
                                                       "user_accum", "item_accum", "dense_accum"} | more

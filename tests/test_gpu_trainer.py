@@ -339,6 +339,65 @@ def test_checkpoint_resume_continues_the_dropout_stream(dev):
     assert torch.equal(a.dense_flat, b2.dense_flat) and torch.equal(a.dense_accum, b2.dense_accum)
 
 
+ALL_FEATURES_KEYS = {
+    "sgd": {"config", "dense", "step_index", "dropout_seed", "user_table", "item_table", "cat_table", "title_table", "item_titles",
+            "history_table", "user_history", "user_features", "user_feature_mean", "user_feature_inv_std", "item_features",
+            "item_feature_mean", "item_feature_inv_std"},
+}
+ALL_FEATURES_KEYS["adagrad"] = ALL_FEATURES_KEYS["sgd"] | {"user_accum", "item_accum", "cat_accum", "title_accum", "history_accum",
+                                                           "dense_accum"}
+ALL_FEATURES_KEYS["adam"] = ALL_FEATURES_KEYS["sgd"] | {"user_m", "user_v", "item_m", "item_v", "cat_m", "cat_v", "title_m", "title_v",
+                                                        "history_m", "history_v", "dense_m", "dense_v", "adam_step"}
+
+
+@pytest.mark.parametrize("opt", ["sgd", "adagrad", "adam"])
+def test_all_features_checkpoint_round_trip_is_bit_identical(dev, opt):
+    """All five embedding tables and every block of dense_flat at once: a run resumed from a checkpoint (a trainer built from
+    the checkpoint's config, other initial values) continues bit for bit like the uninterrupted one, and the checkpoint holds
+    exactly the keys written out above."""
+    from two_tower_amazon_recommender_amd import data
+    seed, b, lh = 23, 64, 5
+    cfg = TwoTowerConfig(n_users=300, n_items=200, embedding_dim=32, tower_dims=[64, 32], batch_size=b, optimizer=opt,
+                         n_category_buckets=7, n_title_buckets=50, title_max_tokens=4, user_history_len=lh, history_pooling="attention",
+                         n_user_features=3, n_item_features=2, rating_weight=0.5, rating_hidden=32, cross_layers=2,
+                         normalize_embeddings=True)
+
+    def fresh():
+        tr = TwoTowerTrainer(TwoTowerConfig(**cfg.__dict__), dev, seed=seed)
+        pairs = [tr.synthetic_batch(seed, s, "Z") for s in range(4)]
+        u, i = (torch.cat([p[k] for p in pairs]).cpu().numpy() for k in (0, 1))
+        tr.set_user_histories(torch.from_numpy(data.user_histories(u, i, cfg.n_users, lh)).to(dev))
+        tr.set_item_titles(tr.synthetic_item_titles(seed))
+        tr.set_user_features(tr.synthetic_user_features(seed)); tr.set_item_features(tr.synthetic_item_features(seed))
+        return tr
+
+    def run(tr, steps):
+        for s in steps:
+            u, i = tr.synthetic_batch(seed, s, "Z")
+            tr.step(u, i, category_ids=tr.synthetic_categories(seed, s), ratings=((u + 2 * i) % 5 + 1).to(torch.float32))
+    a = fresh()
+    assert set(a.tables) == {"user", "item", "cat", "title", "history"} and len(a._segs) == cfg.dense_segment_count() == 8 + 2 + 2 + 2 + 1
+    run(a, range(4))
+    bt = fresh()
+    run(bt, range(2))
+    sd = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in bt.state_dict().items()}
+    assert set(sd) == ALL_FEATURES_KEYS[opt]
+    c = TwoTowerTrainer(TwoTowerConfig(**sd["config"]), dev, seed=seed + 1)          # other initial values, nothing set
+    assert not torch.equal(c.dense_flat, bt.dense_flat)
+    c.load_state_dict(sd)
+    run(c, range(2, 4))
+    a.check_ids(); c.check_ids()
+    names = ["dense_flat", "loss", "history_attn", "item_titles", "user_history"] + [f"{p}_table" for p in a.tables]
+    names += {"sgd": [], "adagrad": ["dense_accum"] + [f"{p}_accum" for p in a.tables],
+              "adam": ["dense_m", "dense_v"] + [f"{p}_{k}" for p in a.tables for k in "mv"]}[opt]
+    for k in names:
+        assert torch.equal(getattr(a, k), getattr(c, k)), k
+    assert a.step_index == c.step_index == 4 and a.adam_step == c.adam_step == (5 if opt == "adam" else 1)
+    assert a.history_attn.any() and not torch.equal(a.dense_flat, bt.dense_flat)      # every block trained on the way
+    for t in a.tables.values():
+        assert not torch.equal(t.table, bt.tables[t.prefix].table), t.prefix
+
+
 def test_out_of_range_id_is_reported_by_the_periodic_poll_with_its_step(dev):
     """No per-epoch wait: step() polls the flag every `flag_poll_every` steps through an asynchronous 4-byte copy and
     raises one interval later, naming the step range."""

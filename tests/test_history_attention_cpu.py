@@ -113,7 +113,7 @@ def test_field_order_checkpoint_keys_and_segment_count():
     assert names[k - 2:k] == ["user_history_len", "history_pooling"] and names[-3:] == ["n_title_buckets", "title_max_tokens", "title_pooling"]
     k = names.index("n_user_features")
     assert names[k - 1] == "cross_layers" and names[k:k + 3] == ["n_user_features", "n_item_features", "feature_clip"]
-    from two_tower_amazon_recommender_amd.trainer import TwoTowerTrainer
+    from two_tower_amazon_recommender_amd.trainer import EmbeddingTable, TwoTowerTrainer
 
     class Stub:
         pass
@@ -121,10 +121,10 @@ def test_field_order_checkpoint_keys_and_segment_count():
     for pooling in ("mean", "attention"):
         s = Stub()
         s.cfg = TwoTowerConfig(n_users=10, n_items=10, optimizer="adam", user_history_len=3, history_pooling=pooling)
-        for name in ("user_table", "item_table", "dense_flat", "user_accum", "item_accum", "dense_accum", "user_m", "user_v", "item_m",
-                     "item_v", "dense_m", "dense_v", "history_accum", "history_m", "history_v", "user_history", "history_table"):
+        for name in ("dense_flat", "dense_accum", "dense_m", "dense_v"):
             setattr(s, name, name)
-        s.cat_table = s.title_table = None
+        s.tables = {p: EmbeddingTable.new(s.cfg, "cpu", p, 0, 10, None, {"user_history": "user_history"} if p == "history" else None)
+                    for p in ("user", "item", "history")}                                              # (the records: CPU tensors)
         s.step_index, s.dropout_seed, s.adam_step = 0, 0, 1
         sd = TwoTowerTrainer.state_dict(s)
         keys[pooling] = set(sd)

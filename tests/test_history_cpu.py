@@ -160,7 +160,7 @@ def test_feature_off_keeps_the_field_order_and_the_checkpoint_keys():
     names = [f.name for f in dataclasses.fields(TwoTowerConfig)]
     k = names.index("n_title_buckets")
     assert names[k - 2:k] == ["user_history_len", "history_pooling"] and names[-3:] == ["n_title_buckets", "title_max_tokens", "title_pooling"]
-    from two_tower_amazon_recommender_amd.trainer import TwoTowerTrainer
+    from two_tower_amazon_recommender_amd.trainer import EmbeddingTable, TwoTowerTrainer
 
     class Stub:
         pass
@@ -169,11 +169,11 @@ def test_feature_off_keeps_the_field_order_and_the_checkpoint_keys():
         for hist in (False, True):
             s = Stub()
             s.cfg = TwoTowerConfig(n_users=10, n_items=10, optimizer=opt, user_history_len=3 if hist else 0)
-            for name in ("user_table", "item_table", "dense_flat", "user_accum", "item_accum", "dense_accum", "user_m", "user_v", "item_m",
-                         "item_v", "dense_m", "dense_v", "history_accum", "history_m", "history_v", "user_history"):
+            for name in ("dense_flat", "dense_accum", "dense_m", "dense_v"):
                 setattr(s, name, name)
-            s.cat_table = s.title_table = None
-            s.history_table = "history_table" if hist else None
+            s.tables = {p: EmbeddingTable.new(s.cfg, "cpu", p, 0, 10, None) for p in ("user", "item")}     # (the records: CPU tensors)
+            if hist:
+                s.tables["history"] = EmbeddingTable.new(s.cfg, "cpu", "history", 0, 10, None, {"user_history": "user_history"})
             s.step_index, s.dropout_seed, s.adam_step = 0, 0, 1
             sd = TwoTowerTrainer.state_dict(s)
             more = set()

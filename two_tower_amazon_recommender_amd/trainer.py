@@ -142,12 +142,11 @@ class TwoTowerConfig:
         return self.user_history_len > 0 and self.history_pooling == "attention"
 
     def dense_segment_count(self, cross: bool = True, attention: bool = True) -> int:
-        """Segments of the dense optimizer launches: a kernel and a bias per Dense layer, a projection kernel per side with
-        numeric features, two for the rating head, two for the cross layers (``cross=False``: without those), one for the
-        history attention's vector (``attention=False``: without it)."""
-        return (2 * (len(self.user_dims) + len(self.item_dims)) + (self.n_user_features > 0) + (self.n_item_features > 0)
-                + 2 * (self.rating_weight > 0) + 2 * (bool(cross) and self.cross_layers > 0)
-                + (bool(attention) and self.history_attention))
+        """Segments of the dense optimizer launches (``dense_layout``): a kernel and a bias per Dense layer, a projection kernel
+        per side with numeric features, two for the rating head, two for the cross layers (``cross=False``: without those), one
+        for the history attention's vector (``attention=False``: without it)."""
+        skip = {g for g, on in (("cross", cross), ("attention", attention)) if not on}
+        return sum(s.group not in skip for s in dense_layout(self).segments)
 
     def validate(self):
         if self.optimizer not in ("sgd", "adagrad", "adam"):
@@ -226,13 +225,124 @@ class TwoTowerConfig:
             raise ValueError(f"cross_layers must be an int in 0..{MAX_CROSS_LAYERS} (0: no cross layers)")
         if cl and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
             raise ValueError(f"cross_layers > 0 needs an embedding_dim that is a multiple of 32 in 32..256 (got {self.embedding_dim})")
-        if self.history_attention and self.dense_segment_count(attention=False) <= _lib.TT_MAX_DENSE_SEGS < self.dense_segment_count():
-            raise NotImplementedError(f"the history attention adds one dense segment to the model's "
-                                      f"{self.dense_segment_count(attention=False)}: the optimizer launches take at most "
-                                      f"{_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers, or drop a feature)")
-        if cl and self.dense_segment_count(False) <= _lib.TT_MAX_DENSE_SEGS < self.dense_segment_count():
-            raise NotImplementedError(f"the cross layers add two dense segments to the model's {self.dense_segment_count(False)}: the "
-                                      f"optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
+        # the optimizer launches take TT_MAX_DENSE_SEGS segments.  Refused: a model whose optional blocks do not fit - blamed on
+        # the block that holds the first segment past the limit (towers that are over it on their own: on the first optional block)
+        segs = dense_layout(self).segments
+        if len(segs) > _lib.TT_MAX_DENSE_SEGS and segs[-1].group != "towers":
+            first = max(_lib.TT_MAX_DENSE_SEGS, sum(s.group == "towers" for s in segs))
+            group = segs[first].group
+            raise NotImplementedError(f"{_SEGMENT_GROUPS[group]} to the model's {[s.group for s in segs].index(group)}: the optimizer "
+                                      f"launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers, or drop a feature)")
+
+
+# what each optional block of ``dense_layout`` adds to the dense optimizer launches (validate's refusal)
+_SEGMENT_GROUPS = {"features": "the numeric side features add one dense segment per side",
+                   "head": "the rating head adds two dense segments",
+                   "cross": "the cross layers add two dense segments",
+                   "attention": "the history attention adds one dense segment"}
+
+
+@dataclass(frozen=True)
+class DenseBlock:
+    """One parameter of ``dense_flat``: the floats [offset, end) viewed as ``shape``.  ``glorot`` = (tensor id of the synthetic
+    initialiser, fan_in + fan_out) of a kernel; None: the parameter starts at zero."""
+    name: str
+    offset: int
+    shape: tuple
+    glorot: tuple | None = None
+
+    @property
+    def end(self) -> int:
+        return self.offset + math.prod(self.shape)
+
+    def view(self, flat):
+        return flat[self.offset:self.end].view(self.shape)
+
+
+@dataclass(frozen=True)
+class DenseSegment:
+    """One segment of the dense optimizer launches: the floats [lo, hi) of ``dense_flat`` (and of its accumulator / moments),
+    whether the l2 term applies, the floats between two of its gradient slabs, and the block group it belongs to."""
+    name: str
+    lo: int
+    hi: int
+    l2: bool
+    stride: int
+    group: str                                   # "towers" | "features" | "head" | "cross" | "attention"
+
+    @property
+    def size(self) -> int:
+        return self.hi - self.lo
+
+
+@dataclass(frozen=True)
+class DenseLayout:
+    blocks: dict                                 # name -> DenseBlock, in the order of dense_flat
+    segments: tuple                              # DenseSegment, in the order of the optimizer launches
+    total: int                                   # floats of dense_flat
+
+    def segment(self, name: str) -> DenseSegment:
+        return next(s for s in self.segments if s.name == name)
+
+
+def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
+    """Where every dense parameter sits in ``dense_flat`` and which optimizer segment covers it - a function of the config alone
+    (plain integers: no device, no library), and the ONE place that knows.  In floats and in this order:
+
+        user tower, item tower     per layer W [k, n] | b [n]; a segment per W (l2) and per b
+        P_user [Fu, D], P_item     the numeric side features' projection kernels, a segment each (l2)
+        rating head                W1 [2S, H] | w2 [H] | b1 [H] | b2 [1]; the segments W1 | w2 (l2) and b1 | b2
+        cross layers               from a 16-byte boundary (the head's parameter count is odd, the cross launches load float4s -
+                                   up to 3 idle floats): user W_0 .. W_{L-1} | item W_0 .. | user b_0 .. | item b_0 ..; every
+                                   kernel is one segment (l2), every bias another - their gradient slabs are laid out like the
+                                   parameters, so both segments' slab stride is the whole cross block
+        history attention          from a 16-byte boundary (the launches load a as float4s): [a (D) | p (user_history_len)],
+                                   one segment, no l2
+
+    Every optional block sits BEHIND what was there before it: switching one on moves no existing offset, and without the
+    attention vector dense_flat ends behind the cross block with no trailing pad."""
+    blocks, segs, off = {}, [], 0
+    d = cfg.embedding_dim
+
+    def block(name, shape, glorot=None):
+        nonlocal off
+        blocks[name] = blk = DenseBlock(name, off, tuple(shape), glorot)
+        off = blk.end
+        return blk
+
+    def segment(group, name, first, last, l2, stride=None):
+        segs.append(DenseSegment(name, first.offset, last.end, l2, last.end - first.offset if stride is None else stride, group))
+
+    sides = (("user", cfg.user_dims, cfg.n_user_features, TID_USER_FEATURE_PROJ),
+             ("item", cfg.item_dims, cfg.n_item_features, TID_ITEM_FEATURE_PROJ))
+    for t, (side, dims, _, _) in enumerate(sides):
+        for l, (k, n) in enumerate(zip([d] + dims, dims)):
+            w = block(f"{side}.W{l}", (k, n), (TID_DENSE_BASE + 2 * l + t, k + n))
+            b = block(f"{side}.b{l}", (n,))
+            segment("towers", w.name, w, w, True)
+            segment("towers", b.name, b, b, False)
+    for side, _, f, tid in sides:
+        if f:
+            p = block(f"P_{side}", (f, d), (tid, f + d))
+            segment("features", p.name, p, p, True)
+    if cfg.rating_weight > 0:                    # (w2 is the [H, 1] kernel of the output unit)
+        s, h = cfg.tower_dims[-1], cfg.rating_hidden
+        w1, w2 = block("head.W1", (2 * s, h), (TID_RATING_W1, 2 * s + h)), block("head.w2", (h,), (TID_RATING_W2, h + 1))
+        b1, b2 = block("head.b1", (h,)), block("head.b2", (1,))
+        segment("head", "head.kernels", w1, w2, True)
+        segment("head", "head.biases", b1, b2, False)
+    if cfg.cross_layers:
+        off = start = (off + 3) // 4 * 4
+        ws = [block(f"cross.{side}.W{l}", (d, d), (TID_CROSS_BASE + 2 * l + t, 2 * d))
+              for t, (side, _, _, _) in enumerate(sides) for l in range(cfg.cross_layers)]
+        bs = [block(f"cross.{side}.b{l}", (d,)) for side, _, _, _ in sides for l in range(cfg.cross_layers)]
+        segment("cross", "cross.kernels", ws[0], ws[-1], True, off - start)
+        segment("cross", "cross.biases", bs[0], bs[-1], False, off - start)
+    if cfg.history_attention:
+        off = (off + 3) // 4 * 4
+        a = block("history_attn", (d + cfg.user_history_len,))
+        segment("attention", a.name, a, a, False)
+    return DenseLayout(blocks, tuple(segs), off)
 
 
 class Tower:
@@ -473,6 +583,120 @@ def towers_backward(ut: "Tower", it: "Tower", dropout_rate: float = 0.0, on_embe
         layer(l, False, True)
 
 
+@dataclass
+class EmbeddingTable:
+    """One embedding table of the trainer with everything that belongs to it: the checkpoint prefix (``user`` -> the keys
+    ``user_table``, ``user_accum``, ``user_m``, ``user_v``), the tensor id of the synthetic initialiser, the optimizer state of the
+    configured optimizer (Adagrad: ``accum``; lazy Adam: ``m``, ``v``; else None), the sort plan of its updates, and ``extra`` -
+    the tensors checkpointed beside it under their own keys (the title / history token rows)."""
+    prefix: str
+    tensor_id: int
+    table: torch.Tensor
+    accum: torch.Tensor | None = None
+    m: torch.Tensor | None = None
+    v: torch.Tensor | None = None
+    plan: object = None
+    extra: dict = field(default_factory=dict)
+
+    @classmethod
+    def new(cls, cfg: TwoTowerConfig, dev, prefix: str, tensor_id: int, rows: int, plan, extra=None) -> "EmbeddingTable":
+        table = torch.empty(rows, cfg.embedding_dim, device=dev)
+        accum = torch.full_like(table, cfg.adagrad_initial_accumulator) if cfg.optimizer == "adagrad" else None
+        m, v = (torch.zeros_like(table), torch.zeros_like(table)) if cfg.optimizer == "adam" else (None, None)
+        return cls(prefix, tensor_id, table, accum, m, v, plan, dict(extra or {}))
+
+    def state(self) -> dict:
+        """Checkpoint key -> tensor."""
+        named = {"table": self.table, "accum": self.accum, "m": self.m, "v": self.v}
+        return {**{f"{self.prefix}_{k}": t for k, t in named.items() if t is not None}, **self.extra}
+
+    def init_synthetic(self, cfg: TwoTowerConfig, seed: int):
+        """Keras Embedding's U(-0.05, 0.05) from the counter-based generator; the optimizer state as freshly allocated."""
+        ops.fill_uniform_(self.table, seed, self.tensor_id, -0.05, 0.1)
+        if self.accum is not None:
+            self.accum.fill_(cfg.adagrad_initial_accumulator)
+        if self.m is not None:
+            self.m.zero_(), self.v.zero_()
+
+    def apply(self, cfg: TwoTowerConfig, grads, adam_step: int, adam_segs=()):
+        """The configured optimizer's update from this table's sort plan (which has run; a ``BagPlan`` after its ``backward``:
+        ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same lazy-Adam call."""
+        if cfg.optimizer == "adam":
+            ops.adam_step_([(self.table, self.m, self.v, grads, self.plan)], list(adam_segs),
+                           ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
+        elif cfg.optimizer == "sgd":
+            ops.sparse_sgd_(self.table, grads, self.plan, cfg.learning_rate)
+        else:
+            ops.sparse_adagrad_(self.table, self.accum, grads, self.plan, cfg.learning_rate, cfg.adagrad_epsilon)
+
+
+@dataclass
+class FeatureSide:
+    """The numeric side features of one tower: the fixed [rows, F] matrix with its normalisation, the projection kernel (a view
+    of dense_flat), the step's normalised rows (kept for the backward launch), the projection's gradient slabs and the tower
+    whose input rows the projected features are added to."""
+    side: str                                    # "user" | "item": the checkpoint keys' prefix
+    features: torch.Tensor
+    mean: torch.Tensor
+    inv_std: torch.Tensor
+    P: torch.Tensor
+    z: torch.Tensor
+    slabs: torch.Tensor
+    n_slabs: int
+    tower: object = None
+
+    def state(self) -> dict:
+        """Checkpoint key -> tensor (the kernel itself is part of ``dense``)."""
+        return {f"{self.side}_features": self.features, f"{self.side}_feature_mean": self.mean, f"{self.side}_feature_inv_std": self.inv_std}
+
+
+def _side_fields(fs: FeatureSide | None):
+    return (None,) * 6 if fs is None else (fs.features, fs.mean, fs.inv_std, fs.P, fs.z, fs.slabs)
+
+
+def _table_fields(t: EmbeddingTable | None):
+    return (None,) * 5 if t is None else (t.table, t.accum, t.m, t.v, t.plan)
+
+
+def _glorot_uniform_(w, seed: int, tensor_id: int, fan: int):
+    """Keras Glorot-uniform, limit sqrt(6 / (fan_in + fan_out)) - formed in f64 and rounded once to f32, the scale as the f32 sum
+    lim + lim: bit for bit what oracle.two_tower.synthetic_state draws."""
+    lim = torch.tensor(math.sqrt(6.0 / fan), dtype=torch.float64).to(torch.float32)
+    ops.fill_uniform_(w, seed, tensor_id, -lim.item(), (lim + lim).item())
+
+
+# what of the checkpoint's config must equal the trainer's: (key, its value in a checkpoint from before the key existed - such
+# a checkpoint loads into a trainer without the feature -, what to add to the refusal, the config field that must be on for
+# the check to apply or None).  rating_weight: whether there is a head must agree, not the weight.
+_CHECKPOINT_CHECKS = (
+    ("n_users", None, "", None), ("n_items", None, "", None), ("embedding_dim", None, "", None), ("tower_dims", None, "", None),
+    ("item_tower_dims", None, "", None), ("optimizer", None, "", None), ("n_category_buckets", 0, "", None),
+    ("n_user_features", 0, ": the numeric side features (and their projection kernels in 'dense') belong to the trained model", None),
+    ("n_item_features", 0, ": the numeric side features (and their projection kernels in 'dense') belong to the trained model", None),
+    ("rating_weight", 0.0, " (with / without a rating head): the head's parameters in 'dense' belong to the trained model", None),
+    ("rating_hidden", TwoTowerConfig.rating_hidden, "", "rating_weight"),
+    ("cross_layers", 0, ": the cross kernels in 'dense' belong to the trained model", None),
+    ("n_title_buckets", 0, "", None), ("user_history_len", 0, "", None), ("history_pooling", "mean", "", "user_history_len"),
+    ("title_max_tokens", None, "", "n_title_buckets"), ("title_pooling", None, "", "n_title_buckets"))
+
+
+# what graph replay is not implemented for: (config -> bool, the refusal)
+_GRAPH_REFUSALS = (
+    (lambda c: c.dropout_rate > 0.0, "dropout: the per-step counter is a kernel argument"),
+    (lambda c: c.optimizer == "adam", "optimizer='adam': the global step, and so the bias-corrected step size, is a kernel argument"),
+    (lambda c: c.candidate_sampling == "mixed", "candidate_sampling='mixed' is not implemented: the sampler's counter is a kernel "
+     "argument and the step is the Python sequence of per-tower launches"),
+    (lambda c: c.n_title_buckets, "the title feature (n_title_buckets > 0) is not implemented: the warm-up step's update of the "
+     "title table is not undone"),
+    (lambda c: c.user_history_len, "the user-history feature (user_history_len > 0) is not implemented: the warm-up step's update "
+     "of the history table is not undone"),
+    (lambda c: c.n_user_features or c.n_item_features, "the numeric side features (n_user_features / n_item_features > 0) is not "
+     "implemented: the step is the Python sequence of launches over materialised tower inputs"),
+    (lambda c: c.rating_weight > 0, "the rating head (rating_weight > 0) is not implemented: the step is the Python sequence of launches"),
+    (lambda c: c.cross_layers, "cross layers (cross_layers > 0) is not implemented: the step is the Python sequence of launches over "
+     "materialised tower inputs"))
+
+
 class TwoTowerTrainer:
     def __init__(self, cfg: TwoTowerConfig, device="cuda:0", seed: int | None = None):
         cfg.validate()
@@ -486,155 +710,136 @@ class TwoTowerTrainer:
         self.mixed = cfg.candidate_sampling == "mixed"
         bi = b + (cfg.n_sampled_negatives if self.mixed else 0)
         adagrad, adam = cfg.optimizer == "adagrad", cfg.optimizer == "adam"
-        self.user_table = torch.empty(cfg.n_users, d, device=dev)
-        self.item_table = torch.empty(cfg.n_items, d, device=dev)
-        self.user_accum = torch.full_like(self.user_table, cfg.adagrad_initial_accumulator) if adagrad else None
-        self.item_accum = torch.full_like(self.item_table, cfg.adagrad_initial_accumulator) if adagrad else None
-        n_user, n_item = Tower.param_count(cfg, cfg.user_dims), Tower.param_count(cfg, cfg.item_dims)
-        # numeric side features: the two projection kernels sit BEHIND both towers' parameters (no existing offset moves)
-        fu, fi = cfg.n_user_features, cfg.n_item_features
-        # the rating head sits behind those again, W1 | w2 | b1 | b2 (the head-off layout is unchanged)
+        # where every dense parameter sits and which optimizer segment covers it: dense_layout, the one place that knows
+        self.layout = lay = dense_layout(cfg)
         self.rating_on = cfg.rating_weight > 0
-        sd, rh = cfg.tower_dims[-1], cfg.rating_hidden
-        n_head = (2 * sd * rh + rh + rh + 1) if self.rating_on else 0
-        # the cross layers sit behind the head: [user W_0 .. W_{L-1} | item W_0 .. | user b_0 .. | item b_0 ..]
-        # (from a 16-byte boundary: the head's parameter count is odd, the cross launches load float4s - up to 3 idle floats)
-        ncl = cfg.cross_layers
-        n_cross = 2 * ncl * (d * d + d)
-        n_front = n_user + n_item + (fu + fi) * d + n_head
-        c_off = (n_front + 3) // 4 * 4 if ncl else n_front
-        # the history attention's vector [a | p] sits behind the cross parameters, from a 16-byte boundary (the launches load a
-        # as float4s); with any other pooling dense_flat keeps its size
         self._attn_on = cfg.history_attention
-        a_off = (c_off + n_cross + 3) // 4 * 4
-        self.dense_flat = torch.zeros(a_off + d + cfg.user_history_len if self._attn_on else c_off + n_cross, device=dev)
+        sd, rh, ncl = cfg.tower_dims[-1], cfg.rating_hidden, cfg.cross_layers
+        self.dense_flat = torch.zeros(lay.total, device=dev)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
         # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
         # global step the bias correction is taken from - part of the optimizer state (checkpointed)
-        self.user_m, self.user_v = (torch.zeros_like(self.user_table), torch.zeros_like(self.user_table)) if adam else (None, None)
-        self.item_m, self.item_v = (torch.zeros_like(self.item_table), torch.zeros_like(self.item_table)) if adam else (None, None)
         self.dense_m, self.dense_v = (torch.zeros_like(self.dense_flat), torch.zeros_like(self.dense_flat)) if adam else (None, None)
-        self.cat_m = self.cat_v = None
         self.adam_step = 1
-        self.user_tower = Tower(cfg, cfg.user_dims, self.dense_flat, self.dense_accum, 0, dev)
-        self.item_tower = Tower(cfg, cfg.item_dims, self.dense_flat, self.dense_accum, n_user, dev, rows=bi)
+        self.user_tower = ut = Tower(cfg, cfg.user_dims, self.dense_flat, self.dense_accum, lay.blocks["user.W0"].offset, dev)
+        self.item_tower = it = Tower(cfg, cfg.item_dims, self.dense_flat, self.dense_accum, lay.blocks["item.W0"].offset, dev, rows=bi)
+        grad_slabs = {}                          # segment name -> (its gradient slabs, their count): the segment loop below
+        for side, tower in (("user", ut), ("item", it)):
+            for l in range(tower.n_layers):
+                grad_slabs[f"{side}.W{l}"] = (tower.dw_slabs[l], tower.n_slabs)
+                grad_slabs[f"{side}.b{l}"] = (tower.db_slabs[l], tower.n_slabs)
         self.ws = torch.empty(ops.retrieval_workspace_bytes(b, bi, sd), dtype=torch.uint8, device=dev)
         self.lse = torch.empty(b, device=dev)
         self.per_row = torch.empty(b, device=dev)
         self.loss = torch.empty(1, device=dev)
         self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.user_plan = ops.SparsePlan(b, dev)
-        self.item_plan = ops.SparsePlan(bi, dev)
         # mixed: the step's candidate ids and (once set_item_frequencies ran) their probabilities under the mixture of the two
         # candidate streams, both written by the sampler launch; the frequency vectors and the alias table of the unigram sampler
         self.cand_ids = torch.empty(bi, dtype=torch.int64, device=dev) if self.mixed else None
         self.cand_prob = torch.empty(bi, device=dev) if self.mixed else None
         self.item_freq = self.sampler_prob = self.alias = None
-        self.cat_table = self.cat_accum = self.cat_plan = None
+        # the embedding tables, one record each (EmbeddingTable: table, optimizer state, sort plan); a table that is off is None
+        user = EmbeddingTable.new(cfg, dev, "user", TID_USER_TABLE, cfg.n_users, ops.SparsePlan(b, dev))
+        item = EmbeddingTable.new(cfg, dev, "item", TID_ITEM_TABLE, cfg.n_items, ops.SparsePlan(bi, dev))
+        cat = title = history = None
         if cfg.n_category_buckets:
-            self.cat_table = torch.empty(cfg.n_category_buckets, d, device=dev)
-            self.cat_accum = torch.full_like(self.cat_table, cfg.adagrad_initial_accumulator) if adagrad else None
-            self.cat_plan = ops.SparsePlan(b, dev)
-            if adam:
-                self.cat_m, self.cat_v = torch.zeros_like(self.cat_table), torch.zeros_like(self.cat_table)
+            cat = EmbeddingTable.new(cfg, dev, "cat", TID_CATEGORY_TABLE, cfg.n_category_buckets, ops.SparsePlan(b, dev))
         # pooled item-title feature: the bag table with its optimizer state, every item's token row (all padding until
         # set_item_titles), and the per-step buffers the bag launches fill - the slot tokens the sort plan sorts, the pooling
         # scales, and (mean / sqrtn) the scaled gradient rows
-        self.title_table = self.title_accum = self.title_m = self.title_v = None
-        self.item_titles = self.title_plan = self.title_ids = self.title_inv = self.title_gs = None
+        self.item_titles = self.title_ids = self.title_inv = self.title_gs = None
         if cfg.n_title_buckets:
             lt = cfg.title_max_tokens
-            self.title_table = torch.empty(cfg.n_title_buckets, d, device=dev)
-            self.title_accum = torch.full_like(self.title_table, cfg.adagrad_initial_accumulator) if adagrad else None
-            if adam:
-                self.title_m, self.title_v = torch.zeros_like(self.title_table), torch.zeros_like(self.title_table)
             self.item_titles = torch.full((cfg.n_items, lt), -1, dtype=torch.int32, device=dev)
-            self.title_plan = ops.BagPlan(bi, lt, dev)
+            title = EmbeddingTable.new(cfg, dev, "title", TID_TITLE_TABLE, cfg.n_title_buckets, ops.BagPlan(bi, lt, dev),
+                                       {"item_titles": self.item_titles})
             self.title_ids = torch.empty(bi * lt, dtype=torch.int64, device=dev)
             self.title_inv = torch.empty(bi, device=dev)
             self.title_gs = torch.empty(bi, d, device=dev) if cfg.title_pooling != "sum" else None
         # pooled user-history feature: the mirror on the user side - a [n_items, dim] table of its own with its optimizer state,
         # every user's history row (all padding until set_user_histories) and the per-step buffers of the bag launches
-        self.history_table = self.history_accum = self.history_m = self.history_v = None
-        self.user_history = self.history_plan = self.history_ids = self.history_inv = self.history_gs = None
+        self.user_history = self.history_ids = self.history_inv = self.history_gs = None
         self.history_attn = self.history_weights = self.history_pooled = self.history_slot_grads = self._ha_slabs = None
         if cfg.user_history_len:
             lh = cfg.user_history_len
-            self.history_table = torch.empty(cfg.n_items, d, device=dev)
-            self.history_accum = torch.full_like(self.history_table, cfg.adagrad_initial_accumulator) if adagrad else None
-            if adam:
-                self.history_m, self.history_v = torch.zeros_like(self.history_table), torch.zeros_like(self.history_table)
             self.user_history = torch.full((cfg.n_users, lh), -1, dtype=torch.int32, device=dev)
             self.history_ids = torch.empty(b * lh, dtype=torch.int64, device=dev)
             if self._attn_on:
                 # attention pooling: the slots' gradient rows differ, so the update takes one row per slot through a plain sort
                 # plan; the step keeps the weights and the pooled rows for the backward launch, which also writes the slabs of
                 # the attention vector's dense segment
-                self.history_plan = ops.SparsePlan(b * lh, dev)
-                self.history_attn = self.dense_flat[a_off:a_off + d + lh]
+                plan = ops.SparsePlan(b * lh, dev)
+                self.history_attn = lay.blocks["history_attn"].view(self.dense_flat)
                 self.history_weights = torch.empty(b, lh, device=dev)
                 self.history_pooled = torch.empty(b, d, device=dev)
                 self.history_slot_grads = torch.zeros(b * lh, d, device=dev)
-                self._ha_nslabs = ops.history_attention_num_slabs(b)
-                self._ha_slabs = torch.empty(self._ha_nslabs, d + lh, device=dev)
+                ns = ops.history_attention_num_slabs(b)
+                self._ha_slabs = torch.empty(ns, self.history_attn.numel(), device=dev)
+                grad_slabs["history_attn"] = (self._ha_slabs, ns)
             else:
-                self.history_plan = ops.BagPlan(b, lh, dev)
+                plan = ops.BagPlan(b, lh, dev)
                 self.history_inv = torch.empty(b, device=dev)
                 self.history_gs = torch.empty(b, d, device=dev) if cfg.history_pooling != "sum" else None
+            history = EmbeddingTable.new(cfg, dev, "history", TID_HISTORY_TABLE, cfg.n_items, plan, {"user_history": self.user_history})
+        self.tables = {t.prefix: t for t in (user, item, cat, title, history) if t is not None}
+        # the records' fields under the names the rest of the project reads (here and for the feature sides below)
+        self.user_table, self.user_accum, self.user_m, self.user_v, self.user_plan = _table_fields(user)
+        self.item_table, self.item_accum, self.item_m, self.item_v, self.item_plan = _table_fields(item)
+        self.cat_table, self.cat_accum, self.cat_m, self.cat_v, self.cat_plan = _table_fields(cat)
+        self.title_table, self.title_accum, self.title_m, self.title_v, self.title_plan = _table_fields(title)
+        self.history_table, self.history_accum, self.history_m, self.history_v, self.history_plan = _table_fields(history)
+        # what the fused optimizer calls take for the tables of the pairs' ids - every pointer is fixed from here on, so the
+        # lists are built once (the category row's gradient is the item-tower input gradient itself)
+        trio = [(user, ut.demb), (item, it.demb)] + ([(cat, it.demb)] if cat is not None else [])
+        self._opt_tables = [(t.table, t.accum, g, t.plan) for t, g in trio]
+        self._adam_tables = [(t.table, t.m, t.v, g, t.plan) for t, g in trio]
         # numeric side features, per side: the fixed feature matrix with its normalisation (zeros / mean 0 / inv_std 1 until the
         # setter ran: z = 0, nothing is added), the projection kernel (a view of dense_flat), the step's normalised rows (kept for
         # the backward launch) and the gradient slabs the dense optimizer segment sums
-        self.user_features = self.user_feature_mean = self.user_feature_inv_std = self.P_user = self._fz_user = self._fslabs_user = None
-        self.item_features = self.item_feature_mean = self.item_feature_inv_std = self.P_item = self._fz_item = self._fslabs_item = None
-        self._feature_sides = []                 # (side, projection kernel, gradient slabs, slab count)
-        off = n_user + n_item
-        for side, f, rows, nb in (("user", fu, cfg.n_users, b), ("item", fi, cfg.n_items, bi)):
-            if not f:
-                continue
-            ns = ops.dense_features_num_slabs(nb)
-            setattr(self, f"{side}_features", torch.zeros(rows, f, device=dev))
-            setattr(self, f"{side}_feature_mean", torch.zeros(f, device=dev))
-            setattr(self, f"{side}_feature_inv_std", torch.ones(f, device=dev))
-            setattr(self, f"P_{side}", self.dense_flat[off:off + f * d].view(f, d))
-            setattr(self, f"_fz_{side}", torch.empty(nb, f, device=dev))
-            setattr(self, f"_fslabs_{side}", torch.empty(ns, f, d, device=dev))
-            self._feature_sides.append((side, getattr(self, f"P_{side}"), getattr(self, f"_fslabs_{side}"), ns))
-            off += f * d
+        self.sides = {}
+        for side, f, rows, nb, tower in (("user", cfg.n_user_features, cfg.n_users, b, ut), ("item", cfg.n_item_features, cfg.n_items, bi, it)):
+            if f:
+                ns = ops.dense_features_num_slabs(nb)
+                self.sides[side] = fs = FeatureSide(side, torch.zeros(rows, f, device=dev), torch.zeros(f, device=dev), torch.ones(f, device=dev),
+                                                    lay.blocks[f"P_{side}"].view(self.dense_flat), torch.empty(nb, f, device=dev),
+                                                    torch.empty(ns, f, d, device=dev), ns, tower)
+                grad_slabs[f"P_{side}"] = (fs.slabs, ns)
+        self.user_features, self.user_feature_mean, self.user_feature_inv_std, self.P_user, self._fz_user, self._fslabs_user = \
+            _side_fields(self.sides.get("user"))
+        self.item_features, self.item_feature_mean, self.item_feature_inv_std, self.P_item, self._fz_item, self._fslabs_item = \
+            _side_fields(self.sides.get("item"))
+        self._feature_sides = [(fs.side, fs.P, fs.slabs, fs.n_slabs) for fs in self.sides.values()]
         # rating head: the four parameters (views of dense_flat), the step's predictions and hidden activations (kept for the
         # backward launch) and the gradient slabs of the two dense segments (W1 | w2 with l2, b1 | b2 without)
         self.W1_rating = self.w2_rating = self.b1_rating = self.b2_rating = None
         self.rating_pred = self._r_h = self._r_kslabs = self._r_bslabs = self._r_se = None
-        self._r_slabs = 0
         self.eval_rating_se = self.eval_rating_count = None
         if self.rating_on:
-            nk = 2 * sd * rh
-            self.W1_rating = self.dense_flat[off:off + nk].view(2 * sd, rh)
-            self.w2_rating = self.dense_flat[off + nk:off + nk + rh]
-            self.b1_rating = self.dense_flat[off + nk + rh:off + nk + 2 * rh]
-            self.b2_rating = self.dense_flat[off + nk + 2 * rh:off + nk + 2 * rh + 1]
-            self._r_off = off
-            self._r_slabs = ns = ops.rating_head_num_slabs(b)
+            self.W1_rating, self.w2_rating, self.b1_rating, self.b2_rating = \
+                (lay.blocks[f"head.{k}"].view(self.dense_flat) for k in ("W1", "w2", "b1", "b2"))
+            ns = ops.rating_head_num_slabs(b)
             self.rating_pred = torch.zeros(b, device=dev)
             self._r_h = torch.empty(b, rh, device=dev)
-            self._r_kslabs = torch.empty(ns, nk + rh, device=dev)
-            self._r_bslabs = torch.empty(ns, rh + 1, device=dev)
+            self._r_kslabs = torch.empty(ns, lay.segment("head.kernels").size, device=dev)
+            self._r_bslabs = torch.empty(ns, lay.segment("head.biases").size, device=dev)
             self._r_se = torch.zeros(ns, device=dev)
+            grad_slabs["head.kernels"], grad_slabs["head.biases"] = (self._r_kslabs, ns), (self._r_bslabs, ns)
         # cross layers: the parameters (views of dense_flat) and ONE gradient-slab array for all layers of both towers, laid out
         # like the parameters, so that two dense segments - every kernel (l2 like any kernel), every bias - sum it
-        self._c_off = c_off
         self._c_slabs = None
         self._c_nslabs = 0
         if ncl:
-            nk, stride = 2 * ncl * d * d, n_cross
+            kernels, biases = lay.segment("cross.kernels"), lay.segment("cross.biases")
             self._c_nslabs = ns = ops.cross_num_slabs(bi)
-            self._c_slabs = torch.empty(ns * stride, device=dev)
-            for ti, tower in enumerate((self.user_tower, self.item_tower)):
-                ko = [(ti * ncl + l) * d * d for l in range(ncl)]
-                bo = [nk + (ti * ncl + l) * d for l in range(ncl)]
-                tower.set_cross([self.dense_flat[self._c_off + o:self._c_off + o + d * d].view(d, d) for o in ko],
-                                [self.dense_flat[self._c_off + o:self._c_off + o + d] for o in bo],
-                                [self._c_slabs[o:] for o in ko], [self._c_slabs[o:] for o in bo], ns, stride)
+            self._c_slabs = torch.empty(ns * kernels.stride, device=dev)
+            for side, tower in (("user", ut), ("item", it)):
+                ws = [lay.blocks[f"cross.{side}.W{l}"] for l in range(ncl)]
+                bs = [lay.blocks[f"cross.{side}.b{l}"] for l in range(ncl)]
+                tower.set_cross([w.view(self.dense_flat) for w in ws], [x.view(self.dense_flat) for x in bs],
+                                [self._c_slabs[w.offset - kernels.lo:] for w in ws], [self._c_slabs[x.offset - kernels.lo:] for x in bs],
+                                ns, kernels.stride)
+            grad_slabs["cross.kernels"], grad_slabs["cross.biases"] = (self._c_slabs, ns), (self._c_slabs[biases.lo - kernels.lo:], ns)
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -690,62 +895,18 @@ class TwoTowerTrainer:
         self._skew_state = False
         self._skew_dev = self._skew_host = self._skew_event = None
         self.dropout_seed = 0 if seed is None else seed
-        self._segs = self.user_tower.segments(cfg.l2_regularization) + self.item_tower.segments(cfg.l2_regularization)
-        self._adam_segs = None
-        if adam:        # the same segments (parameter, gradient slabs, l2) with the moments' views of dense_m / dense_v
-            self._adam_segs = []
-            for tower in (self.user_tower, self.item_tower):
-                for l in range(tower.n_layers):
-                    for prm, slabs, reg in ((tower.w[l], tower.dw_slabs[l], cfg.l2_regularization), (tower.b[l], tower.db_slabs[l], 0.0)):
-                        lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
-                        self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, tower.n_slabs, reg))
-        for _, prm, slabs, ns in self._feature_sides:      # the projection kernels: Dense kernels like any other (l2 included)
-            lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
-            self._segs.append(ops.make_dense_seg(prm, None if self.dense_accum is None else self.dense_accum[lo:hi], slabs, ns,
-                                                 cfg.l2_regularization))
+        # the dense optimizer's segments, in the layout's order: parameter range, gradient slabs, l2 and slab stride are stated
+        # once, and the accumulator's / the moments' views are cut with the same range
+        self._segs = []
+        self._adam_segs = [] if adam else None
+        for seg in lay.segments:
+            lo, hi = seg.lo, seg.hi
+            (slabs, ns), reg = grad_slabs[seg.name], cfg.l2_regularization if seg.l2 else 0.0
+            self._segs.append(ops.make_dense_seg(self.dense_flat[lo:hi], None if self.dense_accum is None else self.dense_accum[lo:hi],
+                                                 slabs, ns, reg, slab_stride=seg.stride))
             if adam:
-                self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, ns, cfg.l2_regularization))
-        n_tower_segs = len(self._segs) - len(self._feature_sides)
-        if self.rating_on:                       # two more Dense segments: the kernels W1 | w2 (l2 like any kernel) and the biases b1 | b2
-            nk = 2 * sd * rh + rh
-            for lo, hi, slabs, reg in ((self._r_off, self._r_off + nk, self._r_kslabs, cfg.l2_regularization),
-                                       (self._r_off + nk, self._r_off + nk + rh + 1, self._r_bslabs, 0.0)):
-                self._segs.append(ops.make_dense_seg(self.dense_flat[lo:hi], None if self.dense_accum is None else self.dense_accum[lo:hi],
-                                                     slabs, self._r_slabs, reg))
-                if adam:
-                    self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs,
-                                                             self._r_slabs, reg))
-        n_before_cross = len(self._segs)
-        if ncl:                                  # two more Dense segments: every cross kernel (l2 like any kernel), every cross bias
-            nk = 2 * ncl * d * d
-            for lo, hi, slabs, reg in ((self._c_off, self._c_off + nk, self._c_slabs, cfg.l2_regularization),
-                                       (self._c_off + nk, self._c_off + n_cross, self._c_slabs[nk:], 0.0)):
-                self._segs.append(ops.make_dense_seg(self.dense_flat[lo:hi], None if self.dense_accum is None else self.dense_accum[lo:hi],
-                                                     slabs, self._c_nslabs, reg, slab_stride=n_cross))
-                if adam:
-                    self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs,
-                                                             self._c_nslabs, reg, slab_stride=n_cross))
-        if self._attn_on:                        # one more segment: the attention vector [a | p], no l2
-            prm = self.history_attn
-            lo, hi = prm.storage_offset(), prm.storage_offset() + prm.numel()
-            if len(self._segs) == _lib.TT_MAX_DENSE_SEGS:
-                raise NotImplementedError(f"the history attention adds one dense segment to the model's {len(self._segs)}: the "
-                                          f"optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 "
-                                          "layers, or drop a feature)")
-            self._segs.append(ops.make_dense_seg(prm, None if self.dense_accum is None else self.dense_accum[lo:hi], self._ha_slabs,
-                                                 self._ha_nslabs, 0.0))
-            if adam:
-                self._adam_segs.append(ops.make_adam_seg(prm, self.dense_m[lo:hi], self.dense_v[lo:hi], self._ha_slabs,
-                                                         self._ha_nslabs, 0.0))
-        if len(self._segs) > _lib.TT_MAX_DENSE_SEGS and n_before_cross <= _lib.TT_MAX_DENSE_SEGS:
-            raise NotImplementedError(f"the cross layers add two dense segments to the model's {n_before_cross}: the optimizer launches "
-                                      f"take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
-        if len(self._segs) > _lib.TT_MAX_DENSE_SEGS and not self._feature_sides:
-            raise NotImplementedError(f"the rating head adds two dense segments to the towers' {n_tower_segs}: the optimizer launches "
-                                      f"take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
-        if len(self._segs) > _lib.TT_MAX_DENSE_SEGS:
-            raise NotImplementedError(f"the numeric side features add one dense segment per side to the towers' {n_tower_segs}: "
-                                      f"the optimizer launches take at most {_lib.TT_MAX_DENSE_SEGS} (use towers of at most 3 layers)")
+                self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, ns,
+                                                         reg, slab_stride=seg.stride))
         if seed is not None:
             self.init_synthetic(seed)
 
@@ -753,40 +914,16 @@ class TwoTowerTrainer:
     def init_synthetic(self, seed: int):
         """Keras defaults (Embedding U(-0.05,0.05), Dense Glorot-uniform, zero bias) from the counter-based
         generator: identical, bit for bit, to oracle.two_tower.synthetic_state(seed, ...)."""
-        ops.fill_uniform_(self.user_table, seed, TID_USER_TABLE, -0.05, 0.1)
-        ops.fill_uniform_(self.item_table, seed, TID_ITEM_TABLE, -0.05, 0.1)
-        if self.cat_table is not None:
-            ops.fill_uniform_(self.cat_table, seed, TID_CATEGORY_TABLE, -0.05, 0.1)
-        if self.title_table is not None:
-            ops.fill_uniform_(self.title_table, seed, TID_TITLE_TABLE, -0.05, 0.1)
-        if self.history_table is not None:
-            ops.fill_uniform_(self.history_table, seed, TID_HISTORY_TABLE, -0.05, 0.1)
+        for t in self.tables.values():
+            t.init_synthetic(self.cfg, seed)
         self.dense_flat.zero_()
-        for t, tower in enumerate((self.user_tower, self.item_tower)):
-            for l, w in enumerate(tower.w):
-                lim = torch.tensor(math.sqrt(6.0 / (w.shape[0] + w.shape[1])), dtype=torch.float64).to(torch.float32)
-                lim32 = lim.item()
-                scale32 = (lim + lim).item()
-                ops.fill_uniform_(w, seed, TID_DENSE_BASE + 2 * l + t, -lim32, scale32)
-        for side, w, _, _ in self._feature_sides:            # Glorot-uniform, like the Dense kernels
-            lim = torch.tensor(math.sqrt(6.0 / (w.shape[0] + w.shape[1])), dtype=torch.float64).to(torch.float32)
-            ops.fill_uniform_(w, seed, TID_USER_FEATURE_PROJ if side == "user" else TID_ITEM_FEATURE_PROJ, -lim.item(), (lim + lim).item())
-        if self.rating_on:                                   # Glorot-uniform kernels (w2 as the [H, 1] kernel it is), zero biases
-            for w, tid, fan in ((self.W1_rating, TID_RATING_W1, sum(self.W1_rating.shape)), (self.w2_rating, TID_RATING_W2, self.w2_rating.numel() + 1)):
-                lim = torch.tensor(math.sqrt(6.0 / fan), dtype=torch.float64).to(torch.float32)
-                ops.fill_uniform_(w, seed, tid, -lim.item(), (lim + lim).item())
-        for t, tower in enumerate((self.user_tower, self.item_tower)):     # Glorot-uniform [D, D] kernels, zero biases
-            for l, w in enumerate(tower.cross_w):
-                lim = torch.tensor(math.sqrt(6.0 / (w.shape[0] + w.shape[1])), dtype=torch.float64).to(torch.float32)
-                ops.fill_uniform_(w, seed, TID_CROSS_BASE + 2 * l + t, -lim.item(), (lim + lim).item())
-        if self.cfg.optimizer == "adagrad":
-            for a in (self.user_accum, self.item_accum, self.dense_accum, self.cat_accum, self.title_accum, self.history_accum):
-                if a is not None:
-                    a.fill_(self.cfg.adagrad_initial_accumulator)
-        for a in (self.user_m, self.user_v, self.item_m, self.item_v, self.cat_m, self.cat_v, self.title_m, self.title_v,
-                  self.history_m, self.history_v, self.dense_m, self.dense_v):
-            if a is not None:
-                a.zero_()
+        for blk in self.layout.blocks.values():                # Glorot-uniform kernels, zero biases
+            if blk.glorot is not None:
+                _glorot_uniform_(blk.view(self.dense_flat), seed, *blk.glorot)
+        if self.dense_accum is not None:
+            self.dense_accum.fill_(self.cfg.adagrad_initial_accumulator)
+        if self.dense_m is not None:
+            self.dense_m.zero_(), self.dense_v.zero_()
         self.adam_step = 1
 
     def init_rating_bias(self, x: float):
@@ -862,9 +999,10 @@ class TwoTowerTrainer:
     def _set_features(self, side: str, x, mean, inv_std):
         import numpy as np
         what = f"set_{side}_features"
-        dst = getattr(self, f"{side}_features")
-        if dst is None:
+        fs = self.sides.get(side)
+        if fs is None:
             raise ValueError(f"{what}: the model has no numeric {side} features (cfg.n_{side}_features == 0)")
+        dst = fs.features
         a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
         if tuple(a.shape) != tuple(dst.shape):
             raise ValueError(f"{what}: x must be {list(dst.shape)} (rows, n_{side}_features), got {list(a.shape)}")
@@ -882,8 +1020,8 @@ class TwoTowerTrainer:
                 raise ValueError(f"{what}: {name} must hold {a.shape[1]} finite entries")
             stats.append(t)
         dst.copy_(torch.from_numpy(a))
-        getattr(self, f"{side}_feature_mean").copy_(torch.from_numpy(stats[0]))
-        getattr(self, f"{side}_feature_inv_std").copy_(torch.from_numpy(stats[1]))
+        fs.mean.copy_(torch.from_numpy(stats[0]))
+        fs.inv_std.copy_(torch.from_numpy(stats[1]))
 
     def set_user_features(self, x, mean=None, inv_std=None):
         """x [n_users, n_user_features]: every user's numeric features (finite; ``data.rating_features``).  ``mean`` / ``inv_std``
@@ -959,22 +1097,19 @@ class TwoTowerTrainer:
         launch for the sides that have the feature; ``keep``: the normalised rows stay for the backward launch (train step)."""
         probs = []
         for side, arg in (("user", user), ("item", item)):
-            feat = getattr(self, f"{side}_features")
-            if feat is None or arg is None:
+            fs = self.sides.get(side)
+            if fs is None or arg is None:
                 continue
             ids, out = arg
-            z = getattr(self, f"_fz_{side}") if keep else None
-            probs.append((feat, ids, getattr(self, f"{side}_feature_mean"), getattr(self, f"{side}_feature_inv_std"),
-                          getattr(self, f"P_{side}"), out, True, z))
+            probs.append((fs.features, ids, fs.mean, fs.inv_std, fs.P, out, True, fs.z if keep else None))
         if probs:
             ops.dense_features(*probs, clip=self.cfg.feature_clip, oob_flag=self.oob)
 
     def _features_backward(self):
         """The projection kernels' gradient slabs from the towers' input gradients (demb) and the kept normalised rows: one
         launch for both sides, after the towers' backward."""
-        if self._feature_sides:
-            towers = {"user": self.user_tower, "item": self.item_tower}
-            ops.dense_features_bwd(*[(getattr(self, f"_fz_{side}"), towers[side].demb, slabs) for side, _, slabs, _ in self._feature_sides])
+        if self.sides:
+            ops.dense_features_bwd(*[(fs.z, fs.tower.demb, fs.slabs) for fs in self.sides.values()])
 
     def _history_backward(self):
         """Attention pooling: the slots' gradient rows and the attention vector's gradient slabs from the user tower's input
@@ -1176,20 +1311,14 @@ class TwoTowerTrainer:
     def _apply_table_gradients_mixed(self):
         """The two tables' plans hold different id counts (B and B + N): one sparse launch sequence per table.  The sampled
         items' rows are trained like the positives' (their gradient rows are demb[B:])."""
-        cfg, ut, it = self.cfg, self.user_tower, self.item_tower
-        if cfg.optimizer == "adam":              # the user table with every tower segment, then the item table: the same step t
-            h = ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, self.adam_step)
-            ops.adam_step_([(self.user_table, self.user_m, self.user_v, ut.demb, self.user_plan)], self._adam_segs, h)
-            ops.adam_step_([(self.item_table, self.item_m, self.item_v, it.demb, self.item_plan)], [], h)
+        cfg, adam = self.cfg, self.cfg.optimizer == "adam"
+        if not adam:
+            ops.dense_update_(self._segs, cfg.optimizer, cfg.learning_rate, cfg.adagrad_epsilon)
+        # (lazy Adam: the user table with every dense segment in one call, then the item table - the same step t)
+        self.tables["user"].apply(cfg, self.user_tower.demb, self.adam_step, self._adam_segs if adam else ())
+        self.tables["item"].apply(cfg, self.item_tower.demb, self.adam_step)
+        if adam:
             self.adam_step += 1
-            return
-        ops.dense_update_(self._segs, cfg.optimizer, cfg.learning_rate, cfg.adagrad_epsilon)
-        for table, accum, tower, plan in ((self.user_table, self.user_accum, ut, self.user_plan),
-                                          (self.item_table, self.item_accum, it, self.item_plan)):
-            if cfg.optimizer == "sgd":
-                ops.sparse_sgd_(table, tower.demb, plan, cfg.learning_rate)
-            else:
-                ops.sparse_adagrad_(table, accum, tower.demb, plan, cfg.learning_rate, cfg.adagrad_epsilon)
 
     def apply_gradients(self, step_ids=None):
         """``step_ids`` = [user ids, item ids (, category ids)]: the optimizer launch sorts them itself (no plan launch ran).
@@ -1216,13 +1345,7 @@ class TwoTowerTrainer:
             gs = self.history_slot_grads
         else:
             gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
-        if cfg.optimizer == "adam":
-            ops.adam_step_([(self.history_table, self.history_m, self.history_v, gs, plan)], [],
-                           ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
-        elif cfg.optimizer == "sgd":
-            ops.sparse_sgd_(self.history_table, gs, plan, cfg.learning_rate)
-        else:
-            ops.sparse_adagrad_(self.history_table, self.history_accum, gs, plan, cfg.learning_rate, cfg.adagrad_epsilon)
+        self.tables["history"].apply(cfg, gs, adam_step)
 
     def _apply_title_gradients(self, adam_step: int):
         """The title table's update: sort plan over the step's slot tokens, one launch that scales the item-tower input gradient
@@ -1231,49 +1354,26 @@ class TwoTowerTrainer:
         cfg, plan = self.cfg, self.title_plan
         plan.run(self.title_ids, cfg.n_title_buckets)
         gs = plan.backward(self.item_tower.demb, self.title_inv, self.title_gs)
-        if cfg.optimizer == "adam":
-            ops.adam_step_([(self.title_table, self.title_m, self.title_v, gs, plan)], [],
-                           ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
-        elif cfg.optimizer == "sgd":
-            ops.sparse_sgd_(self.title_table, gs, plan, cfg.learning_rate)
-        else:
-            ops.sparse_adagrad_(self.title_table, self.title_accum, gs, plan, cfg.learning_rate, cfg.adagrad_epsilon)
+        self.tables["title"].apply(cfg, gs, adam_step)
 
     def _apply_table_gradients(self, step_ids=None):
         cfg = self.cfg
         if cfg.optimizer == "adam":  # every table and every tower segment in ONE call (two launches), from the sort plans
-            tables = [(self.user_table, self.user_m, self.user_v, self.user_tower.demb, self.user_plan),
-                      (self.item_table, self.item_m, self.item_v, self.item_tower.demb, self.item_plan)]
-            if self.cat_table is not None:   # the category row's gradient is the item-tower input gradient itself
-                tables.append((self.cat_table, self.cat_m, self.cat_v, self.item_tower.demb, self.cat_plan))
-            ops.adam_step_(tables, self._adam_segs, ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon,
-                                                                  self.adam_step))
+            ops.adam_step_(self._adam_tables, self._adam_segs, ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2,
+                                                                             cfg.adam_epsilon, self.adam_step))
             self.adam_step += 1
             return
         if step_ids is not None:     # sort + sparse update of every table + dense update: ONE launch, straight from the raw ids
-            tables = [(self.user_table, self.user_accum, self.user_tower.demb, step_ids[0], self.user_plan),
-                      (self.item_table, self.item_accum, self.item_tower.demb, step_ids[1], self.item_plan)]
-            if self.cat_table is not None:
-                tables.append((self.cat_table, self.cat_accum, self.item_tower.demb, step_ids[2], self.cat_plan))
+            tables = [(table, accum, grads, ids, plan) for (table, accum, grads, plan), ids in zip(self._opt_tables, step_ids)]
             ops.optimizer_step_ids_(cfg.optimizer, tables, self._segs, cfg.learning_rate, cfg.adagrad_epsilon)
             return
         if self.fuse_optimizer:      # sparse update of every table + dense update of every tower segment: one launch
-            tables = [(self.user_table, self.user_accum, self.user_tower.demb, self.user_plan),
-                      (self.item_table, self.item_accum, self.item_tower.demb, self.item_plan)]
-            if self.cat_table is not None:   # the category row's gradient is the item-tower input gradient itself
-                tables.append((self.cat_table, self.cat_accum, self.item_tower.demb, self.cat_plan))
-            ops.optimizer_step_(cfg.optimizer, tables, self._segs, cfg.learning_rate, cfg.adagrad_epsilon)
+            ops.optimizer_step_(cfg.optimizer, self._opt_tables, self._segs, cfg.learning_rate, cfg.adagrad_epsilon)
             return
         ops.dense_update_(self._segs, cfg.optimizer, cfg.learning_rate, cfg.adagrad_epsilon)
-        ops.sparse_update2_(cfg.optimizer, self.user_table, self.user_accum, self.user_tower.demb, self.user_plan,
-                            self.item_table, self.item_accum, self.item_tower.demb, self.item_plan,
-                            cfg.learning_rate, cfg.adagrad_epsilon)
-        if self.cat_table is not None:       # the category row's gradient is the item-tower input gradient itself
-            if cfg.optimizer == "sgd":
-                ops.sparse_sgd_(self.cat_table, self.item_tower.demb, self.cat_plan, cfg.learning_rate)
-            else:
-                ops.sparse_adagrad_(self.cat_table, self.cat_accum, self.item_tower.demb, self.cat_plan, cfg.learning_rate,
-                                    cfg.adagrad_epsilon)
+        ops.sparse_update2_(cfg.optimizer, *self._opt_tables[0], *self._opt_tables[1], cfg.learning_rate, cfg.adagrad_epsilon)
+        if self.cat_table is not None:
+            self.tables["cat"].apply(cfg, self.item_tower.demb, self.adam_step)
 
     def step(self, user_ids: torch.Tensor, item_ids: torch.Tensor, **loss_kw) -> torch.Tensor:
         """One train step; returns the (device, unsynchronised) retrieval loss (SUM over the batch).
@@ -1357,9 +1457,7 @@ class TwoTowerTrainer:
         st.retrieval_ws, st.retrieval_ws_bytes = p(self.ws), self.ws.numel()
         st.lse, st.per_row, st.loss = p(self.lse), p(self.per_row), p(self.loss)
         st.opt = ops._OPT[cfg.optimizer]
-        tabs = [(self.user_table, self.user_accum, ut.demb, self.user_plan), (self.item_table, self.item_accum, it.demb, self.item_plan)]
-        if self.cat_table is not None:          # the category row's gradient is the item-tower input gradient itself
-            tabs.append((self.cat_table, self.cat_accum, it.demb, self.cat_plan))
+        tabs = self._opt_tables
         st.n_tables = len(tabs)
         for i, (table, accum, grads, plan) in enumerate(tabs):
             t = st.tables[i]
@@ -1568,89 +1666,28 @@ class TwoTowerTrainer:
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self) -> dict:
-        sd = {"config": dict(self.cfg.__dict__), "user_table": self.user_table, "item_table": self.item_table,
-              "dense": self.dense_flat, "step_index": self.step_index, "dropout_seed": self.dropout_seed}
+        sd = {"config": dict(self.cfg.__dict__), "dense": self.dense_flat, "step_index": self.step_index, "dropout_seed": self.dropout_seed}
+        for rec in (*self.tables.values(), *getattr(self, "sides", {}).values()):    # (the projection kernels are part of "dense")
+            sd.update(rec.state())
         if getattr(self, "item_freq", None) is not None:     # mixed negative sampling: the correction (and the unigram sampler) is rebuilt from it
             sd["item_freq"] = self.item_freq
-        if self.cat_table is not None:
-            sd["cat_table"] = self.cat_table
-        if self.title_table is not None:
-            sd.update(title_table=self.title_table, item_titles=self.item_titles)
-            if self.cfg.optimizer == "adagrad":
-                sd["title_accum"] = self.title_accum
-            if self.cfg.optimizer == "adam":
-                sd.update(title_m=self.title_m, title_v=self.title_v)
-        if getattr(self, "history_table", None) is not None:
-            sd.update(history_table=self.history_table, user_history=self.user_history)
-            if self.cfg.optimizer == "adagrad":
-                sd["history_accum"] = self.history_accum
-            if self.cfg.optimizer == "adam":
-                sd.update(history_m=self.history_m, history_v=self.history_v)
-        for side, _, _, _ in getattr(self, "_feature_sides", ()):    # the projection kernels are part of "dense" (and its state)
-            for k in (f"{side}_features", f"{side}_feature_mean", f"{side}_feature_inv_std"):
-                sd[k] = getattr(self, k)
         if self.cfg.optimizer == "adagrad":
-            sd.update(user_accum=self.user_accum, item_accum=self.item_accum, dense_accum=self.dense_accum)
-            if self.cat_table is not None:
-                sd["cat_accum"] = self.cat_accum
+            sd["dense_accum"] = self.dense_accum
         if self.cfg.optimizer == "adam":
-            sd.update(user_m=self.user_m, user_v=self.user_v, item_m=self.item_m, item_v=self.item_v, dense_m=self.dense_m,
-                      dense_v=self.dense_v, adam_step=self.adam_step)
-            if self.cat_table is not None:
-                sd.update(cat_m=self.cat_m, cat_v=self.cat_v)
+            sd.update(dense_m=self.dense_m, dense_v=self.dense_v, adam_step=self.adam_step)
         return sd
 
     def load_state_dict(self, sd: dict):
-        for k in ("n_users", "n_items", "embedding_dim", "tower_dims", "item_tower_dims", "optimizer", "n_category_buckets"):
-            if sd["config"].get(k, 0 if k == "n_category_buckets" else None) != getattr(self.cfg, k):
-                raise ValueError(f"checkpoint {k}={sd['config'].get(k)!r} does not match the trainer's {getattr(self.cfg, k)!r}")
-        # the numeric side features: a checkpoint from before they existed has no key and loads into a trainer without them
-        for k in ("n_user_features", "n_item_features"):
-            if sd["config"].get(k, 0) != getattr(self.cfg, k):
-                raise ValueError(f"checkpoint {k}={sd['config'].get(k, 0)!r} does not match the trainer's {getattr(self.cfg, k)!r}: "
-                                 "the numeric side features (and their projection kernels in 'dense') belong to the trained model")
-        # the rating head: a checkpoint from before it existed has no field and loads with the head off
-        ck_w, ck_h = float(sd["config"].get("rating_weight", 0.0)), int(sd["config"].get("rating_hidden", TwoTowerConfig.rating_hidden))
-        if (ck_w > 0) != self.rating_on:
-            raise ValueError(f"checkpoint rating_weight={ck_w!r} ({'with' if ck_w > 0 else 'without'} a rating head) does not match the "
-                             f"trainer's {self.cfg.rating_weight!r}: the head's parameters in 'dense' belong to the trained model")
-        if self.rating_on and ck_h != self.cfg.rating_hidden:
-            raise ValueError(f"checkpoint rating_hidden={ck_h!r} does not match the trainer's {self.cfg.rating_hidden!r}")
-        # the cross layers: a checkpoint from before they existed has no field and loads as 0
-        if int(sd["config"].get("cross_layers", 0)) != self.cfg.cross_layers:
-            raise ValueError(f"checkpoint cross_layers={sd['config'].get('cross_layers', 0)!r} does not match the trainer's "
-                             f"{self.cfg.cross_layers!r}: the cross kernels in 'dense' belong to the trained model")
-        # a checkpoint from before the title feature existed has none: it loads into a trainer without it, as before
-        if sd["config"].get("n_title_buckets", 0) != self.cfg.n_title_buckets:
-            raise ValueError(f"checkpoint n_title_buckets={sd['config'].get('n_title_buckets', 0)!r} does not match the trainer's "
-                             f"{self.cfg.n_title_buckets!r}")
-        # likewise the history feature: a checkpoint from before it existed has no key and loads into a trainer without it
-        if sd["config"].get("user_history_len", 0) != self.cfg.user_history_len:
-            raise ValueError(f"checkpoint user_history_len={sd['config'].get('user_history_len', 0)!r} does not match the trainer's "
-                             f"{self.cfg.user_history_len!r}")
-        if self.cfg.user_history_len and sd["config"].get("history_pooling", "mean") != self.cfg.history_pooling:
-            raise ValueError(f"checkpoint history_pooling={sd['config'].get('history_pooling')!r} does not match the trainer's "
-                             f"{self.cfg.history_pooling!r}")
-        if self.title_table is not None:
-            for k in ("title_max_tokens", "title_pooling"):
-                if sd["config"].get(k) != getattr(self.cfg, k):
-                    raise ValueError(f"checkpoint {k}={sd['config'].get(k)!r} does not match the trainer's {getattr(self.cfg, k)!r}")
-            self.title_table.copy_(sd["title_table"]); self.item_titles.copy_(sd["item_titles"])
-            if self.cfg.optimizer == "adagrad":
-                self.title_accum.copy_(sd["title_accum"])
-            if self.cfg.optimizer == "adam":
-                self.title_m.copy_(sd["title_m"]); self.title_v.copy_(sd["title_v"])
-        if self.history_table is not None:
-            self.history_table.copy_(sd["history_table"]); self.user_history.copy_(sd["user_history"])
-            if self.cfg.optimizer == "adagrad":
-                self.history_accum.copy_(sd["history_accum"])
-            if self.cfg.optimizer == "adam":
-                self.history_m.copy_(sd["history_m"]); self.history_v.copy_(sd["history_v"])
-        self.user_table.copy_(sd["user_table"]); self.item_table.copy_(sd["item_table"]); self.dense_flat.copy_(sd["dense"])
-        for side, _, _, _ in self._feature_sides:
-            for k in (f"{side}_features", f"{side}_feature_mean", f"{side}_feature_inv_std"):
-                getattr(self, k).copy_(sd[k])
-        if self._feature_sides:                  # the clip belongs to the trained model, like the normalisation switch below
+        for k, default, note, needs in _CHECKPOINT_CHECKS:
+            ck, mine = sd["config"].get(k, default), getattr(self.cfg, k)
+            same = (ck > 0) == (mine > 0) if k == "rating_weight" else ck == mine
+            if not same and (needs is None or getattr(self.cfg, needs)):
+                raise ValueError(f"checkpoint {k}={ck!r} does not match the trainer's {mine!r}{note}")
+        for rec in (*self.tables.values(), *self.sides.values()):
+            for k, dst in rec.state().items():
+                dst.copy_(sd[k])
+        self.dense_flat.copy_(sd["dense"])
+        if self.sides:                  # the clip belongs to the trained model, like the normalisation switch below
             self.cfg.feature_clip = float(sd["config"].get("feature_clip", 0.0))
         # whether the embeddings are normalised belongs to the trained model, not to the run that loads it: the checkpoint's
         # value replaces the trainer's (a checkpoint from before the switch existed: off)
@@ -1665,57 +1702,30 @@ class TwoTowerTrainer:
         # checkpoint from before they existed, or from an in-batch run, loads as before); a mixed trainer takes the frequencies
         if self.mixed and sd.get("item_freq") is not None:
             self.set_item_frequencies(sd["item_freq"])
-        if self.cat_table is not None:
-            self.cat_table.copy_(sd["cat_table"])
-            if self.cfg.optimizer == "adagrad":
-                self.cat_accum.copy_(sd["cat_accum"])
         if self.cfg.optimizer == "adagrad":
-            self.user_accum.copy_(sd["user_accum"]); self.item_accum.copy_(sd["item_accum"])
             self.dense_accum.copy_(sd["dense_accum"])
         if self.cfg.optimizer == "adam":
-            for k in ("user_m", "user_v", "item_m", "item_v", "dense_m", "dense_v") + (("cat_m", "cat_v") if self.cat_table is not None else ()):
-                getattr(self, k).copy_(sd[k])
+            self.dense_m.copy_(sd["dense_m"]); self.dense_v.copy_(sd["dense_v"])
             self.adam_step = int(sd["adam_step"])
 
     # ------------------------------------------------------------------ HIP graph replay of the whole step
     def capture_graph(self):
         """Capture one train step (its 8-9 launches, one stream) into a HIP graph.  ``step_graph(u, i)`` then
         copies the ids into the captured buffers and replays: one host call per step, no launch gaps."""
-        if self.cfg.dropout_rate > 0.0:
-            raise NotImplementedError("graph replay with dropout: the per-step counter is a kernel argument")
-        if self.cfg.optimizer == "adam":
-            raise NotImplementedError("graph replay with optimizer='adam': the global step, and so the bias-corrected step size, "
-                                      "is a kernel argument")
-        if self.mixed:
-            raise NotImplementedError("graph replay with candidate_sampling='mixed' is not implemented: the sampler's counter is a "
-                                      "kernel argument and the step is the Python sequence of per-tower launches")
-        if self.cfg.n_title_buckets:
-            raise NotImplementedError("graph replay with the title feature (n_title_buckets > 0) is not implemented: the warm-up "
-                                      "step's update of the title table is not undone")
-        if self.cfg.user_history_len:
-            raise NotImplementedError("graph replay with the user-history feature (user_history_len > 0) is not implemented: the "
-                                      "warm-up step's update of the history table is not undone")
-        if self.cfg.n_user_features or self.cfg.n_item_features:
-            raise NotImplementedError("graph replay with the numeric side features (n_user_features / n_item_features > 0) is not "
-                                      "implemented: the step is the Python sequence of launches over materialised tower inputs")
-        if self.rating_on:
-            raise NotImplementedError("graph replay with the rating head (rating_weight > 0) is not implemented: the step is the "
-                                      "Python sequence of launches")
-        if self.cfg.cross_layers:
-            raise NotImplementedError("graph replay with cross layers (cross_layers > 0) is not implemented: the step is the "
-                                      "Python sequence of launches over materialised tower inputs")
+        for refused, what in _GRAPH_REFUSALS:
+            if refused(self.cfg):
+                raise NotImplementedError(f"graph replay with {what}")
         b = self.cfg.batch_size
         self._g_uid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_iid = torch.zeros(b, dtype=torch.int64, device=self.dev)
         self._g_kw = {}
         if self.cat_table is not None:
             self._g_kw["category_ids"] = torch.zeros(b, dtype=torch.int64, device=self.dev)
-        cat_state = None if self.cat_table is None else \
-            [self.cat_table[:1].clone(), None if self.cat_accum is None else self.cat_accum[:1].clone()]
-        state = [t.clone() for t in (self.user_table[:1], self.item_table[:1], self.dense_flat)]
-        acc = None
-        if self.cfg.optimizer == "adagrad":
-            acc = [t.clone() for t in (self.user_accum[:1], self.item_accum[:1], self.dense_accum)]
+        # what the warm-up steps touch and the undo below restores: row 0 of every table (ids 0), the dense parameters, and
+        # their Adagrad accumulators
+        touched = [x[:1] for t in self.tables.values() for x in (t.table, t.accum) if x is not None] + \
+                  [x for x in (self.dense_flat, self.dense_accum) if x is not None]
+        state = [x.clone() for x in touched]
         # one graph per optimizer path (r04): the skew probe runs OUTSIDE the graphs (step_graph) and picks which one to replay
         poll, load, state_was = self.flag_poll_every, self.range_load, self._skew_state
         self.flag_poll_every = 0                       # (no probe / flag poll inside the warm-up or the capture)
@@ -1735,14 +1745,8 @@ class TwoTowerTrainer:
                     self.step(self._g_uid, self._g_iid, **self._g_kw)
                 torch.cuda.synchronize()
                 self._graphs[skewed] = g
-                # undo the warm-up step's update (row 0 of both tables, dense parameters)
-                self.user_table[:1].copy_(state[0]); self.item_table[:1].copy_(state[1]); self.dense_flat.copy_(state[2])
-                if acc is not None:
-                    self.user_accum[:1].copy_(acc[0]); self.item_accum[:1].copy_(acc[1]); self.dense_accum.copy_(acc[2])
-                if cat_state is not None:
-                    self.cat_table[:1].copy_(cat_state[0])
-                    if cat_state[1] is not None:
-                        self.cat_accum[:1].copy_(cat_state[1])
+                for x, saved in zip(touched, state):      # undo the warm-up step's update
+                    x.copy_(saved)
         finally:
             self.flag_poll_every, self.range_load, self._skew_state = poll, load, state_was
         self._graph = self._graphs[False]
@@ -1827,14 +1831,9 @@ class TwoTowerTrainer:
     def l2_penalty(self) -> torch.Tensor:
         """l2 * sum(W^2) over the Dense kernels — reporting only (the gradient term is fused in the update)."""
         tot = torch.zeros((), device=self.dev, dtype=torch.float64)
-        for tower in (self.user_tower, self.item_tower):
-            for w in tower.w:
-                tot += (w.double() ** 2).sum()
-        for _, w, _, _ in self._feature_sides:
-            tot += (w.double() ** 2).sum()
-        if getattr(self, "rating_on", False):
-            tot += (self.W1_rating.double() ** 2).sum() + (self.w2_rating.double() ** 2).sum()
-        for tower in (self.user_tower, self.item_tower):
-            for w in tower.cross_w:
-                tot += (w.double() ** 2).sum()
+        for seg in self.layout.segments:
+            if seg.l2:                           # (kernel by kernel: one f64 sum per parameter, as it was always reported)
+                for blk in self.layout.blocks.values():
+                    if seg.lo <= blk.offset < seg.hi:
+                        tot += (blk.view(self.dense_flat).double() ** 2).sum()
         return self.cfg.l2_regularization * tot
