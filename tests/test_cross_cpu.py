@@ -41,6 +41,34 @@ def test_layer_backward_is_the_f64_autograd_gradient():
     assert np.abs(got0["dw"] - wt.grad.numpy()).max() <= 1e-13 and np.abs(got0["db"] - bt.grad.numpy()).max() <= 1e-13
 
 
+def test_f32_evaluation_meets_the_kernel_bars_at_every_gpu_shape():
+    """The bars of tests/test_gpu_cross.py (1e-5 of max|ref|) can be met in float32 on its own problems, the widths that are no
+    power of two included: the same math as torch-CPU f32 operations against the f64 restatement, both backward forms from the
+    restatement's u rounded to f32 (what the GPU test hands the launch)."""
+    import test_gpu_cross as tg
+    assert set(tg.SHAPES) >= {(77, 96), (130, 160), (45, 192), (65, 224)} and sorted({d for _, d in tg.SHAPES}) == list(range(32, 257, 32))
+    f = torch.from_numpy
+    for n, d in tg.SHAPES:
+        p = tg._problem(n, d)
+        x0, x, w, b, g, prev = (f(p[k]) for k in ("x0", "x", "w", "b", "g", "prev"))
+        worst = 0.0
+        for xx, is0 in ((x, False), (x0, True)):
+            want_u, want_y = cc.layer_forward(p["x0"], xx.numpy(), p["w"], p["b"])
+            u = torch.addmm(b, xx, w)
+            errs = dict(u=tg.rel_err(u.numpy(), want_u), y=tg.rel_err((x0 * u + xx).numpy(), want_y))
+            u = f(want_u.astype(np.float32))
+            want = cc.layer_backward(p["x0"], xx.numpy(), u.numpy(), p["w"], p["g"], x_is_x0=is0, dx0_in=p["prev"])
+            t = g * x0
+            dx = g + t @ w.t()
+            errs.update(dx=tg.rel_err((dx + g * u + prev if is0 else dx).numpy(), want["dx"]), dw=tg.rel_err((xx.t() @ t).numpy(), want["dw"]),
+                        db=tg.rel_err(t.sum(0).numpy(), want["db"]))
+            if not is0:
+                errs["dx0"] = tg.rel_err((prev + g * u).numpy(), want["dx0"])
+            assert max(errs.values()) <= 1e-5, (n, d, is0, errs)
+            worst = max(worst, *errs.values())
+        print(f"n {n} D {d}: worst f32 error {worst:.2e}")
+
+
 def test_the_backward_chain_of_the_issue_is_the_stack_gradient():
     """G_l = G_{l+1} + t W_l^T, A += G_{l+1} * u_l, demb = ((G_1 + t W_0^T) + G_1 * u_0) + A - against autograd of the stack."""
     rng = np.random.default_rng(1)

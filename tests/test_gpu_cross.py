@@ -15,7 +15,11 @@ from two_tower_amazon_recommender_amd.trainer import Tower, TwoTowerConfig, TwoT
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(77, 32), (33, 64), (1000, 128), (256, 256)]     # ragged tiles, one and several column blocks per wave, the largest LDS tile
+SHAPES = [(77, 32), (33, 64), (1000, 128), (256, 256),     # ragged tiles, one and several column blocks per wave, the largest LDS tile
+          # widths that are no power of two: 256 / (D / 4) = 10, 6, 5, 4 rows of t per pass of the dW role (idle threads, a ragged
+          # last pass) and 3, 5, 6, 7 column blocks over the four waves (D = 96: wave 3 owns none; D = 224: wave 3 owns one, the
+          # others two).  tests/test_cross_cpu.py: the same math in f32 stays within the bars on these problems
+          (77, 96), (130, 160), (45, 192), (65, 224)]
 LR, LR_SGD = 0.001, 0.0001
 
 
@@ -136,7 +140,7 @@ def test_backward_matches_f64(dev, n, d):
 
 
 # ------------------------------------------------------------------------------------------ 3. two problems per launch
-@pytest.mark.parametrize("d", [32, 128])
+@pytest.mark.parametrize("d", [32, 96, 128])
 def test_two_problems_of_different_n_equal_two_launches_and_repeat(dev, d):
     pa, pb = _problem(256, d, 1), _problem(352, d, 2)
     da, db = ({k: T(v, dev) for k, v in p.items()} for p in (pa, pb))

@@ -35,55 +35,18 @@ def _bad(got, want):
     return int(b.sum()), np.argwhere(b)[:4].tolist()
 
 
-def _errs(got, want):
-    """(max-abs error / max|ref|, relative error in the 2-norm) against an f64 reference."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    scale, norm = np.abs(want).max(), np.sqrt((want ** 2).sum())
-    assert np.isfinite(got).all() and scale > 0
-    return np.abs(got - want).max() / scale, np.sqrt(((got - want) ** 2).sum()) / norm
+_errs = atc.errs                                  # (max-abs error / max|ref|, relative error in the 2-norm) against an f64 reference
+_problem = atc.problem                            # the special bags
 
 
-def _within(got, want, what, worst=None):
-    """Asserts the bars; ``worst`` collects the largest error per result name (the last entry of ``what``)."""
-    e = _errs(got, want)
+def _within(got, want, what, worst=None, zero_scale=None):
+    """Asserts the bars; ``worst`` collects the largest error per result name (the last entry of ``what``).  ``zero_scale``: the
+    size of the terms of a reference that may be zero in every entry (``attention_check.uncancelled_scales``)."""
+    e = _errs(got, want, zero_scale)
     if worst is not None:
         worst[what[-1]] = max(worst.get(what[-1], 0.0), *e)
     assert e[0] <= BAR and e[1] <= BAR, (what, e)
     return e
-
-
-def _problem(rng, n_rows, n_bags, L, rows, indirect):
-    """(tokens [n_rows, L], bag_rows or None, exclude [n_bags]) - the special bags of tests/test_gpu_history.py.  Tokens lie in
-    [0, rows - 1): token rows - 1 stands in no bag.  Bags 0..7 (bag b pools token row b, bag 7 - indirect only - the row -1):
-      0 padding in the middle, an exclude value that is in range and matches nothing     4 as 1, but exclude = -1
-      1 one token in every slot, excluded: a repeated match and an emptied bag           5 exclude >= rows (matches nothing, no flag)
-      2 the match in the first valid slot (L >= 3: behind a padding slot)                6 random tokens, the in-range no-match value
-      3 the match in the last valid slot (L >= 3: in front of a padding slot)
-    The other bags exclude a slot of their own row (a padding slot: -1) half of the time, a random item otherwise."""
-    tok = rng.integers(0, rows - 1, (n_rows, L)).astype(np.int32)
-    tok[rng.random((n_rows, L)) < 0.25] = -1
-    tok[8:][rng.random(n_rows - 8) < 0.1] = -1
-    tok[0:7] = rng.integers(0, rows - 1, (7, L))
-    tok[1], tok[4] = 11, 12
-    tok[2, -1] = tok[2, 0]
-    tok[2, 1:-1] = np.where(tok[2, 1:-1] == tok[2, 0], tok[2, 0] + 1, tok[2, 1:-1])
-    if L >= 3:
-        tok[0, 1] = -1
-        tok[2, 0], tok[2, 1], tok[2, -1] = -1, 21, 22
-        tok[2, 2:-1] = np.where(tok[2, 2:-1] == 21, 23, tok[2, 2:-1])
-        tok[3, -1], tok[3, -2] = -1, 31
-        tok[3, :-2] = np.where(tok[3, :-2] == 31, 32, tok[3, :-2])
-    bag_rows = None
-    if indirect:
-        bag_rows = rng.integers(0, n_rows, n_bags).astype(np.int64)
-        bag_rows[rng.random(n_bags) < 0.08] = -1
-        bag_rows[:8] = [0, 1, 2, 3, 4, 5, 6, -1]
-    br = np.arange(n_bags) if bag_rows is None else bag_rows
-    own = tok[np.maximum(br, 0), rng.integers(0, L, n_bags)].astype(np.int64)
-    exclude = np.where(rng.random(n_bags) < 0.5, own, rng.integers(0, rows, n_bags))
-    first3 = tok[3][tok[3] >= 0]
-    exclude[:7] = [rows - 1, 11, tok[2][tok[2] >= 0][0], first3[-1], -1, rows + 5, rows - 1]
-    return tok, bag_rows, exclude.astype(np.int64)
 
 
 def _device_forward(dev, table_t, tok, bag_rows, exclude, base_t, attn_t):
@@ -162,10 +125,9 @@ def test_forward_matches_the_restatement_and_keeps_its_bitwise_properties(dev, d
     print(f"dim {dim}: worst errors {({k: f'{v:.2e}' for k, v in worst.items()})}")
 
 
-@pytest.mark.parametrize("dim", [4, 36, 128, 516])
-def test_forward_extreme_logits_and_zero_attention(dev, dim):
-    """A bag whose logits reach -200 and +200 (a scaled query; the running max moves up AND stays: slots -200, small, +200,
-    small, -200): finite, the one-hot pool of the restatement.  With attn = 0 the weights are 1 / cnt and out is the mean bag's."""
+def _extreme_problem(dim):
+    """(table [8, dim], attn, tokens [3, 5], base_table, base_ids, the generator): rows 0 and 1 are u and -u, a is u scaled so
+    that their logits are +200 and -200, the other rows' are small."""
     rng = np.random.default_rng(1000 + dim)
     table = (0.1 * rng.standard_normal((8, dim))).astype(np.float32)
     u = rng.standard_normal(dim).astype(np.float32)
@@ -176,6 +138,14 @@ def test_forward_extreme_logits_and_zero_attention(dev, dim):
     tok = np.array([[1, 2, 0, 3, 1], [0, 1, 4, 5, 6], [2, -1, 1, 0, -1]], dtype=np.int32)
     base_table = rng.standard_normal((3, dim)).astype(np.float32)
     base_ids = np.arange(3, dtype=np.int64)
+    return table, attn, tok, base_table, base_ids, rng
+
+
+@pytest.mark.parametrize("dim", [4, 36, 128, 516])
+def test_forward_extreme_logits_and_zero_attention(dev, dim):
+    """A bag whose logits reach -200 and +200 (a scaled query; the running max moves up AND stays: slots -200, small, +200,
+    small, -200): finite, the one-hot pool of the restatement.  With attn = 0 the weights are 1 / cnt and out is the mean bag's."""
+    table, attn, tok, base_table, base_ids, _ = _extreme_problem(dim)
     want = atc.attention_forward(table, tok, attn, None, None, (base_table, base_ids))
     e = table[tok[0]].astype(np.float64) @ attn[:dim].astype(np.float64) / np.sqrt(dim)
     assert e.max() > 195 and e.min() < -195 and want[1].max(1).min() >= 1 - 1e-12          # the restatement is one-hot
@@ -317,6 +287,197 @@ def test_backward_matches_the_closed_form(dev, n_bags, dim):
     assert ops.history_attention_num_slabs(n_bags) == n_bags // 8
 
 
+def _forward_tensors(dev, table_t, tok, bag_rows, exclude, base_t, attn_t):
+    """The device forward into pre-filled buffers, kept on the device: (batch_ids, weights, pooled)."""
+    n_bags = len(tok) if bag_rows is None else len(bag_rows)
+    L, dim = tok.shape[1], table_t.shape[1]
+    ids = torch.full((n_bags * L,), -7, dtype=torch.int64, device=dev)
+    w = torch.full((n_bags, L), -7.0, device=dev)
+    pooled = torch.full((n_bags, dim), -7.0, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    ops.history_attention(table_t, T(tok, dev), attn_t, T(bag_rows, dev), T(exclude, dev), base_t, batch_ids=ids, weights=w,
+                          pooled=pooled, oob_flag=flag)
+    assert flag.item() == 0
+    return ids, w, pooled
+
+
+def _guarded_backward(dev, table_t, ids, w, pooled, dy_t, attn_t, L, n_slabs):
+    """The backward launch into NaN-filled buffers with one row more than the launch is given: (slot_grads [n_bags * L + 1, dim],
+    slabs [n_slabs + 1, dim + L]) - the last row of each is the guard behind what the launch may write."""
+    n_bags, dim = dy_t.shape
+    sg = torch.full((n_bags * L + 1, dim), float("nan"), device=dev)
+    slabs = torch.full((n_slabs + 1, dim + L), float("nan"), device=dev)
+    ops.history_attention_bwd(table_t, ids, w, pooled, dy_t, attn_t, L, slot_grads=sg[:-1], dattn_slabs=slabs[:-1])
+    return sg, slabs
+
+
+def _same_bits(a, b):
+    return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def _is_nan_fill(t):
+    return bool((t.view(torch.int32) == NAN_BITS).all().item())
+
+
+def _zero_floor(ref, zero_scale):
+    """max|ref|, or - where the reference is zero but for its own rounding - the size of its terms."""
+    m = np.abs(ref).max()
+    return zero_scale if m <= 1e-9 * zero_scale else m
+
+
+def _backward_sweep(dev, dim, shapes):
+    """Every check of the backward sweep for one dim over ``shapes`` = ((L, n_bags), ...); returns the worst error per result."""
+    rng = np.random.default_rng(dim)
+    base_table_t = T(rng.standard_normal((40, dim)).astype(np.float32), dev)
+    worst = {}
+    for L, n_bags in shapes:
+        what = (dim, L, n_bags)
+        p = atc.backward_problem(dim, L, n_bags)
+        table_t, dy_t, attn_t = T(p["table"], dev), T(p["dy"], dev), T(p["attn"], dev)
+        base_t = (base_table_t, T(rng.integers(0, 40, n_bags).astype(np.int64), dev))
+        ids, w, pooled = _forward_tensors(dev, table_t, p["tokens"], p["bag_rows"], p["exclude"], base_t, attn_t)
+        f = atc.attention_forward(p["table"], p["tokens"], p["attn"], p["bag_rows"], p["exclude"], None)
+        assert np.array_equal(N(ids), f[3]), what
+        ref = (p["table"], f[3], f[1], f[2], p["dy"], p["attn"], L)
+        want_sg, want_da, want_dp, _ = atc.attention_backward(*ref)
+        bag_da, bag_dp = atc.attention_dattn_per_bag(*ref)
+        za, zp = atc.uncancelled_scales(*ref[:5], L)
+        full_a, full_p = _zero_floor(want_da, za), _zero_floor(want_dp, zp)
+        sum_a = np.concatenate([np.zeros((1, dim)), np.cumsum(bag_da, 0)])
+        sum_p = np.concatenate([np.zeros((1, L)), np.cumsum(bag_dp, 0)])
+        valid = f[3] >= 0
+        assert valid.any() and (L < 3 or valid.reshape(n_bags, L).all(1).any()), what
+        first = None
+        for n_slabs in (1, 3, ops.history_attention_num_slabs(n_bags), n_bags + 2):
+            sg, slabs = _guarded_backward(dev, table_t, ids, w, pooled, dy_t, attn_t, L, n_slabs)
+            sg2, slabs2 = _guarded_backward(dev, table_t, ids, w, pooled, dy_t, attn_t, L, n_slabs)
+            assert _same_bits(sg, sg2) and _same_bits(slabs, slabs2), (what, n_slabs)                   # a second launch: the same bits
+            assert _is_nan_fill(sg[-1]) and _is_nan_fill(slabs[-1]), (what, n_slabs)                    # the guards
+            if first is None:
+                first = sg
+                g = N(sg[:-1])
+                assert (bc.bits(g[~valid]) == NAN_BITS).all(), what                                     # skipped slots' rows are untouched
+                _within(g[valid], want_sg[valid], what + ("slot_grads",), worst)
+            else:
+                assert _same_bits(sg, first), (what, n_slabs)                                           # the slot rows do not depend on n_slabs
+            sl = N(slabs[:-1])
+            assert np.isfinite(sl).all(), (what, n_slabs)
+            total = sl.astype(np.float64).sum(0)
+            _within(total[:dim], want_da, what + (n_slabs, "da"), worst, za)
+            _within(total[dim:], want_dp, what + (n_slabs, "dp"), worst, zp)
+            zero = abs(total[dim:].sum()) / full_p
+            worst["sum(dp)"] = max(worst.get("sum(dp)", 0.0), zero)
+            assert zero <= BAR, (what, n_slabs, zero)
+            # slab s holds the sums over ITS bags; a slab without bags is +0 in every entry
+            per = -(-n_bags // n_slabs)
+            lo = np.minimum(np.arange(n_slabs) * per, n_bags)
+            hi = np.minimum(lo + per, n_bags)
+            empty = lo == hi
+            assert empty.any() == (n_slabs > n_bags) and (n_slabs != n_bags + 2 or empty.sum() >= 2), (what, n_slabs)
+            assert not bc.bits(sl[empty]).any(), (what, n_slabs)
+            for part, cum, full, name in ((sl[:, :dim], sum_a, full_a, "slab da"), (sl[:, dim:], sum_p, full_p, "slab dp")):
+                want = cum[hi] - cum[lo]
+                bound = BAR * np.maximum(np.abs(want).max(1), full)
+                err = np.abs(part - want).max(1)
+                worst[name] = max(worst.get(name, 0.0), float((err / np.maximum(np.abs(want).max(1), full)).max()))
+                assert (err <= bound).all(), (what, n_slabs, name, int(np.argmax(err / bound)), float((err / bound).max()))
+        if n_bags == 300:          # a bag's gradient rows depend on that bag only: the first 37 bags, launched alone
+            sg37, _ = _guarded_backward(dev, table_t, ids[:37 * L], w[:37], pooled[:37], dy_t[:37], attn_t, L, 5)
+            assert _same_bits(sg37[:-1], first[:37 * L]) and _is_nan_fill(sg37[-1]), what
+    return worst
+
+
+@pytest.mark.parametrize("dim", atc.SWEEP_DIMS)
+def test_backward_sweep_matches_the_closed_form_slab_by_slab_and_touches_nothing_else(dev, dim):
+    """The forward's sweep for the backward: dim (every lane-group width 1 .. 64, a partly filled group, NV 1 .. 4, KF 4 and 2)
+    x L {1, 7, 37, 64} (up to 64 chunks of the slot loop at dim 4, 3 and 4 at dim 36, 2 at dim 128; the halved workgroup at
+    dim 4, L 64 and the last full one at L 37) x {1, 37, 300} bags x n_slabs {1, 3, the default, n_bags + 2}, on the problems of
+    ``attention_check.backward_problem`` (tests/test_history_attention_cpu.py: the closed form in float32 meets a tenth of the
+    bar on every one of them).  The device forward - exclude, indirect bag rows, a base row - feeds the device backward.
+
+    Where da and dp are zero in every entry (L = 1: one slot per bag) they are held to the bar of the size of their terms."""
+    worst = _backward_sweep(dev, dim, [(L, n_bags) for L in atc.SWEEP_LS for n_bags in atc.SWEEP_BAGS])
+    print(f"dim {dim}: worst errors {({k: f'{v:.2e}' for k, v in worst.items()})}")
+
+
+@pytest.mark.parametrize("dim,L,n_bags", atc.NV2_SHAPES)
+def test_backward_with_two_float4_per_lane(dev, dim, L, n_bags):
+    """The sweep's dims leave out NV = 2 (dim 260 .. 512): one float4 of the second round at dim 260, both rounds full at 512."""
+    assert atc.backward_launch_shape(dim, L) == (64, 2, 4, 256, 1)
+    worst = _backward_sweep(dev, dim, [(L, n_bags)])
+    print(f"dim {dim}: worst errors {({k: f'{v:.2e}' for k, v in worst.items()})}")
+
+
+@pytest.mark.parametrize("dim", [4, 36, 128, 516])
+def test_backward_extreme_logits_zero_attention_and_skipped_ids(dev, dim):
+    """One-hot weights (the forward's extreme-logit bags: logits of -200 and +200), attn = 0 (the mean bag) and batch ids the
+    launch promises to skip without reading their weights.
+
+    With one-hot weights pooled IS the one kept row, so t = G and da, dp are zero in every entry: they are held to the bar of
+    the size of their terms (``attention_check.uncancelled_scales``)."""
+    # 1. one-hot weights from the device forward
+    table, attn, tok, base_table, base_ids, rng = _extreme_problem(dim)
+    n_bags, L = tok.shape
+    dy = rng.standard_normal((n_bags, dim)).astype(np.float32)
+    table_t, attn_t, dy_t = T(table, dev), T(attn, dev), T(dy, dev)
+    ids, w, pooled = _forward_tensors(dev, table_t, tok, None, None, (T(base_table, dev), T(base_ids, dev)), attn_t)
+    wn, idn = N(w), N(ids).reshape(n_bags, L)
+    valid = idn >= 0
+    assert np.array_equal(np.argmax(wn, 1), [2, 0, 3]) and (wn.max(1) == 1.0).all() and (wn.sum(1) == 1.0).all()
+    none = valid & (wn == 0)
+    assert none.sum() == 4 + 4 + 2 and (~valid).sum() == 2
+    ref = atc.attention_backward(table, idn, wn, N(pooled), dy, attn, L)                  # the closed form fed the SAME weights
+    za, zp = atc.uncancelled_scales(table, idn, wn, N(pooled), dy, L)
+    for n_slabs in (1, 3):
+        sg, slabs = _guarded_backward(dev, table_t, ids, w, pooled, dy_t, attn_t, L, n_slabs)
+        g, sl = N(sg[:-1]).reshape(n_bags, L, dim), N(slabs[:-1])
+        assert np.isfinite(g[valid]).all() and np.isfinite(sl).all() and (bc.bits(g[~valid]) == NAN_BITS).all()
+        assert _is_nan_fill(sg[-1]) and _is_nan_fill(slabs[-1])
+        assert (g[none] == 0).all()                                                        # weight exactly 0: a row that compares equal to 0
+        for b, j in enumerate(np.argmax(wn, 1)):
+            print(dim, "one-hot row", b, _within(g[b, j], dy[b], (dim, "one-hot", n_slabs, b, "slot_grads")))
+        total = sl.astype(np.float64).sum(0)
+        print(dim, "one-hot da, dp", _within(total[:dim], ref[1], (dim, "one-hot", n_slabs, "da"), zero_scale=za),
+              _within(total[dim:], ref[2], (dim, "one-hot", n_slabs, "dp"), zero_scale=zp))
+    # 2. attn = 0: weights 1 / cnt, rows g / cnt
+    L, n_bags = 7, 37
+    p = atc.backward_problem(dim, L, n_bags, seed=1)
+    table_t, dy_t, zero_t = T(p["table"], dev), T(p["dy"], dev), torch.zeros(dim + L, device=dev)
+    ids, w, pooled = _forward_tensors(dev, table_t, p["tokens"], p["bag_rows"], p["exclude"], None, zero_t)
+    f = atc.attention_forward(p["table"], p["tokens"], np.zeros(dim + L, np.float32), p["bag_rows"], p["exclude"], None)
+    valid = f[3].reshape(n_bags, L) >= 0
+    cnt = valid.sum(1)
+    assert np.array_equal(N(ids), f[3]) and np.array_equal(N(w), np.where(valid, np.float32(1) / np.maximum(cnt, 1).astype(np.float32)[:, None], 0))
+    ref = atc.attention_backward(p["table"], f[3], f[1], f[2], p["dy"], np.zeros(dim + L), L)
+    sg, slabs = _guarded_backward(dev, table_t, ids, w, pooled, dy_t, zero_t, L, 5)
+    g = N(sg[:-1]).reshape(n_bags, L, dim)
+    rows = np.broadcast_to((p["dy"].astype(np.float64) / np.maximum(cnt, 1)[:, None])[:, None, :], g.shape)
+    total = N(slabs[:-1]).astype(np.float64).sum(0)
+    print(dim, "attn = 0", _within(g[valid], rows[valid], (dim, "attn = 0", "slot_grads")), _within(total[:dim], ref[1], (dim, "attn = 0", "da")),
+          _within(total[dim:], ref[2], (dim, "attn = 0", "dp")))
+    assert (bc.bits(g[~valid]) == NAN_BITS).all() and _is_nan_fill(sg[-1]) and _is_nan_fill(slabs[-1])
+    # 3. ids >= table_rows and ids < -1: skipped like -1, their weights never read
+    L, n_bags = 37, 37
+    p = atc.backward_problem(dim, L, n_bags, seed=2)
+    table_t, dy_t, attn_t = T(p["table"], dev), T(p["dy"], dev), T(p["attn"], dev)
+    ids, w, pooled = _forward_tensors(dev, table_t, p["tokens"], p["bag_rows"], p["exclude"], None, attn_t)
+    idn, wn = N(ids), N(w).reshape(-1)
+    kept = np.flatnonzero(idn >= 0)
+    assert (idn[8 * L:9 * L] >= 0).all()                                                   # bag 8 is full: a skipped id in each part of it
+    at = np.unique(np.concatenate([kept[[0, 1, len(kept) // 2, -1]], 8 * L + np.array([0, 3, L // 2, L - 2, L - 1])]))
+    bad_ids, bad_w, clean_ids, clean_w = idn.copy(), wn.copy(), idn.copy(), wn.copy()
+    bad_ids[at] = np.resize([atc.ROWS, atc.ROWS + 7, -5], len(at))
+    bad_w[at] = np.nan
+    clean_ids[at], clean_w[at] = -1, 0.0
+    n_slabs = ops.history_attention_num_slabs(n_bags)
+    bad = _guarded_backward(dev, table_t, T(bad_ids, dev), T(bad_w.reshape(n_bags, L), dev), pooled, dy_t, attn_t, L, n_slabs)
+    clean = _guarded_backward(dev, table_t, T(clean_ids, dev), T(clean_w.reshape(n_bags, L), dev), pooled, dy_t, attn_t, L, n_slabs)
+    assert _same_bits(bad[0], clean[0]) and _same_bits(bad[1], clean[1])
+    assert _is_nan_fill(bad[0][:-1][T(at, dev)]) and _is_nan_fill(bad[0][-1]) and torch.isfinite(bad[1][:-1]).all().item()
+    untouched = _guarded_backward(dev, table_t, ids, w, pooled, dy_t, attn_t, L, n_slabs)
+    assert not _same_bits(untouched[1], bad[1]) and torch.isfinite(untouched[0][:-1][T(at, dev)]).all().item()   # the slots DID count before
+
+
 # ------------------------------------------------------------------------------------------ 4. the update
 @pytest.mark.parametrize("opt", ["sgd", "adagrad", "adam"])
 def test_update_from_the_slot_rows_is_bit_exact(dev, update_problem, opt):
@@ -389,24 +550,30 @@ def _towers64(tr):
     return tuple(([cut(w) for w in tw.w], [cut(b) for b in tw.b]) for tw in (tr.user_tower, tr.item_tower))
 
 
-def test_trainer_matches_the_f64_restatement_and_trains(dev):
-    """L = 5: loss and every gradient - the history table's (the scatter-add of the slot rows), da and dp included - within the
+@pytest.mark.parametrize("L", [5, 20])
+def test_trainer_matches_the_f64_restatement_and_trains(dev, L):
+    """L = 5 (one chunk of the backward's slot loop at dim 32, where a lane group is 8 lanes) and L = 20 (three chunks: some users'
+    histories fill more than 8 slots): loss and every gradient - the history table's (the scatter-add of the slot rows), da and dp included - within the
     bars of the f64 autograd restatement given the device's ReLU masks, with attn set to random values first (at zero the second
     term of the slot rows vanishes); then 20 Adam steps from the zero initialisation lower the loss and move attn off zero.  The
     item tower's last bias gradient is identically zero under the in-batch softmax and is held to 1e-4 of max|dc|, as in the
     history feature's test."""
-    seed, batch, L = 1001, 256, 5
-    tr = _history_trainer(dev, "sgd", seed)
+    seed, batch = 1001, 256
+    tr = _history_trainer(dev, "sgd", seed, L=L)
     assert not tr.fuse_lookup and tr.history_attn.storage_offset() % 4 == 0 and not tr.history_attn.any()
-    assert len(tr._segs) == len(_history_trainer(dev, "sgd", seed, pooling="mean")._segs) + 1 == tr.cfg.dense_segment_count()
+    assert len(tr._segs) == len(_history_trainer(dev, "sgd", seed, pooling="mean", L=L)._segs) + 1 == tr.cfg.dense_segment_count()
     _set_attn(tr, 5)
     hist = tr.user_history.cpu().numpy()
+    assert hist.shape == (300, L) and atc.backward_launch_shape(32, L)[:2] == (8, 1)
+    if L == 20:                                                                    # histories that reach into a second and a third chunk
+        assert ((hist >= 0).sum(1) > 8).sum() >= 3 and ((hist >= 0).sum(1) > 16).any()
     d = tr.cfg.embedding_dim
     for step in range(2):
         u, i = tr.synthetic_batch(seed, step, "Z")
         un, inn = u.cpu().numpy(), i.cpu().numpy()
         valid = hist[un] >= 0
         match = valid & (hist[un] == inn[:, None])
+        assert L == 5 or ((valid & ~match).sum(1) > 8).sum() >= 8                   # ... in this batch, after the leave-one-out
         assert match.any() and (valid.any(1) & (match.sum(1) == valid.sum(1))).any() and (valid & ~match).any()
         before = {k: getattr(tr, k).cpu().numpy().astype(np.float64) for k in ("user_table", "item_table", "history_table")}
         attn = tr.history_attn.cpu().numpy().astype(np.float64)
@@ -447,7 +614,7 @@ def test_trainer_matches_the_f64_restatement_and_trains(dev):
         a0 = tr.history_attn.clone()
         tr.apply_gradients(step_ids=[u, i])
         assert not torch.equal(a0, tr.history_attn)                                # the dense segment trains the vector
-    tr2 = _history_trainer(dev, "adam", seed)
+    tr2 = _history_trainer(dev, "adam", seed, L=L)
     batch0 = tr2.synthetic_batch(seed, 0, "Z")
     t0 = tr2.history_table.clone()
     losses = [tr2.step(*batch0).item() for _ in range(20)]
@@ -536,34 +703,51 @@ def test_inference_paths_attend_over_the_full_history(dev):
 
 # ------------------------------------------------------------------------------------------ 8. custom ops, CLIs
 def test_custom_ops_pass_opcheck_equal_the_ops_calls_and_differentiate_attn(dev):
+    """(dim 64, L 6) and (dim 32, L 20): a lane group of 8 walks 20 slots in 3 chunks.  The gradient of attn through the op is held
+    to the closed form and to f64 autograd of ``attention_forward_torch`` on the op's own batch ids."""
     from two_tower_amazon_recommender_amd import torch_ops  # noqa: F401
     rng = np.random.default_rng(3)
-    dim, L = 64, 6
-    table_np = rng.standard_normal((80, dim)).astype(np.float32)
-    table = T(table_np, dev)
-    base_table = T(rng.standard_normal((30, dim)).astype(np.float32), dev)
-    tok, bag_rows, exclude = _problem(rng, 33, 50, L, 80, True)
-    tok_t, rows, ex = T(tok, dev), T(bag_rows, dev), T(exclude, dev)
-    base_ids = T(rng.integers(0, 30, 50).astype(np.int64), dev)
-    attn_np = rng.standard_normal(dim + L).astype(np.float32)
-    tok33 = tok_t[:33]
-    for args in ((table, tok33, None, None, None, None), (table, tok_t, rows, ex, None, None), (table, tok_t, rows, ex, base_table, base_ids)):
-        attn = T(attn_np, dev).requires_grad_(True)
-        torch.library.opcheck(torch.ops.twotower.history_attention, args + (attn,))
-        out, w, pooled, ids = torch.ops.twotower.history_attention(*args, attn)
-        base = None if args[4] is None else (args[4], args[5])
-        ids2 = torch.empty_like(ids)
-        want = ops.history_attention(table, args[1], attn.detach(), args[2], args[3], base, batch_ids=ids2)
-        assert torch.equal(out, want[0]) and torch.equal(w, want[1]) and torch.equal(pooled, want[2]) and torch.equal(ids, ids2)
-        n_bags = out.shape[0]
-        dy = T(rng.uniform(-1, 1, (n_bags, dim)).astype(np.float32), dev)
-        out.backward(dy)
-        sg, dattn = torch.ops.twotower.history_attention_bwd(table, ids, w.detach(), pooled.detach(), dy, attn.detach())
-        assert torch.equal(attn.grad, dattn)
-        ref = atc.attention_backward(table_np, N(ids), N(w), N(pooled), N(dy), attn_np, L)
-        print("dattn", _within(N(attn.grad), np.concatenate([ref[1], ref[2]]), "autograd dattn"))
-        print("slot rows", _within(N(sg), ref[0], "custom-op slot rows"))          # (the op zero-fills the skipped slots' rows)
-        torch.library.opcheck(torch.ops.twotower.history_attention_bwd, (table, ids, w.detach(), pooled.detach(), dy, attn.detach()))
+    for dim, L in ((64, 6), (32, 20)):
+        assert atc.backward_launch_shape(dim, L)[4] == (1 if L == 6 else 3)
+        table_np = rng.standard_normal((80, dim)).astype(np.float32)
+        table = T(table_np, dev)
+        base_np = rng.standard_normal((30, dim)).astype(np.float32)
+        base_table = T(base_np, dev)
+        tok, bag_rows, exclude = _problem(rng, 33, 50, L, 80, True)
+        tok_t, rows, ex = T(tok, dev), T(bag_rows, dev), T(exclude, dev)
+        base_ids_np = rng.integers(0, 30, 50).astype(np.int64)
+        base_ids = T(base_ids_np, dev)
+        attn_np = rng.standard_normal(dim + L).astype(np.float32)
+        tok33 = tok_t[:33]
+        for args in ((table, tok33, None, None, None, None), (table, tok_t, rows, ex, None, None), (table, tok_t, rows, ex, base_table, base_ids)):
+            attn = T(attn_np, dev).requires_grad_(True)
+            torch.library.opcheck(torch.ops.twotower.history_attention, args + (attn,))
+            out, w, pooled, ids = torch.ops.twotower.history_attention(*args, attn)
+            base = None if args[4] is None else (args[4], args[5])
+            ids2 = torch.empty_like(ids)
+            want = ops.history_attention(table, args[1], attn.detach(), args[2], args[3], base, batch_ids=ids2)
+            assert torch.equal(out, want[0]) and torch.equal(w, want[1]) and torch.equal(pooled, want[2]) and torch.equal(ids, ids2)
+            n_bags = out.shape[0]
+            dy = T(rng.uniform(-1, 1, (n_bags, dim)).astype(np.float32), dev)
+            out.backward(dy)
+            sg, dattn = torch.ops.twotower.history_attention_bwd(table, ids, w.detach(), pooled.detach(), dy, attn.detach())
+            assert torch.equal(attn.grad, dattn)
+            ref = atc.attention_backward(table_np, N(ids), N(w), N(pooled), N(dy), attn_np, L)
+            print("dattn", _within(N(attn.grad), np.concatenate([ref[1], ref[2]]), "autograd dattn"))
+            print("slot rows", _within(N(sg), ref[0], "custom-op slot rows"))          # (the op zero-fills the skipped slots' rows)
+            # f64 autograd through the forward restatement, from the op's ids
+            kept = ids.cpu().view(n_bags, L)
+            assert (kept >= 0).sum(1).max().item() > 8 or L == 6                       # bags that reach into a second chunk
+            a64 = torch.tensor(attn_np.astype(np.float64), requires_grad=True)
+            t64 = torch.tensor(table_np.astype(np.float64), requires_grad=True)
+            base_rows = None if base is None else torch.from_numpy(base_np.astype(np.float64))[torch.from_numpy(base_ids_np)]
+            o64 = atc.attention_forward_torch(t64, kept, a64, base_rows)[0]
+            (o64 * dy.cpu().double()).sum().backward()
+            print("dattn (f64 autograd)", _within(N(attn.grad), a64.grad.numpy(), (dim, L, "autograd dattn against f64 autograd")))
+            g_table = np.zeros((80, dim))
+            np.add.at(g_table, N(ids)[N(ids) >= 0], N(sg).astype(np.float64)[N(ids) >= 0])
+            print("table (f64 autograd)", _within(g_table, t64.grad.numpy(), (dim, L, "scattered slot rows against f64 autograd")))
+            torch.library.opcheck(torch.ops.twotower.history_attention_bwd, (table, ids, w.detach(), pooled.detach(), dy, attn.detach()))
     with pytest.raises(ValueError, match="go together"):
         torch.ops.twotower.history_attention(table, tok_t, rows, ex, base_table, None, T(attn_np, dev))
 

@@ -73,6 +73,54 @@ def test_closed_form_backward_equals_f64_autograd():
     assert not dh[~valid].any()
 
 
+def _f32_closed_form_errors(dim, shapes):
+    """The worst errors of the float32 closed form against the f64 one over ``shapes`` = ((L, n_bags), ...), each held to BAR / 10."""
+    worst = {}
+    for L, n_bags in shapes:
+        p = atc.backward_problem(dim, L, n_bags)
+        _, w, pooled, ids, flag = atc.attention_forward(p["table"], p["tokens"], p["attn"], p["bag_rows"], p["exclude"], None)
+        assert flag == 0 and len(ids) == n_bags * L
+        valid = ids >= 0
+        want = atc.attention_backward(p["table"], ids, w, pooled, p["dy"], p["attn"], L)
+        got = atc.attention_backward_f32(p["table"], ids, w, pooled, p["dy"], p["attn"], L)
+        za, zp = atc.uncancelled_scales(p["table"], ids, w, pooled, p["dy"], L)
+        zero = np.abs(want[1]).max() <= 1e-9 * za and np.abs(want[2]).max() <= 1e-9 * zp
+        assert zero == (L == 1)                                                # one slot per bag: da = dp = 0, and only then
+        for name, g, r, z in (("slot_grads", got[0][valid], want[0][valid], None), ("da", got[1], want[1], za), ("dp", got[2], want[2], zp)):
+            e = atc.errs(g, r, z)
+            worst[name] = max(worst.get(name, 0.0), *e)
+            assert e[0] <= atc.BAR / 10 and e[1] <= atc.BAR / 10, (dim, L, n_bags, name, e)
+        assert abs(float(want[2].sum())) <= 1e-12 * zp
+    return worst
+
+
+@pytest.mark.parametrize("dim", atc.SWEEP_DIMS)
+def test_f32_closed_form_meets_a_tenth_of_the_bar_at_every_sweep_shape(dim):
+    """The GPU sweep of the backward (tests/test_gpu_history_attention.py) holds a float32 kernel to BAR = 1e-4 of the f64 closed
+    form on the problems of ``attention_check.backward_problem``.  That the problems allow it: at every (dim, L, n_bags) of the
+    sweep the closed form evaluated in float32 - both from the f64 forward's weights and pooled rows - stays within BAR / 10 of
+    the f64 one under both error measures, for the slot rows of the kept slots, da and dp."""
+    worst = _f32_closed_form_errors(dim, [(L, n_bags) for L in atc.SWEEP_LS for n_bags in atc.SWEEP_BAGS])
+    print(f"dim {dim}: worst f32 errors {({k: f'{v:.2e}' for k, v in worst.items()})}")
+
+
+@pytest.mark.parametrize("dim,L,n_bags", atc.NV2_SHAPES)
+def test_f32_closed_form_meets_a_tenth_of_the_bar_with_two_float4_per_lane(dim, L, n_bags):
+    print(f"dim {dim}: worst f32 errors {({k: f'{v:.2e}' for k, v in _f32_closed_form_errors(dim, [(L, n_bags)]).items()})}")
+
+
+def test_backward_launch_shapes_of_the_sweep():
+    """The forms of the backward launch the sweep reaches, as (lpr, NV, KF, threads, chunks)."""
+    got = {(dim, L): atc.backward_launch_shape(dim, L) for dim in atc.SWEEP_DIMS for L in atc.SWEEP_LS}
+    assert got[(4, 37)] == (1, 1, 4, 256, 37) and got[(4, 64)] == (1, 1, 4, 128, 64)          # just under the LDS limit; halved
+    assert got[(36, 37)] == (16, 1, 4, 256, 3) and got[(36, 64)] == (16, 1, 4, 256, 4)
+    assert got[(128, 37)] == got[(128, 64)] == (32, 1, 4, 256, 2) and got[(128, 7)] == (32, 1, 4, 256, 1)
+    assert got[(256, 64)] == (64, 1, 4, 256, 1) and got[(516, 64)] == (64, 3, 2, 256, 1) and got[(1024, 64)] == (64, 4, 2, 256, 1)
+    assert atc.backward_launch_shape(32, 20) == (8, 1, 4, 256, 3) and atc.backward_launch_shape(32, 5)[4] == 1   # the trainer tests
+    assert all(atc.backward_launch_shape(d, L) == (64, 2, 4, 256, 1) for d, L, _ in atc.NV2_SHAPES) and not any(v[1] == 2 for v in got.values())
+    assert atc.backward_launch_shape(4, 44)[3] == 256 and atc.backward_launch_shape(4, 45)[3] == 128
+
+
 # ------------------------------------------------------------------------------------------ 2. config
 def test_config_validation_yaml_and_cli(tmp_path):
     base = dict(n_users=10, n_items=10)
