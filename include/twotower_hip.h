@@ -49,8 +49,8 @@ const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
  * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args,
  * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args, 15 tt_dense_features_bwd_args,
- * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args; else - 9, 13 and 16 included, which stay unassigned - -1): a binding checks its
- * mirrors with it. */
+ * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args; else - 9, 13, 16, 19 and
+ * 20 included, which stay unassigned - -1): a binding checks its mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
 /* ---------------------------------------------------------------------------------------
@@ -65,7 +65,7 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
  * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
  * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32), cross_fwd, cross_bwd
- * (tt_cross_*_f32).
+ * (tt_cross_*_f32), layer_norm_fwd, layer_norm_bwd (tt_layer_norm_*_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -598,6 +598,59 @@ typedef struct tt_cross_bwd_args {
 int tt_cross_fwd_f32(const tt_cross_fwd_args* probs, int32_t n_probs, int32_t D, tt_stream_t stream);
 int tt_cross_bwd_f32(const tt_cross_bwd_args* probs, int32_t n_probs, int32_t D, tt_stream_t stream);
 int32_t tt_cross_num_slabs(int64_t n);
+
+/* ---------------------------------------------------------------------------------------
+ * Layer normalisation of the tower hidden layers (added to v10: new symbols and structs only, the version is unchanged;
+ * csrc/layernorm.hip) - Keras LayerNormalization between a hidden Dense layer (run without activation) and its ReLU.  Per row
+ * of z [rows, dim], with gamma and beta [dim]:
+ *   mu = mean(z)   var = mean((z - mu)^2)   r = 1 / sqrt(var + eps)   xhat = (z - mu) * r        (biased variance, two-pass)
+ *   y  = dropout(relu(xhat * gamma + beta))         product and sum rounded separately; division and square root correctly rounded
+ * relu != 0 applies the ReLU; drop_rate > 0 applies inverted dropout with the stream of tt_dense_fwd_batched_f32: key
+ * (seed, dropout_tensor_id), element (r, c) at counter_offset + r * dim + c, dropped iff the top 24 bits of its hash are below
+ * round(drop_rate * 2^24), kept entries times 1 / (1 - drop_rate).  relu_bits (optional) receives the sign bits of y in the
+ * format tt_dense_fwd_args.relu_bits documents ([rows, dim/32] words, bit c % 32 of word [r][c / 32] = (y[r][c] > 0)).
+ * Backward, for dn = dL/d(xhat * gamma + beta) - what the dx epilogue of the layer above writes when it masks by the sign bits:
+ *   g = dn * gamma   dz = r * ((g - mean(g)) - xhat * mean(g * xhat))
+ *   dgamma_slabs[s * slab_stride + c] = sum of dn[r,c] * xhat[r,c],   dbeta_slabs[s * slab_stride + c] = sum of dn[r,c]
+ * over the rows r of slab s = [s * R, min((s + 1) * R, rows)), R = ceil(rows / n_slabs).  mu and r are recomputed from z: no
+ * saved statistics.  Every slab is written in full - one without rows as zeros - and only its dim floats behind each of the two
+ * addresses; dgamma_slabs and dbeta_slabs are the addresses of slab 0 and share slab_stride, so all layers and both towers can
+ * write into one [n_slabs][slab_stride] array that one tt_dense_seg / tt_adam_seg sums.  A problem with rows == 0 beside one
+ * with rows still writes its (zero) slabs.  dz MAY ALIAS dn: every lane reads the elements it owns before it writes them and
+ * touches no others.  y must not alias z, dz must not alias z (pointer-equal aliases are refused).
+ * Up to two problems (both towers) per launch, every one with its own rows; `probs` is a HOST array.  A group of lanes sized
+ * to the row (8 lanes at dim 32 ... a whole wave from dim 256 on) holds it in registers and reduces it with a fixed-order
+ * butterfly: no atomics; row r of y and of dz depends on row r alone and is bit-identical across runs, n_probs, the grid and
+ * the number of rows; the slabs' bits depend on (rows, n_slabs, dim) alone.  The backward launch has one workgroup per slab and
+ * problem: tt_layer_norm_num_slabs(rows) is a host query for a count that keeps it parallel (32-row slabs, at most 256); any
+ * n_slabs in 1..65535 is accepted.  HBM-bound: 8 * rows * dim bytes per problem forward, 12 * rows * dim backward.
+ * TT_ERR_INVALID_ARG before any launch: n_probs outside 1..2, dim not a multiple of 32 in 32..1024, eps <= 0, drop_rate outside
+ * [0, 1), rows < 0, n_slabs outside 1..65535, slab_stride < 2 * dim with more than one slab, and for a problem with rows a NULL
+ * pointer (relu_bits excepted), a pointer that is not 16-byte aligned (the slabs need 4) or one of the aliases above.  rows == 0
+ * in every problem: no launch, TT_OK.                                                                                        */
+typedef struct tt_layer_norm_fwd_args {
+  const float* z;            /* [rows, dim]: the Dense layer's pre-activation          */
+  const float* gamma;        /* [dim]                                                  */
+  const float* beta;         /* [dim]                                                  */
+  float* y;                  /* [rows, dim]                                            */
+  uint32_t* relu_bits;       /* [rows, dim/32] or NULL                                 */
+  uint64_t dropout_tensor_id;/* counter stream of this problem's dropout mask (ignored at rate 0) */
+  int64_t rows;
+} tt_layer_norm_fwd_args;
+typedef struct tt_layer_norm_bwd_args {
+  const float* z;            /* [rows, dim]                                            */
+  const float* gamma;        /* [dim]                                                  */
+  const float* dn;           /* [rows, dim]                                            */
+  float* dz;                 /* [rows, dim]; may be dn                                 */
+  float* dgamma_slabs;       /* slab s: dim floats at dgamma_slabs + s * slab_stride   */
+  float* dbeta_slabs;        /* slab s: dim floats at dbeta_slabs + s * slab_stride    */
+  int64_t rows;
+} tt_layer_norm_bwd_args;
+int tt_layer_norm_fwd_f32(const tt_layer_norm_fwd_args* probs, int32_t n_probs, int32_t dim, float eps, int32_t relu,
+                          float drop_rate, uint64_t seed, uint64_t counter_offset, tt_stream_t stream);
+int tt_layer_norm_bwd_f32(const tt_layer_norm_bwd_args* probs, int32_t n_probs, int32_t dim, float eps, int32_t n_slabs,
+                          int64_t slab_stride, tt_stream_t stream);
+int32_t tt_layer_norm_num_slabs(int64_t rows);
 
 /* Dense parameter update over up to TT_MAX_DENSE_SEGS segments in one launch.
  *   g = sum_s grad_slabs[s*slab_stride + i] (s ascending) + 2*l2*w[i]

@@ -137,10 +137,23 @@ class CrossBwdArgs(C.Structure):
                 ("accumulate_dx0", C.c_int32)]
 
 
-# tt_abi_struct_bytes index of each mirror (9, 13 and 16 are unassigned: the library answers -1 for them)
+class LayerNormFwdArgs(C.Structure):
+    """Mirror of ``tt_layer_norm_fwd_args`` (one problem of ``tt_layer_norm_fwd_f32``)."""
+    _fields_ = [("z", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p), ("relu_bits", C.c_void_p),
+                ("dropout_tensor_id", C.c_uint64), ("rows", C.c_int64)]
+
+
+class LayerNormBwdArgs(C.Structure):
+    """Mirror of ``tt_layer_norm_bwd_args`` (one problem of ``tt_layer_norm_bwd_f32``)."""
+    _fields_ = [("z", C.c_void_p), ("gamma", C.c_void_p), ("dn", C.c_void_p), ("dz", C.c_void_p), ("dgamma_slabs", C.c_void_p),
+                ("dbeta_slabs", C.c_void_p), ("rows", C.c_int64)]
+
+
+# tt_abi_struct_bytes index of each mirror (9, 13, 16, 19 and 20 are unassigned: the library answers -1 for them)
 ABI_STRUCT_INDEX = {"AdamTable": 10, "AdamSeg": 11, "AdamHyper": 12}
 FEATURES_STRUCT_INDEX = {"DenseFeaturesFwdArgs": 14, "DenseFeaturesBwdArgs": 15}
 CROSS_STRUCT_INDEX = {"CrossFwdArgs": 17, "CrossBwdArgs": 18}
+LAYER_NORM_STRUCT_INDEX = {"LayerNormFwdArgs": 21, "LayerNormBwdArgs": 22}
 
 
 class TrainStep(C.Structure):
@@ -193,6 +206,9 @@ SIGNATURES = {
     "tt_cross_fwd_f32": (C.c_int, [C.POINTER(CrossFwdArgs), _i32, _i32, _p]),
     "tt_cross_bwd_f32": (C.c_int, [C.POINTER(CrossBwdArgs), _i32, _i32, _p]),
     "tt_cross_num_slabs": (_i32, [_i64]),
+    "tt_layer_norm_fwd_f32": (C.c_int, [C.POINTER(LayerNormFwdArgs), _i32, _i32, _f, _i32, _f, _u64, _u64, _p]),
+    "tt_layer_norm_bwd_f32": (C.c_int, [C.POINTER(LayerNormBwdArgs), _i32, _i32, _f, _i32, _i64, _p]),
+    "tt_layer_norm_num_slabs": (_i32, [_i64]),
     "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),

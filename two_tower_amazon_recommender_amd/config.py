@@ -2,6 +2,8 @@
 ``/root/reference/configs/data_config.yaml:54-71`` (no code in the reference reads it)."""
 from __future__ import annotations
 
+import math
+
 import yaml
 
 from .trainer import TwoTowerConfig
@@ -62,6 +64,26 @@ def cross_from_dict(doc: dict) -> dict:
     return {"layers": layers}
 
 
+def layer_norm_from_dict(doc: dict) -> dict:
+    """{enabled, epsilon} of the optional ``model.layer_norm`` block (not in the reference's schema): Keras LayerNormalization
+    between every hidden Dense layer of both towers and its ReLU.  Without the block: off, epsilon 1e-3 (Keras's default)."""
+    block = (doc.get("model") or {}).get("layer_norm")
+    default = TwoTowerConfig.layer_norm_epsilon
+    if block is None:
+        return {"enabled": False, "epsilon": default}
+    if not isinstance(block, dict):
+        raise ValueError("model.layer_norm must be a mapping {enabled, epsilon}")
+    unknown = sorted(set(block) - {"enabled", "epsilon"})
+    if unknown:
+        raise ValueError(f"model.layer_norm: unknown keys {unknown} (center / scale switches, other axes and RMS scaling are not implemented)")
+    enabled, eps = block.get("enabled", False), block.get("epsilon", default)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"model.layer_norm.enabled must be a bool, got {enabled!r}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"model.layer_norm.epsilon must be a finite number > 0, got {eps!r}")
+    return {"enabled": enabled, "epsilon": float(eps)}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -90,6 +112,8 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     ranking = ranking_from_dict(doc)
     # likewise model.cross {layers} - DCN-v2 cross layers in both towers
     cross = cross_from_dict(doc)
+    # likewise model.layer_norm {enabled, epsilon} - layer normalisation of the towers' hidden layers
+    norm = layer_norm_from_dict(doc)
     cfg = TwoTowerConfig(
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
@@ -103,7 +127,8 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         user_history_len=int(hist.get("max_items", 0)), history_pooling=str(hist.get("pooling", "mean")),
         feature_clip=numeric["clip"], rating_weight=ranking["weight"], rating_hidden=ranking["hidden_dim"],
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
-        title_pooling=str(title.get("pooling", "mean")), cross_layers=cross["layers"])
+        title_pooling=str(title.get("pooling", "mean")), cross_layers=cross["layers"],
+        layer_norm=norm["enabled"], layer_norm_epsilon=norm["epsilon"])
     loop = dict(epochs=int(tr.get("epochs", 1)), patience=int(tr.get("patience", 5)),
                 validation_freq=int(tr.get("validation_freq", 1)), top_k_eval=list(rt.get("top_k_eval", [])))
     return cfg, loop

@@ -1329,6 +1329,131 @@ def cross_layer_bwd(*problems, x_is_x0: bool = False, accumulate_dx0: bool = Fal
                  for dx, dx0, dws, dbs, ns, stride, d in outs)
 
 
+# ----------------------------------------------------------------------------- layer normalisation of the hidden layers
+LAYER_NORM_EPS = 1e-3          # Keras LayerNormalization's default epsilon
+
+
+def _chk_layer_norm(what: str, z, gamma):
+    _chk(z, torch.float32, "z", 2)
+    _chk(gamma, torch.float32, "gamma", 1)
+    n, d = z.shape
+    if d % 32 or not 32 <= d <= 1024:
+        raise RuntimeError(f"{what}: the row width must be a multiple of 32 in 32..1024, got {d}")
+    if gamma.numel() != d:
+        raise RuntimeError(f"{what}: gamma must hold {d} entries, got {gamma.numel()}")
+    return n, d
+
+
+def layer_norm2(*problems, eps: float = LAYER_NORM_EPS, relu: bool = False, dropout=None):
+    """Layer normalisation (Keras LayerNormalization, biased two-pass variance) with an optional ReLU and dropout for one or
+    two problems - both towers - in ONE launch (``tt_layer_norm_fwd_f32``).  Every problem is ``(z, gamma, beta, y, relu_bits)``:
+    ``z`` [rows, dim] the Dense layer's pre-activation, ``gamma`` / ``beta`` [dim], ``y`` [rows, dim] or None (allocated; must
+    not be ``z``), ``relu_bits`` None or a ``relu_bits_like(rows, dim)`` buffer that receives the sign bits of y.  dim is a
+    multiple of 32 in 32..1024 and the same in every problem; every problem has its own rows.
+    ``dropout`` = (rate, seed, tensor_ids, counter_offset) - ``tensor_ids`` one id or one per problem - applies the inverted
+    dropout of ``dense_fwd`` (same stream, same mask) behind the ReLU.  Returns the tuple of the problems' ``y``."""
+    if len(problems) not in (1, 2):
+        raise ValueError("layer_norm2: one or two problems")
+    if not eps > 0:
+        raise ValueError(f"layer_norm2: eps must be > 0, got {eps}")
+    rate, seed, tids, off = dropout if dropout is not None else (0.0, 0, 0, 0)
+    tids = (int(tids),) * len(problems) if not isinstance(tids, (tuple, list)) else tuple(int(t) for t in tids)
+    if len(tids) != len(problems):
+        raise ValueError("layer_norm2: dropout holds one tensor id per problem")
+    arr = (_lib.LayerNormFwdArgs * len(problems))()
+    outs, dim = [], None
+    for i, prob in enumerate(problems):
+        if len(prob) != 5:
+            raise ValueError("layer_norm2: a problem is (z, gamma, beta, y, relu_bits)")
+        z, gamma, beta, y, bits = prob
+        n, d = _chk_layer_norm("layer_norm2", z, gamma)
+        _chk(beta, torch.float32, "beta", 1)
+        if dim is None:
+            dim = d
+        if d != dim or beta.numel() != d:
+            raise RuntimeError("layer_norm2: every problem needs the same dim, and beta must hold dim entries")
+        y = torch.empty((n, d), dtype=torch.float32, device=z.device) if y is None else y
+        _chk(y, torch.float32, "y", 2)
+        if tuple(y.shape) != (n, d):
+            raise RuntimeError(f"layer_norm2: y must be [{n}, {d}], got {tuple(y.shape)}")
+        if y.data_ptr() == z.data_ptr() and n:
+            raise ValueError("layer_norm2: y must not alias z (the backward pass reads z)")
+        _chk_bits(bits, n, d, "layer_norm2: relu_bits")
+        arr[i] = _lib.LayerNormFwdArgs(_p(z), _p(gamma), _p(beta), _p(y), _p(bits), tids[i], n)
+        outs.append(y)
+    _lib.check(_lib.load().tt_layer_norm_fwd_f32(arr, len(problems), dim, float(eps), int(bool(relu)), float(rate), int(seed), int(off),
+                                                 _stream()), "tt_layer_norm_fwd_f32")
+    return tuple(outs)
+
+
+def layer_norm_num_slabs(rows: int) -> int:
+    """Slab count of ``layer_norm_bwd2`` for ``rows`` rows (``tt_layer_norm_num_slabs``, a host query)."""
+    return int(_lib.load().tt_layer_norm_num_slabs(rows))
+
+
+def layer_norm_bwd2(*problems, eps: float = LAYER_NORM_EPS, n_slabs: int | None = None, slab_stride: int | None = None):
+    """The backward pass of ``layer_norm2`` for one or two problems in ONE launch (``tt_layer_norm_bwd_f32``).  Every problem is
+    ``(z, gamma, dn, dz, dgamma_slabs, dbeta_slabs)``: ``dn`` [rows, dim] the gradient w.r.t. xhat * gamma + beta (the ReLU /
+    dropout mask already applied), ``dz`` [rows, dim], None (allocated) or ``dn`` itself (in place); mean and variance are
+    recomputed from ``z``.  ``dgamma_slabs`` / ``dbeta_slabs``: flat f32 tensors that START at slab 0 of
+    dgamma = (dn * xhat).sum(0) and dbeta = dn.sum(0); slab s sits ``slab_stride`` floats further on, so all layers and both
+    towers can share one [n_slabs, slab_stride] array (both None: an [n_slabs, 2 dim] array of the problem's own).  All
+    problems share ``n_slabs`` (default ``layer_norm_num_slabs`` of the longest problem) and ``slab_stride``; slab s covers
+    ceil(rows / n_slabs) contiguous rows of its problem and every slab is written in full (an empty one as zeros).  Returns one
+    ``(dz, dgamma_slabs [n_slabs, dim], dbeta_slabs [n_slabs, dim])`` per problem (views)."""
+    if len(problems) not in (1, 2):
+        raise ValueError("layer_norm_bwd2: one or two problems")
+    if not eps > 0:
+        raise ValueError(f"layer_norm_bwd2: eps must be > 0, got {eps}")
+    for prob in problems:
+        if len(prob) != 6:
+            raise ValueError("layer_norm_bwd2: a problem is (z, gamma, dn, dz, dgamma_slabs, dbeta_slabs)")
+    own = [prob[4] is None for prob in problems]
+    if any((prob[4] is None) != (prob[5] is None) for prob in problems) or len(set(own)) != 1:
+        raise ValueError("layer_norm_bwd2: dgamma_slabs and dbeta_slabs are given both or neither, for every problem alike")
+    if own[0]:
+        if slab_stride is not None:
+            raise ValueError("layer_norm_bwd2: slab_stride belongs to caller-provided slabs")
+        ns = max(layer_norm_num_slabs(max(prob[0].shape[0] for prob in problems)), 1) if n_slabs is None else int(n_slabs)
+        stride = 2 * problems[0][0].shape[1]
+    else:
+        if n_slabs is None or slab_stride is None:
+            raise ValueError("layer_norm_bwd2: dgamma_slabs / dbeta_slabs need n_slabs and slab_stride")
+        ns, stride = int(n_slabs), int(slab_stride)
+    if ns < 1:
+        raise ValueError(f"layer_norm_bwd2: n_slabs must be >= 1, got {ns}")
+    arr = (_lib.LayerNormBwdArgs * len(problems))()
+    outs, dim = [], None
+    for i, (z, gamma, dn, dz, dgs, dbs) in enumerate(problems):
+        n, d = _chk_layer_norm("layer_norm_bwd2", z, gamma)
+        if dim is None:
+            dim = d
+        if d != dim:
+            raise RuntimeError("layer_norm_bwd2: every problem needs the same dim")
+        dz = torch.empty((n, d), dtype=torch.float32, device=z.device) if dz is None else dz
+        for t, name in ((dn, "dn"), (dz, "dz")):
+            _chk(t, torch.float32, name, 2)
+            if tuple(t.shape) != (n, d):
+                raise RuntimeError(f"layer_norm_bwd2: {name} must be [{n}, {d}], got {tuple(t.shape)}")
+        if n and (dz.data_ptr() == z.data_ptr() or dn.data_ptr() == z.data_ptr()):
+            raise ValueError("layer_norm_bwd2: dz and dn must not alias z (dz may be dn)")
+        if dgs is None:
+            slabs = torch.empty(ns * stride, dtype=torch.float32, device=z.device)
+            dgs, dbs = slabs, slabs[d:]
+        else:
+            _chk(dgs, torch.float32, "dgamma_slabs", 1)
+            _chk(dbs, torch.float32, "dbeta_slabs", 1)
+            if stride < 2 * d and ns > 1:
+                raise RuntimeError(f"layer_norm_bwd2: slab_stride must be >= 2 * dim = {2 * d}, got {stride}")
+            if dgs.numel() < (ns - 1) * stride + d or dbs.numel() < (ns - 1) * stride + d:
+                raise RuntimeError("layer_norm_bwd2: dgamma_slabs / dbeta_slabs must reach n_slabs slabs of slab_stride floats")
+        arr[i] = _lib.LayerNormBwdArgs(_p(z), _p(gamma), _p(dn), _p(dz), _p(dgs), _p(dbs), n)
+        outs.append((dz, dgs, dbs, d))
+    _lib.check(_lib.load().tt_layer_norm_bwd_f32(arr, len(problems), dim, float(eps), ns, stride, _stream()), "tt_layer_norm_bwd_f32")
+    return tuple((dz, torch.as_strided(dgs, (ns, d), (stride, 1)), torch.as_strided(dbs, (ns, d), (stride, 1)))
+                 for dz, dgs, dbs, d in outs)
+
+
 def adapt_normalization(x):
     """Keras ``Normalization.adapt`` over the rows of ``x`` [rows, F]: mean and variance of every column in f64, ``inv_std`` =
     1 / max(sqrt(var), 1e-7); returns (mean [F], inv_std [F]) as f32 NumPy arrays.  Non-finite input raises."""

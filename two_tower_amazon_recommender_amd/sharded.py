@@ -441,6 +441,10 @@ class ShardedTwoTowerTrainer:
             # the cross kernels' gradients would join the dense all-reduce and the chain run behind the exchanged input rows
             raise NotImplementedError("cross layers (cross_layers > 0) are not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "layer_norm", False):
+            # the gammas' and betas' gradients would join the dense all-reduce and the towers run the per-layer launch sequence
+            raise NotImplementedError("layer normalisation (layer_norm=True) is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "candidate_sampling", "in_batch") != "in_batch":
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "

@@ -695,6 +695,53 @@ def _cross_backward(ctx, grad_y):
 cross_layer.register_autograd(_cross_backward, setup_context=_cross_setup)
 
 
+# --------------------------------------------------------------------------------------------- layer normalisation
+@torch.library.custom_op(f"{NS}::layer_norm", mutates_args=(), device_types="cuda")
+def layer_norm(z: Tensor, gamma: Tensor, beta: Tensor, eps: float, relu: bool) -> Tensor:
+    """y [rows, dim] = act(LayerNorm(z) * gamma + beta) over the last dim (``ops.layer_norm2``: one launch; Keras
+    LayerNormalization, biased two-pass variance, ``relu``: a ReLU behind it; no dropout).  dim a multiple of 32 in 32..1024.
+    Autograd with respect to z, gamma and beta through ``twotower::layer_norm_bwd``."""
+    return ops.layer_norm2((z.contiguous(), gamma.contiguous(), beta.contiguous(), None, None), eps=eps, relu=relu)[0]
+
+
+@layer_norm.register_fake
+def _(z, gamma, beta, eps, relu):
+    return torch.empty_like(z, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op(f"{NS}::layer_norm_bwd", mutates_args=(), device_types="cuda")
+def layer_norm_bwd(z: Tensor, gamma: Tensor, y: Tensor, grad_y: Tensor, eps: float, relu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dz, dgamma, dbeta) of ``layer_norm`` given dL/dy: with ``relu`` the gradient is masked by y > 0 first; mean and variance
+    are recomputed from z by the ONE backward launch, whose slabs are summed here."""
+    z, gamma = z.contiguous(), gamma.contiguous()
+    if z.shape[0] == 0:
+        return torch.zeros_like(z), torch.zeros_like(gamma), torch.zeros_like(gamma)
+    dn = grad_y.to(torch.float32).contiguous()
+    dn = torch.where(y > 0, dn, torch.zeros_like(dn)) if relu else dn.clone()
+    ((dz, dgs, dbs),) = ops.layer_norm_bwd2((z, gamma, dn, dn, None, None), eps=eps)
+    return dz, dgs.sum(dim=0), dbs.sum(dim=0)
+
+
+@layer_norm_bwd.register_fake
+def _(z, gamma, y, grad_y, eps, relu):
+    e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
+    return e(z), e(gamma), e(gamma)
+
+
+def _layer_norm_setup(ctx, inputs, output):
+    z, gamma, _, ctx.eps, ctx.relu = inputs
+    ctx.save_for_backward(z, gamma, output)
+
+
+def _layer_norm_backward(ctx, grad_y):
+    z, gamma, y = ctx.saved_tensors
+    dz, dg, db = torch.ops.twotower.layer_norm_bwd(z, gamma, y, grad_y, ctx.eps, ctx.relu)
+    return dz, dg, db, None, None
+
+
+layer_norm.register_autograd(_layer_norm_backward, setup_context=_layer_norm_setup)
+
+
 # --------------------------------------------------------------------------------------------- a5 sparse optimizer
 @torch.library.custom_op(f"{NS}::sparse_update_", mutates_args=("table", "accum"), device_types="cuda")
 def sparse_update_(table: Tensor, accum: Optional[Tensor], grads: Tensor, ids: Tensor, optimizer: str, lr: float,
@@ -722,4 +769,4 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
 
 
 OPS = ("embedding_gather", "embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "sparse_update_", "sparse_adam_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_")

@@ -97,6 +97,12 @@ def parse(argv=None):
                     help="DCN-v2 cross layers (0..3) in both towers, between the summed input features and the Dense stack: "
                          "x_{l+1} = x_0 * (x_l W_l + b_l) + x_l (overrides model.cross.layers; 0: none; embedding_dim must be a "
                          "multiple of 32 in 32..256); single-GPU trainer only")
+    ap.add_argument("--layer-norm", action="store_true",
+                    help="layer normalisation (Keras LayerNormalization) between every hidden Dense layer of both towers and its "
+                         "ReLU (overrides model.layer_norm.enabled to true; hidden widths must be multiples of 32 in 32..1024); "
+                         "single-GPU trainer only")
+    ap.add_argument("--layer-norm-epsilon", type=float, default=None, metavar="E",
+                    help="epsilon inside the normalisation's square root (default model.layer_norm.epsilon, else Keras's 1e-3)")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -170,6 +176,15 @@ def main(argv=None) -> int:
         raise SystemExit("--cross-layers must be in 0..3")
     if distributed and cross_layers:
         raise NotImplementedError("the cross layers are not implemented for the row-sharded (--distributed) trainer")
+    norm = cfgmod.layer_norm_from_dict(doc)
+    layer_norm = args.layer_norm or norm["enabled"]
+    layer_norm_eps = norm["epsilon"] if args.layer_norm_epsilon is None else args.layer_norm_epsilon
+    if not (layer_norm_eps > 0 and np.isfinite(layer_norm_eps)):
+        raise SystemExit("--layer-norm-epsilon must be a finite number > 0")
+    if args.layer_norm_epsilon is not None and not layer_norm:
+        raise SystemExit("--layer-norm-epsilon needs --layer-norm (or model.layer_norm.enabled)")
+    if distributed and layer_norm:
+        raise NotImplementedError("layer normalisation is not implemented for the row-sharded (--distributed) trainer")
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -217,6 +232,7 @@ def main(argv=None) -> int:
     cfg.n_title_buckets = title_buckets
     cfg.rating_weight, cfg.rating_hidden = float(rating_weight), int(rating_hidden)
     cfg.cross_layers = int(cross_layers)
+    cfg.layer_norm, cfg.layer_norm_epsilon = bool(layer_norm), float(layer_norm_eps)
     if args.title_max_tokens is not None:
         cfg.title_max_tokens = args.title_max_tokens
     if args.title_pooling is not None:

@@ -92,6 +92,13 @@ class TwoTowerConfig:
     # graph capture.
     rating_weight: float = 0.0
     rating_hidden: int = 128
+    # layer normalisation of the hidden layers (Keras LayerNormalization between a hidden Dense layer and its ReLU) in BOTH towers:
+    # hidden layer l becomes Dense (linear) -> LayerNorm (gamma_l, beta_l [n_l]; biased variance, layer_norm_epsilon inside the
+    # square root: Keras's default 1e-3) -> ReLU -> dropout; the output layer is not normalised.  gamma starts at 1, beta at 0,
+    # neither carries the l2 penalty.  Every hidden width must be a multiple of 32 in 32..1024.  Single-GPU trainer, Python
+    # sequence of launches, no graph capture.
+    layer_norm: bool = False
+    layer_norm_epsilon: float = 1e-3
     # DCN-v2 cross layers (tfrs.layers.dcn.Cross, Wang et al. 2021) in BOTH towers, between the summed input rows x_0 and the
     # Dense stack: x_{l+1} = x_0 * (x_l W_l + b_l) + x_l, W_l [embedding_dim, embedding_dim] - explicit bilinear interactions of
     # the features summed into x_0.  0..3 layers; 0 = none.  embedding_dim must be a multiple of 32 in 32..256.  Single-GPU
@@ -144,7 +151,7 @@ class TwoTowerConfig:
     def dense_segment_count(self, cross: bool = True, attention: bool = True) -> int:
         """Segments of the dense optimizer launches (``dense_layout``): a kernel and a bias per Dense layer, a projection kernel
         per side with numeric features, two for the rating head, two for the cross layers (``cross=False``: without those), one
-        for the history attention's vector (``attention=False``: without it)."""
+        for the history attention's vector (``attention=False``: without it), one for the layer normalisation's gammas and betas."""
         skip = {g for g, on in (("cross", cross), ("attention", attention)) if not on}
         return sum(s.group not in skip for s in dense_layout(self).segments)
 
@@ -225,6 +232,17 @@ class TwoTowerConfig:
             raise ValueError(f"cross_layers must be an int in 0..{MAX_CROSS_LAYERS} (0: no cross layers)")
         if cl and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
             raise ValueError(f"cross_layers > 0 needs an embedding_dim that is a multiple of 32 in 32..256 (got {self.embedding_dim})")
+        if not isinstance(self.layer_norm, bool):
+            raise ValueError("layer_norm must be a bool")
+        eps = self.layer_norm_epsilon
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (eps > 0 and math.isfinite(eps)):
+            raise ValueError("layer_norm_epsilon must be a finite number > 0")
+        if self.layer_norm:
+            hidden = self.user_dims[:-1] + self.item_dims[:-1]
+            if len(self.user_dims) < 2 or len(self.item_dims) < 2:
+                raise ValueError("layer_norm=True needs towers with a hidden layer (the output layer is not normalised)")
+            if any(n % 32 or not 32 <= n <= 1024 for n in hidden):
+                raise ValueError(f"layer_norm=True needs hidden widths that are multiples of 32 in 32..1024 (got {hidden})")
         # the optimizer launches take TT_MAX_DENSE_SEGS segments.  Refused: a model whose optional blocks do not fit - blamed on
         # the block that holds the first segment past the limit (towers that are over it on their own: on the first optional block)
         segs = dense_layout(self).segments
@@ -239,17 +257,19 @@ class TwoTowerConfig:
 _SEGMENT_GROUPS = {"features": "the numeric side features add one dense segment per side",
                    "head": "the rating head adds two dense segments",
                    "cross": "the cross layers add two dense segments",
-                   "attention": "the history attention adds one dense segment"}
+                   "attention": "the history attention adds one dense segment",
+                   "norm": "the layer normalisation adds one dense segment"}
 
 
 @dataclass(frozen=True)
 class DenseBlock:
     """One parameter of ``dense_flat``: the floats [offset, end) viewed as ``shape``.  ``glorot`` = (tensor id of the synthetic
-    initialiser, fan_in + fan_out) of a kernel; None: the parameter starts at zero."""
+    initialiser, fan_in + fan_out) of a kernel; None: the parameter starts at ``fill`` (0; the layer normalisation's gammas: 1)."""
     name: str
     offset: int
     shape: tuple
     glorot: tuple | None = None
+    fill: float = 0.0
 
     @property
     def end(self) -> int:
@@ -268,7 +288,7 @@ class DenseSegment:
     hi: int
     l2: bool
     stride: int
-    group: str                                   # "towers" | "features" | "head" | "cross" | "attention"
+    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm"
 
     @property
     def size(self) -> int:
@@ -298,15 +318,18 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
                                    parameters, so both segments' slab stride is the whole cross block
         history attention          from a 16-byte boundary (the launches load a as float4s): [a (D) | p (user_history_len)],
                                    one segment, no l2
+        layer normalisation        from a 16-byte boundary (the launches load gamma and beta as float4s): user gamma_0 .. | item
+                                   gamma_0 .. | user beta_0 .. | item beta_0 .., one entry per hidden layer; ONE segment, no l2 -
+                                   the gradient slabs are laid out like the parameters, so its slab stride is the whole block
 
     Every optional block sits BEHIND what was there before it: switching one on moves no existing offset, and without the
-    attention vector dense_flat ends behind the cross block with no trailing pad."""
+    blocks behind it dense_flat ends behind the cross block with no trailing pad."""
     blocks, segs, off = {}, [], 0
     d = cfg.embedding_dim
 
-    def block(name, shape, glorot=None):
+    def block(name, shape, glorot=None, fill=0.0):
         nonlocal off
-        blocks[name] = blk = DenseBlock(name, off, tuple(shape), glorot)
+        blocks[name] = blk = DenseBlock(name, off, tuple(shape), glorot, fill)
         off = blk.end
         return blk
 
@@ -342,6 +365,12 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         off = (off + 3) // 4 * 4
         a = block("history_attn", (d + cfg.user_history_len,))
         segment("attention", a.name, a, a, False)
+    if cfg.layer_norm:
+        off = (off + 3) // 4 * 4
+        gs = [block(f"norm.{side}.g{l}", (n,), fill=1.0) for side, dims, _, _ in sides for l, n in enumerate(dims[:-1])]
+        bs = [block(f"norm.{side}.b{l}", (n,)) for side, dims, _, _ in sides for l, n in enumerate(dims[:-1])]
+        if gs:
+            segment("norm", "norm", gs[0], bs[-1], False)
     return DenseLayout(blocks, tuple(segs), off)
 
 
@@ -394,6 +423,21 @@ class Tower:
         self.cu = [torch.empty(b, d0, device=dev) for _ in range(nc)]
         self.cg = [torch.empty(b, d0, device=dev) for _ in range(min(nc, 2))]
         self.ca = torch.empty(b, d0, device=dev) if nc > 1 else None
+        # cfg.layer_norm: hidden layer l writes its pre-activation z_l into pre[l]; the normalisation launch reads it and writes
+        # acts[l + 1] and bits[l + 1]; the backward launch reads it again (mean and variance are recomputed) and turns what layer
+        # l + 1's dx epilogue wrote into dz[l] - the gradient w.r.t. the normalised value - into the gradient w.r.t. z_l, in
+        # place.  gamma / beta (views of dense_flat) and the gradient slabs belong to the trainer: ``set_layer_norm``.
+        self.ln = bool(cfg.layer_norm)
+        self.ln_eps = float(cfg.layer_norm_epsilon)
+        self.pre = [torch.empty(b, self.dims[l + 1], device=dev) for l in range(self.n_layers - 1)] if self.ln else []
+        self.ln_gamma, self.ln_beta, self.ln_dg_slabs, self.ln_db_slabs = [], [], [], []
+        self.ln_n_slabs = self.ln_slab_stride = 0
+
+    def set_layer_norm(self, gammas, betas, dg_slabs, db_slabs, n_slabs: int, slab_stride: int):
+        """The normalisation's gamma / beta [n_l] per hidden layer and, per layer, the flat views that start at slab 0 of its
+        dgamma / dbeta in the trainer's shared [n_slabs, slab_stride] gradient-slab array."""
+        self.ln_gamma, self.ln_beta, self.ln_dg_slabs, self.ln_db_slabs = list(gammas), list(betas), list(dg_slabs), list(db_slabs)
+        self.ln_n_slabs, self.ln_slab_stride = int(n_slabs), int(slab_stride)
 
     def set_cross(self, ws, bs, dw_slabs, db_slabs, n_slabs: int, slab_stride: int):
         """The cross stack's parameters [D, D] / [D] per layer and, per layer, the flat views that start at slab 0 of its dW /
@@ -437,6 +481,8 @@ class Tower:
         rows: only the first ``rows`` rows of the buffers (an in-batch evaluation on the longer item tower of mixed sampling)."""
         if self.n_cross and lookup is not None:
             raise ValueError("Tower.forward: the cross layers read materialised input rows (acts[0]), not a fused lookup")
+        if self.ln:
+            return layer_norm_towers_forward((self,), dropouts=(dropout,), lookups=(lookup,), rows=(rows,))[0]
         if rows is not None and rows != self.rows:
             if dropout is not None:
                 raise ValueError("Tower.forward: a partial forward pass is an inference pass (no dropout)")
@@ -460,6 +506,10 @@ class Tower:
     def backward(self, dropout_rate: float = 0.0, dx: bool = True, dw: bool = True, lookup=None):
         """Consumes dz[-1]; leaves demb (dx) and the dw/db slabs (dw).  backward(dx=True, dw=False) followed by
         backward(dx=False, dw=True) is the same computation with every dx first."""
+        if self.ln:
+            if not (dx and dw):
+                raise NotImplementedError("Tower.backward: with layer normalisation dx and dW are computed in one pass")
+            return layer_norm_towers_backward((self,), dropout_rate, lookups=(lookup,))
         scale = 1.0
         if dropout_rate > 0.0:      # the same f32 arithmetic as the forward kernel's launcher: 1.0f / (1.0f - rate)
             one = torch.ones((), dtype=torch.float32)
@@ -505,11 +555,116 @@ def cross_backward(towers):
                             n_slabs=towers[0].cross_n_slabs, slab_stride=towers[0].cross_slab_stride)
 
 
+def _dropout_scale(dropout_rate: float) -> float:
+    """1 / (1 - rate) in the f32 arithmetic of the forward kernels' launchers."""
+    if not dropout_rate > 0.0:
+        return 1.0
+    one = torch.ones((), dtype=torch.float32)
+    return (one / (one - torch.tensor(dropout_rate, dtype=torch.float32))).item()
+
+
+def layer_norm_towers_forward(towers, dropouts=None, lookups=None, rows=None):
+    """The forward pass of one or both towers under cfg.layer_norm, layer by layer: every hidden layer is a linear Dense launch
+    into pre[l] followed by the normalisation launch (LayerNorm -> ReLU -> dropout), which writes acts[l + 1] and bits[l + 1];
+    the output layer is the plain linear launch.  Per tower: ``dropouts`` = (rate, seed, tower_index, first_global_row) in
+    training or None (inference), ``lookups`` (layer 0 may gather its input rows itself), ``rows`` (None: all; fewer: an
+    inference pass over the first rows).  Towers whose layer shapes and row counts agree share the Dense launch; towers whose
+    hidden widths agree share the normalisation launch, whatever their row counts (mixed sampling's longer item tower).
+    Returns the towers' outputs."""
+    n = len(towers)
+    dropouts, lookups, rows = (tuple(x) if x is not None else (None,) * n for x in (dropouts, lookups, rows))
+    nrows = [t.rows if r is None else int(r) for t, r in zip(towers, rows)]
+    for t, d, nr in zip(towers, dropouts, nrows):
+        if nr != t.rows and d is not None:
+            raise ValueError("layer_norm_towers_forward: a partial forward pass is an inference pass (no dropout)")
+    if towers[0].n_cross:
+        if any(lk is not None for lk in lookups):
+            raise ValueError("the cross layers read materialised input rows (acts[0]), not a fused lookup")
+        cross_forward(towers, keep_u=dropouts[0] is not None, rows=nrows)
+    for l in range(max(t.n_layers for t in towers)):
+        act = [i for i, t in enumerate(towers) if l < t.n_layers]
+        hid = [i for i in act if l < towers[i].n_layers - 1]
+        xs = {i: towers[i].layer_input(l, nrows[i]) for i in act}
+        ys = {i: (towers[i].pre[l] if i in hid else towers[i].acts[l + 1])[:nrows[i]] for i in act}
+        lks = {i: lookups[i] if l == 0 else None for i in act}
+        a, b = (towers[i] for i in act) if len(act) == 2 else (None, None)
+        if len(act) == 2 and a.dims[l:l + 2] == b.dims[l:l + 2] and nrows[0] == nrows[1] and (lks[0] is None) == (lks[1] is None):
+            ops.dense_fwd2((xs[0], xs[1]), (a.w[l], b.w[l]), (a.b[l], b.b[l]), (ys[0], ys[1]), relu=False,
+                           lookups=(lks[0], lks[1]) if lks[0] is not None else None)
+        else:
+            for i in act:
+                ops.dense_fwd(xs[i], towers[i].w[l], towers[i].b[l], relu=False, out=ys[i], lookup=lks[i])
+        if not hid:
+            continue
+        probs, drops = {}, {}
+        for i in hid:
+            t = towers[i]
+            probs[i] = (ys[i], t.ln_gamma[l], t.ln_beta[l], t.acts[l + 1][:nrows[i]], t.bits[l + 1][:nrows[i]])
+            drops[i] = None
+            if dropouts[i] is not None and dropouts[i][0] > 0.0:
+                rate, seed, tower, row0 = dropouts[i]
+                drops[i] = (rate, seed, TID_DROPOUT_BASE + 2 * l + tower, row0 * t.dims[l + 1])
+        # one launch for both towers: the same width and one counter offset (the towers' dropout streams differ by tensor id)
+        if len(hid) == 2 and a.dims[l + 1] == b.dims[l + 1] and (drops[0] is None) == (drops[1] is None) \
+                and (drops[0] is None or (drops[0][:2], drops[0][3]) == (drops[1][:2], drops[1][3])):
+            d = None if drops[0] is None else (drops[0][0], drops[0][1], (drops[0][2], drops[1][2]), drops[0][3])
+            ops.layer_norm2(probs[0], probs[1], eps=a.ln_eps, relu=True, dropout=d)
+        else:
+            for i in hid:
+                ops.layer_norm2(probs[i], eps=towers[i].ln_eps, relu=True, dropout=drops[i])
+    return tuple(t.acts[-1][:nr] for t, nr in zip(towers, nrows))
+
+
+def layer_norm_towers_backward(towers, dropout_rate: float = 0.0, lookups=None):
+    """The backward pass of one or both towers under cfg.layer_norm: layer l + 1's dx epilogue masks by the sign bits of
+    acts[l + 1] and applies the dropout scale as it always did, which leaves the gradient w.r.t. the normalised value in dz[l];
+    the normalisation's backward launch turns it into the gradient w.r.t. the pre-activation in place and writes the dgamma /
+    dbeta slabs into the trainer's shared array; Dense layer l's backward then reads dz[l] as before.  Launches are shared as
+    in ``layer_norm_towers_forward``."""
+    n = len(towers)
+    lookups = tuple(lookups) if lookups is not None else (None,) * n
+    scale = _dropout_scale(dropout_rate)
+    for l in range(max(t.n_layers for t in towers) - 1, -1, -1):
+        act = [i for i, t in enumerate(towers) if l < t.n_layers]
+        args = {}
+        for i in act:
+            t = towers[i]
+            args[i] = dict(x=t.layer_input(l), w=t.w[l], dz=t.dz[l], dx=t.dz[l - 1] if l > 0 else t.input_grad(),
+                           bits=t.bits[l] if l > 0 else None, lk=lookups[i] if l == 0 else None)
+        a, b = (towers[i] for i in act) if len(act) == 2 else (None, None)
+        if len(act) == 2 and a.dims[l:l + 2] == b.dims[l:l + 2] and a.rows == b.rows and a.n_slabs == b.n_slabs \
+                and (args[0]["lk"] is None) == (args[1]["lk"] is None):
+            pair = lambda k: (args[0][k], args[1][k])
+            ops.dense_bwd2(pair("x"), pair("w"), pair("dz"), pair("dx"), (None, None), (a.dw_slabs[l], b.dw_slabs[l]),
+                           (a.db_slabs[l], b.db_slabs[l]), dx_scale=scale if l > 0 else 1.0,
+                           lookups=pair("lk") if args[0]["lk"] is not None else None, dx_relu_bits=pair("bits"))
+        else:
+            for i in act:
+                t, g = towers[i], args[i]
+                ops.dense_bwd(g["x"], g["w"], g["dz"], g["dx"], None, t.dw_slabs[l], t.db_slabs[l], dx_scale=scale if l > 0 else 1.0,
+                              lookup=g["lk"], dx_relu_bits=g["bits"])
+        if l == 0:
+            break
+        probs = {i: (towers[i].pre[l - 1], towers[i].ln_gamma[l - 1], towers[i].dz[l - 1], towers[i].dz[l - 1],
+                     towers[i].ln_dg_slabs[l - 1], towers[i].ln_db_slabs[l - 1]) for i in act}
+        kw = dict(eps=towers[0].ln_eps, n_slabs=towers[0].ln_n_slabs, slab_stride=towers[0].ln_slab_stride)
+        if len(act) == 2 and a.dims[l] == b.dims[l]:
+            ops.layer_norm_bwd2(probs[0], probs[1], **kw)
+        else:
+            for i in act:
+                ops.layer_norm_bwd2(probs[i], **kw)
+    if towers[0].n_cross:
+        cross_backward(towers)
+
+
 def towers_forward(ut: "Tower", it: "Tower", dropout=None, lookups=None):
     """Both towers layer by layer, one launch per layer (the towers have identical shapes).
     dropout = (rate, seed, first_global_row) in training, None at inference.
     lookups = (user lookup, item lookup): layer 0 gathers its input rows from the embedding tables itself."""
     L = ut.n_layers
+    if ut.ln:                                    # (never the fused two-layer launch: the normalisation sits between the layers)
+        drops = None if dropout is None else ((dropout[0], dropout[1], 0, dropout[2]), (dropout[0], dropout[1], 1, dropout[2]))
+        return layer_norm_towers_forward((ut, it), dropouts=drops, lookups=lookups)
     if ut.n_cross:
         if lookups is not None:
             raise ValueError("towers_forward: the cross layers read materialised input rows (acts[0]), not a fused lookup")
@@ -548,6 +703,10 @@ def towers_backward(ut: "Tower", it: "Tower", dropout_rate: float = 0.0, on_embe
         one = torch.ones((), dtype=torch.float32)
         scale = (one / (one - torch.tensor(dropout_rate, dtype=torch.float32))).item()
     none2 = (None, None)
+    if ut.ln:
+        if on_embedding_grads is not None:
+            raise NotImplementedError("towers_backward: on_embedding_grads with layer normalisation is not implemented")
+        return layer_norm_towers_backward((ut, it), dropout_rate, lookups=lookups)
 
     def layer_args(l, dx: bool, dw: bool):
         dxs = ((ut.dz[l - 1], it.dz[l - 1]) if l > 0 else (ut.input_grad(), it.input_grad())) if dx else none2
@@ -676,6 +835,8 @@ _CHECKPOINT_CHECKS = (
     ("rating_weight", 0.0, " (with / without a rating head): the head's parameters in 'dense' belong to the trained model", None),
     ("rating_hidden", TwoTowerConfig.rating_hidden, "", "rating_weight"),
     ("cross_layers", 0, ": the cross kernels in 'dense' belong to the trained model", None),
+    ("layer_norm", False, ": the gammas and betas in 'dense' belong to the trained model", None),
+    ("layer_norm_epsilon", TwoTowerConfig.layer_norm_epsilon, "", "layer_norm"),
     ("n_title_buckets", 0, "", None), ("user_history_len", 0, "", None), ("history_pooling", "mean", "", "user_history_len"),
     ("title_max_tokens", None, "", "n_title_buckets"), ("title_pooling", None, "", "n_title_buckets"))
 
@@ -694,7 +855,8 @@ _GRAPH_REFUSALS = (
      "implemented: the step is the Python sequence of launches over materialised tower inputs"),
     (lambda c: c.rating_weight > 0, "the rating head (rating_weight > 0) is not implemented: the step is the Python sequence of launches"),
     (lambda c: c.cross_layers, "cross layers (cross_layers > 0) is not implemented: the step is the Python sequence of launches over "
-     "materialised tower inputs"))
+     "materialised tower inputs"),
+    (lambda c: c.layer_norm, "layer normalisation (layer_norm=True) is not implemented: the step is the Python sequence of launches"))
 
 
 class TwoTowerTrainer:
@@ -716,6 +878,7 @@ class TwoTowerTrainer:
         self._attn_on = cfg.history_attention
         sd, rh, ncl = cfg.tower_dims[-1], cfg.rating_hidden, cfg.cross_layers
         self.dense_flat = torch.zeros(lay.total, device=dev)
+        self._fill_constant_blocks()             # (the layer normalisation's gammas start at 1 with or without a seed)
         self.dense_accum = torch.full_like(self.dense_flat, cfg.adagrad_initial_accumulator) if adagrad else None
         self.dense_grad = torch.empty_like(self.dense_flat)        # summed gradients (multi-GPU all-reduce bucket)
         # lazy Adam: first / second moment beside every table and beside dense_flat (allocated for Adam only), and the 1-based
@@ -840,6 +1003,21 @@ class TwoTowerTrainer:
                                 [self._c_slabs[w.offset - kernels.lo:] for w in ws], [self._c_slabs[x.offset - kernels.lo:] for x in bs],
                                 ns, kernels.stride)
             grad_slabs["cross.kernels"], grad_slabs["cross.biases"] = (self._c_slabs, ns), (self._c_slabs[biases.lo - kernels.lo:], ns)
+        # layer normalisation: gamma / beta per hidden layer (views of dense_flat) and ONE gradient-slab array for all layers of
+        # both towers, laid out like the parameters, which the block's one dense segment sums
+        self._ln_slabs = None
+        self._ln_nslabs = 0
+        if cfg.layer_norm:
+            norm = lay.segment("norm")
+            self._ln_nslabs = ns = ops.layer_norm_num_slabs(bi)
+            self._ln_slabs = torch.empty(ns * norm.stride, device=dev)
+            for side, tower in (("user", ut), ("item", it)):
+                gs = [lay.blocks[f"norm.{side}.g{l}"] for l in range(tower.n_layers - 1)]
+                bs = [lay.blocks[f"norm.{side}.b{l}"] for l in range(tower.n_layers - 1)]
+                tower.set_layer_norm([g.view(self.dense_flat) for g in gs], [x.view(self.dense_flat) for x in bs],
+                                     [self._ln_slabs[g.offset - norm.lo:] for g in gs], [self._ln_slabs[x.offset - norm.lo:] for x in bs],
+                                     ns, norm.stride)
+            grad_slabs["norm"] = (self._ln_slabs, ns)
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -868,12 +1046,14 @@ class TwoTowerTrainer:
         # the whole step behind ONE C call (tt_train_step_f32: the same launches - eight at cfg3 -, enqueued in C - one FFI crossing per step
         # instead of nine; cfg1 is host-bound).  TT_COMPOSITE_STEP=0: the Python sequence of the separate entry points.
         self.use_composite = os.environ.get("TT_COMPOSITE_STEP", "1") != "0"
+        if cfg.layer_norm:                       # tt_train_step_f32 cannot describe the normalisation launches between the layers
+            self.use_composite = False
         self._cstep = None
         self._id_bucket_ws = None
         # layers 1 and 0 of the backward pass in ONE launch (tt_tower_bwd2_batched_f32: the lower layer's tiles wait inside the
         # launch for the rows of dz they read); TT_BWD2=0: one launch per layer
         self.bwd2_ws = None
-        if (os.environ.get("TT_BWD2", "0") != "0" and cfg.symmetric and len(cfg.tower_dims) >= 2
+        if (os.environ.get("TT_BWD2", "0") != "0" and cfg.symmetric and len(cfg.tower_dims) >= 2 and not cfg.layer_norm
                 and ops.tower_bwd2_supported(b, d, cfg.tower_dims[0], cfg.tower_dims[1])):
             self.bwd2_ws = ops.tower_bwd2_workspace(b, dev)
         self.flag_poll_every = 50                # steps between asynchronous polls of the out-of-range flag (0 = never)
@@ -917,6 +1097,7 @@ class TwoTowerTrainer:
         for t in self.tables.values():
             t.init_synthetic(self.cfg, seed)
         self.dense_flat.zero_()
+        self._fill_constant_blocks()
         for blk in self.layout.blocks.values():                # Glorot-uniform kernels, zero biases
             if blk.glorot is not None:
                 _glorot_uniform_(blk.view(self.dense_flat), seed, *blk.glorot)
@@ -925,6 +1106,12 @@ class TwoTowerTrainer:
         if self.dense_m is not None:
             self.dense_m.zero_(), self.dense_v.zero_()
         self.adam_step = 1
+
+    def _fill_constant_blocks(self):
+        """The parameters that start at a constant other than zero (``DenseBlock.fill``: the layer normalisation's gammas)."""
+        for blk in self.layout.blocks.values():
+            if blk.glorot is None and blk.fill != 0.0:
+                blk.view(self.dense_flat).fill_(blk.fill)
 
     def init_rating_bias(self, x: float):
         """Sets the head's output bias b2 (train.py: the mean finite training rating, so that the head starts from the constant
@@ -1211,6 +1398,9 @@ class TwoTowerTrainer:
         row0 = self.step_index * cfg.batch_size
         if cfg.symmetric:        # same shapes: every layer of both towers in one launch
             q, c = towers_forward(ut, it, (cfg.dropout_rate, self.dropout_seed, row0), lookups=lks if lks[0] else None)
+        elif cfg.layer_norm:     # hidden layers of one width share the normalisation launch
+            layer_norm_towers_forward((ut, it), dropouts=((cfg.dropout_rate, self.dropout_seed, 0, row0), (cfg.dropout_rate, self.dropout_seed, 1, row0)),
+                                      lookups=lks)
         else:
             q = ut.forward((cfg.dropout_rate, self.dropout_seed, 0, row0), lookup=lks[0])
             c = it.forward((cfg.dropout_rate, self.dropout_seed, 1, row0), lookup=lks[1])
@@ -1227,6 +1417,8 @@ class TwoTowerTrainer:
             ops.l2_normalize_bwd2((ut.acts[-1], it.acts[-1]), (dq, dc), (ut.dz[-1], it.dz[-1]), cfg.normalize_eps)
         if cfg.symmetric:
             towers_backward(ut, it, cfg.dropout_rate, lookups=lks if lks[0] else None, bwd2_ws=self.bwd2_ws)
+        elif cfg.layer_norm:
+            layer_norm_towers_backward((ut, it), cfg.dropout_rate, lookups=lks)
         else:
             ut.backward(cfg.dropout_rate, lookup=lks[0])
             it.backward(cfg.dropout_rate, lookup=lks[1])
@@ -1272,8 +1464,12 @@ class TwoTowerTrainer:
                                   accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
             self._add_features((user_ids, ut.acts[0]), (cand, it.acts[0]), keep=True)   # cand_ids: the sampled rows too
         # the dropout streams count rows per tower: consecutive steps never share a position
-        ut.forward((cfg.dropout_rate, self.dropout_seed, 0, self.step_index * ut.rows), lookup=lk_u)
-        it.forward((cfg.dropout_rate, self.dropout_seed, 1, self.step_index * it.rows), lookup=lk_i)
+        drop_u, drop_i = ((cfg.dropout_rate, self.dropout_seed, t, self.step_index * tw.rows) for t, tw in enumerate((ut, it)))
+        if cfg.layer_norm:                       # one normalisation launch per layer over both towers' row counts
+            layer_norm_towers_forward((ut, it), dropouts=(drop_u, drop_i), lookups=(lk_u, lk_i))
+        else:
+            ut.forward(drop_u, lookup=lk_u)
+            it.forward(drop_i, lookup=lk_i)
         q, c = self._outputs(ut, it)
         dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
         ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
@@ -1284,8 +1480,11 @@ class TwoTowerTrainer:
         if cfg.normalize_embeddings:
             ops.l2_normalize_bwd2((ut.acts[-1],), (dq,), (ut.dz[-1],), cfg.normalize_eps)
             ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
-        ut.backward(cfg.dropout_rate, lookup=lk_u)
-        it.backward(cfg.dropout_rate, lookup=lk_i)
+        if cfg.layer_norm:
+            layer_norm_towers_backward((ut, it), cfg.dropout_rate, lookups=(lk_u, lk_i))
+        else:
+            ut.backward(cfg.dropout_rate, lookup=lk_u)
+            it.backward(cfg.dropout_rate, lookup=lk_i)
         self._features_backward()
         self.step_index += 1
         return self.loss
@@ -1405,7 +1604,7 @@ class TwoTowerTrainer:
         fused_sort = shape_ok and not self._skewed()
         if fused_sort:
             if (self.use_composite and self.fuse_lookup and self.cfg.symmetric and not self.cfg.normalize_embeddings
-                    and not self.rating_on and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
+                    and not self.cfg.layer_norm and not self.rating_on and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
                 return self._step_composite(ids, **loss_kw)
             loss = self.forward_backward(user_ids, item_ids, **loss_kw)
             self.apply_gradients(step_ids=ids)
