@@ -54,8 +54,8 @@ def main():
                                                             none2, none2, none2, dx_relu_bits=bits))
         res[f"bwd_L{l}_dw_only"] = t(lambda: ops.dense_bwd2((ut.acts[l], it.acts[l]), (ut.w[l], it.w[l]), (ut.dz[l], it.dz[l]), none2,
                                                             none2, (ut.dw_slabs[l], it.dw_slabs[l]), (ut.db_slabs[l], it.db_slabs[l])))
-    res["towers_fwd_all"] = t(lambda: towers_forward(ut, it))
-    res["towers_bwd_all"] = t(lambda: towers_backward(ut, it))
+    res["towers_fwd_all"] = t(lambda: towers_forward((ut, it)))
+    res["towers_bwd_all"] = t(lambda: towers_backward((ut, it)))
     step_sum = res["fwd_L0"] + res["fwd_L1"] + res["bwd_L1"] + res["bwd_L0"]
     flops = 12 * 2.0 * b * 128 * 256
     res["sum_4_launches_us"] = step_sum

@@ -640,11 +640,7 @@ class ShardedTwoTowerTrainer:
         if next_ids is not None:
             em.lookup_prefetch(next_ids, prefetch_exchange)
         row0 = (self.step_index * w + self.rank) * b          # first global batch row of this rank
-        if cfg.symmetric:
-            q, c = towers_forward(ut, it, (cfg.dropout_rate, self.dropout_seed, row0), lookups=lks)
-        else:
-            q = ut.forward((cfg.dropout_rate, self.dropout_seed, 0, row0), lookup=lks[0] if lks else None)
-            c = it.forward((cfg.dropout_rate, self.dropout_seed, 1, row0), lookup=lks[1] if lks else None)
+        q, c = towers_forward((ut, it), tuple((cfg.dropout_rate, self.dropout_seed, t, row0) for t in (0, 1)), lookups=lks)
         inv_t = 1.0 / cfg.temperature
         cp = self._cand_prob(candidate_sampling_probability)
         ci = self._cand_ids(candidate_ids)
@@ -669,16 +665,10 @@ class ShardedTwoTowerTrainer:
                 ops.sparse_sgd_(self.cat_grad, it.demb, self.cat_plan, -1.0)
         if cfg.symmetric and not self.collectives:
             # nothing to overlap the dw GEMMs with: the fused dx + dw launches of the plain trainer, then the scatter
-            towers_backward(ut, it, cfg.dropout_rate, lookups=lks)
+            towers_backward((ut, it), cfg.dropout_rate, lookups=lks)
             send()
-        elif cfg.symmetric:
-            towers_backward(ut, it, cfg.dropout_rate, on_embedding_grads=send, lookups=lks)
         else:
-            ut.backward(cfg.dropout_rate, dx=True, dw=False)
-            it.backward(cfg.dropout_rate, dx=True, dw=False)
-            send()
-            ut.backward(cfg.dropout_rate, dx=False, dw=True, lookup=lks[0] if lks else None)
-            it.backward(cfg.dropout_rate, dx=False, dw=True, lookup=lks[1] if lks else None)
+            towers_backward((ut, it), cfg.dropout_rate, lookups=lks, on_embedding_grads=send)
         self.step_index += 1
         if not self.collectives:
             # one rank, no collectives: owner sort + duplicate sums + sparse update + dense update in ONE launch
@@ -737,7 +727,7 @@ class ShardedTwoTowerTrainer:
         from .trainer import towers_forward
         cfg, ops, ut, it = self.cfg, self.ops, self.user_tower, self.item_tower
         self._inputs(user_ids, item_ids, category_ids)
-        q, c = towers_forward(ut, it) if cfg.symmetric else (ut.forward(), it.forward())
+        q, c = towers_forward((ut, it))
         cp = self._cand_prob(candidate_sampling_probability)
         ci = self._cand_ids(candidate_ids)
         if self.negatives == "local" or not self.collectives:

@@ -20,6 +20,7 @@ implemented the step itself (``src/training/__init__.py:1``).
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from dataclasses import dataclass, field
@@ -432,18 +433,23 @@ class Tower:
         self.pre = [torch.empty(b, self.dims[l + 1], device=dev) for l in range(self.n_layers - 1)] if self.ln else []
         self.ln_gamma, self.ln_beta, self.ln_dg_slabs, self.ln_db_slabs = [], [], [], []
         self.ln_n_slabs = self.ln_slab_stride = 0
+        # what each kind of pass launches, built on first use (towers_forward / towers_backward).  The plans hold views of the
+        # buffers and parameters above: whoever rebinds one of those after a pass has run clears them.
+        self.plans = {}
 
     def set_layer_norm(self, gammas, betas, dg_slabs, db_slabs, n_slabs: int, slab_stride: int):
         """The normalisation's gamma / beta [n_l] per hidden layer and, per layer, the flat views that start at slab 0 of its
         dgamma / dbeta in the trainer's shared [n_slabs, slab_stride] gradient-slab array."""
         self.ln_gamma, self.ln_beta, self.ln_dg_slabs, self.ln_db_slabs = list(gammas), list(betas), list(dg_slabs), list(db_slabs)
         self.ln_n_slabs, self.ln_slab_stride = int(n_slabs), int(slab_stride)
+        self.plans.clear()
 
     def set_cross(self, ws, bs, dw_slabs, db_slabs, n_slabs: int, slab_stride: int):
         """The cross stack's parameters [D, D] / [D] per layer and, per layer, the flat views that start at slab 0 of its dW /
         db in the trainer's shared [n_slabs, slab_stride] gradient-slab array."""
         self.cross_w, self.cross_b, self.cross_dw_slabs, self.cross_db_slabs = list(ws), list(bs), list(dw_slabs), list(db_slabs)
         self.cross_n_slabs, self.cross_slab_stride = int(n_slabs), int(slab_stride)
+        self.plans.clear()
 
     def layer_input(self, l: int, rows: int | None = None):
         """What Dense layer ``l`` reads: acts[l] - for layer 0 under cross layers the crossed rows x_L."""
@@ -475,56 +481,16 @@ class Tower:
         return sum(dims[l] * dims[l + 1] + dims[l + 1] for l in range(len(tower_dims)))
 
     def forward(self, dropout=None, lookup=None, rows: int | None = None):
-        """dropout = (rate, seed, tower_index, first_global_row) in training; None = inference (no dropout).
-        Inverted dropout follows every hidden (ReLU) layer, fused in the GEMM epilogue.
-        lookup (ops.make_lookup): layer 0 reads its input rows from the embedding table (acts[0] is not used).
-        rows: only the first ``rows`` rows of the buffers (an in-batch evaluation on the longer item tower of mixed sampling)."""
-        if self.n_cross and lookup is not None:
-            raise ValueError("Tower.forward: the cross layers read materialised input rows (acts[0]), not a fused lookup")
-        if self.ln:
-            return layer_norm_towers_forward((self,), dropouts=(dropout,), lookups=(lookup,), rows=(rows,))[0]
-        if rows is not None and rows != self.rows:
-            if dropout is not None:
-                raise ValueError("Tower.forward: a partial forward pass is an inference pass (no dropout)")
-            cross_forward((self,), keep_u=False, rows=(rows,))
-            for l in range(self.n_layers):
-                bits = self.bits[l + 1]
-                ops.dense_fwd(self.layer_input(l, rows), self.w[l], self.b[l], relu=l < self.n_layers - 1, out=self.acts[l + 1][:rows],
-                              lookup=lookup if l == 0 else None, relu_bits=None if bits is None else bits[:rows])
-            return self.acts[-1][:rows]
-        cross_forward((self,), keep_u=dropout is not None)       # (training passes a dropout tuple even at rate 0)
-        for l in range(self.n_layers):
-            hidden = l < self.n_layers - 1
-            d = None
-            if dropout is not None and hidden and dropout[0] > 0.0:
-                rate, seed, tower, row0 = dropout
-                d = (rate, seed, TID_DROPOUT_BASE + 2 * l + tower, row0 * self.dims[l + 1])
-            ops.dense_fwd(self.layer_input(l), self.w[l], self.b[l], relu=hidden, out=self.acts[l + 1], dropout=d,
-                          lookup=lookup if l == 0 else None, relu_bits=self.bits[l + 1])
-        return self.acts[-1]
+        """This tower alone through ``towers_forward``: dropout = (rate, seed, tower_index, first_global_row) in training, None =
+        inference; lookup (ops.make_lookup): layer 0 reads its input rows from the embedding table (acts[0] is not used); rows:
+        only the first ``rows`` rows of the buffers (an in-batch evaluation on the longer item tower of mixed sampling)."""
+        return towers_forward((self,), None if dropout is None else (dropout,), None if lookup is None else (lookup,),
+                              None if rows is None else (rows,))[0]
 
     def backward(self, dropout_rate: float = 0.0, dx: bool = True, dw: bool = True, lookup=None):
-        """Consumes dz[-1]; leaves demb (dx) and the dw/db slabs (dw).  backward(dx=True, dw=False) followed by
-        backward(dx=False, dw=True) is the same computation with every dx first."""
-        if self.ln:
-            if not (dx and dw):
-                raise NotImplementedError("Tower.backward: with layer normalisation dx and dW are computed in one pass")
-            return layer_norm_towers_backward((self,), dropout_rate, lookups=(lookup,))
-        scale = 1.0
-        if dropout_rate > 0.0:      # the same f32 arithmetic as the forward kernel's launcher: 1.0f / (1.0f - rate)
-            one = torch.ones((), dtype=torch.float32)
-            scale = (one / (one - torch.tensor(dropout_rate, dtype=torch.float32))).item()
-        for l in range(self.n_layers - 1, -1, -1):
-            dxo = (self.dz[l - 1] if l > 0 else self.input_grad()) if dx else None
-            bits = self.bits[l] if (l > 0 and dx) else None
-            mask_src = self.acts[l] if (l > 0 and dx and bits is None) else None   # acts[l] = (dropped-out) ReLU output of layer l-1
-            ops.dense_bwd(self.layer_input(l), self.w[l], self.dz[l], dxo, mask_src, self.dw_slabs[l] if dw else None,
-                          self.db_slabs[l] if dw else None, dx_scale=scale if l > 0 else 1.0,
-                          lookup=lookup if l == 0 else None, dx_relu_bits=bits)
-        if self.n_cross:
-            if not (dx and dw):
-                raise NotImplementedError("Tower.backward: the cross layers' backward launch computes dx and dW together")
-            cross_backward((self,))
+        """This tower alone through the backward driver: consumes dz[-1]; leaves demb (dx) and the dw/db slabs (dw).
+        backward(dx=True, dw=False) followed by backward(dx=False, dw=True) is the same computation with every dx first."""
+        _backward_pass((self,), dropout_rate, None if lookup is None else (lookup,), dx, dw)
 
     def segments(self, l2: float, grad_flat=None, grad_offset: int = 0):
         segs = []
@@ -538,23 +504,13 @@ class Tower:
         return segs
 
 
-def cross_forward(towers, keep_u: bool, rows=None):
-    """The cross stacks of ``towers`` (one or both), one launch per layer for all of them: xc[l] = x_0 * (x_l W_l + b_l) + x_l.
-    ``keep_u``: u_l stays in cu[l] for the backward chain (train step).  ``rows``: rows per tower (default: all)."""
-    for l in range(towers[0].n_cross):
-        probs, us = zip(*[t.cross_fwd_problem(l, keep_u, None if rows is None else rows[i]) for i, t in enumerate(towers)])
-        ops.cross_layer(*probs, u=us if keep_u else None)
-
-
-def cross_backward(towers):
-    """The cross stacks' backward chain, one launch per layer for all ``towers``: from G_L (cg[0], written by Dense layer 0)
-    down to demb, the parameter gradients into the trainer's shared slab array."""
-    L = towers[0].n_cross
-    for l in range(L - 1, -1, -1):
-        ops.cross_layer_bwd(*[t.cross_bwd_problem(l) for t in towers], x_is_x0=l == 0, accumulate_dx0=0 < l < L - 1,
-                            n_slabs=towers[0].cross_n_slabs, slab_stride=towers[0].cross_slab_stride)
-
-
+# ---------------------------------------------------------------------------------------------------------------------------
+# The two drivers of the tower stacks.  ``towers`` is a tuple of one or two Towers; what a pass launches depends only on the
+# towers, its row counts, which towers read through a lookup and whether it trains, so it is decided ONCE per such key
+# (``Tower.plans``): a plan is the list of (launcher, args, kwargs) with every buffer view already cut, plus the slots of those
+# kwargs that a step fills in - the dropout tuples, the lookup structs, the dx scale.  A step fills the slots and walks the list.
+# ---------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
 def _dropout_scale(dropout_rate: float) -> float:
     """1 / (1 - rate) in the f32 arithmetic of the forward kernels' launchers."""
     if not dropout_rate > 0.0:
@@ -563,183 +519,235 @@ def _dropout_scale(dropout_rate: float) -> float:
     return (one / (one - torch.tensor(dropout_rate, dtype=torch.float32))).item()
 
 
-def layer_norm_towers_forward(towers, dropouts=None, lookups=None, rows=None):
-    """The forward pass of one or both towers under cfg.layer_norm, layer by layer: every hidden layer is a linear Dense launch
-    into pre[l] followed by the normalisation launch (LayerNorm -> ReLU -> dropout), which writes acts[l + 1] and bits[l + 1];
-    the output layer is the plain linear launch.  Per tower: ``dropouts`` = (rate, seed, tower_index, first_global_row) in
-    training or None (inference), ``lookups`` (layer 0 may gather its input rows itself), ``rows`` (None: all; fewer: an
-    inference pass over the first rows).  Towers whose layer shapes and row counts agree share the Dense launch; towers whose
-    hidden widths agree share the normalisation launch, whatever their row counts (mixed sampling's longer item tower).
-    Returns the towers' outputs."""
-    n = len(towers)
-    dropouts, lookups, rows = (tuple(x) if x is not None else (None,) * n for x in (dropouts, lookups, rows))
-    nrows = [t.rows if r is None else int(r) for t, r in zip(towers, rows)]
-    for t, d, nr in zip(towers, dropouts, nrows):
-        if nr != t.rows and d is not None:
-            raise ValueError("layer_norm_towers_forward: a partial forward pass is an inference pass (no dropout)")
-    if towers[0].n_cross:
-        if any(lk is not None for lk in lookups):
-            raise ValueError("the cross layers read materialised input rows (acts[0]), not a fused lookup")
-        cross_forward(towers, keep_u=dropouts[0] is not None, rows=nrows)
-    for l in range(max(t.n_layers for t in towers)):
-        act = [i for i, t in enumerate(towers) if l < t.n_layers]
-        hid = [i for i in act if l < towers[i].n_layers - 1]
-        xs = {i: towers[i].layer_input(l, nrows[i]) for i in act}
-        ys = {i: (towers[i].pre[l] if i in hid else towers[i].acts[l + 1])[:nrows[i]] for i in act}
-        lks = {i: lookups[i] if l == 0 else None for i in act}
-        a, b = (towers[i] for i in act) if len(act) == 2 else (None, None)
-        if len(act) == 2 and a.dims[l:l + 2] == b.dims[l:l + 2] and nrows[0] == nrows[1] and (lks[0] is None) == (lks[1] is None):
-            ops.dense_fwd2((xs[0], xs[1]), (a.w[l], b.w[l]), (a.b[l], b.b[l]), (ys[0], ys[1]), relu=False,
-                           lookups=(lks[0], lks[1]) if lks[0] is not None else None)
-        else:
-            for i in act:
-                ops.dense_fwd(xs[i], towers[i].w[l], towers[i].b[l], relu=False, out=ys[i], lookup=lks[i])
-        if not hid:
-            continue
-        probs, drops = {}, {}
-        for i in hid:
-            t = towers[i]
-            probs[i] = (ys[i], t.ln_gamma[l], t.ln_beta[l], t.acts[l + 1][:nrows[i]], t.bits[l + 1][:nrows[i]])
-            drops[i] = None
-            if dropouts[i] is not None and dropouts[i][0] > 0.0:
-                rate, seed, tower, row0 = dropouts[i]
-                drops[i] = (rate, seed, TID_DROPOUT_BASE + 2 * l + tower, row0 * t.dims[l + 1])
-        # one launch for both towers: the same width and one counter offset (the towers' dropout streams differ by tensor id)
-        if len(hid) == 2 and a.dims[l + 1] == b.dims[l + 1] and (drops[0] is None) == (drops[1] is None) \
-                and (drops[0] is None or (drops[0][:2], drops[0][3]) == (drops[1][:2], drops[1][3])):
-            d = None if drops[0] is None else (drops[0][0], drops[0][1], (drops[0][2], drops[1][2]), drops[0][3])
-            ops.layer_norm2(probs[0], probs[1], eps=a.ln_eps, relu=True, dropout=d)
-        else:
-            for i in hid:
-                ops.layer_norm2(probs[i], eps=towers[i].ln_eps, relu=True, dropout=drops[i])
-    return tuple(t.acts[-1][:nr] for t, nr in zip(towers, nrows))
+def _layer_dropout(drops, l: int, width: int):
+    """The dropout tuple of ONE launch behind hidden layer ``l`` (``width`` columns) from its towers' (rate, seed, tower_index,
+    first_global_row): the stream of tower t is tensor id TID_DROPOUT_BASE + 2 l + t - a shared launch takes the pair of ids -
+    and starts at element first_global_row * width.  None: nothing is dropped (training at rate 0)."""
+    rate, seed, _, row0 = drops[0]
+    if not rate > 0.0:
+        return None
+    tids = tuple(TID_DROPOUT_BASE + 2 * l + d[2] for d in drops)
+    return (rate, seed, tids if len(tids) == 2 else tids[0], row0 * width)
 
 
-def layer_norm_towers_backward(towers, dropout_rate: float = 0.0, lookups=None):
-    """The backward pass of one or both towers under cfg.layer_norm: layer l + 1's dx epilogue masks by the sign bits of
-    acts[l + 1] and applies the dropout scale as it always did, which leaves the gradient w.r.t. the normalised value in dz[l];
-    the normalisation's backward launch turns it into the gradient w.r.t. the pre-activation in place and writes the dgamma /
-    dbeta slabs into the trainer's shared array; Dense layer l's backward then reads dz[l] as before.  Launches are shared as
-    in ``layer_norm_towers_forward``."""
-    n = len(towers)
-    lookups = tuple(lookups) if lookups is not None else (None,) * n
-    scale = _dropout_scale(dropout_rate)
-    for l in range(max(t.n_layers for t in towers) - 1, -1, -1):
-        act = [i for i, t in enumerate(towers) if l < t.n_layers]
-        args = {}
-        for i in act:
-            t = towers[i]
-            args[i] = dict(x=t.layer_input(l), w=t.w[l], dz=t.dz[l], dx=t.dz[l - 1] if l > 0 else t.input_grad(),
-                           bits=t.bits[l] if l > 0 else None, lk=lookups[i] if l == 0 else None)
-        a, b = (towers[i] for i in act) if len(act) == 2 else (None, None)
-        if len(act) == 2 and a.dims[l:l + 2] == b.dims[l:l + 2] and a.rows == b.rows and a.n_slabs == b.n_slabs \
-                and (args[0]["lk"] is None) == (args[1]["lk"] is None):
-            pair = lambda k: (args[0][k], args[1][k])
-            ops.dense_bwd2(pair("x"), pair("w"), pair("dz"), pair("dx"), (None, None), (a.dw_slabs[l], b.dw_slabs[l]),
-                           (a.db_slabs[l], b.db_slabs[l]), dx_scale=scale if l > 0 else 1.0,
-                           lookups=pair("lk") if args[0]["lk"] is not None else None, dx_relu_bits=pair("bits"))
-        else:
-            for i in act:
-                t, g = towers[i], args[i]
-                ops.dense_bwd(g["x"], g["w"], g["dz"], g["dx"], None, t.dw_slabs[l], t.db_slabs[l], dx_scale=scale if l > 0 else 1.0,
-                              lookup=g["lk"], dx_relu_bits=g["bits"])
-        if l == 0:
-            break
-        probs = {i: (towers[i].pre[l - 1], towers[i].ln_gamma[l - 1], towers[i].dz[l - 1], towers[i].dz[l - 1],
-                     towers[i].ln_dg_slabs[l - 1], towers[i].ln_db_slabs[l - 1]) for i in act}
-        kw = dict(eps=towers[0].ln_eps, n_slabs=towers[0].ln_n_slabs, slab_stride=towers[0].ln_slab_stride)
-        if len(act) == 2 and a.dims[l] == b.dims[l]:
-            ops.layer_norm_bwd2(probs[0], probs[1], **kw)
-        else:
-            for i in act:
-                ops.layer_norm_bwd2(probs[i], **kw)
-    if towers[0].n_cross:
-        cross_backward(towers)
+def _share(towers, l: int, looks, relu: bool = False) -> bool:
+    """Whether Dense layer ``l`` of ``towers`` is ONE launch: two towers that agree on the layer's (k, n), on their rows (hence
+    on n_slabs) and on whether layer 0 reads through a lookup.  ``relu``: the launch applies the layer's activation, so the
+    layer must be hidden in both towers or the output of both."""
+    if len(towers) < 2 or l >= min(t.n_layers for t in towers):
+        return False
+    a, b = towers
+    return (a.dims[l:l + 2] == b.dims[l:l + 2] and a.rows == b.rows and a.n_slabs == b.n_slabs and (l > 0 or looks[0] == looks[1])
+            and not (relu and (l < a.n_layers - 1) != (l < b.n_layers - 1)))
 
 
-def towers_forward(ut: "Tower", it: "Tower", dropout=None, lookups=None):
-    """Both towers layer by layer, one launch per layer (the towers have identical shapes).
-    dropout = (rate, seed, first_global_row) in training, None at inference.
-    lookups = (user lookup, item lookup): layer 0 gathers its input rows from the embedding tables itself."""
-    L = ut.n_layers
-    if ut.ln:                                    # (never the fused two-layer launch: the normalisation sits between the layers)
-        drops = None if dropout is None else ((dropout[0], dropout[1], 0, dropout[2]), (dropout[0], dropout[1], 1, dropout[2]))
-        return layer_norm_towers_forward((ut, it), dropouts=drops, lookups=lookups)
-    if ut.n_cross:
-        if lookups is not None:
+class _Plan:
+    """Launches in order and the kwargs slots a step fills: ``drops`` (kwargs, tower indices, layer, width), ``looks`` (dict,
+    key, tower index or None for both), ``scales`` (kwargs, key).  ``shared``: some launch serves both towers - two towers that
+    share none run one after the other instead, each through its own plan (a tower's activations are still in cache when its
+    next layer reads them)."""
+
+    def __init__(self):
+        self.launches, self.drops, self.looks, self.scales, self.outputs, self.shared = [], [], [], [], None, False
+
+    def add(self, fn, args, problems: int = 1, **kw):
+        self.launches.append((fn, args, kw))
+        self.shared |= problems > 1
+        return kw
+
+
+def _forward_plan(towers, rows, looks, train: bool, together: bool) -> _Plan:
+    plan, n, ln = _Plan(), len(towers), towers[0].ln
+    cut = lambda x, i: None if x is None else x[:rows[i]]
+    if towers[0].n_cross:                        # the cross stack in front of layer 0, one launch per layer for all towers
+        if any(looks):
             raise ValueError("towers_forward: the cross layers read materialised input rows (acts[0]), not a fused lookup")
-        cross_forward((ut, it), keep_u=dropout is not None)
+        for l in range(towers[0].n_cross):
+            probs, us = zip(*[t.cross_fwd_problem(l, train, rows[i]) for i, t in enumerate(towers)])
+            plan.add(ops.cross_layer, probs, n, u=us if train else None)       # u_l stays for the backward chain
+    depth = max(t.n_layers for t in towers)
     # the last two layers (ReLU hidden + linear output) of both towers in ONE launch when their shapes allow it: the hidden tile
     # never leaves the CU between them (csrc/tower.hip); two-layer towers are that launch alone (with the lookup inside), deeper
-    # ones - the reference's [512, 256, 128] - run the layers below one by one first
-    fused = L >= 2 and ops.tower_fwd2_supported(ut.acts[1].shape[0], ut.dims[L - 2], ut.dims[L - 1], ut.dims[L])
-    for l in range(L - 2 if fused else L):
-        hidden = l < L - 1
-        d = None
-        if dropout is not None and hidden and dropout[0] > 0.0:
-            rate, seed, row0 = dropout
-            d = (rate, seed, (TID_DROPOUT_BASE + 2 * l, TID_DROPOUT_BASE + 2 * l + 1), row0 * ut.dims[l + 1])
-        ops.dense_fwd2((ut.layer_input(l), it.layer_input(l)), (ut.w[l], it.w[l]), (ut.b[l], it.b[l]), (ut.acts[l + 1], it.acts[l + 1]),
-                       relu=hidden, dropout=d, lookups=lookups if l == 0 else None, relu_bits=(ut.bits[l + 1], it.bits[l + 1]))
-    if fused:
-        a = L - 2
-        d = None
-        if dropout is not None and dropout[0] > 0.0:
-            rate, seed, row0 = dropout
-            d = (rate, seed, (TID_DROPOUT_BASE + 2 * a, TID_DROPOUT_BASE + 2 * a + 1), row0 * ut.dims[a + 1])
-        ops.tower_fwd2((ut.layer_input(a), it.layer_input(a)), (ut.w[a], it.w[a]), (ut.b[a], it.b[a]), (ut.acts[a + 1], it.acts[a + 1]),
-                       (ut.bits[a + 1], it.bits[a + 1]), (ut.w[a + 1], it.w[a + 1]), (ut.b[a + 1], it.b[a + 1]),
-                       (ut.acts[a + 2], it.acts[a + 2]), dropout=d, lookups=lookups if a == 0 else None)
-    return ut.acts[-1], it.acts[-1]
+    # ones - the reference's [512, 256, 128] - run the layers below one by one first.  Never with layer normalisation, which
+    # sits between the two layers.
+    a = towers[0]
+    tail = (n == 2 and depth >= 2 and a.n_layers == towers[1].n_layers and not ln and together
+            and _share(towers, depth - 2, looks, True) and _share(towers, depth - 1, looks, True)
+            and ops.tower_fwd2_supported(rows[0], a.dims[depth - 2], a.dims[depth - 1], a.dims[depth]))
+    for l in range(depth):
+        act = [i for i, t in enumerate(towers) if l < t.n_layers]
+        hid = [i for i in act if l < towers[i].n_layers - 1]
+        x = {i: towers[i].layer_input(l, rows[i]) for i in act}
+        # with layer normalisation a hidden layer is the linear launch into pre[l] and the normalisation launch, which applies
+        # ReLU and dropout and writes acts[l + 1] and bits[l + 1]
+        y = {i: cut(towers[i].pre[l] if (ln and i in hid) else towers[i].acts[l + 1], i) for i in act}
+        bits = {i: None if ln else cut(towers[i].bits[l + 1], i) for i in act}
+        drop = lambda idx: (idx, l, towers[idx[0]].dims[l + 1])
+        pair = lambda v: tuple(v(towers[i]) if callable(v) else v[i] for i in act)
+        if tail and l == depth - 2:
+            kw = plan.add(ops.tower_fwd2, (pair(x), pair(lambda t: t.w[l]), pair(lambda t: t.b[l]), pair(y), pair(bits),
+                                           pair(lambda t: t.w[l + 1]), pair(lambda t: t.b[l + 1]), pair(lambda t: t.acts[l + 2])),
+                          2, dropout=None, lookups=None)
+            plan.drops.append((kw,) + drop((0, 1)))
+            if l == 0 and looks[0]:
+                plan.looks.append((kw, "lookups", None))
+            break
+        if _share(towers, l, looks, relu=not ln) and together:
+            kw = plan.add(ops.dense_fwd2, (pair(x), pair(lambda t: t.w[l]), pair(lambda t: t.b[l]), pair(y)), 2, relu=bool(hid) and not ln,
+                          dropout=None, lookups=None, relu_bits=pair(bits))
+            if hid and not ln:
+                plan.drops.append((kw,) + drop((0, 1)))
+            if l == 0 and looks[0]:
+                plan.looks.append((kw, "lookups", None))
+        else:
+            for i in act:
+                t = towers[i]
+                kw = plan.add(ops.dense_fwd, (x[i], t.w[l], t.b[l]), relu=i in hid and not ln, out=y[i], dropout=None, lookup=None,
+                              relu_bits=bits[i])
+                if i in hid and not ln:
+                    plan.drops.append((kw,) + drop((i,)))
+                if l == 0 and looks[i]:
+                    plan.looks.append((kw, "lookup", i))
+        if ln and hid:
+            probs = {i: (y[i], towers[i].ln_gamma[l], towers[i].ln_beta[l], cut(towers[i].acts[l + 1], i), cut(towers[i].bits[l + 1], i))
+                     for i in hid}
+            # one launch for both towers where the widths agree, whatever the rows (mixed sampling's longer item tower)
+            shared = len(hid) == 2 and towers[0].dims[l + 1] == towers[1].dims[l + 1] and together
+            for idx in ([tuple(hid)] if shared else [(i,) for i in hid]):
+                kw = plan.add(ops.layer_norm2, tuple(probs[i] for i in idx), len(idx), eps=towers[idx[0]].ln_eps, relu=True, dropout=None)
+                plan.drops.append((kw,) + drop(idx))
+    if not train:
+        plan.drops = []
+    plan.outputs = tuple(cut(t.acts[-1], i) for i, t in enumerate(towers))
+    return plan
 
 
-def towers_backward(ut: "Tower", it: "Tower", dropout_rate: float = 0.0, on_embedding_grads=None, lookups=None, bwd2_ws=None):
-    """Backward of both towers, one launch per layer (dx and dw+db tiles of both towers side by side).
-    With ``on_embedding_grads`` every dx is computed first, the callback runs as soon as demb is complete (the
-    sharded trainer starts the gradient exchange there) and the dw+db launches follow, beside the transfer.
-    ``bwd2_ws`` (ops.tower_bwd2_workspace): layers 1 and 0 in ONE launch where the shape allows (tt_tower_bwd2_batched_f32)."""
-    scale = 1.0
-    if dropout_rate > 0.0:
-        one = torch.ones((), dtype=torch.float32)
-        scale = (one / (one - torch.tensor(dropout_rate, dtype=torch.float32))).item()
-    none2 = (None, None)
-    if ut.ln:
-        if on_embedding_grads is not None:
-            raise NotImplementedError("towers_backward: on_embedding_grads with layer normalisation is not implemented")
-        return layer_norm_towers_backward((ut, it), dropout_rate, lookups=lookups)
+def towers_forward(towers, dropouts=None, lookups=None, rows=None):
+    """The forward pass of ``towers`` (one Tower, or both), layer by layer; returns their outputs.  Per tower: ``dropouts`` =
+    (rate, seed, tower_index, first_global_row) in training (also at rate 0), None = inference - inverted dropout follows every
+    hidden (ReLU) layer, fused into the launch that applies the ReLU; ``lookups`` (ops.make_lookup): layer 0 gathers its input
+    rows from the embedding table itself (acts[0] is not used); ``rows``: fewer than the tower holds = an inference pass over the
+    first rows of every buffer, which shares no launch with the other tower.  Towers that share no launch run one after the other."""
+    n = len(towers)
+    train = dropouts is not None and dropouts[0] is not None
+    nrows = tuple(t.rows if rows is None or rows[i] is None else int(rows[i]) for i, t in enumerate(towers))
+    alone = lambda: tuple(towers_forward((t,), None if dropouts is None else (dropouts[i],), None if lookups is None else (lookups[i],),
+                                         (nrows[i],))[0] for i, t in enumerate(towers))
+    if any(r != t.rows for t, r in zip(towers, nrows)):
+        if train:
+            raise ValueError("towers_forward: a partial forward pass is an inference pass (no dropout)")
+        if n > 1:
+            return alone()
+    looks = (False,) * n if lookups is None else tuple(lk is not None for lk in lookups)
+    # a shared launch that drops out needs one (rate, seed, offset) for both towers: equal rows give exactly that; mixed
+    # sampling's towers count their rows separately (and share only the normalisation launch of step 0)
+    together = not train or len({(d[0], d[1], d[3]) if d[0] > 0.0 else None for d in dropouts}) == 1
+    key = ("forward", towers[1:], nrows, looks, train, together)
+    plan = towers[0].plans.get(key)
+    if plan is None:
+        plan = towers[0].plans[key] = _forward_plan(towers, nrows, looks, train, together)
+    if n > 1 and not plan.shared:
+        return alone()
+    for kw, idx, l, width in plan.drops:
+        kw["dropout"] = _layer_dropout([dropouts[i] for i in idx], l, width)
+    for kw, name, i in plan.looks:
+        kw[name] = lookups if i is None else lookups[i]
+    for fn, args, kw in plan.launches:
+        fn(*args, **kw)
+    return plan.outputs
 
-    def layer_args(l, dx: bool, dw: bool):
-        dxs = ((ut.dz[l - 1], it.dz[l - 1]) if l > 0 else (ut.input_grad(), it.input_grad())) if dx else none2
-        bits = (ut.bits[l], it.bits[l]) if (l > 0 and dx and ut.bits[l] is not None) else none2
-        masks = (ut.acts[l], it.acts[l]) if (l > 0 and dx and bits[0] is None) else none2
-        return dict(xs=(ut.layer_input(l), it.layer_input(l)), ws=(ut.w[l], it.w[l]), dzs=(ut.dz[l], it.dz[l]), dxs=dxs, dx_relu_srcs=masks,
-                    dw_slabs=(ut.dw_slabs[l], it.dw_slabs[l]) if dw else none2, db_slabs=(ut.db_slabs[l], it.db_slabs[l]) if dw else none2,
-                    lookups=lookups if l == 0 else None, dx_relu_bits=bits)
 
-    def layer(l, dx: bool, dw: bool):
-        a = layer_args(l, dx, dw)
-        ops.dense_bwd2(a["xs"], a["ws"], a["dzs"], a["dxs"], a["dx_relu_srcs"], a["dw_slabs"], a["db_slabs"],
-                       dx_scale=scale if l > 0 else 1.0, lookups=a["lookups"], dx_relu_bits=a["dx_relu_bits"])
+def _backward_plan(towers, looks, dx: bool, dw: bool, bwd2_ws) -> _Plan:
+    plan, n, ln = _Plan(), len(towers), towers[0].ln
+    if not (dx and dw) and (ln or towers[0].n_cross):
+        raise NotImplementedError("towers_backward: the backward launches of layer normalisation and of the cross layers compute dx and "
+                                  "dW in one pass (no dx-first split, no on_embedding_grads)")
+    depth = max(t.n_layers for t in towers)
 
-    if on_embedding_grads is None:
-        last = -1
-        if (bwd2_ws is not None and ut.n_layers >= 2
-                and ops.tower_bwd2_supported(ut.dz[0].shape[0], ut.dims[0], ut.dims[1], ut.dims[2])):
-            last = 1
-        for l in range(ut.n_layers - 1, last, -1):
-            layer(l, True, True)
-        if last == 1:
-            ops.tower_bwd2(layer_args(1, True, True), layer_args(0, True, True), bwd2_ws, dx_scale_upper=scale, dx_scale_lower=1.0)
-        if ut.n_cross:
-            cross_backward((ut, it))
+    def layer(l, idx):
+        """dense_bwd2's arguments of layer ``l`` for the towers ``idx``: the mask of dx comes from bits[l], from acts[l] - the
+        (dropped-out) ReLU output of layer l - 1 - where the width is not a multiple of 32."""
+        ts = [towers[i] for i in idx]
+        bits = tuple(t.bits[l] if (l > 0 and dx) else None for t in ts)
+        return dict(xs=tuple(t.layer_input(l) for t in ts), ws=tuple(t.w[l] for t in ts), dzs=tuple(t.dz[l] for t in ts),
+                    dxs=tuple((t.dz[l - 1] if l > 0 else t.input_grad()) if dx else None for t in ts),
+                    dx_relu_srcs=tuple(t.acts[l] if (l > 0 and dx and b is None) else None for t, b in zip(ts, bits)),
+                    dw_slabs=tuple(t.dw_slabs[l] if dw else None for t in ts), db_slabs=tuple(t.db_slabs[l] if dw else None for t in ts),
+                    lookups=None, dx_relu_bits=bits)
+
+    # layers 1 and 0 of both towers in ONE launch (tt_tower_bwd2_batched_f32) where a workspace is given and the shapes allow it
+    a = towers[0]
+    head = (bwd2_ws is not None and dx and dw and n == 2 and depth >= 2 and a.n_layers == towers[1].n_layers and not ln
+            and _share(towers, 1, looks) and _share(towers, 0, looks) and ops.tower_bwd2_supported(a.rows, a.dims[0], a.dims[1], a.dims[2]))
+    for l in range(depth - 1, -1, -1):
+        act = tuple(i for i, t in enumerate(towers) if l < t.n_layers)
+        if head and l == 1:
+            upper, lower = layer(1, act), layer(0, act)
+            plan.scales.append((plan.add(ops.tower_bwd2, (upper, lower, bwd2_ws), 2, dx_scale_upper=1.0, dx_scale_lower=1.0), "dx_scale_upper"))
+            if looks[0]:
+                plan.looks.append((lower, "lookups", None))
+            break
+        for idx in ([act] if _share(towers, l, looks) else [(i,) for i in act]):
+            g = layer(l, idx)
+            if len(idx) == 2:
+                kw = plan.add(ops.dense_bwd2, (g["xs"], g["ws"], g["dzs"], g["dxs"], g["dx_relu_srcs"], g["dw_slabs"], g["db_slabs"]),
+                              2, dx_scale=1.0, lookups=None, dx_relu_bits=g["dx_relu_bits"])
+            else:
+                kw = plan.add(ops.dense_bwd, tuple(g[k][0] for k in ("xs", "ws", "dzs", "dxs", "dx_relu_srcs", "dw_slabs", "db_slabs")),
+                              dx_scale=1.0, lookup=None, dx_relu_bits=g["dx_relu_bits"][0])
+            if l > 0:
+                plan.scales.append((kw, "dx_scale"))
+            elif looks[idx[0]]:
+                plan.looks.append((kw, "lookups", None) if len(idx) == 2 else (kw, "lookup", idx[0]))
+        if ln and l > 0:
+            # layer l's dx epilogue left the gradient w.r.t. the normalised value in dz[l - 1]; the normalisation's backward launch
+            # turns it into the gradient w.r.t. the pre-activation IN PLACE (and writes the dgamma / dbeta slabs) before Dense
+            # layer l - 1 reads it.  One launch for both towers where the widths agree.
+            probs = {i: (towers[i].pre[l - 1], towers[i].ln_gamma[l - 1], towers[i].dz[l - 1], towers[i].dz[l - 1],
+                         towers[i].ln_dg_slabs[l - 1], towers[i].ln_db_slabs[l - 1]) for i in act}
+            shared = len(act) == 2 and towers[0].dims[l] == towers[1].dims[l]
+            for idx in ([act] if shared else [(i,) for i in act]):
+                plan.add(ops.layer_norm_bwd2, tuple(probs[i] for i in idx), len(idx), eps=a.ln_eps, n_slabs=a.ln_n_slabs, slab_stride=a.ln_slab_stride)
+    L = a.n_cross                                # the cross chain behind layer 0: from G_L (cg[0]) down to demb
+    for l in range(L - 1, -1, -1):
+        plan.add(ops.cross_layer_bwd, tuple(t.cross_bwd_problem(l) for t in towers), n, x_is_x0=l == 0, accumulate_dx0=0 < l < L - 1,
+                 n_slabs=a.cross_n_slabs, slab_stride=a.cross_slab_stride)
+    return plan
+
+
+def _backward_pass(towers, dropout_rate: float, lookups, dx: bool = True, dw: bool = True, bwd2_ws=None):
+    """One walk down the Dense stacks (and the cross chains): dx and dW + db of every layer, or only the one or the other."""
+    if not dw:
+        lookups = None                           # dx = dz W^T reads no layer input: the dx-only pass of layer 0 needs no lookup
+    looks = (False,) * len(towers) if lookups is None else tuple(lk is not None for lk in lookups)
+    key = ("backward", towers[1:], looks, dx, dw, id(bwd2_ws))
+    plan = towers[0].plans.get(key)
+    if plan is None:
+        plan = towers[0].plans[key] = _backward_plan(towers, looks, dx, dw, bwd2_ws)
+    if len(towers) > 1 and not plan.shared:
+        for i, t in enumerate(towers):
+            _backward_pass((t,), dropout_rate, None if lookups is None else (lookups[i],), dx, dw)
         return
-    if ut.n_cross:
-        raise NotImplementedError("towers_backward: on_embedding_grads with cross layers is not implemented")
-    for l in range(ut.n_layers - 1, -1, -1):
-        layer(l, True, False)
+    scale = _dropout_scale(dropout_rate)
+    for kw, name in plan.scales:
+        kw[name] = scale
+    for kw, name, i in plan.looks:
+        kw[name] = lookups if i is None else lookups[i]
+    for fn, args, kw in plan.launches:
+        fn(*args, **kw)
+
+
+def towers_backward(towers, dropout_rate: float = 0.0, lookups=None, on_embedding_grads=None, bwd2_ws=None):
+    """The backward pass of ``towers`` (one Tower, or both): consumes dz[-1]; leaves demb and the dw / db slabs.  ``lookups`` as in
+    ``towers_forward`` (dW = x^T dz of layer 0 reads the rows through them).  With ``on_embedding_grads`` every dx launch of every
+    layer comes first, the callback runs as soon as demb is complete (the sharded trainer starts the gradient exchange there) and
+    the dW + db launches follow, beside the transfer.  ``bwd2_ws`` (ops.tower_bwd2_workspace): layers 1 and 0 in ONE launch
+    where the shapes allow it - never in the split pass."""
+    if on_embedding_grads is None:
+        return _backward_pass(towers, dropout_rate, lookups, bwd2_ws=bwd2_ws)
+    _backward_pass(towers, dropout_rate, lookups, dx=True, dw=False)
     on_embedding_grads()
-    for l in range(ut.n_layers - 1, -1, -1):
-        layer(l, False, True)
+    _backward_pass(towers, dropout_rate, lookups, dx=False, dw=True)
 
 
 @dataclass
@@ -1394,16 +1402,8 @@ class TwoTowerTrainer:
         lks = self._lookups(user_ids, item_ids, category_ids)
         if lks is None:
             self._item_inputs(user_ids, item_ids, category_ids, train=True)
-            lks = (None, None)
         row0 = self.step_index * cfg.batch_size
-        if cfg.symmetric:        # same shapes: every layer of both towers in one launch
-            q, c = towers_forward(ut, it, (cfg.dropout_rate, self.dropout_seed, row0), lookups=lks if lks[0] else None)
-        elif cfg.layer_norm:     # hidden layers of one width share the normalisation launch
-            layer_norm_towers_forward((ut, it), dropouts=((cfg.dropout_rate, self.dropout_seed, 0, row0), (cfg.dropout_rate, self.dropout_seed, 1, row0)),
-                                      lookups=lks)
-        else:
-            q = ut.forward((cfg.dropout_rate, self.dropout_seed, 0, row0), lookup=lks[0])
-            c = it.forward((cfg.dropout_rate, self.dropout_seed, 1, row0), lookup=lks[1])
+        towers_forward((ut, it), tuple((cfg.dropout_rate, self.dropout_seed, t, row0) for t in (0, 1)), lookups=lks)
         q, c = self._outputs(ut, it)
         # normalised: the scorer's gradients are w.r.t. the unit vectors; one launch turns them into the last layer's dz
         dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
@@ -1415,13 +1415,7 @@ class TwoTowerTrainer:
             self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
         if cfg.normalize_embeddings:
             ops.l2_normalize_bwd2((ut.acts[-1], it.acts[-1]), (dq, dc), (ut.dz[-1], it.dz[-1]), cfg.normalize_eps)
-        if cfg.symmetric:
-            towers_backward(ut, it, cfg.dropout_rate, lookups=lks if lks[0] else None, bwd2_ws=self.bwd2_ws)
-        elif cfg.layer_norm:
-            layer_norm_towers_backward((ut, it), cfg.dropout_rate, lookups=lks)
-        else:
-            ut.backward(cfg.dropout_rate, lookup=lks[0])
-            it.backward(cfg.dropout_rate, lookup=lks[1])
+        towers_backward((ut, it), cfg.dropout_rate, lookups=lks, bwd2_ws=self.bwd2_ws)
         self._features_backward()
         self._history_backward()
         self.step_index += 1
@@ -1452,10 +1446,9 @@ class TwoTowerTrainer:
         if not sampled:
             self.sample_candidates(item_ids)
         cand = self.cand_ids
-        lk_u = lk_i = None
+        lks = None
         if self.fuse_lookup and it.rows <= ops.MAX_FUSED_LOOKUP_ROWS:
-            lk_u = ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob)
-            lk_i = ops.make_lookup(self.item_table, cand, oob_flag=self.oob)
+            lks = (ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob), ops.make_lookup(self.item_table, cand, oob_flag=self.oob))
         else:
             ops.embedding_gather(self.user_table, user_ids, out=ut.acts[0], oob_flag=self.oob)
             ops.embedding_gather(self.item_table, cand, out=it.acts[0], oob_flag=self.oob)
@@ -1464,12 +1457,8 @@ class TwoTowerTrainer:
                                   accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
             self._add_features((user_ids, ut.acts[0]), (cand, it.acts[0]), keep=True)   # cand_ids: the sampled rows too
         # the dropout streams count rows per tower: consecutive steps never share a position
-        drop_u, drop_i = ((cfg.dropout_rate, self.dropout_seed, t, self.step_index * tw.rows) for t, tw in enumerate((ut, it)))
-        if cfg.layer_norm:                       # one normalisation launch per layer over both towers' row counts
-            layer_norm_towers_forward((ut, it), dropouts=(drop_u, drop_i), lookups=(lk_u, lk_i))
-        else:
-            ut.forward(drop_u, lookup=lk_u)
-            it.forward(drop_i, lookup=lk_i)
+        towers_forward((ut, it), tuple((cfg.dropout_rate, self.dropout_seed, t, self.step_index * tw.rows) for t, tw in enumerate((ut, it))),
+                       lookups=lks)
         q, c = self._outputs(ut, it)
         dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
         ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
@@ -1480,11 +1469,7 @@ class TwoTowerTrainer:
         if cfg.normalize_embeddings:
             ops.l2_normalize_bwd2((ut.acts[-1],), (dq,), (ut.dz[-1],), cfg.normalize_eps)
             ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
-        if cfg.layer_norm:
-            layer_norm_towers_backward((ut, it), cfg.dropout_rate, lookups=(lk_u, lk_i))
-        else:
-            ut.backward(cfg.dropout_rate, lookup=lk_u)
-            it.backward(cfg.dropout_rate, lookup=lk_i)
+        towers_backward((ut, it), cfg.dropout_rate, lookups=lks)
         self._features_backward()
         self.step_index += 1
         return self.loss
@@ -1730,8 +1715,7 @@ class TwoTowerTrainer:
                 ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=cfg.title_pooling,
                                   out=it.acts[0][:b], accumulate=True, oob_flag=self.oob)
             self._add_features((user_ids, ut.acts[0]), (item_ids, it.acts[0][:b]))
-            ut.forward()
-            it.forward(rows=b)
+            towers_forward((ut, it), rows=(b, b))
             q, c = self._outputs_rows((ut, it), [b, b])
             if self.rating_on:
                 self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
@@ -1741,9 +1725,7 @@ class TwoTowerTrainer:
         lks = self._lookups(user_ids, item_ids, loss_kw.get("category_ids"))
         if lks is None:
             self._item_inputs(user_ids, item_ids, loss_kw.get("category_ids"))
-            q, c = towers_forward(ut, it) if cfg.symmetric else (ut.forward(), it.forward())
-        else:
-            q, c = towers_forward(ut, it, lookups=lks) if cfg.symmetric else (ut.forward(lookup=lks[0]), it.forward(lookup=lks[1]))
+        towers_forward((ut, it), lookups=lks)
         q, c = self._outputs(ut, it)
         if self.rating_on:
             self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
