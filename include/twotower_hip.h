@@ -49,8 +49,8 @@ const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
  * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args,
  * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args, 15 tt_dense_features_bwd_args,
- * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args; else - 9, 13, 16, 19 and
- * 20 included, which stay unassigned - -1): a binding checks its mirrors with it. */
+ * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args, 23 tt_clip_buffer; else -
+ * 9, 13, 16, 19 and 20 included, which stay unassigned - -1): a binding checks its mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
 /* ---------------------------------------------------------------------------------------
@@ -671,6 +671,50 @@ typedef struct tt_dense_seg {
 } tt_dense_seg;
 int tt_dense_update_f32(const tt_dense_seg* segs, int32_t n_segs, int32_t opt, int32_t apply,
                         float lr, float eps, tt_stream_t stream);
+/* ---------------------------------------------------------------------------------------
+ * Global-norm gradient clipping (added to v10: new symbols and one struct only, the version is unchanged; csrc/clip.hip) -
+ * tf.clip_by_global_norm over ALL gradient buffers of a step in two launches, whatever their number:
+ *   sumsq = sum over dense buffers, over e in [0, count), of (sum_s data[s * slab_stride + e])^2    (slabs added in f32, s ascending)
+ *         + sum over row buffers, over rows r, of f_r * |data[r, :]|^2
+ *   norm  = sqrtf(sumsq)    scale = clip_norm / fmaxf(norm, clip_norm)   (IEEE division; exactly 1 when norm <= clip_norm; NaN
+ *   when norm is not finite)    every buffer *= scale in place: all n_slabs slabs of a dense buffer ([0, count) of each, never
+ *   the padding up to slab_stride), every row of a row buffer (also those with f_r == 0).
+ * The factor of row r is f_r = weight + w(mode): TT_CLIP_ROWS 0; the bag modes count n_r = the entries >= 0 of slot_ids[r, 0..L)
+ * and add n_r (TT_CLIP_BAG_SUM), 1 / n_r (TT_CLIP_BAG_MEAN) or 1 (TT_CLIP_BAG_SQRTN), 0 for an empty bag - the squared norm of
+ * the per-occurrence gradient rows of a pooled embedding bag whose pooled-row gradient is data[r]; TT_CLIP_SLOT_MASK adds 1
+ * where slot_ids[r] >= 0 (one id per row).  `weight` counts the tables that consume the row as it stands (an input gradient
+ * shared by k id tables: k).  A row with f_r == 0 is not read by the norm: it may hold anything, also non-finite values.
+ * Launch 1 writes one f32 partial per workgroup into `workspace` (wave shuffles, then LDS; no atomics); in launch 2 every
+ * workgroup adds the partials in one fixed order (in f64), workgroup 0 writes stats[0] = norm and stats[1] = scale, and all of
+ * them scale (nothing is read or stored when scale == 1).  Both grids depend on the buffers' shapes alone: equal inputs give
+ * equal bits.  Nothing is read back to the host.  16-byte loads where data is 16-byte aligned and slab_stride % 4 == 0, scalar
+ * loads for a dense buffer's last count % 4 elements and for unaligned dense buffers.  `bufs` is a HOST array of up to
+ * TT_CLIP_MAX_BUFFERS entries, passed to the kernels by value.  No buffers, or only empty ones: no launch, stats = {0, 1}.
+ * tt_clip_workspace_bytes: a host query (>= 256, a multiple of 256; -1 for an invalid list) - the workspace needs no
+ * initialisation.  HBM: reads every gradient byte once, and once more with a write where scale != 1.
+ * TT_ERR_INVALID_ARG before any launch: a NULL bufs / stats / workspace, n_bufs outside 0..TT_CLIP_MAX_BUFFERS, clip_norm <= 0 or
+ * not finite, an unknown mode, n_slabs < 1, count / rows < 0, slab_stride < count with more than one slab, dim < 4 or
+ * dim % 4 != 0, L < 1 in a bag mode, and for a buffer with elements a NULL data, a NULL slot_ids where the mode reads them, a
+ * row buffer that is not 16-byte aligned or a dense one that is not 4-byte aligned.  TT_ERR_WORKSPACE: workspace_bytes too small. */
+#define TT_CLIP_MAX_BUFFERS (8 + TT_MAX_DENSE_SEGS)
+enum { TT_CLIP_DENSE = 0, TT_CLIP_ROWS = 1, TT_CLIP_BAG_SUM = 2, TT_CLIP_BAG_MEAN = 3, TT_CLIP_BAG_SQRTN = 4, TT_CLIP_SLOT_MASK = 5 };
+typedef struct tt_clip_buffer {
+  float* data;               /* dense: slab s at data + s * slab_stride; rows: [rows, dim]          */
+  const int64_t* slot_ids;   /* bag modes: [rows, L]; TT_CLIP_SLOT_MASK: [rows]; else ignored       */
+  int64_t rows;              /* row buffers                                                         */
+  int64_t count;             /* dense: floats per slab                                              */
+  int64_t slab_stride;       /* dense: floats between two slabs                                     */
+  int32_t dim;               /* row buffers: a multiple of 4                                        */
+  int32_t L;                 /* bag modes: slots per row                                            */
+  int32_t n_slabs;           /* dense: >= 1                                                         */
+  int32_t mode;              /* TT_CLIP_*                                                           */
+  float weight;              /* row buffers: the constant part of f_r (>= 0)                        */
+  int32_t reserved;
+} tt_clip_buffer;
+int64_t tt_clip_workspace_bytes(const tt_clip_buffer* bufs, int32_t n_bufs);
+int tt_clip_global_norm_f32(const tt_clip_buffer* bufs, int32_t n_bufs, float clip_norm, void* workspace, int64_t workspace_bytes,
+                            float* stats, tt_stream_t stream);
+
 /* tt_dense_bwd_batched_f32 with a dense parameter update RIDING in the same launch (ABI v9): `segs` (apply = 1 semantics of
  * tt_dense_update_f32) must belong to ANOTHER layer - in a backward pass, the layer above, whose gradient slabs the previous
  * backward launch completed; a segment whose slabs this launch writes or whose weights it reads is refused.  The update's

@@ -23,6 +23,8 @@ TT_IDS_UNIFORM, TT_IDS_POWERLAW = 0, 1
 TT_POOL_SUM, TT_POOL_MEAN, TT_POOL_SQRTN = 0, 1, 2
 TT_SAMPLER_UNIFORM, TT_SAMPLER_ALIAS = 0, 1
 TT_MAX_DENSE_SEGS = 16
+TT_CLIP_MAX_BUFFERS = 8 + TT_MAX_DENSE_SEGS
+TT_CLIP_DENSE, TT_CLIP_ROWS, TT_CLIP_BAG_SUM, TT_CLIP_BAG_MEAN, TT_CLIP_BAG_SQRTN, TT_CLIP_SLOT_MASK = range(6)
 TT_MAX_TOWER_LAYERS = 8
 TT_TOPK_MAX_K = 256
 
@@ -149,6 +151,14 @@ class LayerNormBwdArgs(C.Structure):
                 ("dbeta_slabs", C.c_void_p), ("rows", C.c_int64)]
 
 
+class ClipBuffer(C.Structure):
+    """Mirror of ``tt_clip_buffer`` (one gradient buffer of ``tt_clip_global_norm_f32``)."""
+    _fields_ = [("data", C.c_void_p), ("slot_ids", C.c_void_p), ("rows", C.c_int64), ("count", C.c_int64), ("slab_stride", C.c_int64),
+                ("dim", C.c_int32), ("L", C.c_int32), ("n_slabs", C.c_int32), ("mode", C.c_int32), ("weight", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+CLIP_STRUCT_INDEX = {"ClipBuffer": 23}
 # tt_abi_struct_bytes index of each mirror (9, 13, 16, 19 and 20 are unassigned: the library answers -1 for them)
 ABI_STRUCT_INDEX = {"AdamTable": 10, "AdamSeg": 11, "AdamHyper": 12}
 FEATURES_STRUCT_INDEX = {"DenseFeaturesFwdArgs": 14, "DenseFeaturesBwdArgs": 15}
@@ -239,6 +249,8 @@ SIGNATURES = {
     "tt_l2_normalize_bwd_f32": (C.c_int, [C.POINTER(L2NormBwdArgs), _i32, _i64, _i32, _f, _p]),
     "tt_dense_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     "tt_dense_update_f32": (C.c_int, [C.POINTER(DenseSeg), _i32, _i32, _i32, _f, _f, _p]),
+    "tt_clip_workspace_bytes": (_i64, [C.POINTER(ClipBuffer), _i32]),
+    "tt_clip_global_norm_f32": (C.c_int, [C.POINTER(ClipBuffer), _i32, _f, _p, _i64, _p, _p]),
     "tt_optimizer_step_f32": (C.c_int, [_i32, C.POINTER(SparseTable), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, _f, _f, _p]),
     "tt_optimizer_step_ids_f32": (C.c_int, [_i32, C.POINTER(SparseTableIds), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, _f, _f, _p]),
     "tt_optimizer_ids_geometry": (C.c_int, [C.POINTER(_i64), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, C.POINTER(_i32),

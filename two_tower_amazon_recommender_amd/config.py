@@ -6,7 +6,7 @@ import math
 
 import yaml
 
-from .trainer import TwoTowerConfig
+from .trainer import LR_DECAYS, TwoTowerConfig
 
 
 def load_yaml(path) -> dict:
@@ -84,6 +84,40 @@ def layer_norm_from_dict(doc: dict) -> dict:
     return {"enabled": enabled, "epsilon": float(eps)}
 
 
+LR_SCHEDULE_KEYS = ("warmup_steps", "decay", "decay_steps", "min_ratio")
+
+
+def optimization_from_dict(doc: dict) -> dict:
+    """{global_clipnorm, warmup_steps, decay, decay_steps, min_ratio} of the optional keys ``model.training.global_clipnorm: C``
+    and ``model.training.lr_schedule: {warmup_steps, decay, decay_steps, min_ratio}`` (not in the reference's schema): global-norm
+    gradient clipping (0: off) and the learning-rate schedule around ``model.training.learning_rate``, its peak.
+    ``decay_steps`` is an int or "auto" (train.py: epochs x steps per epoch - warmup_steps).  Without the keys: both off."""
+    tr = (doc.get("model") or {}).get("training") or {}
+    clip = tr.get("global_clipnorm", 0.0)
+    if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not (clip >= 0.0 and math.isfinite(clip)):
+        raise ValueError(f"model.training.global_clipnorm must be a finite number >= 0, got {clip!r}")
+    block = tr.get("lr_schedule")
+    if block is None:
+        block = {}
+    if not isinstance(block, dict):
+        raise ValueError("model.training.lr_schedule must be a mapping {warmup_steps, decay, decay_steps, min_ratio}")
+    unknown = sorted(set(block) - set(LR_SCHEDULE_KEYS))
+    if unknown:
+        raise ValueError(f"model.training.lr_schedule: unknown keys {unknown} (known: {list(LR_SCHEDULE_KEYS)})")
+    warm, decay = block.get("warmup_steps", 0), block.get("decay", "none")
+    steps, ratio = block.get("decay_steps", 0), block.get("min_ratio", 0.0)
+    if isinstance(warm, bool) or not isinstance(warm, int) or warm < 0:
+        raise ValueError(f"model.training.lr_schedule.warmup_steps must be an int >= 0, got {warm!r}")
+    decay = "none" if decay is None else str(decay).lower()
+    if decay not in LR_DECAYS:
+        raise ValueError(f"model.training.lr_schedule.decay must be one of {LR_DECAYS}, got {decay!r}")
+    if steps != "auto" and (isinstance(steps, bool) or not isinstance(steps, int) or steps < 0):
+        raise ValueError(f"model.training.lr_schedule.decay_steps must be an int >= 0 or 'auto', got {steps!r}")
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 <= ratio <= 1.0:
+        raise ValueError(f"model.training.lr_schedule.min_ratio must be in [0, 1], got {ratio!r}")
+    return {"global_clipnorm": float(clip), "warmup_steps": warm, "decay": decay, "decay_steps": steps, "min_ratio": float(ratio)}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -114,7 +148,12 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     cross = cross_from_dict(doc)
     # likewise model.layer_norm {enabled, epsilon} - layer normalisation of the towers' hidden layers
     norm = layer_norm_from_dict(doc)
+    # likewise model.training.global_clipnorm and model.training.lr_schedule {warmup_steps, decay, decay_steps, min_ratio}
+    # (decay_steps "auto": left 0 here - train.py, which knows the number of steps, reads the block itself and resolves it)
+    opt = optimization_from_dict(doc)
     cfg = TwoTowerConfig(
+        global_clipnorm=opt["global_clipnorm"], lr_warmup_steps=opt["warmup_steps"], lr_decay=opt["decay"],
+        lr_decay_steps=0 if opt["decay_steps"] == "auto" else opt["decay_steps"], lr_min_ratio=opt["min_ratio"],
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,
         item_tower_dims=None if item_dims == user_dims else item_dims,
         temperature=float(rt.get("temperature", 1.0)), l2_regularization=float(m.get("l2_regularization", 0.0)),

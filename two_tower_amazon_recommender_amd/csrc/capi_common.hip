@@ -139,7 +139,8 @@ extern "C" int tt_abi_version(void) { return TT_ABI_VERSION; }
 // sizeof of the ABI's structs, so that a binding can check its mirrors (which = 0 tt_train_step, 1 tt_dense_fwd_args,
 // 2 tt_dense_bwd_args, 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args,
 // 8 tt_l2norm_bwd_args, 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args,
-// 15 tt_dense_features_bwd_args, 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args;
+// 15 tt_dense_features_bwd_args, 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args,
+// 23 tt_clip_buffer;
 // anything else - 9, 13, 16, 19 and 20 stay unassigned -: -1)
 extern "C" int64_t tt_abi_struct_bytes(int32_t which) {
   switch (which) {
@@ -161,6 +162,7 @@ extern "C" int64_t tt_abi_struct_bytes(int32_t which) {
     case 18: return (int64_t)sizeof(tt_cross_bwd_args);
     case 21: return (int64_t)sizeof(tt_layer_norm_fwd_args);
     case 22: return (int64_t)sizeof(tt_layer_norm_bwd_args);
+    case 23: return (int64_t)sizeof(tt_clip_buffer);
     default: return -1;
   }
 }

@@ -932,6 +932,81 @@ def make_dense_seg(param, accum, grad_slabs, n_slabs: int, l2: float, grad_out=N
                     n_slabs, l2)
 
 
+# ----------------------------------------------------------------------------- global-norm gradient clipping
+CLIP_MODES = {"rows": _lib.TT_CLIP_ROWS, "sum": _lib.TT_CLIP_BAG_SUM, "mean": _lib.TT_CLIP_BAG_MEAN, "sqrtn": _lib.TT_CLIP_BAG_SQRTN,
+              "mask": _lib.TT_CLIP_SLOT_MASK}
+
+
+def make_clip_rows(grads, weight: float = 1.0, slot_ids=None, mode: str = "rows") -> "_lib.ClipBuffer":
+    """One gradient-row buffer of ``clip_global_norm_``: ``grads`` [rows, dim] f32, row r counts ``weight`` + w(mode) times -
+    "rows": nothing more; "sum" / "mean" / "sqrtn": ``slot_ids`` [rows, L] int64, n_r = its entries >= 0, + n_r / 1 / n_r / 1 (an
+    empty bag: 0); "mask": ``slot_ids`` [rows] int64, + 1 where the id is >= 0.  The caller keeps the tensors alive."""
+    _chk(grads, torch.float32, "grads", 2)
+    if mode not in CLIP_MODES:
+        raise ValueError(f"make_clip_rows: mode must be one of {tuple(CLIP_MODES)}, got {mode!r}")
+    rows, dim = grads.shape
+    L = 0
+    if mode == "rows":
+        slot_ids = None
+    else:
+        _chk(slot_ids, torch.int64, "slot_ids")
+        if slot_ids.numel() == 0 and rows:
+            raise RuntimeError("make_clip_rows: slot_ids is empty")
+        L = 1 if mode == "mask" else slot_ids.numel() // max(rows, 1)
+        if slot_ids.numel() != rows * L:
+            raise RuntimeError(f"make_clip_rows: slot_ids must hold rows * L ids (mask: one per row), got {slot_ids.numel()} for {rows} rows")
+    return _lib.ClipBuffer(_p(grads), _p(slot_ids), rows, 0, 0, dim, L, 0, CLIP_MODES[mode], float(weight), 0)
+
+
+def make_clip_dense(grad_slabs, count: int, n_slabs: int = 1, slab_stride: int | None = None) -> "_lib.ClipBuffer":
+    """One dense gradient of ``clip_global_norm_``: ``n_slabs`` slabs of ``count`` floats, ``slab_stride`` (default count) apart,
+    which are summed (slab order) before they are squared - what ``make_dense_seg`` / ``make_adam_seg`` hand the optimizer."""
+    _chk(grad_slabs, torch.float32, "grad_slabs")
+    stride = int(count) if slab_stride is None else int(slab_stride)
+    if n_slabs >= 1 and count >= 0 and grad_slabs.numel() < (n_slabs - 1) * stride + count:
+        raise RuntimeError("make_clip_dense: grad_slabs must hold n_slabs slabs of slab_stride >= count floats")
+    return _lib.ClipBuffer(_p(grad_slabs), None, 0, int(count), stride, 0, 0, int(n_slabs), _lib.TT_CLIP_DENSE, 0.0, 0)
+
+
+class ClipList:
+    """The buffer list of ``clip_global_norm_``, built once for buffers that stay where they are: ``row_buffers`` =
+    ``make_clip_rows`` descriptors, ``dense_segs`` = ``make_clip_dense`` descriptors or the optimizer's own segments
+    (``make_dense_seg`` / ``make_adam_seg``: their gradient slabs are taken).  ``workspace_bytes``: what the call needs."""
+
+    def __init__(self, row_buffers, dense_segs=()):
+        bufs = list(row_buffers)
+        for s in dense_segs:
+            bufs.append(s if isinstance(s, _lib.ClipBuffer) else
+                        _lib.ClipBuffer(s.grad_slabs, None, 0, s.count, s.slab_stride, 0, 0, s.n_slabs, _lib.TT_CLIP_DENSE, 0.0, 0))
+        if len(bufs) > _lib.TT_CLIP_MAX_BUFFERS:
+            raise ValueError(f"clip_global_norm_: at most {_lib.TT_CLIP_MAX_BUFFERS} buffers per call (got {len(bufs)})")
+        self.n = len(bufs)
+        self.arr = (_lib.ClipBuffer * max(self.n, 1))(*bufs)
+        self.workspace_bytes = int(_lib.load().tt_clip_workspace_bytes(self.arr, self.n))
+        if self.workspace_bytes < 0:
+            raise ValueError("clip_global_norm_: " + _lib.load().tt_last_error().decode("utf-8", "replace"))
+
+
+def clip_global_norm_(row_buffers, dense_segs=(), clipnorm: float = 1.0, workspace=None, stats=None):
+    """tf.clip_by_global_norm over all the buffers IN PLACE, two launches (``tt_clip_global_norm_f32``): every buffer is
+    multiplied by clipnorm / max(norm, clipnorm).  ``row_buffers`` may be a prebuilt ``ClipList`` (then ``dense_segs`` is not
+    read).  Returns ``stats`` (2 f32 on the device, unsynchronised): [the norm before clipping, the scale applied]."""
+    lst = row_buffers if isinstance(row_buffers, ClipList) else ClipList(row_buffers, dense_segs)
+    given = [t.device for t in (stats, workspace) if t is not None]
+    dev = given[0] if given else torch.device("cuda", torch.cuda.current_device())
+    if stats is None:
+        stats = torch.empty(2, device=dev)
+    _chk(stats, torch.float32, "stats", 1)
+    if stats.numel() < 2:
+        raise RuntimeError("clip_global_norm_: stats needs 2 floats")
+    if workspace is None:
+        workspace = torch.empty(lst.workspace_bytes, dtype=torch.uint8, device=dev)
+    _chk(workspace, torch.uint8, "workspace")
+    _lib.check(_lib.load().tt_clip_global_norm_f32(lst.arr, lst.n, float(clipnorm), _p(workspace), workspace.numel(), _p(stats), _stream()),
+               "tt_clip_global_norm_f32")
+    return stats
+
+
 # ----------------------------------------------------------------------------- lazy Adam
 def adam_workspace_bytes(n_ids: int, dim: int) -> int:
     """Piece-sum workspace of ``adam_step_`` per table: 256-byte aligned, needs no initialisation; 0 for no ids."""

@@ -449,6 +449,13 @@ class ShardedTwoTowerTrainer:
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "global_clipnorm", 0.0) > 0:
+            # the norm would have to be all-reduced over the ranks' table shards between the gradient exchange and the update
+            raise NotImplementedError("gradient clipping (global_clipnorm > 0) is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "lr_schedule_on", False):
+            raise NotImplementedError("a learning-rate schedule (lr_warmup_steps / lr_decay) is not implemented for the row-sharded "
+                                      "trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
         from . import ops
         from .trainer import Tower, TID_USER_TABLE, TID_ITEM_TABLE
         cfg.validate()

@@ -21,7 +21,7 @@ settings ``configs/data_config.yaml:54-71``; the task object's call signature: S
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -768,5 +768,24 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
     ops.adam_step_([(table, exp_avg, exp_avg_sq, grads.contiguous(), plan)], [], ops.AdamHyper(lr, beta1, beta2, eps, step))
 
 
-OPS = ("embedding_gather", "embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
+# --------------------------------------------------------------------------------------------- global-norm gradient clipping
+@torch.library.custom_op(f"{NS}::clip_by_global_norm_", mutates_args=("tensors",), device_types="cuda")
+def clip_by_global_norm_(tensors: List[Tensor], clip_norm: float) -> Tensor:
+    """tf.clip_by_global_norm / ``torch.nn.utils.clip_grad_norm_`` over contiguous f32 gradient tensors IN PLACE, two launches
+    for all of them (``ops.clip_global_norm_``: up to 24 tensors per call): every tensor *= clip_norm / max(norm, clip_norm).
+    Returns [the norm before clipping, the scale] (2 f32 on the device, unsynchronised)."""
+    for t in tensors:
+        ops._chk(t, torch.float32, "tensors")
+    if not tensors:
+        raise ValueError("clip_by_global_norm_: no tensors")
+    stats = torch.empty(2, device=tensors[0].device)
+    return ops.clip_global_norm_([], [ops.make_clip_dense(t.view(-1), t.numel()) for t in tensors], clip_norm, stats=stats)
+
+
+@clip_by_global_norm_.register_fake
+def _(tensors, clip_norm):
+    return torch.empty(2, dtype=torch.float32, device=tensors[0].device)
+
+
+OPS = ("clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_")

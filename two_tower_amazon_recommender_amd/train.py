@@ -103,6 +103,17 @@ def parse(argv=None):
                          "single-GPU trainer only")
     ap.add_argument("--layer-norm-epsilon", type=float, default=None, metavar="E",
                     help="epsilon inside the normalisation's square root (default model.layer_norm.epsilon, else Keras's 1e-3)")
+    ap.add_argument("--global-clipnorm", type=float, default=None, metavar="C",
+                    help="clip every step's gradient to the global norm C (Keras global_clipnorm / tf.clip_by_global_norm over the "
+                         "dense gradients and the embedding rows, two launches; overrides model.training.global_clipnorm; 0: off); "
+                         "single-GPU trainer only")
+    ap.add_argument("--lr-warmup-steps", type=int, default=None, metavar="W",
+                    help="linear warm-up of the learning rate over the first W steps (overrides model.training.lr_schedule.warmup_steps)")
+    ap.add_argument("--lr-decay", default=None, choices=["none", "cosine", "linear", "inverse_sqrt"],
+                    help="how the rate falls from its peak (model.training.learning_rate) after the warm-up")
+    ap.add_argument("--lr-decay-steps", default=None, metavar="N|auto",
+                    help="steps of the cosine / linear decay; auto = epochs x steps per epoch - warm-up steps")
+    ap.add_argument("--lr-min-ratio", type=float, default=None, metavar="M", help="floor of the decayed rate as a fraction of the peak (0..1)")
     ap.add_argument("--correct-sampling-bias", action="store_true",
                     help="pass every candidate's empirical frequency as candidate_sampling_probability (the logQ correction "
                          "of tfrs.tasks.Retrieval): in-batch negatives otherwise push popular items down")
@@ -185,6 +196,25 @@ def main(argv=None) -> int:
         raise SystemExit("--layer-norm-epsilon needs --layer-norm (or model.layer_norm.enabled)")
     if distributed and layer_norm:
         raise NotImplementedError("layer normalisation is not implemented for the row-sharded (--distributed) trainer")
+    sched = cfgmod.optimization_from_dict(doc)
+    for key, arg in (("global_clipnorm", args.global_clipnorm), ("warmup_steps", args.lr_warmup_steps), ("decay", args.lr_decay),
+                     ("min_ratio", args.lr_min_ratio)):
+        if arg is not None:
+            sched[key] = arg
+    if args.lr_decay_steps is not None:
+        if args.lr_decay_steps != "auto" and not args.lr_decay_steps.isdigit():
+            raise SystemExit("--lr-decay-steps must be a non-negative integer or 'auto'")
+        sched["decay_steps"] = "auto" if args.lr_decay_steps == "auto" else int(args.lr_decay_steps)
+    if not (sched["global_clipnorm"] >= 0.0 and np.isfinite(sched["global_clipnorm"])):
+        raise SystemExit("--global-clipnorm must be a finite number >= 0")
+    if sched["warmup_steps"] < 0:
+        raise SystemExit("--lr-warmup-steps must be >= 0")
+    if not 0.0 <= sched["min_ratio"] <= 1.0:
+        raise SystemExit("--lr-min-ratio must be in [0, 1]")
+    if distributed and sched["global_clipnorm"] > 0:
+        raise NotImplementedError("gradient clipping (global_clipnorm) is not implemented for the row-sharded (--distributed) trainer")
+    if distributed and (sched["warmup_steps"] > 0 or sched["decay"] != "none"):
+        raise NotImplementedError("a learning-rate schedule is not implemented for the row-sharded (--distributed) trainer")
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -306,6 +336,15 @@ def main(argv=None) -> int:
     va_idx = va_idx[:len(va_idx) // per * per][rank::world]
     if len(tr_idx) < cfg.batch_size:
         raise SystemExit(f"only {len(tr_idx)} training interactions per rank for batch_size {cfg.batch_size}")
+    cfg.global_clipnorm = float(sched["global_clipnorm"])
+    cfg.lr_warmup_steps, cfg.lr_decay, cfg.lr_min_ratio = int(sched["warmup_steps"]), sched["decay"], float(sched["min_ratio"])
+    if sched["decay_steps"] == "auto":          # the whole run behind the warm-up: epochs x steps per epoch - warmup_steps
+        cfg.lr_decay_steps = max(epochs * (len(tr_idx) // cfg.batch_size) - cfg.lr_warmup_steps, 1)
+    else:
+        cfg.lr_decay_steps = int(sched["decay_steps"])
+    if cfg.lr_schedule_on or cfg.global_clipnorm > 0:
+        log.info("global_clipnorm %g; learning rate: peak %g, warm-up %d steps, decay %s over %d steps, floor %g x peak",
+                 cfg.global_clipnorm, cfg.learning_rate, cfg.lr_warmup_steps, cfg.lr_decay, cfg.lr_decay_steps, cfg.lr_min_ratio)
     if distributed:
         trainer = ShardedTwoTowerTrainer(cfg, args.device, seed=args.seed, negatives=args.negatives)
     else:
@@ -377,6 +416,10 @@ def main(argv=None) -> int:
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "train_loss_per_pair": total(tot) / (len(train_it) * cfg.batch_size * world),
                "pairs_per_sec": len(train_it) * cfg.batch_size * world / dt}
+        # of the epoch's last step (the norm is read behind the synchronise above: no extra one)
+        rec["lr"] = cfg.learning_rate if distributed else trainer.learning_rate
+        if cfg.global_clipnorm > 0:
+            rec["grad_norm"] = trainer.grad_norm.item()
         if len(val_it) and (epoch + 1) % loop["validation_freq"] == 0:
             vt = torch.zeros((), device=trainer.dev, dtype=torch.float64)
             vse = torch.zeros((), device=trainer.dev, dtype=torch.float64)

@@ -44,6 +44,7 @@ TID_CROSS_BASE = 48                          # the cross kernels: layer l of tow
 MAX_CROSS_LAYERS = 3
 # poolings of the user-history feature: the bag launch's three and the attention pool (csrc/history_attn.hip), history only
 HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention",)
+LR_DECAYS = ("none", "cosine", "linear", "inverse_sqrt")
 TID_DROPOUT_BASE = 64
 
 
@@ -65,6 +66,19 @@ class TwoTowerConfig:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_epsilon: float = 1e-7
+    # global-norm gradient clipping (Keras optimizers' global_clipnorm=, tf.clip_by_global_norm): every gradient of the step -
+    # dense parameters and the embedding tables' per-occurrence rows (IndexedSlices.values: duplicates not merged) - is scaled by
+    # c / max(norm, c) between the backward pass and the optimizer, in two launches (csrc/clip.hip).  The l2 term, which the
+    # optimizer kernels add, is neither counted nor scaled.  0 = off.  Single-GPU trainer, Python sequence of launches, no graph
+    # capture.
+    global_clipnorm: float = 0.0
+    # learning-rate schedule (Keras LearningRateSchedule; a host function, ``learning_rate_at``): learning_rate is the PEAK, reached
+    # after lr_warmup_steps linear warm-up steps; then lr_decay "none" | "cosine" | "linear" (over lr_decay_steps steps, down to
+    # lr_min_ratio * peak, constant from there) | "inverse_sqrt" (peak * sqrt(max(warmup, 1) / (step + 1)), not below the floor).
+    lr_warmup_steps: int = 0
+    lr_decay: str = "none"
+    lr_decay_steps: int = 0
+    lr_min_ratio: float = 0.0
     batch_size: int = 1024                         # :62
     dropout_rate: float = 0.0                      # :58 is 0.1; parity/bench runs use 0
     # BASELINE configs[4] "30 categories as hash features": a [n_category_buckets, embedding_dim] table whose row
@@ -131,6 +145,27 @@ class TwoTowerConfig:
     n_title_buckets: int = 0
     title_max_tokens: int = 16
     title_pooling: str = "mean"
+
+    @property
+    def lr_schedule_on(self) -> bool:
+        return self.lr_warmup_steps > 0 or self.lr_decay != "none"
+
+    def learning_rate_at(self, step: int) -> float:
+        """The rate of the step with 0-based index ``step`` (f64 arithmetic; the kernels take it rounded to f32, like a constant
+        rate).  Without a schedule: learning_rate itself."""
+        if self.lr_decay == "none" and self.lr_warmup_steps <= 0:        # (first: the default step reads this every time)
+            return self.learning_rate
+        peak, s, warm = float(self.learning_rate), int(step), int(self.lr_warmup_steps)
+        if s < warm:
+            return peak * (s + 1) / warm
+        t, total, m = s - warm, int(self.lr_decay_steps), float(self.lr_min_ratio)
+        if self.lr_decay == "cosine":
+            return peak * (m + (1.0 - m) * 0.5 * (1.0 + math.cos(math.pi * min(t, total) / total)))
+        if self.lr_decay == "linear":
+            return peak * (m + (1.0 - m) * (1.0 - min(t, total) / total))
+        if self.lr_decay == "inverse_sqrt":
+            return peak * max(m, math.sqrt(max(warm, 1) / (s + 1)))
+        return peak
 
     @property
     def user_dims(self) -> list:
@@ -244,6 +279,20 @@ class TwoTowerConfig:
                 raise ValueError("layer_norm=True needs towers with a hidden layer (the output layer is not normalised)")
             if any(n % 32 or not 32 <= n <= 1024 for n in hidden):
                 raise ValueError(f"layer_norm=True needs hidden widths that are multiples of 32 in 32..1024 (got {hidden})")
+        c = self.global_clipnorm
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not (c >= 0.0 and math.isfinite(c)):
+            raise ValueError("global_clipnorm must be a finite number >= 0 (0: no clipping)")
+        for name in ("lr_warmup_steps", "lr_decay_steps"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be an int >= 0")
+        if self.lr_decay not in LR_DECAYS:
+            raise ValueError(f"lr_decay must be one of {LR_DECAYS}, got {self.lr_decay!r}")
+        if self.lr_decay in ("cosine", "linear") and self.lr_decay_steps < 1:
+            raise ValueError(f"lr_decay={self.lr_decay!r} needs lr_decay_steps >= 1")
+        m = self.lr_min_ratio
+        if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0.0 <= m <= 1.0:
+            raise ValueError("lr_min_ratio must be in [0, 1]")
         # the optimizer launches take TT_MAX_DENSE_SEGS segments.  Refused: a model whose optional blocks do not fit - blamed on
         # the block that holds the first segment past the limit (towers that are over it on their own: on the first optional block)
         segs = dense_layout(self).segments
@@ -785,16 +834,18 @@ class EmbeddingTable:
         if self.m is not None:
             self.m.zero_(), self.v.zero_()
 
-    def apply(self, cfg: TwoTowerConfig, grads, adam_step: int, adam_segs=()):
+    def apply(self, cfg: TwoTowerConfig, grads, adam_step: int, adam_segs=(), lr: float | None = None):
         """The configured optimizer's update from this table's sort plan (which has run; a ``BagPlan`` after its ``backward``:
-        ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same lazy-Adam call."""
+        ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same lazy-Adam call.  ``lr``: the
+        step's rate (the trainer's ``learning_rate``; default: the configured one)."""
+        lr = cfg.learning_rate if lr is None else lr
         if cfg.optimizer == "adam":
             ops.adam_step_([(self.table, self.m, self.v, grads, self.plan)], list(adam_segs),
-                           ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
+                           ops.AdamHyper(lr, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
         elif cfg.optimizer == "sgd":
-            ops.sparse_sgd_(self.table, grads, self.plan, cfg.learning_rate)
+            ops.sparse_sgd_(self.table, grads, self.plan, lr)
         else:
-            ops.sparse_adagrad_(self.table, self.accum, grads, self.plan, cfg.learning_rate, cfg.adagrad_epsilon)
+            ops.sparse_adagrad_(self.table, self.accum, grads, self.plan, lr, cfg.adagrad_epsilon)
 
 
 @dataclass
@@ -864,7 +915,10 @@ _GRAPH_REFUSALS = (
     (lambda c: c.rating_weight > 0, "the rating head (rating_weight > 0) is not implemented: the step is the Python sequence of launches"),
     (lambda c: c.cross_layers, "cross layers (cross_layers > 0) is not implemented: the step is the Python sequence of launches over "
      "materialised tower inputs"),
-    (lambda c: c.layer_norm, "layer normalisation (layer_norm=True) is not implemented: the step is the Python sequence of launches"))
+    (lambda c: c.layer_norm, "layer normalisation (layer_norm=True) is not implemented: the step is the Python sequence of launches"),
+    (lambda c: c.global_clipnorm > 0, "gradient clipping (global_clipnorm > 0) is not implemented: the step is the Python sequence of "
+     "launches"),
+    (lambda c: c.lr_schedule_on, "a learning-rate schedule (lr_warmup_steps / lr_decay): the step's rate is a kernel argument"))
 
 
 class TwoTowerTrainer:
@@ -1034,6 +1088,11 @@ class TwoTowerTrainer:
         # cost more than the kernel: cfg3 step 0.687-0.689 ms against 0.677-0.681 ms; DESIGN.md section 4, K2 plan)
         self.plan_on_side_stream = os.environ.get("TT_PLAN_STREAM", "main") == "side"
         self.step_index = 0                      # counter of the dropout stream (global batch row = step*batch + r)
+        # the step the learning-rate schedule is read at: the one in progress - forward_backward (or the composite call) sets it
+        # before it counts step_index on, so apply_gradients still sees the step whose gradients it applies
+        self._lr_step = 0
+        # cfg.global_clipnorm: the buffer list of the two clip launches, their workspace and [norm, scale] - built on first use
+        self._clip = self._clip_ws = self._clip_stats = None
         # K1 inside the first tower layer's GEMMs (0: gather2 launch + acts[0]).  Every 64-column tile of the first layer reads
         # the embedding rows through the ids again: up to 256 columns that costs less than materialising them (cfg3: 13.6 us
         # of gather against +3.6 us in the GEMMs; cfg4 1.875 vs 1.881 ms), at 512 columns it costs more (cfg5: the layer-0
@@ -1418,8 +1477,65 @@ class TwoTowerTrainer:
         towers_backward((ut, it), cfg.dropout_rate, lookups=lks, bwd2_ws=self.bwd2_ws)
         self._features_backward()
         self._history_backward()
+        self._lr_step = self.step_index
         self.step_index += 1
         return self.loss
+
+    # ------------------------------------------------------------------ learning-rate schedule and gradient clipping
+    def learning_rate_at(self, step: int) -> float:
+        """The schedule's rate at the 0-based step ``step`` (``TwoTowerConfig.learning_rate_at``)."""
+        return self.cfg.learning_rate_at(step)
+
+    @property
+    def learning_rate(self) -> float:
+        """The rate of the step in progress (after ``forward_backward``: of the step whose gradients wait for
+        ``apply_gradients``) - what every optimizer launch takes.  Without a schedule: cfg.learning_rate."""
+        return self.cfg.learning_rate_at(self._lr_step)
+
+    def _clip_list(self):
+        """Every gradient buffer as it stands between the backward pass and ``apply_gradients``, with the factor of its rows:
+        the towers' input gradients count once per id table that consumes them (user; item, category) plus w(n) per bag that is
+        pooled into them (title; history by sum / mean / sqrtn - the bags' scaled rows are formed from them later, inside
+        ``apply_gradients``), the attention pool's slot rows count where the slot was kept (a skipped slot's row is stale), and
+        every dense segment's slabs are summed before they are squared."""
+        cfg = self.cfg
+        user = dict(weight=1.0)
+        if self.history_table is not None and not self._attn_on:
+            user.update(slot_ids=self.history_ids, mode=cfg.history_pooling)
+        item = dict(weight=2.0 if self.cat_table is not None else 1.0)
+        if self.title_table is not None:
+            item.update(slot_ids=self.title_ids, mode=cfg.title_pooling)
+        rows = [ops.make_clip_rows(self.user_tower.demb, **user), ops.make_clip_rows(self.item_tower.demb, **item)]
+        if self._attn_on:
+            rows.append(ops.make_clip_rows(self.history_slot_grads, 0.0, self.history_ids, "mask"))
+        return ops.ClipList(rows, self._adam_segs if cfg.optimizer == "adam" else self._segs)
+
+    def clip_gradients(self):
+        """cfg.global_clipnorm > 0: scales every gradient of the step IN PLACE by c / max(global norm, c) - two launches, between
+        ``forward_backward`` and ``apply_gradients`` (``step`` calls it there).  Leaves ``grad_norm`` and ``clip_scale``.  The l2
+        term is added by the optimizer launches: it is neither counted nor scaled.  Off: nothing happens."""
+        if not self.cfg.global_clipnorm > 0:
+            return None
+        if self._clip is None:
+            self._clip = self._clip_list()
+            self._clip_ws = torch.empty(self._clip.workspace_bytes, dtype=torch.uint8, device=self.dev)
+            self._clip_stats = torch.zeros(2, device=self.dev)
+        return ops.clip_global_norm_(self._clip, clipnorm=self.cfg.global_clipnorm, workspace=self._clip_ws, stats=self._clip_stats)
+
+    def _clip_stat(self, i: int, what: str) -> torch.Tensor:
+        if self._clip_stats is None:
+            raise ValueError(f"{what}: no step has been clipped (cfg.global_clipnorm == 0, or clip_gradients has not run)")
+        return self._clip_stats[i]
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """The global gradient norm of the last clipped step BEFORE clipping; device scalar, unsynchronised."""
+        return self._clip_stat(0, "grad_norm")
+
+    @property
+    def clip_scale(self) -> torch.Tensor:
+        """c / max(grad_norm, c) of the last clipped step; device scalar, unsynchronised."""
+        return self._clip_stat(1, "clip_scale")
 
     # ------------------------------------------------------------------ mixed negative sampling
     def sample_candidates(self, item_ids: torch.Tensor) -> torch.Tensor:
@@ -1471,6 +1587,7 @@ class TwoTowerTrainer:
             ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
         towers_backward((ut, it), cfg.dropout_rate, lookups=lks)
         self._features_backward()
+        self._lr_step = self.step_index
         self.step_index += 1
         return self.loss
 
@@ -1489,18 +1606,19 @@ class TwoTowerTrainer:
         self.sample_candidates(item_ids)          # in front of everything else: the plans and both lookups read cand_ids
         self._run_plans_mixed(user_ids)
         loss = self._forward_backward_mixed(user_ids, item_ids, sample_weight, sampled=True, ratings=ratings)
+        self.clip_gradients()
         self.apply_gradients()
         return loss
 
     def _apply_table_gradients_mixed(self):
         """The two tables' plans hold different id counts (B and B + N): one sparse launch sequence per table.  The sampled
         items' rows are trained like the positives' (their gradient rows are demb[B:])."""
-        cfg, adam = self.cfg, self.cfg.optimizer == "adam"
+        cfg, adam, lr = self.cfg, self.cfg.optimizer == "adam", self.learning_rate
         if not adam:
-            ops.dense_update_(self._segs, cfg.optimizer, cfg.learning_rate, cfg.adagrad_epsilon)
+            ops.dense_update_(self._segs, cfg.optimizer, lr, cfg.adagrad_epsilon)
         # (lazy Adam: the user table with every dense segment in one call, then the item table - the same step t)
-        self.tables["user"].apply(cfg, self.user_tower.demb, self.adam_step, self._adam_segs if adam else ())
-        self.tables["item"].apply(cfg, self.item_tower.demb, self.adam_step)
+        self.tables["user"].apply(cfg, self.user_tower.demb, self.adam_step, self._adam_segs if adam else (), lr=lr)
+        self.tables["item"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
         if adam:
             self.adam_step += 1
 
@@ -1529,7 +1647,7 @@ class TwoTowerTrainer:
             gs = self.history_slot_grads
         else:
             gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
-        self.tables["history"].apply(cfg, gs, adam_step)
+        self.tables["history"].apply(cfg, gs, adam_step, lr=self.learning_rate)
 
     def _apply_title_gradients(self, adam_step: int):
         """The title table's update: sort plan over the step's slot tokens, one launch that scales the item-tower input gradient
@@ -1538,26 +1656,26 @@ class TwoTowerTrainer:
         cfg, plan = self.cfg, self.title_plan
         plan.run(self.title_ids, cfg.n_title_buckets)
         gs = plan.backward(self.item_tower.demb, self.title_inv, self.title_gs)
-        self.tables["title"].apply(cfg, gs, adam_step)
+        self.tables["title"].apply(cfg, gs, adam_step, lr=self.learning_rate)
 
     def _apply_table_gradients(self, step_ids=None):
-        cfg = self.cfg
+        cfg, lr = self.cfg, self.learning_rate
         if cfg.optimizer == "adam":  # every table and every tower segment in ONE call (two launches), from the sort plans
-            ops.adam_step_(self._adam_tables, self._adam_segs, ops.AdamHyper(cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2,
+            ops.adam_step_(self._adam_tables, self._adam_segs, ops.AdamHyper(lr, cfg.adam_beta1, cfg.adam_beta2,
                                                                              cfg.adam_epsilon, self.adam_step))
             self.adam_step += 1
             return
         if step_ids is not None:     # sort + sparse update of every table + dense update: ONE launch, straight from the raw ids
             tables = [(table, accum, grads, ids, plan) for (table, accum, grads, plan), ids in zip(self._opt_tables, step_ids)]
-            ops.optimizer_step_ids_(cfg.optimizer, tables, self._segs, cfg.learning_rate, cfg.adagrad_epsilon)
+            ops.optimizer_step_ids_(cfg.optimizer, tables, self._segs, lr, cfg.adagrad_epsilon)
             return
         if self.fuse_optimizer:      # sparse update of every table + dense update of every tower segment: one launch
-            ops.optimizer_step_(cfg.optimizer, self._opt_tables, self._segs, cfg.learning_rate, cfg.adagrad_epsilon)
+            ops.optimizer_step_(cfg.optimizer, self._opt_tables, self._segs, lr, cfg.adagrad_epsilon)
             return
-        ops.dense_update_(self._segs, cfg.optimizer, cfg.learning_rate, cfg.adagrad_epsilon)
-        ops.sparse_update2_(cfg.optimizer, *self._opt_tables[0], *self._opt_tables[1], cfg.learning_rate, cfg.adagrad_epsilon)
+        ops.dense_update_(self._segs, cfg.optimizer, lr, cfg.adagrad_epsilon)
+        ops.sparse_update2_(cfg.optimizer, *self._opt_tables[0], *self._opt_tables[1], lr, cfg.adagrad_epsilon)
         if self.cat_table is not None:
-            self.tables["cat"].apply(cfg, self.item_tower.demb, self.adam_step)
+            self.tables["cat"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
 
     def step(self, user_ids: torch.Tensor, item_ids: torch.Tensor, **loss_kw) -> torch.Tensor:
         """One train step; returns the (device, unsynchronised) retrieval loss (SUM over the batch).
@@ -1587,11 +1705,14 @@ class TwoTowerTrainer:
         if shape_ok:
             self._poll_skew(ids, rows)
         fused_sort = shape_ok and not self._skewed()
+        clip = self.cfg.global_clipnorm > 0      # the clip launches sit between the backward pass and the optimizer: never composite
         if fused_sort:
-            if (self.use_composite and self.fuse_lookup and self.cfg.symmetric and not self.cfg.normalize_embeddings
+            if (not clip and self.use_composite and self.fuse_lookup and self.cfg.symmetric and not self.cfg.normalize_embeddings
                     and not self.cfg.layer_norm and not self.rating_on and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
                 return self._step_composite(ids, **loss_kw)
             loss = self.forward_backward(user_ids, item_ids, **loss_kw)
+            if clip:
+                self.clip_gradients()
             self.apply_gradients(step_ids=ids)
             return loss
         if self.plan_on_side_stream:
@@ -1603,6 +1724,8 @@ class TwoTowerTrainer:
         loss = self.forward_backward(user_ids, item_ids, **loss_kw)
         if self.plan_on_side_stream:
             main.wait_stream(self._side)
+        if clip:
+            self.clip_gradients()
         self.apply_gradients()
         return loss
 
@@ -1691,7 +1814,8 @@ class TwoTowerTrainer:
         st.dropout_seed = self.dropout_seed
         st.dropout_row0 = self.step_index * self.cfg.batch_size
         st.scorer_precision = ops.SCORER_PRECISIONS.index(self.cfg.scorer_precision)   # (may be switched between steps: bench's second line)
-        st.lr, st.eps = self.cfg.learning_rate, self.cfg.adagrad_epsilon                 # (re-read every step, like the Python sequence)
+        self._lr_step = self.step_index
+        st.lr, st.eps = self.learning_rate, self.cfg.adagrad_epsilon                     # (re-read every step, like the Python sequence)
         st.inv_temperature, st.dropout_rate = 1.0 / self.cfg.temperature, self.cfg.dropout_rate
         st.sample_weight, st.cand_prob, st.cand_ids = p(sample_weight), p(candidate_sampling_probability), p(candidate_ids)
         _lib.check(_lib.load().tt_train_step_f32(st, ops._stream()), "tt_train_step_f32")
@@ -1877,7 +2001,7 @@ class TwoTowerTrainer:
         if self.cfg.normalize_embeddings:
             self.user_tower.alloc_unit(); self.item_tower.alloc_unit()
         # the counter-based dropout stream continues where the checkpoint stopped (no replayed masks)
-        self.step_index = int(sd.get("step_index", 0))
+        self.step_index = self._lr_step = int(sd.get("step_index", 0))      # (the learning-rate schedule continues there too)
         self.dropout_seed = int(sd.get("dropout_seed", self.dropout_seed))
         # how the candidates are drawn belongs to the run, not to the model: the trainer keeps its own sampling settings (a
         # checkpoint from before they existed, or from an in-batch run, loads as before); a mixed trainer takes the frequencies
