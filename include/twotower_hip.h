@@ -49,7 +49,8 @@ const char* tt_last_error(void);
 /* sizeof of the structs below as this library was built (0 tt_train_step, 1 tt_dense_fwd_args, 2 tt_dense_bwd_args,
  * 3 tt_sparse_table_ids, 4 tt_dense_seg, 5 tt_id_buckets, 6 tt_dense_lookup, 7 tt_l2norm_fwd_args, 8 tt_l2norm_bwd_args,
  * 10 tt_adam_table, 11 tt_adam_seg, 12 tt_adam_hyper, 14 tt_dense_features_fwd_args, 15 tt_dense_features_bwd_args,
- * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args, 23 tt_clip_buffer; else -
+ * 17 tt_cross_fwd_args, 18 tt_cross_bwd_args, 21 tt_layer_norm_fwd_args, 22 tt_layer_norm_bwd_args, 23 tt_clip_buffer,
+ * 24 tt_rowwise_table; else -
  * 9, 13, 16, 19 and 20 included, which stay unassigned - -1): a binding checks its mirrors with it. */
 int64_t tt_abi_struct_bytes(int32_t which);
 
@@ -65,7 +66,8 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * tt_ivf_search_i8_f32 call, whose other launches carry the tags of the code they share: topk_select, topk_merge, ivf_bucket,
  * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
  * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32), cross_fwd, cross_bwd
- * (tt_cross_*_f32), layer_norm_fwd, layer_norm_bwd (tt_layer_norm_*_f32).
+ * (tt_cross_*_f32), layer_norm_fwd, layer_norm_bwd (tt_layer_norm_*_f32), rowwise_sparse, rowwise_finish (the two launches of
+ * tt_rowwise_adagrad_step_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -829,6 +831,53 @@ typedef struct tt_adam_hyper {
 int64_t tt_adam_workspace_bytes(int64_t n_ids, int32_t dim);
 int tt_adam_step_f32(const tt_adam_table* tables, int32_t n_tables, int32_t dim, int64_t n_ids,
                      const tt_adam_seg* segs, int32_t n_segs, const tt_adam_hyper* h, tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Row-wise Adagrad (added to v10: new symbols and one struct only, the version is unchanged; csrc/rowwise.hip) - the "exact
+ * row-wise" Adagrad of FBGEMM / TorchRec for embedding tables, with THIS project's epsilon placement: ONE accumulator float per
+ * table row, fed with the mean of the row's squared gradient.  The sparse update of up to 3 embedding tables AND the
+ * element-wise Adagrad update of every dense segment in one call.  Only the rows of this batch's ids are read or written - every
+ * other row keeps w AND its accumulator bit for bit; ids outside [0, rows) (the plan's sentinel and the padding id -1 included)
+ * are skipped.
+ * Arithmetic (f32, one rounding per operation, no contraction: __fadd_rn, __fmul_rn, __fdiv_rn, sqrtf).  For every distinct
+ * valid id u of a table:
+ *   g      = the sum of the gradient rows of u in the order of tt_sparse_{sgd,adagrad}_f32 (runs cut at global multiples of 64
+ *            sorted slots, pieces sequential, pieces added in index order): bit-identical to the g SGD, Adagrad and Adam see
+ *   q_j    = g_j * g_j
+ *   S      = sum_j q_j                       in the fixed order below
+ *   s      = S * inv_dim                     inv_dim = 1.0f / (float)dim, formed once on the host
+ *   a'[u]  = a[u] + s                        a: [rows] f32 (the caller initialises it, e.g. to Keras's 0.1)
+ *   w'[u]  = w[u] - (lr * g) / sqrt(a'[u] + eps)          eps INSIDE the root, as tt_sparse_adagrad_f32 (Keras), not
+ *                                                         FBGEMM's sqrt(a) + eps
+ * Order of S - a function of dim alone, the same in both launches: a lane group of lpr = min(32, dim/4 rounded up to a power
+ * of two) lanes owns the row; lane l holds the float4 chunks c = l, l + lpr, ... (< dim/4); it forms p_l by adding its q values
+ * one after the other, chunks in ascending c, elements in ascending order inside a chunk, the sum starting AT its first value;
+ * a lane with no chunk (dim = 96: 32 lanes, 24 chunks) has p_l = +0; then the group runs a butterfly p_l = p_l + p_{l xor off}
+ * for off = 1, 2, 4, ... < lpr, after which every lane holds the same bits: S.  (All terms are >= 0, so an idle lane's +0 is
+ * exact.)  tests/rowwise_check.py restates exactly this in NumPy f32.
+ * Dense segments: the existing element-wise Adagrad of tt_dense_update_f32 (opt = TT_OPT_ADAGRAD, apply = 1; `accum` non-NULL;
+ * grad_out, when given, receives the summed gradient as there): bit-identical to it.
+ * Consumes tt_sparse_plan / tt_sparse_plan_batched outputs (every table: the same dim and n_ids).  Row order[j] of grads is the
+ * gradient of sorted slot j; grads need not have n_ids rows.  `tables` and `segs` are HOST data.  n_tables in 0..3 (0: dense
+ * only), n_segs in 0..TT_MAX_DENSE_SEGS (0: sparse only); n_ids == 0 with n_segs == 0 is a no-op.  Null pointers, dim % 4 != 0,
+ * rows <= 0, eps <= 0, a non-finite lr, a table or grads not 16-byte aligned, a workspace not 256-byte aligned:
+ * TT_ERR_INVALID_ARG before any launch.  dim > 512 (more than 4 float4 chunks per lane): TT_ERR_UNSUPPORTED before any launch.
+ * Two stream-ordered launches and no communication inside either (no tickets, no wait between workgroups, no atomics): the
+ * first sums every piece and reduces and updates the runs that lie inside one 64-slot block; the second finishes the runs that
+ * cross a block boundary from the piece sums the first stored in `workspace` and carries the dense segments as extra workgroups.
+ * workspace: tt_rowwise_adagrad_workspace_bytes(n_ids, dim) bytes PER TABLE (0 for n_ids == 0), 256-byte aligned; needs NO
+ * initialisation (the second launch reads only what the first wrote in the same call).                              */
+typedef struct tt_rowwise_table {
+  float* table;                          /* [rows, dim] parameters                  */
+  float* row_accum;                      /* [rows] one accumulator per row          */
+  int64_t rows;
+  const float* grads;                    /* per-position gradient rows; row order[j] belongs to sorted slot j */
+  const int64_t* sorted_ids; const int32_t* order;   /* tt_sparse_plan outputs      */
+  void* workspace;                       /* tt_rowwise_adagrad_workspace_bytes(n_ids, dim) */
+} tt_rowwise_table;
+int64_t tt_rowwise_adagrad_workspace_bytes(int64_t n_ids, int32_t dim);
+int tt_rowwise_adagrad_step_f32(const tt_rowwise_table* tables, int32_t n_tables, int32_t dim, int64_t n_ids,
+                                const tt_dense_seg* segs, int32_t n_segs, float lr, float eps, tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * The WHOLE train step as one call (ABI v8): what `train-model` (pyproject.toml:67, src/training/train.py - declared,

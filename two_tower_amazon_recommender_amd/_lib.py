@@ -112,6 +112,12 @@ class AdamHyper(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int64)]
 
 
+class RowwiseTable(C.Structure):
+    """Mirror of ``tt_rowwise_table`` (one embedding table of ``tt_rowwise_adagrad_step_f32``)."""
+    _fields_ = [("table", C.c_void_p), ("row_accum", C.c_void_p), ("rows", C.c_int64), ("grads", C.c_void_p),
+                ("sorted_ids", C.c_void_p), ("order", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class DenseFeaturesFwdArgs(C.Structure):
     """Mirror of ``tt_dense_features_fwd_args`` (one problem of ``tt_dense_features_fwd_f32``)."""
     _fields_ = [("feat", C.c_void_p), ("feat_rows", C.c_int64), ("F", C.c_int32), ("accumulate", C.c_int32),
@@ -159,6 +165,7 @@ class ClipBuffer(C.Structure):
 
 
 CLIP_STRUCT_INDEX = {"ClipBuffer": 23}
+ROWWISE_STRUCT_INDEX = {"RowwiseTable": 24}
 # tt_abi_struct_bytes index of each mirror (9, 13, 16, 19 and 20 are unassigned: the library answers -1 for them)
 ABI_STRUCT_INDEX = {"AdamTable": 10, "AdamSeg": 11, "AdamHyper": 12}
 FEATURES_STRUCT_INDEX = {"DenseFeaturesFwdArgs": 14, "DenseFeaturesBwdArgs": 15}
@@ -259,6 +266,8 @@ SIGNATURES = {
     "tt_id_range_load": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(_i64), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, _p, _p]),
     "tt_adam_workspace_bytes": (_i64, [_i64, _i32]),
     "tt_adam_step_f32": (C.c_int, [C.POINTER(AdamTable), _i32, _i32, _i64, C.POINTER(AdamSeg), _i32, C.POINTER(AdamHyper), _p]),
+    "tt_rowwise_adagrad_workspace_bytes": (_i64, [_i64, _i32]),
+    "tt_rowwise_adagrad_step_f32": (C.c_int, [C.POINTER(RowwiseTable), _i32, _i32, _i64, C.POINTER(DenseSeg), _i32, _f, _f, _p]),
     "tt_train_step_f32": (C.c_int, [C.POINTER(TrainStep), _p]),
     "tt_retrieval_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "tt_retrieval_num_splits": (_i32, [_i64, _i64, _i32, _i32]),

@@ -163,6 +163,7 @@ extern "C" int64_t tt_abi_struct_bytes(int32_t which) {
     case 21: return (int64_t)sizeof(tt_layer_norm_fwd_args);
     case 22: return (int64_t)sizeof(tt_layer_norm_bwd_args);
     case 23: return (int64_t)sizeof(tt_clip_buffer);
+    case 24: return (int64_t)sizeof(tt_rowwise_table);
     default: return -1;
   }
 }

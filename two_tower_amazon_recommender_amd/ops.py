@@ -497,6 +497,7 @@ class SparsePlan:
         self.order = torch.empty(n_ids, dtype=torch.int32, device=device)
         self._apply_ws = None
         self._adam_ws = None
+        self._rowwise_ws = None
 
     @property
     def grad_order(self) -> torch.Tensor:
@@ -514,6 +515,13 @@ class SparsePlan:
         if self._adam_ws is None or self._adam_ws.numel() < need:
             self._adam_ws = torch.empty(need, dtype=torch.uint8, device=self.sorted_ids.device)
         return self._adam_ws
+
+    def rowwise_ws(self, dim: int) -> torch.Tensor:
+        """Piece-sum workspace of ``rowwise_adagrad_step_`` for rows of ``dim`` floats (allocated once; never initialised)."""
+        need = max(rowwise_adagrad_workspace_bytes(self.n_ids, dim), 256)
+        if self._rowwise_ws is None or self._rowwise_ws.numel() < need:
+            self._rowwise_ws = torch.empty(need, dtype=torch.uint8, device=self.sorted_ids.device)
+        return self._rowwise_ws
 
     def apply_ws(self, dim: int) -> torch.Tensor:
         """Piece-sum workspace of the apply kernels for rows of ``dim`` floats (allocated once)."""
@@ -1061,6 +1069,38 @@ def adam_step_(tables, segs, hyper: AdamHyper):
     h = hyper.struct()
     _lib.check(_lib.load().tt_adam_step_f32(arr_t, len(tables), dim, n_ids, arr_s, len(segs), C.byref(h), _stream()),
                "tt_adam_step_f32")
+
+
+# ----------------------------------------------------------------------------- row-wise Adagrad
+def rowwise_adagrad_workspace_bytes(n_ids: int, dim: int) -> int:
+    """Piece-sum workspace of ``rowwise_adagrad_step_`` per table: 256-byte aligned, needs no initialisation; 0 for no ids."""
+    return int(_lib.load().tt_rowwise_adagrad_workspace_bytes(n_ids, dim))
+
+
+def rowwise_adagrad_step_(tables, segs, lr: float, eps: float = 1e-7):
+    """One row-wise Adagrad step (``tt_rowwise_adagrad_step_f32``: two launches): ``tables`` = [(table, row_accum, grads, plan),
+    ...] - up to 3 embedding tables of one width whose plans (``sparse_plan_batched`` / ``SparsePlan.run``) hold the same number
+    of ids, each with ONE accumulator float per row (``row_accum`` [rows]) - and ``segs`` = the ``make_dense_seg`` descriptions of
+    the dense parameters (with their element-wise Adagrad accumulators), which take the plain Adagrad update.  Either list may
+    be empty.  Only the rows of the plans' ids change, their accumulators included."""
+    for table, row_accum, grads, _ in tables:
+        _chk(table, torch.float32, "table", 2)
+        _chk(row_accum, torch.float32, "row_accum", 1)
+        _chk(grads, torch.float32, "grads", 2)
+    dim, n_ids = (tables[0][0].shape[1], tables[0][3].n_ids) if tables else (4, 0)
+    arr_t = (_lib.RowwiseTable * max(len(tables), 1))()
+    for i, (table, row_accum, grads, plan) in enumerate(tables):
+        if row_accum.numel() != table.shape[0]:
+            raise RuntimeError(f"rowwise_adagrad_step_: row_accum must be [rows] = [{table.shape[0]}] (one float per table row), "
+                               f"got {tuple(row_accum.shape)}")
+        if table.shape[1] != dim or plan.n_ids != n_ids or tuple(grads.shape) != (plan.grad_rows, dim):
+            raise RuntimeError("rowwise_adagrad_step_: every table needs the same dim, the same number of ids and [n_ids, dim] "
+                               "gradients ([n_bags, dim] with a BagPlan)")
+        arr_t[i] = _lib.RowwiseTable(_p(table), _p(row_accum), table.shape[0], _p(grads), _p(plan.sorted_ids), _p(plan.grad_order),
+                                     _p(plan.rowwise_ws(dim)))
+    arr_s = (_lib.DenseSeg * max(len(segs), 1))(*segs)
+    _lib.check(_lib.load().tt_rowwise_adagrad_step_f32(arr_t, len(tables), dim, n_ids, arr_s, len(segs), float(lr), float(eps),
+                                                       _stream()), "tt_rowwise_adagrad_step_f32")
 
 
 # ----------------------------------------------------------------------------- L2-normalised tower outputs

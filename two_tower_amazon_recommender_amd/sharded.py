@@ -421,6 +421,10 @@ class ShardedTwoTowerTrainer:
             # owner-side lazy Adam (moments sharded with the rows, one global step counter) is not built
             raise NotImplementedError("optimizer='adam' is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "optimizer", None) == "rowwise_adagrad":
+            # owner-side row-wise Adagrad (one accumulator float sharded with every row) is not built
+            raise NotImplementedError("optimizer='rowwise_adagrad' is not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "n_title_buckets", 0):
             # the bag table would have to be sharded and its pooled rows exchanged like the other tables' rows
             raise NotImplementedError("the title feature (n_title_buckets > 0) is not implemented for the row-sharded trainer "

@@ -15,6 +15,7 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
     torch.ops.twotower.sparse_adam_(table, exp_avg, exp_avg_sq, grads, ids, step, lr, 0.9, 0.999, 1e-7)
+    torch.ops.twotower.sparse_rowwise_adagrad_(table, row_accum, grads, ids, lr, eps)   # row_accum: [rows], one float per row
 
 What the reference would have run through TensorFlow / TFRS for these (``/root/reference/pyproject.toml:22,24``;
 settings ``configs/data_config.yaml:54-71``; the task object's call signature: SURVEY.md Appendix A).
@@ -768,6 +769,15 @@ def sparse_adam_(table: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, grads: Tens
     ops.adam_step_([(table, exp_avg, exp_avg_sq, grads.contiguous(), plan)], [], ops.AdamHyper(lr, beta1, beta2, eps, step))
 
 
+@torch.library.custom_op(f"{NS}::sparse_rowwise_adagrad_", mutates_args=("table", "row_accum"), device_types="cuda")
+def sparse_rowwise_adagrad_(table: Tensor, row_accum: Tensor, grads: Tensor, ids: Tensor, lr: float, eps: float) -> None:
+    """Row-wise Adagrad (FBGEMM / TorchRec's "exact row-wise" Adagrad, Keras's epsilon placement) on the rows ``ids`` of ``table``
+    (in place; duplicates summed first): ``row_accum`` [rows] holds ONE accumulator per row and grows by the mean of the row's
+    squared gradient.  One sort launch + two launches."""
+    plan = _plan(ids.numel(), ids.device).run(ids.contiguous(), table.shape[0])
+    ops.rowwise_adagrad_step_([(table, row_accum, grads.contiguous(), plan)], [], lr, eps)
+
+
 # --------------------------------------------------------------------------------------------- global-norm gradient clipping
 @torch.library.custom_op(f"{NS}::clip_by_global_norm_", mutates_args=("tensors",), device_types="cuda")
 def clip_by_global_norm_(tensors: List[Tensor], clip_norm: float) -> Tensor:
@@ -788,4 +798,4 @@ def _(tensors, clip_norm):
 
 
 OPS = ("clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")

@@ -56,9 +56,11 @@ def parse(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N synthetic interactions instead of --data")
     ap.add_argument("--synthetic-users", type=int, default=10_000)
     ap.add_argument("--synthetic-items", type=int, default=10_000)
-    ap.add_argument("--optimizer", default="adagrad", choices=["sgd", "adagrad", "adam"],
+    ap.add_argument("--optimizer", default="adagrad", choices=["sgd", "adagrad", "adam", "rowwise_adagrad"],
                     help="adam = lazy Adam (only the rows of a batch's ids are touched): what model.training.learning_rate 0.001 "
-                         "is the Keras default of; single-GPU trainer only")
+                         "is the Keras default of; rowwise_adagrad = one Adagrad accumulator per embedding row (the mean of the "
+                         "row's squared gradient; rows instead of rows x dim floats of state), element-wise Adagrad on the dense "
+                         "parameters; both: single-GPU trainer only")
     ap.add_argument("--adam-beta1", type=float, default=0.9)
     ap.add_argument("--adam-beta2", type=float, default=0.999)
     ap.add_argument("--adam-epsilon", type=float, default=1e-7)
@@ -220,6 +222,8 @@ def main(argv=None) -> int:
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
     if distributed and args.optimizer == "adam":
         raise NotImplementedError("optimizer 'adam' is not implemented for the row-sharded (--distributed) trainer")
+    if distributed and args.optimizer == "rowwise_adagrad":
+        raise NotImplementedError("optimizer 'rowwise_adagrad' is not implemented for the row-sharded (--distributed) trainer")
     if distributed:
         import torch.distributed as dist
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))

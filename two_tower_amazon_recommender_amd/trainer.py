@@ -6,7 +6,8 @@ This is the explicit (no autograd) engine that ``train.py`` and ``bench.py`` dri
         ──► fused scorer + softmax loss (pass 1: loss + dq, combine, pass 2: dc, slab reduction: 4 launches)
         ──► tower bwd (dx + dw + db per layer: 2 launches)
         ──► optimizer (sort of the ids, duplicate sums, sparse SGD/Adagrad of all tables, dense update: 1 launch;
-                       lazy Adam: sort plan + two launches, ``ops.adam_step_``)
+                       lazy Adam: sort plan + two launches, ``ops.adam_step_``; row-wise Adagrad: sort plan + two
+                       launches, ``ops.rowwise_adagrad_step_``)
 
 All buffers are allocated once for a fixed batch size; ``step`` enqueues those 8 launches (cfg3; one more per extra tower
 layer) through ONE C call (``tt_train_step_f32``) on the current stream and never synchronises (it can be captured in a
@@ -61,6 +62,9 @@ class TwoTowerConfig:
     optimizer: str = "sgd"                         # unspecified by the reference; north_star: SGD / Adagrad; "adam" = lazy Adam
     adagrad_initial_accumulator: float = 0.1       # Keras 2.15 default
     adagrad_epsilon: float = 1e-7                  # Keras 2.15 default
+    # optimizer="rowwise_adagrad": FBGEMM / TorchRec's exact row-wise Adagrad on the embedding tables - ONE accumulator float per
+    # row, fed with the mean of the row's squared gradient (rows floats of state instead of rows x dim) - and the element-wise
+    # Adagrad above on the dense parameters; both adagrad_* settings apply (epsilon inside the root, as "adagrad")
     # optimizer="adam": lazy Adam (TF-Addons LazyAdam / torch.optim.SparseAdam) - only the rows of the batch's ids are touched,
     # the bias correction comes from the global step; Keras 2.15 Adam's defaults (its learning_rate default is :63's 0.001)
     adam_beta1: float = 0.9
@@ -192,8 +196,8 @@ class TwoTowerConfig:
         return sum(s.group not in skip for s in dense_layout(self).segments)
 
     def validate(self):
-        if self.optimizer not in ("sgd", "adagrad", "adam"):
-            raise ValueError(f"optimizer must be 'sgd', 'adagrad' or 'adam', got {self.optimizer!r}")
+        if self.optimizer not in ("sgd", "adagrad", "adam", "rowwise_adagrad"):
+            raise ValueError(f"optimizer must be 'sgd', 'adagrad', 'adam' or 'rowwise_adagrad', got {self.optimizer!r}")
         if not 0.0 <= self.adam_beta1 < 1.0:
             raise ValueError("adam_beta1 must be in [0, 1)")
         if not 0.0 <= self.adam_beta2 < 1.0:
@@ -802,9 +806,10 @@ def towers_backward(towers, dropout_rate: float = 0.0, lookups=None, on_embeddin
 @dataclass
 class EmbeddingTable:
     """One embedding table of the trainer with everything that belongs to it: the checkpoint prefix (``user`` -> the keys
-    ``user_table``, ``user_accum``, ``user_m``, ``user_v``), the tensor id of the synthetic initialiser, the optimizer state of the
-    configured optimizer (Adagrad: ``accum``; lazy Adam: ``m``, ``v``; else None), the sort plan of its updates, and ``extra`` -
-    the tensors checkpointed beside it under their own keys (the title / history token rows)."""
+    ``user_table``, ``user_accum``, ``user_m``, ``user_v``, ``user_row_accum``), the tensor id of the synthetic initialiser, the
+    optimizer state of the configured optimizer (Adagrad: ``accum``; lazy Adam: ``m``, ``v``; row-wise Adagrad: ``row_accum``
+    [rows], and ``accum`` stays None so that no kernel that expects [rows, dim] can be handed it; else None), the sort plan of its
+    updates, and ``extra`` - the tensors checkpointed beside it under their own keys (the title / history token rows)."""
     prefix: str
     tensor_id: int
     table: torch.Tensor
@@ -813,17 +818,21 @@ class EmbeddingTable:
     v: torch.Tensor | None = None
     plan: object = None
     extra: dict = field(default_factory=dict)
+    row_accum: torch.Tensor | None = None
 
     @classmethod
     def new(cls, cfg: TwoTowerConfig, dev, prefix: str, tensor_id: int, rows: int, plan, extra=None) -> "EmbeddingTable":
         table = torch.empty(rows, cfg.embedding_dim, device=dev)
         accum = torch.full_like(table, cfg.adagrad_initial_accumulator) if cfg.optimizer == "adagrad" else None
         m, v = (torch.zeros_like(table), torch.zeros_like(table)) if cfg.optimizer == "adam" else (None, None)
-        return cls(prefix, tensor_id, table, accum, m, v, plan, dict(extra or {}))
+        row_accum = None
+        if cfg.optimizer == "rowwise_adagrad":
+            row_accum = torch.full((rows,), cfg.adagrad_initial_accumulator, device=dev)
+        return cls(prefix, tensor_id, table, accum, m, v, plan, dict(extra or {}), row_accum)
 
     def state(self) -> dict:
         """Checkpoint key -> tensor."""
-        named = {"table": self.table, "accum": self.accum, "m": self.m, "v": self.v}
+        named = {"table": self.table, "accum": self.accum, "m": self.m, "v": self.v, "row_accum": self.row_accum}
         return {**{f"{self.prefix}_{k}": t for k, t in named.items() if t is not None}, **self.extra}
 
     def init_synthetic(self, cfg: TwoTowerConfig, seed: int):
@@ -833,15 +842,20 @@ class EmbeddingTable:
             self.accum.fill_(cfg.adagrad_initial_accumulator)
         if self.m is not None:
             self.m.zero_(), self.v.zero_()
+        if self.row_accum is not None:
+            self.row_accum.fill_(cfg.adagrad_initial_accumulator)
 
     def apply(self, cfg: TwoTowerConfig, grads, adam_step: int, adam_segs=(), lr: float | None = None):
         """The configured optimizer's update from this table's sort plan (which has run; a ``BagPlan`` after its ``backward``:
-        ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same lazy-Adam call.  ``lr``: the
-        step's rate (the trainer's ``learning_rate``; default: the configured one)."""
+        ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same lazy-Adam call (row-wise
+        Adagrad: the Adagrad segments that ride in its call).  ``lr``: the step's rate (the trainer's ``learning_rate``; default:
+        the configured one)."""
         lr = cfg.learning_rate if lr is None else lr
         if cfg.optimizer == "adam":
             ops.adam_step_([(self.table, self.m, self.v, grads, self.plan)], list(adam_segs),
                            ops.AdamHyper(lr, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
+        elif cfg.optimizer == "rowwise_adagrad":
+            ops.rowwise_adagrad_step_([(self.table, self.row_accum, grads, self.plan)], list(adam_segs), lr, cfg.adagrad_epsilon)
         elif cfg.optimizer == "sgd":
             ops.sparse_sgd_(self.table, grads, self.plan, lr)
         else:
@@ -904,6 +918,8 @@ _CHECKPOINT_CHECKS = (
 _GRAPH_REFUSALS = (
     (lambda c: c.dropout_rate > 0.0, "dropout: the per-step counter is a kernel argument"),
     (lambda c: c.optimizer == "adam", "optimizer='adam': the global step, and so the bias-corrected step size, is a kernel argument"),
+    (lambda c: c.optimizer == "rowwise_adagrad", "optimizer='rowwise_adagrad' is not implemented: the warm-up step's update of the "
+     "row accumulators is not undone"),
     (lambda c: c.candidate_sampling == "mixed", "candidate_sampling='mixed' is not implemented: the sampler's counter is a kernel "
      "argument and the step is the Python sequence of per-tower launches"),
     (lambda c: c.n_title_buckets, "the title feature (n_title_buckets > 0) is not implemented: the warm-up step's update of the "
@@ -933,7 +949,8 @@ class TwoTowerTrainer:
         # batch's items followed by the sampled ones (bi rows); the user side keeps b
         self.mixed = cfg.candidate_sampling == "mixed"
         bi = b + (cfg.n_sampled_negatives if self.mixed else 0)
-        adagrad, adam = cfg.optimizer == "adagrad", cfg.optimizer == "adam"
+        # (row-wise Adagrad: the dense parameters keep the element-wise Adagrad accumulator, exactly as under "adagrad")
+        adagrad, adam = cfg.optimizer in ("adagrad", "rowwise_adagrad"), cfg.optimizer == "adam"
         # where every dense parameter sits and which optimizer segment covers it: dense_layout, the one place that knows
         self.layout = lay = dense_layout(cfg)
         self.rating_on = cfg.rating_weight > 0
@@ -1019,6 +1036,11 @@ class TwoTowerTrainer:
         trio = [(user, ut.demb), (item, it.demb)] + ([(cat, it.demb)] if cat is not None else [])
         self._opt_tables = [(t.table, t.accum, g, t.plan) for t, g in trio]
         self._adam_tables = [(t.table, t.m, t.v, g, t.plan) for t, g in trio]
+        # row-wise Adagrad: the user and the item table in ONE call (the category table goes through EmbeddingTable.apply)
+        self._rowwise_tables = [(t.table, t.row_accum, g, t.plan) for t, g in trio[:2]]
+        for t in (user, item, cat, title, history):
+            if t is not None:
+                setattr(self, f"{t.prefix}_row_accum", t.row_accum)
         # numeric side features, per side: the fixed feature matrix with its normalisation (zeros / mean 0 / inv_std 1 until the
         # setter ran: z = 0, nothing is added), the projection kernel (a view of dense_flat), the step's normalised rows (kept for
         # the backward launch) and the gradient slabs the dense optimizer segment sums
@@ -1614,10 +1636,13 @@ class TwoTowerTrainer:
         """The two tables' plans hold different id counts (B and B + N): one sparse launch sequence per table.  The sampled
         items' rows are trained like the positives' (their gradient rows are demb[B:])."""
         cfg, adam, lr = self.cfg, self.cfg.optimizer == "adam", self.learning_rate
-        if not adam:
+        rowwise = cfg.optimizer == "rowwise_adagrad"
+        if not adam and not rowwise:
             ops.dense_update_(self._segs, cfg.optimizer, lr, cfg.adagrad_epsilon)
-        # (lazy Adam: the user table with every dense segment in one call, then the item table - the same step t)
-        self.tables["user"].apply(cfg, self.user_tower.demb, self.adam_step, self._adam_segs if adam else (), lr=lr)
+        # (lazy Adam: the user table with every dense segment in one call, then the item table - the same step t; row-wise
+        # Adagrad likewise, with the Adagrad segments)
+        riding = self._adam_segs if adam else self._segs if rowwise else ()
+        self.tables["user"].apply(cfg, self.user_tower.demb, self.adam_step, riding, lr=lr)
         self.tables["item"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
         if adam:
             self.adam_step += 1
@@ -1665,6 +1690,11 @@ class TwoTowerTrainer:
                                                                              cfg.adam_epsilon, self.adam_step))
             self.adam_step += 1
             return
+        if cfg.optimizer == "rowwise_adagrad":  # user + item table and every dense segment in ONE call, from the sort plans
+            ops.rowwise_adagrad_step_(self._rowwise_tables, self._segs, lr, cfg.adagrad_epsilon)
+            if self.cat_table is not None:
+                self.tables["cat"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
+            return
         if step_ids is not None:     # sort + sparse update of every table + dense update: ONE launch, straight from the raw ids
             tables = [(table, accum, grads, ids, plan) for (table, accum, grads, plan), ids in zip(self._opt_tables, step_ids)]
             ops.optimizer_step_ids_(cfg.optimizer, tables, self._segs, lr, cfg.adagrad_epsilon)
@@ -1699,8 +1729,8 @@ class TwoTowerTrainer:
             plans.append(self.cat_plan); ids.append(loss_kw["category_ids"]); rows.append(self.cfg.n_category_buckets)
         # fuse_sort: no plan launch at all - the optimizer launch's workgroups sort the ids of their own row range in LDS
         # and update exactly those rows (tt_optimizer_step_ids_f32; lists up to 65536 ids) - unless the batches are skewed
-        # (lazy Adam always takes the sort plan: it has no composite call, no one-launch form and so no skew probe)
-        shape_ok = (self.cfg.optimizer != "adam" and self.fuse_sort and self.fuse_optimizer
+        # (lazy Adam and row-wise Adagrad always take the sort plan: no composite call, no one-launch form and so no skew probe)
+        shape_ok = (self.cfg.optimizer not in ("adam", "rowwise_adagrad") and self.fuse_sort and self.fuse_optimizer
                     and user_ids.numel() <= ops.optimizer_ids_max_ids() and (self.cat_table is None) == (len(ids) == 2))
         if shape_ok:
             self._poll_skew(ids, rows)
@@ -1976,7 +2006,7 @@ class TwoTowerTrainer:
             sd.update(rec.state())
         if getattr(self, "item_freq", None) is not None:     # mixed negative sampling: the correction (and the unigram sampler) is rebuilt from it
             sd["item_freq"] = self.item_freq
-        if self.cfg.optimizer == "adagrad":
+        if self.cfg.optimizer in ("adagrad", "rowwise_adagrad"):
             sd["dense_accum"] = self.dense_accum
         if self.cfg.optimizer == "adam":
             sd.update(dense_m=self.dense_m, dense_v=self.dense_v, adam_step=self.adam_step)
@@ -2007,7 +2037,7 @@ class TwoTowerTrainer:
         # checkpoint from before they existed, or from an in-batch run, loads as before); a mixed trainer takes the frequencies
         if self.mixed and sd.get("item_freq") is not None:
             self.set_item_frequencies(sd["item_freq"])
-        if self.cfg.optimizer == "adagrad":
+        if self.cfg.optimizer in ("adagrad", "rowwise_adagrad"):
             self.dense_accum.copy_(sd["dense_accum"])
         if self.cfg.optimizer == "adam":
             self.dense_m.copy_(sd["dense_m"]); self.dense_v.copy_(sd["dense_v"])
