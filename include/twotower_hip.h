@@ -67,7 +67,7 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
  * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32), cross_fwd, cross_bwd
  * (tt_cross_*_f32), layer_norm_fwd, layer_norm_bwd (tt_layer_norm_*_f32), rowwise_sparse, rowwise_finish (the two launches of
- * tt_rowwise_adagrad_step_f32).
+ * tt_rowwise_adagrad_step_f32), freq_update, freq_estimate (the two launches of tt_frequency_estimate_i64).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -252,6 +252,39 @@ int tt_sample_candidates_i64(const int64_t* pos_ids, int64_t n_pos, int64_t n_it
                              const float* alias_thr, const int32_t* alias_idx, const float* item_freq,
                              const float* sampler_prob, uint64_t seed, uint64_t tensor_id, uint64_t start,
                              int64_t* cand_ids, float* cand_prob, int32_t* oob_flag, tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Streaming item-frequency estimation (added to v10: a new symbol only, the version is unchanged) - Yi et al. 2019, Algorithms 2
+ * and 3 (csrc/freq.hip): the sampling probability of the logQ correction from a hashed sketch of "steps since this item was last
+ * a positive", updated by every batch - no offline count of the training split.
+ * State: sketch, int64 [hashes, slots], zero-initialised.  A slot is ONE 64-bit word: the low 32 bits `last` (int32, the 1-based
+ * step at which the slot was last hit, 0 = never), the high 32 bits the bits of `delta` (f32, the estimated gap in steps).
+ * Hash: the slot of id under hash h is ((x >> 32) * slots) >> 32 with x = splitmix64 element (uint64)id of the stream
+ * (seed, tensor_id + h) - the generator and the bucket rule of tt_fill_ids_i64 - so slots is any integer in 1..2^32.
+ * One call, over ids int64 [n] at the 1-based `step`, behaves as if the following ran in order:
+ *   1. update: every (h, slot) hit by an in-range id among ids[0 : n_update] (the step's positives) whose last != step is
+ *      updated EXACTLY ONCE, however many ids or duplicates hit it:  gap = (float)(step - last);
+ *      delta = last == 0 ? gap : (1 - alpha) * delta + alpha * gap;  last = step.   (f32, one rounding per operation, no
+ *      contraction; 1 - alpha is formed once on the host in f32.)  A second call with the same step changes nothing.
+ *   2. estimate, for EVERY j < n, after the update: d_h = last == 0 ? (float)step : delta of the id's slot under each hash,
+ *      D = max over h (Algorithm 3: a collision can only shorten a gap, so the largest is the least contaminated); D >= 1.
+ *   3. prob[j] = 1 / D                                                       (mix == 0), or
+ *      prob[j] = (1 / D + (float)N * u_id) / (float)(B + N), B = n_update, N = n - n_update                  (mix == 1):
+ *      tt_sample_candidates_i64's mixture with B * item_freq[id] replaced by the sketch's expected in-batch count 1 / D;
+ *      u_id = sampler_prob[id] (f32 [n_items]; NULL: 1.0f / (float)n_items).  mix needs 1 <= n_update < n.
+ * An id outside [0, n_items) updates nothing, gets prob 1.0 and sets *oob_flag (device int32, may be NULL).
+ * One deviation from the paper: on a slot's FIRST sighting delta is the gap itself (step), not alpha * step - the paper's zero
+ * start biases every estimate by (1 - alpha)^k, which never decays for tail items.  A property: a gap cannot be below one
+ * step, so 1 / D saturates at 1 for items that occur several times per batch.
+ * Launches: one over ids[0 : n_update] and, stream-ordered behind it, one over the rest (each only if non-empty).  Slots are
+ * read and written with single 64-bit relaxed atomic accesses, so the result does not depend on how workgroups interleave;
+ * bit-reproducible, independent of the grid.
+ * TT_ERR_INVALID_ARG before any launch: hashes outside 1..4; slots or n_items outside 1..2^32; step outside 1..2^31-1; alpha
+ * outside (0, 1]; n outside 0..2^31-1; n_update outside 0..n; mix not 0 / 1, or 1 without 1 <= n_update < n; sampler_prob
+ * without mix; a null ids / sketch / prob.  n == 0 (with mix == 0) is a no-op that returns TT_OK.                          */
+int tt_frequency_estimate_i64(const int64_t* ids, int64_t n, int64_t n_update, int64_t n_items, int64_t* sketch,
+                              int32_t hashes, int64_t slots, int64_t step, float alpha, uint64_t seed, uint64_t tensor_id,
+                              const float* sampler_prob, int32_t mix, float* prob, int32_t* oob_flag, tt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a5 — sparse optimizer on embedding rows (Keras SGD / Adagrad on IndexedSlices,

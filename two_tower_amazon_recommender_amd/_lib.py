@@ -227,6 +227,7 @@ SIGNATURES = {
     "tt_layer_norm_bwd_f32": (C.c_int, [C.POINTER(LayerNormBwdArgs), _i32, _i32, _f, _i32, _i64, _p]),
     "tt_layer_norm_num_slabs": (_i32, [_i64]),
     "tt_sample_candidates_i64": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
+    "tt_frequency_estimate_i64": (C.c_int, [_p, _i64, _i64, _i64, _p, _i32, _i64, _i64, _f, _u64, _u64, _p, _i32, _p, _p, _p]),
     "tt_route_by_owner_i64": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
     "tt_route_tables_by_owner_i64": (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "tt_scatter_rows_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _p]),

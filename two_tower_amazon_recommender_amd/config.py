@@ -6,7 +6,7 @@ import math
 
 import yaml
 
-from .trainer import LR_DECAYS, TwoTowerConfig
+from .trainer import LR_DECAYS, SAMPLING_BIAS_ESTIMATORS, TwoTowerConfig
 
 
 def load_yaml(path) -> dict:
@@ -118,6 +118,36 @@ def optimization_from_dict(doc: dict) -> dict:
     return {"global_clipnorm": float(clip), "warmup_steps": warm, "decay": decay, "decay_steps": steps, "min_ratio": float(ratio)}
 
 
+SAMPLING_BIAS_KEYS = ("estimator", "alpha", "hashes", "slots")
+
+
+def sampling_bias_from_dict(doc: dict) -> dict:
+    """{estimator, alpha, hashes, slots} of the optional ``model.retrieval.sampling_bias`` block (not in the reference's schema):
+    ``estimator`` streaming - the logQ correction from the streaming frequency estimator (Yi et al. 2019), with the moving-average
+    coefficient ``alpha`` and a sketch of ``hashes`` x ``slots`` (0: min(2 * n_items, 2^25)) - or none.  Without the block: none."""
+    block = ((doc.get("model") or {}).get("retrieval") or {}).get("sampling_bias")
+    d = TwoTowerConfig
+    if block is None:
+        block = {}
+    if not isinstance(block, dict):
+        raise ValueError("model.retrieval.sampling_bias must be a mapping {estimator, alpha, hashes, slots}")
+    unknown = sorted(set(block) - set(SAMPLING_BIAS_KEYS))
+    if unknown:
+        raise ValueError(f"model.retrieval.sampling_bias: unknown keys {unknown} (known: {list(SAMPLING_BIAS_KEYS)})")
+    est = block.get("estimator", "none")
+    est = "none" if est is None else str(est).lower()
+    if est not in SAMPLING_BIAS_ESTIMATORS:
+        raise ValueError(f"model.retrieval.sampling_bias.estimator must be one of {SAMPLING_BIAS_ESTIMATORS}, got {est!r}")
+    alpha, hashes, slots = block.get("alpha", d.freq_alpha), block.get("hashes", d.freq_hashes), block.get("slots", d.freq_slots)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < alpha <= 1.0:
+        raise ValueError(f"model.retrieval.sampling_bias.alpha must be in (0, 1], got {alpha!r}")
+    if isinstance(hashes, bool) or not isinstance(hashes, int) or not 1 <= hashes <= 4:
+        raise ValueError(f"model.retrieval.sampling_bias.hashes must be an int in 1..4, got {hashes!r}")
+    if isinstance(slots, bool) or not isinstance(slots, int) or not 0 <= slots <= 1 << 32:
+        raise ValueError(f"model.retrieval.sampling_bias.slots must be an int in 1..2^32 (0: min(2 * n_items, 2^25)), got {slots!r}")
+    return {"estimator": est, "alpha": float(alpha), "hashes": hashes, "slots": slots}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -151,7 +181,10 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     # likewise model.training.global_clipnorm and model.training.lr_schedule {warmup_steps, decay, decay_steps, min_ratio}
     # (decay_steps "auto": left 0 here - train.py, which knows the number of steps, reads the block itself and resolves it)
     opt = optimization_from_dict(doc)
+    # likewise model.retrieval.sampling_bias {estimator, alpha, hashes, slots} - the streaming frequency estimator
+    bias = sampling_bias_from_dict(doc)
     cfg = TwoTowerConfig(
+        sampling_bias_estimator=bias["estimator"], freq_alpha=bias["alpha"], freq_hashes=bias["hashes"], freq_slots=bias["slots"],
         global_clipnorm=opt["global_clipnorm"], lr_warmup_steps=opt["warmup_steps"], lr_decay=opt["decay"],
         lr_decay_steps=0 if opt["decay_steps"] == "auto" else opt["decay_steps"], lr_min_ratio=opt["min_ratio"],
         n_users=n_users, n_items=n_items, embedding_dim=int(m["embedding_dim"]), tower_dims=user_dims,

@@ -442,6 +442,65 @@ def sample_candidates(pos_ids: torch.Tensor, n_items: int, n_neg: int, out_ids: 
     return out_ids[:n], (out_prob[:n] if item_freq is not None else None)
 
 
+# ----------------------------------------------------------------------------- streaming item-frequency estimation
+MAX_FREQ_HASHES = 4
+
+
+def new_frequency_sketch(hashes: int, slots: int, device) -> torch.Tensor:
+    """A fresh sketch of the streaming frequency estimator: int64 [hashes, slots] of zeros (every slot: never hit)."""
+    hashes, slots = int(hashes), int(slots)
+    if not 1 <= hashes <= MAX_FREQ_HASHES:
+        raise ValueError(f"new_frequency_sketch: hashes must be in 1..{MAX_FREQ_HASHES}, got {hashes}")
+    if not 1 <= slots <= 1 << 32:
+        raise ValueError(f"new_frequency_sketch: slots must be in 1..2^32, got {slots}")
+    return torch.zeros(hashes, slots, dtype=torch.int64, device=device)
+
+
+def unpack_frequency_sketch(sketch: torch.Tensor):
+    """(last int32 [hashes, slots], delta f32 [hashes, slots]) of a sketch's packed slots: ``last`` = the 1-based step of the
+    slot's last hit (0 = never), ``delta`` = its estimated gap in steps.  Copies; any device."""
+    if not isinstance(sketch, torch.Tensor) or sketch.dtype != torch.int64 or sketch.dim() != 2:
+        raise RuntimeError("unpack_frequency_sketch: expected an int64 [hashes, slots] tensor")
+    halves = sketch.contiguous().view(torch.int32).reshape(sketch.shape[0], sketch.shape[1], 2)     # little-endian: low half first
+    return halves[..., 0].clone(), halves[..., 1].contiguous().view(torch.float32).clone()
+
+
+def frequency_estimate_(sketch: torch.Tensor, ids: torch.Tensor, n_update: int, step: int, alpha: float, n_items: int,
+                        out: torch.Tensor, *, seed: int, tensor_id: int, sampler_prob: torch.Tensor | None = None,
+                        mix: bool = False, oob_flag: torch.Tensor | None = None) -> torch.Tensor:
+    """The streaming frequency estimator (``tt_frequency_estimate_i64``, Yi et al. 2019): the first ``n_update`` of ``ids`` - the
+    step's positives - update ``sketch`` (``new_frequency_sketch``) IN PLACE at the 1-based ``step`` with the moving-average
+    coefficient ``alpha``, then ``out[j]`` = the estimated probability 1 / D_j of EVERY id, D_j = the largest estimated gap over
+    the sketch's hash rows.  ``mix``: ``out[j]`` = (1 / D_j + N u_j) / (B + N) with B = n_update, N = len(ids) - n_update and u_j =
+    ``sampler_prob[id]`` (None: 1 / n_items) - the candidate probability of mixed negative sampling.  ``n_update = 0`` only reads.
+    ``out`` may be longer than ``ids``; the rest is not touched.  Returns out[:len(ids)]."""
+    _chk(sketch, torch.int64, "sketch", 2)
+    _chk(ids, torch.int64, "ids", 1)
+    _chk(out, torch.float32, "out", 1)
+    n, n_update, n_items, step = ids.numel(), int(n_update), int(n_items), int(step)
+    hashes, slots = sketch.shape
+    if not 1 <= hashes <= MAX_FREQ_HASHES or slots < 1:
+        raise RuntimeError(f"frequency_estimate_: sketch must be [hashes in 1..{MAX_FREQ_HASHES}, slots >= 1], got {list(sketch.shape)}")
+    if out.numel() < n:
+        raise RuntimeError(f"frequency_estimate_: out must hold len(ids) = {n} entries, got {out.numel()}")
+    if ids.device != sketch.device or out.device != sketch.device:
+        raise RuntimeError("frequency_estimate_: sketch, ids and out must be on one device")
+    if sampler_prob is not None:
+        _chk(sampler_prob, torch.float32, "sampler_prob", 1)
+        if sampler_prob.numel() != n_items:
+            raise RuntimeError(f"frequency_estimate_: sampler_prob must have n_items = {n_items} entries, got {sampler_prob.numel()}")
+        if not mix:
+            raise ValueError("frequency_estimate_: sampler_prob is given but mix is off")
+    if oob_flag is not None:
+        _chk(oob_flag, torch.int32, "oob_flag")
+    if not (0 <= int(seed) < 1 << 64 and 0 <= int(tensor_id) < (1 << 64) - MAX_FREQ_HASHES):
+        raise ValueError("frequency_estimate_: seed and tensor_id are unsigned 64-bit counters")
+    _lib.check(_lib.load().tt_frequency_estimate_i64(_p(ids), n, n_update, n_items, _p(sketch), hashes, slots, step, float(alpha),
+                                                     int(seed), int(tensor_id), _p(sampler_prob), 1 if mix else 0, _p(out),
+                                                     _p(oob_flag), _stream()), "tt_frequency_estimate_i64")
+    return out[:n]
+
+
 # ----------------------------------------------------------------------------- sharded routing
 def route_by_owner(ids, world: int, num_rows: int, cap: int, send_ids, pos_flat, flags=None):
     _chk(ids, torch.int64, "ids", 1)

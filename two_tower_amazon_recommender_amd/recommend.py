@@ -133,6 +133,7 @@ def main(argv=None) -> int:
                          "--predict-ratings / --rank-by rating cannot be answered")
     cfg.dropout_rate = 0.0
     cfg.candidate_sampling, cfg.n_sampled_negatives = "in_batch", 0      # serving scores the whole corpus: nothing is sampled
+    cfg.sampling_bias_estimator = "none"                                  # ... and nothing is corrected: no sketch is allocated
     trainer = TwoTowerTrainer(cfg, dev)
     trainer.load_state_dict(ck)
     del ck

@@ -453,6 +453,10 @@ class ShardedTwoTowerTrainer:
             # every rank would have to draw (and route) its own negatives, and the item side of the exchange would grow by them
             raise NotImplementedError("candidate_sampling='mixed' is not implemented for the row-sharded trainer "
                                       "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "sampling_bias_estimator", "none") != "none":
+            # the sketch would have to see every rank's positives each step (an all-gather of the ids) to count one stream
+            raise NotImplementedError("the streaming frequency estimator (sampling_bias_estimator='streaming') is not implemented "
+                                      "for the row-sharded trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "global_clipnorm", 0.0) > 0:
             # the norm would have to be all-reduced over the ranks' table shards between the gradient exchange and the update
             raise NotImplementedError("gradient clipping (global_clipnorm > 0) is not implemented for the row-sharded trainer "

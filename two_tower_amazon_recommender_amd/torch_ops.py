@@ -797,5 +797,24 @@ def _(tensors, clip_norm):
     return torch.empty(2, dtype=torch.float32, device=tensors[0].device)
 
 
-OPS = ("clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
+# --------------------------------------------------------------------------------------------- streaming frequency estimation
+@torch.library.custom_op(f"{NS}::frequency_estimate_", mutates_args=("sketch",), device_types="cuda")
+def frequency_estimate_(sketch: Tensor, ids: Tensor, n_update: int, step: int, alpha: float, n_items: int, seed: int,
+                        tensor_id: int, sampler_prob: Optional[Tensor], mix: bool) -> Tensor:
+    """The streaming frequency estimator of the logQ correction (``ops.frequency_estimate_``, Yi et al. 2019): the first
+    ``n_update`` of ``ids`` update ``sketch`` (int64 [hashes, slots], ``ops.new_frequency_sketch``) IN PLACE at the 1-based
+    ``step``; returns every id's estimated probability [len(ids)] - the ``candidate_sampling_probability`` of
+    ``retrieval_loss`` (``mix``: under the mixture with ``len(ids) - n_update`` sampled negatives)."""
+    prob = torch.empty(ids.numel(), dtype=torch.float32, device=ids.device)
+    ops.frequency_estimate_(sketch, ids.contiguous(), n_update, step, alpha, n_items, prob, seed=seed, tensor_id=tensor_id,
+                            sampler_prob=None if sampler_prob is None else sampler_prob.contiguous(), mix=mix)
+    return prob
+
+
+@frequency_estimate_.register_fake
+def _(sketch, ids, n_update, step, alpha, n_items, seed, tensor_id, sampler_prob, mix):
+    return ids.new_empty((ids.shape[0],), dtype=torch.float32)
+
+
+OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")

@@ -67,6 +67,16 @@ def parse(argv=None):
     ap.add_argument("--category-buckets", type=int, default=0, metavar="N",
                     help="add the hashed category feature: the pair's category (column category / main_category / "
                          "category_encoded) hashed into N buckets, its embedding summed into the item tower input")
+    ap.add_argument("--sampling-bias-estimator", default=None, choices=["none", "streaming"],
+                    help="streaming = the logQ correction from the streaming frequency estimator (Yi et al. 2019): a hashed sketch of "
+                         "every item's gap between sightings, updated by each train batch - no count over the training split; "
+                         "replaces --correct-sampling-bias (pick one; overrides model.retrieval.sampling_bias.estimator); "
+                         "single-GPU trainer only")
+    ap.add_argument("--freq-alpha", type=float, default=None, metavar="A",
+                    help="moving-average coefficient of the estimator, in (0, 1] (default model.retrieval.sampling_bias.alpha, else 0.01)")
+    ap.add_argument("--freq-hashes", type=int, default=None, metavar="H", help="hash rows of the estimator's sketch (1..4; default 2)")
+    ap.add_argument("--freq-slots", type=int, default=None, metavar="M",
+                    help="slots per hash row (default 0: min(2 x items, 2^25))")
     ap.add_argument("--title-buckets", type=int, default=None, metavar="N",
                     help="add the pooled item-title feature: every item's title (column title) is tokenised, its first "
                          "--title-max-tokens tokens are hashed into N buckets and their embeddings pooled into the item tower "
@@ -220,6 +230,16 @@ def main(argv=None) -> int:
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
+    bias = cfgmod.sampling_bias_from_dict(doc)
+    for key, arg in (("estimator", args.sampling_bias_estimator), ("alpha", args.freq_alpha), ("hashes", args.freq_hashes),
+                     ("slots", args.freq_slots)):
+        if arg is not None:
+            bias[key] = arg
+    if bias["estimator"] == "streaming" and args.correct_sampling_bias:
+        raise SystemExit("--sampling-bias-estimator streaming and --correct-sampling-bias both turn the logQ correction on, from "
+                         "the streaming estimator and from a count over the training split: pick one")
+    if distributed and bias["estimator"] == "streaming":
+        raise NotImplementedError("the streaming frequency estimator is not implemented for the row-sharded (--distributed) trainer")
     if distributed and args.optimizer == "adam":
         raise NotImplementedError("optimizer 'adam' is not implemented for the row-sharded (--distributed) trainer")
     if distributed and args.optimizer == "rowwise_adagrad":
@@ -276,6 +296,8 @@ def main(argv=None) -> int:
         cfg.history_pooling = args.history_pooling
     if args.batch_size:
         cfg.batch_size = args.batch_size
+    cfg.sampling_bias_estimator = bias["estimator"]
+    cfg.freq_alpha, cfg.freq_hashes, cfg.freq_slots = float(bias["alpha"]), int(bias["hashes"]), int(bias["slots"])
     if args.candidate_sampling is not None:
         cfg.candidate_sampling = args.candidate_sampling
     if cfg.candidate_sampling == "mixed":

@@ -42,10 +42,12 @@ TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of
 TID_DENSE_BASE = 16
 TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
 TID_CROSS_BASE = 48                          # the cross kernels: layer l of tower t is 48 + 2 l + t (48..53)
+TID_FREQ_HASH_BASE = 56                      # the streaming frequency estimator's hash rows: row h is 56 + h (56..59)
 MAX_CROSS_LAYERS = 3
 # poolings of the user-history feature: the bag launch's three and the attention pool (csrc/history_attn.hip), history only
 HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention",)
 LR_DECAYS = ("none", "cosine", "linear", "inverse_sqrt")
+SAMPLING_BIAS_ESTIMATORS = ("none", "streaming")
 TID_DROPOUT_BASE = 64
 
 
@@ -104,6 +106,15 @@ class TwoTowerConfig:
     n_sampled_negatives: int = 0
     negative_sampler: str = "uniform"
     unigram_power: float = 0.75
+    # where the logQ correction's probabilities come from.  "none": from the caller (candidate_sampling_probability / mixed:
+    # ``set_item_frequencies``), as before.  "streaming": from the streaming frequency estimator of Yi et al. 2019 (csrc/freq.hip) -
+    # a sketch of freq_hashes hash rows x freq_slots slots (0: min(2 * n_items, 2^25)) of "steps since this item was last a
+    # positive", updated by every train batch with the moving-average coefficient freq_alpha; the trainer then applies the
+    # correction by itself, in-batch and mixed.  Single-GPU trainer, no graph capture.
+    sampling_bias_estimator: str = "none"
+    freq_alpha: float = 0.01
+    freq_hashes: int = 2
+    freq_slots: int = 0
     # rating-prediction head (tfrs.tasks.Ranking beside tfrs.tasks.Retrieval): rating_weight > 0 adds one hidden ReLU layer of
     # rating_hidden units (a multiple of 32 in 32..256) over the pair's two tower outputs - the vectors the scorer reads - and a
     # scalar output trained with MSE on the interaction's rating: total = retrieval + rating_weight * L_r, L_r = mean over the
@@ -170,6 +181,11 @@ class TwoTowerConfig:
         if self.lr_decay == "inverse_sqrt":
             return peak * max(m, math.sqrt(max(warm, 1) / (s + 1)))
         return peak
+
+    @property
+    def freq_slot_count(self) -> int:
+        """Slots per hash row of the frequency sketch: freq_slots, or min(2 * n_items, 2^25) when that is 0."""
+        return int(self.freq_slots) if self.freq_slots else min(2 * int(self.n_items), 1 << 25)
 
     @property
     def user_dims(self) -> list:
@@ -261,6 +277,17 @@ class TwoTowerConfig:
             raise ValueError("n_sampled_negatives must be 0 with candidate_sampling='in_batch'")
         if not (self.unigram_power >= 0.0 and math.isfinite(self.unigram_power)):
             raise ValueError("unigram_power must be a finite number >= 0")
+        if self.sampling_bias_estimator not in SAMPLING_BIAS_ESTIMATORS:
+            raise ValueError(f"sampling_bias_estimator must be one of {SAMPLING_BIAS_ESTIMATORS}, got {self.sampling_bias_estimator!r}")
+        a = self.freq_alpha
+        if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 < a <= 1.0:
+            raise ValueError("freq_alpha must be in (0, 1]")
+        fh = self.freq_hashes
+        if isinstance(fh, bool) or not isinstance(fh, int) or not 1 <= fh <= ops.MAX_FREQ_HASHES:
+            raise ValueError(f"freq_hashes must be an int in 1..{ops.MAX_FREQ_HASHES}")
+        fs = self.freq_slots
+        if isinstance(fs, bool) or not isinstance(fs, int) or not 0 <= fs <= 1 << 32:
+            raise ValueError("freq_slots must be an int in 1..2^32, or 0 for min(2 * n_items, 2^25)")
         if isinstance(self.rating_weight, bool) or not isinstance(self.rating_weight, (int, float)) \
                 or not (self.rating_weight >= 0.0 and math.isfinite(self.rating_weight)):
             raise ValueError("rating_weight must be a finite number >= 0 (0: no rating head)")
@@ -922,6 +949,8 @@ _GRAPH_REFUSALS = (
      "row accumulators is not undone"),
     (lambda c: c.candidate_sampling == "mixed", "candidate_sampling='mixed' is not implemented: the sampler's counter is a kernel "
      "argument and the step is the Python sequence of per-tower launches"),
+    (lambda c: c.sampling_bias_estimator == "streaming", "the streaming frequency estimator (sampling_bias_estimator='streaming') "
+     "is not implemented: the step number is a launch argument"),
     (lambda c: c.n_title_buckets, "the title feature (n_title_buckets > 0) is not implemented: the warm-up step's update of the "
      "title table is not undone"),
     (lambda c: c.user_history_len, "the user-history feature (user_history_len > 0) is not implemented: the warm-up step's update "
@@ -981,6 +1010,12 @@ class TwoTowerTrainer:
         self.cand_ids = torch.empty(bi, dtype=torch.int64, device=dev) if self.mixed else None
         self.cand_prob = torch.empty(bi, device=dev) if self.mixed else None
         self.item_freq = self.sampler_prob = self.alias = None
+        # streaming frequency estimator: the sketch (optimizer-like state: checkpointed) and the in-batch candidates'
+        # estimated probabilities, which go to the scorer as cand_prob (mixed: the estimator overwrites ``cand_prob``)
+        self.freq_on = cfg.sampling_bias_estimator == "streaming"
+        self.freq_sketch = ops.new_frequency_sketch(cfg.freq_hashes, cfg.freq_slot_count, dev) if self.freq_on else None
+        self.freq_prob = torch.empty(b, device=dev) if self.freq_on else None
+        self._freq_step = -1                     # the step (0-based) whose estimator launch has run
         # the embedding tables, one record each (EmbeddingTable: table, optimizer state, sort plan); a table that is off is None
         user = EmbeddingTable.new(cfg, dev, "user", TID_USER_TABLE, cfg.n_users, ops.SparsePlan(b, dev))
         item = EmbeddingTable.new(cfg, dev, "item", TID_ITEM_TABLE, cfg.n_items, ops.SparsePlan(bi, dev))
@@ -1480,6 +1515,8 @@ class TwoTowerTrainer:
                                  "candidate_sampling_probability (set_item_frequencies) and category_ids cannot be passed")
             return self._forward_backward_mixed(user_ids, item_ids, sample_weight, ratings=ratings)
         self._check_categories(category_ids)
+        if self.freq_on and not (candidate_sampling_probability is self.freq_prob and self._freq_step == self.step_index):
+            candidate_sampling_probability = self._update_frequencies(item_ids, candidate_sampling_probability)   # (step() has not)
         lks = self._lookups(user_ids, item_ids, category_ids)
         if lks is None:
             self._item_inputs(user_ids, item_ids, category_ids, train=True)
@@ -1568,12 +1605,56 @@ class TwoTowerTrainer:
         unigram = cfg.negative_sampler == "unigram"
         if unigram and self.alias is None:
             raise ValueError("negative_sampler='unigram' needs the item frequencies: call set_item_frequencies first")
+        counted = not self.freq_on           # the correction from set_item_frequencies' vector (streaming: from the sketch, below)
         ops.sample_candidates(item_ids, cfg.n_items, cfg.n_sampled_negatives, self.cand_ids, self.cand_prob,
                               sampler="alias" if unigram else "uniform", alias=self.alias if unigram else None,
-                              item_freq=self.item_freq, sampler_prob=self.sampler_prob if unigram else None,
+                              item_freq=self.item_freq if counted else None,
+                              sampler_prob=self.sampler_prob if unigram and counted else None,
                               seed=self.dropout_seed, tensor_id=TID_SAMPLED_NEGATIVES,
                               start=self.step_index * cfg.n_sampled_negatives, oob_flag=self.oob)
+        if self.freq_on:
+            # right behind the sampler: the batch's items update the sketch, every candidate - sampled ones included - gets the
+            # mixture's probability with the sketch's expected in-batch count in the place of B * item_freq
+            self._estimate(self.cand_ids, cfg.batch_size, self.step_index + 1, self.cand_prob, mix=True,
+                           sampler_prob=self.sampler_prob if unigram else None)
         return self.cand_ids
+
+    # ------------------------------------------------------------------ streaming frequency estimation
+    def _estimate(self, ids, n_update: int, step: int, out, mix: bool = False, sampler_prob=None):
+        """One call of the estimator on the trainer's sketch: hash rows TID_FREQ_HASH_BASE + h of the trainer's seed."""
+        return ops.frequency_estimate_(self.freq_sketch, ids, n_update, step, self.cfg.freq_alpha, self.cfg.n_items, out,
+                                       seed=self.dropout_seed, tensor_id=TID_FREQ_HASH_BASE, sampler_prob=sampler_prob, mix=mix,
+                                       oob_flag=self.oob)
+
+    def _refuse_given_probability(self, given, where: str):
+        if given is not None:
+            raise ValueError(f"{where}: sampling_bias_estimator='streaming' - the trainer estimates every candidate's sampling "
+                             "probability itself, candidate_sampling_probability cannot be passed")
+
+    def _update_frequencies(self, item_ids, given=None):
+        """The in-batch train step's estimator launch, in front of everything else: the batch's items update the sketch at the
+        1-based step step_index + 1 and ``freq_prob`` - the scorer's cand_prob - gets their estimated probabilities."""
+        self._refuse_given_probability(given, "step")
+        ops._chk(item_ids, torch.int64, "item_ids", 1)
+        if item_ids.numel() != self.cfg.batch_size:
+            raise ValueError(f"item_ids must hold batch_size = {self.cfg.batch_size} ids, got {item_ids.numel()}")
+        self._estimate(item_ids, self.cfg.batch_size, self.step_index + 1, self.freq_prob)
+        self._freq_step = self.step_index
+        return self.freq_prob
+
+    def _read_frequencies(self, item_ids, given=None):
+        """``evaluate``'s estimator launch: the in-batch candidates' probabilities as the sketch stands, nothing is updated."""
+        self._refuse_given_probability(given, "evaluate")
+        return self._estimate(item_ids, 0, max(self.step_index, 1), self.freq_prob)
+
+    def estimated_item_probability(self, ids: torch.Tensor) -> torch.Tensor:
+        """The estimator's present probability 1 / D of ANY number of item ids ([n] f32; 1.0 for an id out of range, which also
+        sets the out-of-range flag): an estimate-only call, the sketch is not changed.  The probability of the item being among a
+        step's positives - it saturates at 1 for items that occur several times per batch."""
+        if not self.freq_on:
+            raise ValueError("estimated_item_probability: the trainer has no estimator (cfg.sampling_bias_estimator == 'none')")
+        ids = ids.to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
+        return self._estimate(ids, 0, max(self.step_index, 1), torch.empty(ids.numel(), device=self.dev))
 
     def _forward_backward_mixed(self, user_ids, item_ids, sample_weight=None, sampled: bool = False, ratings=None):
         """forward_backward with the item side over ``cand_ids`` (B + N rows): one launch sequence per tower, the scorer at
@@ -1600,7 +1681,7 @@ class TwoTowerTrainer:
         q, c = self._outputs(ut, it)
         dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
         ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
-                              sample_weight=sample_weight, cand_prob=self.cand_prob if self.item_freq is not None else None,
+                              sample_weight=sample_weight, cand_prob=self.cand_prob if (self.item_freq is not None or self.freq_on) else None,
                               cand_ids=cand, precision=cfg.scorer_precision)
         if self.rating_on:                       # the pairs are the first batch_size candidate rows; the sampled rows get no head gradient
             self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
@@ -1719,6 +1800,8 @@ class TwoTowerTrainer:
             loss_kw.pop("ratings", None)
         self._check_batch(user_ids, item_ids, loss_kw.get("category_ids"), loss_kw.get("sample_weight"),
                           loss_kw.get("candidate_sampling_probability"), loss_kw.get("candidate_ids"))
+        if self.freq_on:             # in front of everything else; its output is the step's cand_prob (the composite call's too)
+            loss_kw["candidate_sampling_probability"] = self._update_frequencies(item_ids, loss_kw.get("candidate_sampling_probability"))
         # (never inside a graph capture: the poll queries an event recorded outside it and would bake a D2H copy into every replay)
         if self.flag_poll_every and self.step_index % self.flag_poll_every == 0 and not torch.cuda.is_current_stream_capturing():
             self.poll_ids()
@@ -1860,6 +1943,9 @@ class TwoTowerTrainer:
         self._check_categories(loss_kw.get("category_ids"))
         self._check_batch(loss_kw.get("sample_weight"), loss_kw.get("candidate_sampling_probability"),
                           loss_kw.get("candidate_ids"))
+        if self.freq_on:             # estimated, not updated: a validation batch is no part of the training stream
+            self._check_batch(item_ids)
+            loss_kw["candidate_sampling_probability"] = self._read_frequencies(item_ids, loss_kw.get("candidate_sampling_probability"))
         if self.mixed:           # the in-batch loss, as without sampling: the first batch_size rows of the item tower's buffers
             self._check_batch(user_ids, item_ids)
             b = cfg.batch_size
@@ -2006,6 +2092,8 @@ class TwoTowerTrainer:
             sd.update(rec.state())
         if getattr(self, "item_freq", None) is not None:     # mixed negative sampling: the correction (and the unigram sampler) is rebuilt from it
             sd["item_freq"] = self.item_freq
+        if getattr(self, "freq_on", False):                  # the streaming frequency estimator's state
+            sd["freq_sketch"] = self.freq_sketch
         if self.cfg.optimizer in ("adagrad", "rowwise_adagrad"):
             sd["dense_accum"] = self.dense_accum
         if self.cfg.optimizer == "adam":
@@ -2037,6 +2125,19 @@ class TwoTowerTrainer:
         # checkpoint from before they existed, or from an in-batch run, loads as before); a mixed trainer takes the frequencies
         if self.mixed and sd.get("item_freq") is not None:
             self.set_item_frequencies(sd["item_freq"])
+        # the estimator, like the sampling settings, belongs to the run: a trainer without one ignores a checkpoint's sketch; a
+        # trainer with one continues on it - a sketch of another shape, or none while the step count is carried on (every slot
+        # would look unseen for step_index steps), is refused
+        if self.freq_on:
+            sk = sd.get("freq_sketch")
+            if sk is None and self.step_index > 0:
+                raise ValueError(f"the checkpoint carries no freq_sketch but continues at step {self.step_index}: the streaming "
+                                 "frequency estimator cannot start there (every item would look unseen for that many steps)")
+            if sk is not None:
+                if tuple(sk.shape) != tuple(self.freq_sketch.shape) or sk.dtype != torch.int64:
+                    raise ValueError(f"checkpoint freq_sketch {sk.dtype} {list(sk.shape)} does not match the trainer's int64 "
+                                     f"{list(self.freq_sketch.shape)} (freq_hashes / freq_slots)")
+                self.freq_sketch.copy_(sk)
         if self.cfg.optimizer in ("adagrad", "rowwise_adagrad"):
             self.dense_accum.copy_(sd["dense_accum"])
         if self.cfg.optimizer == "adam":
