@@ -381,6 +381,36 @@ def test_item_corpus_embeddings_equal_the_training_path(dev):
     assert (plain.item_corpus_embeddings() - corpus).abs().max().item() > 1e-3      # the titles do reach the corpus
 
 
+def test_evaluate_between_backward_and_update_leaves_the_update_alone(dev):
+    """An inference pass writes none of the buffers a train step keeps for ``apply_gradients`` - the titles' and the history's
+    slot tokens and pooling scales: forward_backward, evaluate on ANOTHER batch, apply_gradients trains every table and
+    dense_flat to the bits of the same step without the evaluate in between."""
+    seed, b, lh = 29, 64, 5
+    cfg = _cfg("sgd", batch=b, n_users=300, n_items=200, n_title_buckets=50, title_max_tokens=4, user_history_len=lh, history_pooling="mean")
+    rng = np.random.default_rng(seed)
+    histories = rng.integers(-1, cfg.n_items, (cfg.n_users, lh)).astype(np.int32)
+
+    def fresh():
+        tr = TwoTowerTrainer(TwoTowerConfig(**cfg.__dict__), dev, seed=seed)
+        tr.set_item_titles(tr.synthetic_item_titles(seed))
+        tr.set_user_histories(T(histories, dev))
+        return tr
+    a, c = fresh(), fresh()
+    (u0, i0), (u1, i1) = a.synthetic_batch(seed, 0, "Z"), a.synthetic_batch(seed, 1, "Z")
+    assert not torch.equal(i0, i1) and not torch.equal(u0, u1)
+    a.forward_backward(u0, i0)
+    a.apply_gradients(step_ids=[u0, i0])
+    c.forward_backward(u0, i0)
+    c.evaluate(u1, i1)
+    c.apply_gradients(step_ids=[u0, i0])
+    a.check_ids(); c.check_ids()
+    assert set(a.tables) == {"user", "item", "title", "history"}
+    init = fresh()
+    for k in [f"{p}_table" for p in a.tables] + ["dense_flat"]:
+        assert torch.equal(getattr(a, k), getattr(c, k)), k
+        assert not torch.equal(getattr(a, k), getattr(init, k)), k             # (and the step did train it)
+
+
 # ------------------------------------------------------------------------------------------ 4. custom op, CLIs, refusals
 def test_custom_op_passes_opcheck_and_equals_the_ops_call(dev):
     from two_tower_amazon_recommender_amd import torch_ops  # noqa: F401

@@ -872,21 +872,34 @@ class EmbeddingTable:
         if self.row_accum is not None:
             self.row_accum.fill_(cfg.adagrad_initial_accumulator)
 
-    def apply(self, cfg: TwoTowerConfig, grads, adam_step: int, adam_segs=(), lr: float | None = None):
-        """The configured optimizer's update from this table's sort plan (which has run; a ``BagPlan`` after its ``backward``:
-        ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same lazy-Adam call (row-wise
-        Adagrad: the Adagrad segments that ride in its call).  ``lr``: the step's rate (the trainer's ``learning_rate``; default:
-        the configured one)."""
-        lr = cfg.learning_rate if lr is None else lr
+    def opt_args(self, grads) -> tuple:
+        """What this table contributes to the configured optimizer's ``ops`` call with ``grads`` as its gradient rows: the table,
+        the state that optimizer allocated, the gradients and the sort plan - (table, m, v, grads, plan) for lazy Adam, (table,
+        row_accum, grads, plan) for row-wise Adagrad, (table, accum, grads, plan) for SGD (accum None) and Adagrad."""
+        state = (self.m, self.v) if self.m is not None else (self.row_accum,) if self.row_accum is not None else (self.accum,)
+        return (self.table, *state, grads, self.plan)
+
+    @staticmethod
+    def update(cfg: TwoTowerConfig, tables, segs, lr: float, adam_step: int):
+        """THE place that maps cfg.optimizer to a call: the update of ``tables`` (``opt_args`` tuples) from their sort plans,
+        which have run.  Lazy Adam and row-wise Adagrad take all of them, and the dense segments ``segs`` that ride along, in
+        one call; SGD and Adagrad take one launch per table (their dense segments have a launch of their own)."""
         if cfg.optimizer == "adam":
-            ops.adam_step_([(self.table, self.m, self.v, grads, self.plan)], list(adam_segs),
-                           ops.AdamHyper(lr, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
+            ops.adam_step_(tables, segs, ops.AdamHyper(lr, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon, adam_step))
         elif cfg.optimizer == "rowwise_adagrad":
-            ops.rowwise_adagrad_step_([(self.table, self.row_accum, grads, self.plan)], list(adam_segs), lr, cfg.adagrad_epsilon)
-        elif cfg.optimizer == "sgd":
-            ops.sparse_sgd_(self.table, grads, self.plan, lr)
+            ops.rowwise_adagrad_step_(tables, segs, lr, cfg.adagrad_epsilon)
         else:
-            ops.sparse_adagrad_(self.table, self.accum, grads, self.plan, lr, cfg.adagrad_epsilon)
+            for table, accum, grads, plan in tables:
+                if cfg.optimizer == "sgd":
+                    ops.sparse_sgd_(table, grads, plan, lr)
+                else:
+                    ops.sparse_adagrad_(table, accum, grads, plan, lr, cfg.adagrad_epsilon)
+
+    def apply(self, cfg: TwoTowerConfig, grads, adam_step: int, adam_segs=(), lr: float | None = None):
+        """The configured optimizer's update of this table alone (``update``) from its sort plan (which has run; a ``BagPlan``
+        after its ``backward``: ``grads`` then holds one row per bag).  ``adam_segs``: dense segments that ride in the same
+        lazy-Adam / row-wise Adagrad call.  ``lr``: the step's rate (default: the configured one)."""
+        self.update(cfg, [self.opt_args(grads)], list(adam_segs), cfg.learning_rate if lr is None else lr, adam_step)
 
 
 @dataclass
@@ -1066,13 +1079,10 @@ class TwoTowerTrainer:
         self.cat_table, self.cat_accum, self.cat_m, self.cat_v, self.cat_plan = _table_fields(cat)
         self.title_table, self.title_accum, self.title_m, self.title_v, self.title_plan = _table_fields(title)
         self.history_table, self.history_accum, self.history_m, self.history_v, self.history_plan = _table_fields(history)
-        # what the fused optimizer calls take for the tables of the pairs' ids - every pointer is fixed from here on, so the
-        # lists are built once (the category row's gradient is the item-tower input gradient itself)
+        # what the configured optimizer's calls take for the tables of the pairs' ids (EmbeddingTable.opt_args) - every pointer is
+        # fixed from here on, so the list is built once (the category row's gradient is the item-tower input gradient itself)
         trio = [(user, ut.demb), (item, it.demb)] + ([(cat, it.demb)] if cat is not None else [])
-        self._opt_tables = [(t.table, t.accum, g, t.plan) for t, g in trio]
-        self._adam_tables = [(t.table, t.m, t.v, g, t.plan) for t, g in trio]
-        # row-wise Adagrad: the user and the item table in ONE call (the category table goes through EmbeddingTable.apply)
-        self._rowwise_tables = [(t.table, t.row_accum, g, t.plan) for t, g in trio[:2]]
+        self._opt_tables = tabs = [t.opt_args(g) for t, g in trio]
         for t in (user, item, cat, title, history):
             if t is not None:
                 setattr(self, f"{t.prefix}_row_accum", t.row_accum)
@@ -1157,11 +1167,11 @@ class TwoTowerTrainer:
         # (r04: at small batches the gather launch's fixed cost decides - the reference's own config, [512, 256, 128] at batch 1024:
         # 0.1631-0.1638 ms fused against 0.1644-0.1654 with the gather launch)
         self.fuse_lookup = os.environ.get("TT_FUSE_LOOKUP", "1" if (cfg.tower_dims[0] < 512 or cfg.batch_size <= 2048) else "0") != "0"
-        if cfg.n_title_buckets:                  # the pooled titles are added to the materialised item-tower input (_item_inputs)
+        if cfg.n_title_buckets:                  # the pooled titles are added to the materialised item-tower input (_tower_inputs)
             self.fuse_lookup = False
-        if cfg.user_history_len:                 # the user tower's input is one bag launch: user row + pooled history (_item_inputs)
+        if cfg.user_history_len:                 # the user tower's input is one bag launch: user row + pooled history (_tower_inputs)
             self.fuse_lookup = False
-        if self._feature_sides:                  # the projected features are added to the materialised tower inputs (_add_features)
+        if self._feature_sides:                  # the projected features are added to the materialised tower inputs (_tower_inputs)
             self.fuse_lookup = False
         if cfg.cross_layers:                     # the cross layers read the materialised tower inputs (Tower.forward)
             self.fuse_lookup = False
@@ -1211,6 +1221,16 @@ class TwoTowerTrainer:
             if adam:
                 self._adam_segs.append(ops.make_adam_seg(self.dense_flat[lo:hi], self.dense_m[lo:hi], self.dense_v[lo:hi], slabs, ns,
                                                          reg, slab_stride=seg.stride))
+        # the segments that ride in the table calls of lazy Adam (its own form of them) and of row-wise Adagrad; None: SGD and
+        # Adagrad, which update the dense parameters in a launch of their own or inside their one fused launch
+        rowwise = cfg.optimizer == "rowwise_adagrad"
+        self._riding = self._adam_segs if adam else self._segs if rowwise else None
+        # how a step groups the id tables into plan-fed calls (EmbeddingTable.update), as (tables, riding segments) - the segments
+        # ride with the first call.  Lazy Adam: every table in ONE call; row-wise Adagrad: user + item in one, then the category
+        # table alone; mixed sampling, whose two plans hold different id counts (B and B + N): one call per table; SGD / Adagrad
+        # otherwise: the category table, behind the unfused sparse_update2_ (their other forms are single fused launches)
+        groups = [tabs[:1], tabs[1:]] if self.mixed else [tabs] if adam else [tabs[:2], tabs[2:]] if rowwise else [tabs[2:]]
+        self._table_calls = [(g, (self._riding or []) if k == 0 else []) for k, g in enumerate(groups) if g]
         if seed is not None:
             self.init_synthetic(seed)
 
@@ -1383,38 +1403,57 @@ class TwoTowerTrainer:
 
     def _lookups(self, user_ids, item_ids, category_ids):
         """K1 fused into the towers' first layer (fwd GEMM and dW GEMM read the table rows themselves): the
-        [batch, dim] tower inputs are never written to HBM.  None when the batch is too long for the fused form."""
-        self._check_batch(user_ids, item_ids, category_ids)
-        if not self.fuse_lookup or self.cfg.batch_size > ops.MAX_FUSED_LOOKUP_ROWS:
+        [batch, dim] tower inputs are never written to HBM.  None when the batch is too long for the fused form.  Mixed
+        sampling's train step passes ``cand_ids`` - the trainer's own list, one id per row of the item tower - as ``item_ids``."""
+        self._check_batch(user_ids, None if item_ids is self.cand_ids else item_ids, category_ids)
+        if not self.fuse_lookup or self.item_tower.rows > ops.MAX_FUSED_LOOKUP_ROWS:
             return None
         return (ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob),
                 ops.make_lookup(self.item_table, item_ids, self.cat_table, category_ids, self.oob))
 
-    def _user_inputs(self, user_ids, out, exclude=None, keep: bool = False):
-        """The user tower's input rows with the history feature, in ONE launch: user_table[u] + the pooled history rows of u,
-        without the items ``exclude`` (the train step's positives).  ``keep``: the slot tokens and scales stay for the update."""
-        if self._attn_on:                        # (the weights and pooled rows of an inference pass are never read)
-            n = user_ids.numel()
-            ops.history_attention(self.history_table, self.user_history, self.history_attn, bag_rows=user_ids, exclude=exclude,
-                                  base=(self.user_table, user_ids), out=out, batch_ids=self.history_ids if keep else None,
-                                  weights=self.history_weights[:n], pooled=self.history_pooled[:n], oob_flag=self.oob)
-            return
-        ops.history_bag(self.history_table, self.user_history, bag_rows=user_ids, exclude=exclude, base=(self.user_table, user_ids),
-                        pooling=self.cfg.history_pooling, out=out, batch_ids=self.history_ids if keep else None,
-                        inv=self.history_inv if keep else None, oob_flag=self.oob)
-
-    def _add_features(self, user=None, item=None, keep: bool = False):
-        """+ the projected numeric features, into materialised tower-input rows: ``user`` / ``item`` = (ids, rows) or None.  ONE
-        launch for the sides that have the feature; ``keep``: the normalised rows stay for the backward launch (train step)."""
-        probs = []
-        for side, arg in (("user", user), ("item", item)):
-            fs = self.sides.get(side)
-            if fs is None or arg is None:
-                continue
-            ids, out = arg
-            probs.append((fs.features, ids, fs.mean, fs.inv_std, fs.P, out, True, fs.z if keep else None))
+    def _tower_inputs(self, user=None, item=None, *, category_ids=None, exclude=None, keep: bool = False, features_only: bool = False):
+        """Materialised tower-input rows (no fused lookup), and the ONE place that knows what is summed into them: the id's table
+        row + the hashed category's row (item) + the pooled title rows (item) + the pooled or attended history rows (user) + the
+        projected numeric features.  ``user`` / ``item`` = (ids, rows to write) or None: any number of ids, either side alone.
+        ``exclude``: the items the history launch leaves out (the train step's positives); ``keep``: the train step - the slot
+        tokens, pooling scales and normalised feature rows stay for the backward launches and the update; an inference pass
+        writes none of those buffers, so it may run between a step's backward pass and its ``apply_gradients``.
+        ``features_only``: the rows already hold everything but the numeric features (``item_corpus_embeddings``)."""
+        cfg = self.cfg
+        if features_only:
+            pass
+        elif self.history_table is not None:     # the item gather, then ONE launch for the user side: user row + pooled history
+            if item is not None:
+                ops.embedding_gather(self.item_table, item[0], out=item[1], oob_flag=self.oob)
+            if user is not None and self._attn_on:   # (the weights and pooled rows of an inference pass are never read)
+                ids, n = user[0], user[0].numel()
+                ops.history_attention(self.history_table, self.user_history, self.history_attn, bag_rows=ids, exclude=exclude,
+                                      base=(self.user_table, ids), out=user[1], batch_ids=self.history_ids if keep else None,
+                                      weights=self.history_weights[:n], pooled=self.history_pooled[:n], oob_flag=self.oob)
+            elif user is not None:
+                ops.history_bag(self.history_table, self.user_history, bag_rows=user[0], exclude=exclude, base=(self.user_table, user[0]),
+                                pooling=cfg.history_pooling, out=user[1], batch_ids=self.history_ids if keep else None,
+                                inv=self.history_inv if keep else None, oob_flag=self.oob)
+        elif user is not None and item is not None and user[0].numel() == item[0].numel():
+            ops.embedding_gather2(self.user_table, user[0], user[1], self.item_table, item[0], item[1], self.oob)
+        else:
+            for table, side in ((self.user_table, user), (self.item_table, item)):
+                if side is not None:
+                    ops.embedding_gather(table, side[0], out=side[1], oob_flag=self.oob)
+        if item is not None and not features_only:
+            if category_ids is not None:
+                ops.embedding_gather_add_(item[1], self.cat_table, category_ids, self.oob)
+            if self.title_table is not None:
+                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item[0], pooling=cfg.title_pooling, out=item[1],
+                                  accumulate=True, batch_ids=self.title_ids if keep else None, inv=self.title_inv if keep else None,
+                                  oob_flag=self.oob)
+        probs = []                               # one launch for the sides that are present and have the feature
+        for name, side in (("user", user), ("item", item)):
+            fs = self.sides.get(name)
+            if fs is not None and side is not None:
+                probs.append((fs.features, side[0], fs.mean, fs.inv_std, fs.P, side[1], True, fs.z if keep else None))
         if probs:
-            ops.dense_features(*probs, clip=self.cfg.feature_clip, oob_flag=self.oob)
+            ops.dense_features(*probs, clip=cfg.feature_clip, oob_flag=self.oob)
 
     def _features_backward(self):
         """The projection kernels' gradient slabs from the towers' input gradients (demb) and the kept normalised rows: one
@@ -1430,46 +1469,34 @@ class TwoTowerTrainer:
                                       self.user_tower.demb, self.history_attn, self.cfg.user_history_len,
                                       slot_grads=self.history_slot_grads, dattn_slabs=self._ha_slabs)
 
-    def _item_inputs(self, user_ids, item_ids, category_ids, train: bool = False):
-        """K1 as its own launch (fuse_lookup = False): both towers' input rows; the hashed category's row is summed
-        into the item tower's input.  ``train``: the history bags leave out the pair's own item and keep what the update needs."""
-        self._check_batch(user_ids, item_ids, category_ids)
-        ut, it = self.user_tower, self.item_tower
-        if self.history_table is not None:
-            ops.embedding_gather(self.item_table, item_ids, out=it.acts[0], oob_flag=self.oob)
-            self._user_inputs(user_ids, ut.acts[0], exclude=item_ids if train else None, keep=train)
-        else:
-            ops.embedding_gather2(self.user_table, user_ids, ut.acts[0], self.item_table, item_ids, it.acts[0], self.oob)
-        if category_ids is not None:
-            ops.embedding_gather_add_(it.acts[0], self.cat_table, category_ids, self.oob)
-        if self.title_table is not None:     # + the pooled title rows of every pair's item; the slot tokens and scales stay for the update
-            ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=self.cfg.title_pooling, out=it.acts[0],
-                              accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
-        self._add_features((user_ids, ut.acts[0]), (item_ids, it.acts[0]), keep=train)
-
-    def _outputs(self, *towers):
+    def _outputs(self, towers, rows=None):
         """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
-        serving: the last layer's output, L2-normalised into ``tower.unit`` (one launch for all of them) when
-        cfg.normalize_embeddings.  The ONE place that decides."""
-        if self.mixed:                       # towers of different row counts (or a partial pass): one launch per tower
-            return self._outputs_rows(towers, [t.rows for t in towers])
-        if not self.cfg.normalize_embeddings:
-            return tuple(t.acts[-1] for t in towers)
-        ops.l2_normalize2(tuple(t.acts[-1] for t in towers), tuple(t.unit for t in towers), self.cfg.normalize_eps)
-        return tuple(t.unit for t in towers)
-
-    def _outputs_rows(self, towers, rows):
-        """``_outputs`` over the first rows[i] rows of towers[i]."""
-        xs = tuple(t.acts[-1][:n] for t, n in zip(towers, rows))
+        serving: the last layer's output, L2-normalised into ``tower.unit`` when cfg.normalize_embeddings - one launch where the
+        towers' row counts agree, else (mixed sampling's longer item tower) one per tower.  ``rows``: only the first rows[i]
+        rows of towers[i] (a partial pass).  The ONE place that decides."""
+        part = lambda bufs: tuple(bufs) if rows is None else tuple(x[:n] for x, n in zip(bufs, rows))
+        xs = part(t.acts[-1] for t in towers)
         if not self.cfg.normalize_embeddings:
             return xs
-        ys = tuple(t.unit[:n] for t, n in zip(towers, rows))
-        if len(set(rows)) == 1:
+        ys = part(t.unit for t in towers)
+        if len(set(rows or [t.rows for t in towers])) == 1:
             ops.l2_normalize2(xs, ys, self.cfg.normalize_eps)
         else:
             for x, y in zip(xs, ys):
                 ops.l2_normalize2((x,), (y,), self.cfg.normalize_eps)
         return ys
+
+    def _outputs_backward(self, towers, grads):
+        """The mirror of ``_outputs`` in the train step: cfg.normalize_embeddings - the scorer's gradients ``grads`` are w.r.t. the
+        unit vectors, and one launch (one per tower where the row counts differ) turns them into the last layers' dz."""
+        if not self.cfg.normalize_embeddings:
+            return
+        xs, dzs = tuple(t.acts[-1] for t in towers), tuple(t.dz[-1] for t in towers)
+        if len({t.rows for t in towers}) == 1:
+            ops.l2_normalize_bwd2(xs, grads, dzs, self.cfg.normalize_eps)
+        else:
+            for x, g, dz in zip(xs, grads, dzs):
+                ops.l2_normalize_bwd2((x,), (g,), (dz,), self.cfg.normalize_eps)
 
     # ------------------------------------------------------------------ the hot path
     def _check_ratings(self, ratings):
@@ -1506,33 +1533,45 @@ class TwoTowerTrainer:
         return self._r_se.sum() / self.cfg.batch_size
 
     def forward_backward(self, user_ids: torch.Tensor, item_ids: torch.Tensor, sample_weight=None,
-                         candidate_sampling_probability=None, candidate_ids=None, category_ids=None, ratings=None):
+                         candidate_sampling_probability=None, candidate_ids=None, category_ids=None, ratings=None, *,
+                         _sampled: bool = False):
+        """Loss and every gradient of one step, for both samplings.  In-batch: the item side is the pairs' items.  Mixed negative
+        sampling: the item side is ``cand_ids`` (B + N rows: the sampler launch runs here unless ``step`` has run it,
+        ``_sampled``), the scorer works at [B] x [B + N] with the positive of query i at candidate i, and ``cand_ids`` always
+        goes to it - a sampled id equal to a row's own positive is a false negative, which the scorer masks."""
         cfg, ut, it = self.cfg, self.user_tower, self.item_tower
         self._check_ratings(ratings)
         if self.mixed:
             if candidate_sampling_probability is not None or candidate_ids is not None or category_ids is not None:
                 raise ValueError("candidate_sampling='mixed': the trainer draws the candidates itself - candidate_ids, "
                                  "candidate_sampling_probability (set_item_frequencies) and category_ids cannot be passed")
-            return self._forward_backward_mixed(user_ids, item_ids, sample_weight, ratings=ratings)
-        self._check_categories(category_ids)
-        if self.freq_on and not (candidate_sampling_probability is self.freq_prob and self._freq_step == self.step_index):
-            candidate_sampling_probability = self._update_frequencies(item_ids, candidate_sampling_probability)   # (step() has not)
-        lks = self._lookups(user_ids, item_ids, category_ids)
-        if lks is None:
-            self._item_inputs(user_ids, item_ids, category_ids, train=True)
-        row0 = self.step_index * cfg.batch_size
-        towers_forward((ut, it), tuple((cfg.dropout_rate, self.dropout_seed, t, row0) for t in (0, 1)), lookups=lks)
-        q, c = self._outputs(ut, it)
-        # normalised: the scorer's gradients are w.r.t. the unit vectors; one launch turns them into the last layer's dz
+            self._check_batch(user_ids, item_ids, sample_weight)
+            if not _sampled:
+                self.sample_candidates(item_ids)
+            ids = candidate_ids = self.cand_ids
+            if self.item_freq is not None or self.freq_on:
+                candidate_sampling_probability = self.cand_prob
+        else:
+            self._check_categories(category_ids)
+            if self.freq_on and not (candidate_sampling_probability is self.freq_prob and self._freq_step == self.step_index):
+                candidate_sampling_probability = self._update_frequencies(item_ids, candidate_sampling_probability)   # (step() has not)
+            ids = item_ids
+        lks = self._lookups(user_ids, ids, category_ids)
+        if lks is None:                          # (the history launch leaves out the pair's own item)
+            self._tower_inputs((user_ids, ut.acts[0]), (ids, it.acts[0]), category_ids=category_ids, exclude=item_ids, keep=True)
+        # the dropout streams count rows per tower: consecutive steps never share a position
+        step, rate, seed = self.step_index, cfg.dropout_rate, self.dropout_seed
+        towers_forward((ut, it), ((rate, seed, 0, step * ut.rows), (rate, seed, 1, step * it.rows)), lookups=lks)
+        q, c = self._outputs((ut, it))
+        # normalised: the scorer's gradients are w.r.t. the unit vectors; _outputs_backward turns them into the last layer's dz
         dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
-        kw = dict(sample_weight=sample_weight, cand_prob=candidate_sampling_probability, cand_ids=candidate_ids)
         # loss + dq + dc in two fused passes over the logits (probabilities never stored; f32: raw dot products kept in self.ws)
-        ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
-                              dq, dc, precision=cfg.scorer_precision, **kw)
-        if self.rating_on:
+        ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
+                              sample_weight=sample_weight, cand_prob=candidate_sampling_probability, cand_ids=candidate_ids,
+                              precision=cfg.scorer_precision)
+        if self.rating_on:                       # the pairs are the first batch_size candidate rows; sampled rows get no head gradient
             self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
-        if cfg.normalize_embeddings:
-            ops.l2_normalize_bwd2((ut.acts[-1], it.acts[-1]), (dq, dc), (ut.dz[-1], it.dz[-1]), cfg.normalize_eps)
+        self._outputs_backward((ut, it), (dq, dc))
         towers_backward((ut, it), cfg.dropout_rate, lookups=lks, bwd2_ws=self.bwd2_ws)
         self._features_backward()
         self._history_backward()
@@ -1567,7 +1606,7 @@ class TwoTowerTrainer:
         rows = [ops.make_clip_rows(self.user_tower.demb, **user), ops.make_clip_rows(self.item_tower.demb, **item)]
         if self._attn_on:
             rows.append(ops.make_clip_rows(self.history_slot_grads, 0.0, self.history_ids, "mask"))
-        return ops.ClipList(rows, self._adam_segs if cfg.optimizer == "adam" else self._segs)
+        return ops.ClipList(rows, self._segs if self._adam_segs is None else self._adam_segs)
 
     def clip_gradients(self):
         """cfg.global_clipnorm > 0: scales every gradient of the step IN PLACE by c / max(global norm, c) - two launches, between
@@ -1656,94 +1695,23 @@ class TwoTowerTrainer:
         ids = ids.to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
         return self._estimate(ids, 0, max(self.step_index, 1), torch.empty(ids.numel(), device=self.dev))
 
-    def _forward_backward_mixed(self, user_ids, item_ids, sample_weight=None, sampled: bool = False, ratings=None):
-        """forward_backward with the item side over ``cand_ids`` (B + N rows): one launch sequence per tower, the scorer at
-        [B] x [B + N] with the positive of query i at candidate i.  A sampled id equal to a row's own positive is a false
-        negative: ``cand_ids`` always goes to the scorer, which masks it."""
-        cfg, ut, it = self.cfg, self.user_tower, self.item_tower
-        self._check_batch(user_ids, item_ids, sample_weight)
-        if not sampled:
-            self.sample_candidates(item_ids)
-        cand = self.cand_ids
-        lks = None
-        if self.fuse_lookup and it.rows <= ops.MAX_FUSED_LOOKUP_ROWS:
-            lks = (ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob), ops.make_lookup(self.item_table, cand, oob_flag=self.oob))
-        else:
-            ops.embedding_gather(self.user_table, user_ids, out=ut.acts[0], oob_flag=self.oob)
-            ops.embedding_gather(self.item_table, cand, out=it.acts[0], oob_flag=self.oob)
-            if self.title_table is not None:
-                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=cand, pooling=cfg.title_pooling, out=it.acts[0],
-                                  accumulate=True, batch_ids=self.title_ids, inv=self.title_inv, oob_flag=self.oob)
-            self._add_features((user_ids, ut.acts[0]), (cand, it.acts[0]), keep=True)   # cand_ids: the sampled rows too
-        # the dropout streams count rows per tower: consecutive steps never share a position
-        towers_forward((ut, it), tuple((cfg.dropout_rate, self.dropout_seed, t, self.step_index * tw.rows) for t, tw in enumerate((ut, it))),
-                       lookups=lks)
-        q, c = self._outputs(ut, it)
-        dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
-        ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
-                              sample_weight=sample_weight, cand_prob=self.cand_prob if (self.item_freq is not None or self.freq_on) else None,
-                              cand_ids=cand, precision=cfg.scorer_precision)
-        if self.rating_on:                       # the pairs are the first batch_size candidate rows; the sampled rows get no head gradient
-            self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
-        if cfg.normalize_embeddings:
-            ops.l2_normalize_bwd2((ut.acts[-1],), (dq,), (ut.dz[-1],), cfg.normalize_eps)
-            ops.l2_normalize_bwd2((it.acts[-1],), (dc,), (it.dz[-1],), cfg.normalize_eps)
-        towers_backward((ut, it), cfg.dropout_rate, lookups=lks)
-        self._features_backward()
-        self._lr_step = self.step_index
-        self.step_index += 1
-        return self.loss
-
-    def _run_plans_mixed(self, user_ids):
-        ops.sparse_plan_batched([self.user_plan, self.item_plan], [user_ids, self.cand_ids], [self.cfg.n_users, self.cfg.n_items])
-
-    def _step_mixed(self, user_ids, item_ids, sample_weight=None, ratings=None, **other):
-        self._check_ratings(ratings)
-        bad = [k for k, v in other.items() if v is not None]
-        if bad:
-            raise ValueError(f"candidate_sampling='mixed': the trainer draws the candidates itself - {', '.join(sorted(bad))} cannot "
-                             "be passed to step() (the correction comes from set_item_frequencies)")
-        self._check_batch(user_ids, item_ids, sample_weight)
-        if self.flag_poll_every and self.step_index % self.flag_poll_every == 0:
-            self.poll_ids()
-        self.sample_candidates(item_ids)          # in front of everything else: the plans and both lookups read cand_ids
-        self._run_plans_mixed(user_ids)
-        loss = self._forward_backward_mixed(user_ids, item_ids, sample_weight, sampled=True, ratings=ratings)
-        self.clip_gradients()
-        self.apply_gradients()
-        return loss
-
-    def _apply_table_gradients_mixed(self):
-        """The two tables' plans hold different id counts (B and B + N): one sparse launch sequence per table.  The sampled
-        items' rows are trained like the positives' (their gradient rows are demb[B:])."""
-        cfg, adam, lr = self.cfg, self.cfg.optimizer == "adam", self.learning_rate
-        rowwise = cfg.optimizer == "rowwise_adagrad"
-        if not adam and not rowwise:
-            ops.dense_update_(self._segs, cfg.optimizer, lr, cfg.adagrad_epsilon)
-        # (lazy Adam: the user table with every dense segment in one call, then the item table - the same step t; row-wise
-        # Adagrad likewise, with the Adagrad segments)
-        riding = self._adam_segs if adam else self._segs if rowwise else ()
-        self.tables["user"].apply(cfg, self.user_tower.demb, self.adam_step, riding, lr=lr)
-        self.tables["item"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
-        if adam:
-            self.adam_step += 1
-
+    # ------------------------------------------------------------------ the optimizer and the step
     def apply_gradients(self, step_ids=None):
         """``step_ids`` = [user ids, item ids (, category ids)]: the optimizer launch sorts them itself (no plan launch ran).
-        Mixed negative sampling: with ``step_ids`` the sort plans run here (over the user ids and ``cand_ids``)."""
-        adam_step = self.adam_step
-        if self.mixed:
-            if step_ids is not None:
-                self._run_plans_mixed(step_ids[0])
-            self._apply_table_gradients_mixed()
-        else:
-            self._apply_table_gradients(step_ids)
+        Mixed negative sampling: with ``step_ids`` the sort plans run here (over the user ids and ``cand_ids``).  The step's rate
+        and lazy Adam's 1-based global step are read ONCE, for every call of the step; the latter counts on at the end."""
+        cfg, lr, t = self.cfg, self.learning_rate, self.adam_step
+        if self.mixed and step_ids is not None:
+            ops.sparse_plan_batched([self.user_plan, self.item_plan], [step_ids[0], self.cand_ids], [cfg.n_users, cfg.n_items])
+        self._apply_table_gradients(step_ids, lr, t)
         if self.title_table is not None:
-            self._apply_title_gradients(adam_step)
+            self._apply_title_gradients(lr, t)
         if self.history_table is not None:
-            self._apply_history_gradients(adam_step)
+            self._apply_history_gradients(lr, t)
+        if self._adam_segs is not None:          # lazy Adam
+            self.adam_step = t + 1
 
-    def _apply_history_gradients(self, adam_step: int):
+    def _apply_history_gradients(self, lr: float, adam_step: int):
         """The history table's update, the mirror of ``_apply_title_gradients`` on the user side: the sort plan over the step's
         slot items (an excluded slot is -1 there: no gradient), the bags' scaled user-tower input gradient rows, the optimizer.
         Attention pooling: the slots' own gradient rows (``_history_backward`` wrote them) through the plain sort plan."""
@@ -1753,93 +1721,96 @@ class TwoTowerTrainer:
             gs = self.history_slot_grads
         else:
             gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
-        self.tables["history"].apply(cfg, gs, adam_step, lr=self.learning_rate)
+        EmbeddingTable.update(cfg, [self.tables["history"].opt_args(gs)], [], lr, adam_step)
 
-    def _apply_title_gradients(self, adam_step: int):
+    def _apply_title_gradients(self, lr: float, adam_step: int):
         """The title table's update: sort plan over the step's slot tokens, one launch that scales the item-tower input gradient
         rows by the bags' pooling scales and turns the plan's slot positions into bag indices, then the configured optimizer on
         [batch, dim] gradient rows (a slot's gradient is its bag's row: no per-token rows)."""
         cfg, plan = self.cfg, self.title_plan
         plan.run(self.title_ids, cfg.n_title_buckets)
         gs = plan.backward(self.item_tower.demb, self.title_inv, self.title_gs)
-        self.tables["title"].apply(cfg, gs, adam_step, lr=self.learning_rate)
+        EmbeddingTable.update(cfg, [self.tables["title"].opt_args(gs)], [], lr, adam_step)
 
-    def _apply_table_gradients(self, step_ids=None):
-        cfg, lr = self.cfg, self.learning_rate
-        if cfg.optimizer == "adam":  # every table and every tower segment in ONE call (two launches), from the sort plans
-            ops.adam_step_(self._adam_tables, self._adam_segs, ops.AdamHyper(lr, cfg.adam_beta1, cfg.adam_beta2,
-                                                                             cfg.adam_epsilon, self.adam_step))
-            self.adam_step += 1
-            return
-        if cfg.optimizer == "rowwise_adagrad":  # user + item table and every dense segment in ONE call, from the sort plans
-            ops.rowwise_adagrad_step_(self._rowwise_tables, self._segs, lr, cfg.adagrad_epsilon)
-            if self.cat_table is not None:
-                self.tables["cat"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
-            return
-        if step_ids is not None:     # sort + sparse update of every table + dense update: ONE launch, straight from the raw ids
-            tables = [(table, accum, grads, ids, plan) for (table, accum, grads, plan), ids in zip(self._opt_tables, step_ids)]
+    def _apply_table_gradients(self, step_ids, lr: float, adam_step: int):
+        """The update of the pairs' id tables and of the dense parameters.  In-batch SGD / Adagrad keep their fused forms, whose
+        grouping was measured: sort + every table + the dense segments in ONE launch straight from the raw ids (``step_ids``),
+        the same from the sort plans, or (fuse_optimizer = False) the dense launch and the user + item launch.  Everything else
+        - lazy Adam, row-wise Adagrad, mixed sampling, the category table behind the unfused pair - is the plan-fed calls of
+        ``_table_calls``, in front of which SGD / Adagrad update the dense segments in a launch of their own."""
+        cfg, tabs = self.cfg, self._opt_tables
+        fused = self._riding is None and not self.mixed
+        if fused and step_ids is not None:
+            tables = [(table, accum, grads, ids, plan) for (table, accum, grads, plan), ids in zip(tabs, step_ids)]
             ops.optimizer_step_ids_(cfg.optimizer, tables, self._segs, lr, cfg.adagrad_epsilon)
             return
-        if self.fuse_optimizer:      # sparse update of every table + dense update of every tower segment: one launch
-            ops.optimizer_step_(cfg.optimizer, self._opt_tables, self._segs, lr, cfg.adagrad_epsilon)
+        if fused and self.fuse_optimizer:
+            ops.optimizer_step_(cfg.optimizer, tabs, self._segs, lr, cfg.adagrad_epsilon)
             return
-        ops.dense_update_(self._segs, cfg.optimizer, lr, cfg.adagrad_epsilon)
-        ops.sparse_update2_(cfg.optimizer, *self._opt_tables[0], *self._opt_tables[1], lr, cfg.adagrad_epsilon)
-        if self.cat_table is not None:
-            self.tables["cat"].apply(cfg, self.item_tower.demb, self.adam_step, lr=lr)
+        if self._riding is None:
+            ops.dense_update_(self._segs, cfg.optimizer, lr, cfg.adagrad_epsilon)
+        if fused:
+            ops.sparse_update2_(cfg.optimizer, *tabs[0], *tabs[1], lr, cfg.adagrad_epsilon)
+        for tables, segs in self._table_calls:
+            EmbeddingTable.update(cfg, tables, segs, lr, adam_step)
 
     def step(self, user_ids: torch.Tensor, item_ids: torch.Tensor, **loss_kw) -> torch.Tensor:
         """One train step; returns the (device, unsynchronised) retrieval loss (SUM over the batch).
         With cfg.normalize_embeddings the step never takes the composite C call (``tt_train_step_f32`` cannot describe the two
         normalisation launches): it runs the Python sequence ``forward_backward`` + ``apply_gradients(step_ids=...)`` - the path
-        asymmetric towers take - with one launch after the towers' forward and one in front of their backward."""
-        if self.mixed:
-            return self._step_mixed(user_ids, item_ids, **loss_kw)
+        asymmetric towers take - with one launch after the towers' forward and one in front of their backward.
+        Mixed negative sampling: the sampler launch comes in front of everything else (the plans and both lookups read
+        ``cand_ids``), the sort plans always run, on the main stream, and the step is the Python sequence."""
+        cfg = self.cfg
         self._check_ratings(loss_kw.get("ratings"))
         if not self.rating_on:
             loss_kw.pop("ratings", None)
+        if self.mixed:
+            bad = [k for k, v in loss_kw.items() if v is not None and k not in ("sample_weight", "ratings")]
+            if bad:
+                raise ValueError(f"candidate_sampling='mixed': the trainer draws the candidates itself - {', '.join(sorted(bad))} cannot "
+                                 "be passed to step() (the correction comes from set_item_frequencies)")
         self._check_batch(user_ids, item_ids, loss_kw.get("category_ids"), loss_kw.get("sample_weight"),
                           loss_kw.get("candidate_sampling_probability"), loss_kw.get("candidate_ids"))
-        if self.freq_on:             # in front of everything else; its output is the step's cand_prob (the composite call's too)
+        if self.freq_on and not self.mixed:      # in front of everything else; its output is the step's cand_prob (the composite call's too)
             loss_kw["candidate_sampling_probability"] = self._update_frequencies(item_ids, loss_kw.get("candidate_sampling_probability"))
         # (never inside a graph capture: the poll queries an event recorded outside it and would bake a D2H copy into every replay)
         if self.flag_poll_every and self.step_index % self.flag_poll_every == 0 and not torch.cuda.is_current_stream_capturing():
             self.poll_ids()
+        item_side = item_ids
+        if self.mixed:                           # (with the streaming estimator the sampler call updates the sketch)
+            item_side = self.sample_candidates(item_ids)
+            loss_kw["_sampled"] = True
         # the sort plans depend on the ids only: one launch for all tables, in front of the forward pass (or beside it)
-        main = torch.cuda.current_stream()
-        plans, ids, rows = [self.user_plan, self.item_plan], [user_ids, item_ids], [self.cfg.n_users, self.cfg.n_items]
+        plans, ids, rows = [self.user_plan, self.item_plan], [user_ids, item_side], [cfg.n_users, cfg.n_items]
         if loss_kw.get("category_ids") is not None and self.cat_plan is not None:
-            plans.append(self.cat_plan); ids.append(loss_kw["category_ids"]); rows.append(self.cfg.n_category_buckets)
+            plans.append(self.cat_plan); ids.append(loss_kw["category_ids"]); rows.append(cfg.n_category_buckets)
         # fuse_sort: no plan launch at all - the optimizer launch's workgroups sort the ids of their own row range in LDS
         # and update exactly those rows (tt_optimizer_step_ids_f32; lists up to 65536 ids) - unless the batches are skewed
-        # (lazy Adam and row-wise Adagrad always take the sort plan: no composite call, no one-launch form and so no skew probe)
-        shape_ok = (self.cfg.optimizer not in ("adam", "rowwise_adagrad") and self.fuse_sort and self.fuse_optimizer
+        # (lazy Adam, row-wise Adagrad and mixed sampling always take the sort plan: no composite call, no one-launch form and so
+        # no skew probe)
+        shape_ok = (self._riding is None and not self.mixed and self.fuse_sort and self.fuse_optimizer
                     and user_ids.numel() <= ops.optimizer_ids_max_ids() and (self.cat_table is None) == (len(ids) == 2))
         if shape_ok:
             self._poll_skew(ids, rows)
         fused_sort = shape_ok and not self._skewed()
-        clip = self.cfg.global_clipnorm > 0      # the clip launches sit between the backward pass and the optimizer: never composite
-        if fused_sort:
-            if (not clip and self.use_composite and self.fuse_lookup and self.cfg.symmetric and not self.cfg.normalize_embeddings
-                    and not self.cfg.layer_norm and not self.rating_on and self.cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
-                return self._step_composite(ids, **loss_kw)
-            loss = self.forward_backward(user_ids, item_ids, **loss_kw)
-            if clip:
-                self.clip_gradients()
-            self.apply_gradients(step_ids=ids)
-            return loss
-        if self.plan_on_side_stream:
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):    # one launch for all tables (csrc/sort.hip)
+        # (the clip launches sit between the backward pass and the optimizer: never composite)
+        if (fused_sort and not cfg.global_clipnorm > 0 and self.use_composite and self.fuse_lookup and cfg.symmetric
+                and not cfg.normalize_embeddings and not cfg.layer_norm and not self.rating_on and cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
+            return self._step_composite(ids, **loss_kw)
+        side = self._side if (self.plan_on_side_stream and not fused_sort and not self.mixed) else None
+        if side is not None:
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):        # one launch for all tables (csrc/sort.hip)
                 ops.sparse_plan_batched(plans, ids, rows)
-        else:
+        elif not fused_sort:
             ops.sparse_plan_batched(plans, ids, rows)
         loss = self.forward_backward(user_ids, item_ids, **loss_kw)
-        if self.plan_on_side_stream:
-            main.wait_stream(self._side)
-        if clip:
-            self.clip_gradients()
-        self.apply_gradients()
+        if side is not None:
+            main.wait_stream(side)
+        self.clip_gradients()
+        self.apply_gradients(step_ids=ids if fused_sort else None)
         return loss
 
     def _build_composite(self):
@@ -1946,33 +1917,21 @@ class TwoTowerTrainer:
         if self.freq_on:             # estimated, not updated: a validation batch is no part of the training stream
             self._check_batch(item_ids)
             loss_kw["candidate_sampling_probability"] = self._read_frequencies(item_ids, loss_kw.get("candidate_sampling_probability"))
-        if self.mixed:           # the in-batch loss, as without sampling: the first batch_size rows of the item tower's buffers
-            self._check_batch(user_ids, item_ids)
-            b = cfg.batch_size
-            ops.embedding_gather(self.user_table, user_ids, out=ut.acts[0], oob_flag=self.oob)
-            ops.embedding_gather(self.item_table, item_ids, out=it.acts[0][:b], oob_flag=self.oob)
-            if self.title_table is not None:
-                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=item_ids, pooling=cfg.title_pooling,
-                                  out=it.acts[0][:b], accumulate=True, oob_flag=self.oob)
-            self._add_features((user_ids, ut.acts[0]), (item_ids, it.acts[0][:b]))
-            towers_forward((ut, it), rows=(b, b))
-            q, c = self._outputs_rows((ut, it), [b, b])
-            if self.rating_on:
-                self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
-            return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
-                                     sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
-                                     cand_ids=loss_kw.get("candidate_ids"), precision=cfg.scorer_precision)
-        lks = self._lookups(user_ids, item_ids, loss_kw.get("category_ids"))
+        # mixed sampling: the in-batch loss, as without sampling - a partial pass over the first batch_size rows of the item
+        # tower's buffers, never through a fused lookup
+        b = cfg.batch_size
+        rows = (b, b) if self.mixed else None
+        self._check_batch(user_ids, item_ids)
+        lks = None if self.mixed else self._lookups(user_ids, item_ids, loss_kw.get("category_ids"))
         if lks is None:
-            self._item_inputs(user_ids, item_ids, loss_kw.get("category_ids"))
-        towers_forward((ut, it), lookups=lks)
-        q, c = self._outputs(ut, it)
+            self._tower_inputs((user_ids, ut.acts[0]), (item_ids, it.acts[0][:b]), category_ids=loss_kw.get("category_ids"))
+        towers_forward((ut, it), lookups=lks, rows=rows)
+        q, c = self._outputs((ut, it), rows)
         if self.rating_on:
             self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
-        kw = dict(sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
-                  cand_ids=loss_kw.get("candidate_ids"))
         return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
-                                 precision=cfg.scorer_precision, **kw)
+                                 sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
+                                 cand_ids=loss_kw.get("candidate_ids"), precision=cfg.scorer_precision)
 
     def _rating_evaluate(self, q, c, ratings, sample_weight=None):
         """The head's forward launch on a validation batch; leaves ``rating_pred`` and two device scalars for the caller's
@@ -2003,20 +1962,11 @@ class TwoTowerTrainer:
         for s in range(0, n, b):
             e = min(s + b, n)
             m = e - s
-            if self.history_table is not None:
-                self._user_inputs(uid[s:e], ut.acts[0][:m])
-            else:
-                ops.embedding_gather(self.user_table, uid[s:e], out=ut.acts[0][:m], oob_flag=self.oob)
-            ops.embedding_gather(self.item_table, iid[s:e], out=it.acts[0][:m], oob_flag=self.oob)
-            if category_ids is not None:
-                ops.embedding_gather_add_(it.acts[0][:m], self.cat_table, category_ids[s:e].to(self.dev).contiguous(), self.oob)
-            if self.title_table is not None:
-                ops.embedding_bag(self.title_table, self.item_titles, bag_rows=iid[s:e], pooling=self.cfg.title_pooling,
-                                  out=it.acts[0][:m], accumulate=True, oob_flag=self.oob)
-            self._add_features(user=(uid[s:e], ut.acts[0][:m]), item=(iid[s:e], it.acts[0][:m]))
+            self._tower_inputs((uid[s:e], ut.acts[0][:m]), (iid[s:e], it.acts[0][:m]),
+                               category_ids=None if category_ids is None else category_ids[s:e].to(self.dev).contiguous())
             ut.forward()
             it.forward()
-            q, c = self._outputs(ut, it)
+            q, c = self._outputs((ut, it))
             self._rating_forward(q, c, rows=m, pred=out[s:e])
         return out
 
@@ -2033,6 +1983,9 @@ class TwoTowerTrainer:
         out = torch.empty(n, it.dims[-1], device=self.dev)
         for s in range(0, n, b):
             e = min(s + b, n)
+            # the one pass that does not build its rows through _tower_inputs: a chunk is a CONTIGUOUS row range, so the table
+            # rows are a copy and the bags pool a slice of the token matrix - no id tensor, no gather; what is summed is restated
+            # here (table row + category row + pooled titles), the numeric features come from the builder
             it.acts[0][:e - s].copy_(self.item_table[s:e])
             if item_category_ids is not None:
                 ops.embedding_gather_add_(it.acts[0][:e - s], self.cat_table, item_category_ids[s:e], self.oob)
@@ -2040,9 +1993,9 @@ class TwoTowerTrainer:
                 ops.embedding_bag(self.title_table, self.item_titles[s:e], pooling=self.cfg.title_pooling, out=it.acts[0][:e - s],
                                   accumulate=True, oob_flag=self.oob)
             if self.item_features is not None:
-                self._add_features(item=(torch.arange(s, e, dtype=torch.int64, device=self.dev), it.acts[0][:e - s]))
+                self._tower_inputs(item=(torch.arange(s, e, dtype=torch.int64, device=self.dev), it.acts[0][:e - s]), features_only=True)
             it.forward()
-            out[s:e].copy_(self._outputs(it)[0][:e - s])
+            out[s:e].copy_(self._outputs((it,))[0][:e - s])
         return out
 
     @torch.no_grad()
@@ -2057,13 +2010,9 @@ class TwoTowerTrainer:
         out = torch.empty(n, ut.dims[-1], device=self.dev)
         for s in range(0, n, b):
             e = min(s + b, n)
-            if self.history_table is not None:     # the full stored history: nothing is left out at inference
-                self._user_inputs(ids[s:e], ut.acts[0][:e - s])
-            else:
-                ops.embedding_gather(self.user_table, ids[s:e], out=ut.acts[0][:e - s], oob_flag=self.oob)
-            self._add_features(user=(ids[s:e], ut.acts[0][:e - s]))
+            self._tower_inputs(user=(ids[s:e], ut.acts[0][:e - s]))     # (the full stored history: nothing is left out at inference)
             ut.forward()
-            out[s:e].copy_(self._outputs(ut)[0][:e - s])
+            out[s:e].copy_(self._outputs((ut,))[0][:e - s])
         return out
 
     @torch.no_grad()
@@ -2074,15 +2023,11 @@ class TwoTowerTrainer:
         if corpus is None:
             corpus = self.item_corpus_embeddings()
         if self.history_table is not None or self.user_features is not None or self.cfg.cross_layers:
-            if self.history_table is not None:
-                self._user_inputs(user_ids, self.user_tower.acts[0])
-            else:
-                ops.embedding_gather(self.user_table, user_ids, out=self.user_tower.acts[0], oob_flag=self.oob)
-            self._add_features(user=(user_ids, self.user_tower.acts[0]))
+            self._tower_inputs(user=(user_ids, self.user_tower.acts[0]))
             self.user_tower.forward()
         else:
             self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
-        (q,) = self._outputs(self.user_tower)
+        (q,) = self._outputs((self.user_tower,))
         return metric.update_state(q, corpus, item_ids)
 
     # ------------------------------------------------------------------ checkpoint
