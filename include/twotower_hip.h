@@ -1151,6 +1151,37 @@ int tt_ivf_search_i8_f32(const float* q, int64_t nq, const float* centroids, int
                          const int64_t* excl_idx, void* workspace, int64_t workspace_bytes, float* out_scores, int64_t* out_idx,
                          tt_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Time-of-interaction context (added to v10: new symbols only, the version is unchanged; csrc/time_context.hip).
+ * timestamps int64 [n]: whole seconds since the Unix epoch, UTC; INT64_MIN = no timestamp.  field_mask: bit 0 hour (24 rows),
+ * bit 1 day of week (7), bit 2 month (12), bit 3 period (buckets rows, 1..4096; buckets must be 0 without bit 3).  The F enabled
+ * fields, in that order, own consecutive row blocks of ONE table [R, dim] f32, R = the sum of their row counts (table_rows must
+ * equal it).  Row of a pair within a field's block - integer arithmetic, floor division, so negative timestamps work:
+ *   days = floor(t / 86400);  hour = (t - 86400 days) / 3600;  day of week = (days + 3) mod 7 (Monday 0; 1970-01-01: Thursday)
+ *   month - 1 by civil-from-days: z = days + 719468, era = floor(z / 146097), doe = z - 146097 era,
+ *     yoe = (doe - doe/1460 + doe/36524 - doe/146096) / 365, doy = doe - (365 yoe + yoe/4 - yoe/100), mp = (5 doy + 2) / 153,
+ *     month = mp < 10 ? mp + 3 : mp - 9
+ *   period = floor(clamp(t - time_min, 0, span) * buckets / (span + 1)), span = time_max - time_min (0 <= span < 2^40)
+ * Forward, one launch:  s = ((row_0 + row_1) + row_2) + row_3 over the enabled fields in order (a pair without a timestamp:
+ * s = +0, its indices are -1), then
+ *   accumulate 0, no base: out[p] = s;   accumulate 1: out[p] = out[p] + s;
+ *   base_table [base_rows, dim] + base_ids [n] (both or neither; accumulate must be 0): out[p] = base_table[base_ids[p]] + s,
+ *   a base id outside [0, base_rows) giving a zero row and (unless it is -1) setting *oob_flag: tt_embedding_gather_f32's rule.
+ * idx_out int32 [n, F] (may be NULL): the F indices of every pair, for the backward launch.  dim a multiple of 4 in 4..512;
+ * table, out and base_table 16-byte aligned; n < 2^31.  n == 0 launches nothing.  Launches only.
+ * Backward, one launch, NO atomics: grad[off_f + r][c] = sum of dy[p][c] over the pairs p with idx[p, f] == r, for every
+ * field f and every row r of it - EVERY row of grad [R, dim] is written in full (a row nobody hit: zeros; the caller does not
+ * clear it; n == 0 writes all zeros).  An index that is negative or >= the field's row count matches nothing.  The order of
+ * the sum is a fixed function of (n, idx), bit-identical across runs: 32 sub-sums, sub-sum g over the matching positions
+ * p = g, g + 32, g + 64, ... in ascending order starting from +0, then (((s_0 + s_1) + s_2) + ... + s_31).
+ * dy and grad 16-byte aligned.  Anything else is TT_ERR_INVALID_ARG before any launch.                                     */
+int tt_time_context_fwd_f32(const int64_t* timestamps, int64_t n, const float* table, int64_t table_rows, int32_t dim,
+                            int32_t field_mask, int32_t buckets, int64_t time_min, int64_t time_max,
+                            float* out, int32_t accumulate, const float* base_table, int64_t base_rows,
+                            const int64_t* base_ids, int32_t* idx_out, int32_t* oob_flag, tt_stream_t stream);
+int tt_time_context_bwd_f32(const int32_t* idx, const float* dy, int64_t n, int32_t dim, int32_t field_mask,
+                            int32_t buckets, int64_t table_rows, float* grad, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

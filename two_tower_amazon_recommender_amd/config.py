@@ -84,6 +84,39 @@ def layer_norm_from_dict(doc: dict) -> dict:
     return {"enabled": enabled, "epsilon": float(eps)}
 
 
+def time_features_from_dict(doc: dict) -> dict:
+    """{fields, buckets} of the optional ``model.features.time`` block (not in the reference's schema; its
+    ``create_temporal_features`` is the model's input here): ``fields`` a list out of hour, day_of_week, month, period - kept in
+    that order - and ``buckets``, the rows of the period field (1..4096, given exactly when ``period`` is on).  Without the
+    block: no fields.  The range the periods cut (time_min, time_max) comes from the training data: train.py sets it."""
+    block = ((doc.get("model") or {}).get("features") or {}).get("time")
+    if block is None:
+        return {"fields": (), "buckets": 0}
+    if not isinstance(block, dict):
+        raise ValueError("model.features.time must be a mapping {fields, buckets}")
+    unknown = sorted(set(block) - {"fields", "buckets"})
+    if unknown:
+        raise ValueError(f"model.features.time: unknown keys {unknown} (known: ['fields', 'buckets'])")
+    return check_time_features(block.get("fields") or (), block.get("buckets", 0), "model.features.time")
+
+
+def check_time_features(fields, buckets, where: str) -> dict:
+    """The validated {fields (in the fixed order), buckets} of a time-feature selection (the YAML block's or the CLI's)."""
+    from .ops import MAX_TIME_BUCKETS, TIME_FIELDS
+    if isinstance(fields, str) or not isinstance(fields, (list, tuple)):
+        raise ValueError(f"{where}: fields must be a list out of {list(TIME_FIELDS)}, got {fields!r}")
+    bad = [f for f in fields if f not in TIME_FIELDS]
+    if bad or len(set(fields)) != len(fields):
+        raise ValueError(f"{where}: unknown or repeated fields {bad or list(fields)} (known: {list(TIME_FIELDS)})")
+    if isinstance(buckets, bool) or not isinstance(buckets, int) or not 0 <= buckets <= MAX_TIME_BUCKETS:
+        raise ValueError(f"{where}: buckets must be an int in 1..{MAX_TIME_BUCKETS}, got {buckets!r}")
+    if "period" in fields and buckets < 1:
+        raise ValueError(f"{where}: the 'period' field needs buckets (1..{MAX_TIME_BUCKETS})")
+    if "period" not in fields and buckets:
+        raise ValueError(f"{where}: buckets is given without the 'period' field")
+    return {"fields": tuple(f for f in TIME_FIELDS if f in fields), "buckets": buckets}
+
+
 LR_SCHEDULE_KEYS = ("warmup_steps", "decay", "decay_steps", "min_ratio")
 
 
@@ -183,7 +216,10 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     opt = optimization_from_dict(doc)
     # likewise model.retrieval.sampling_bias {estimator, alpha, hashes, slots} - the streaming frequency estimator
     bias = sampling_bias_from_dict(doc)
+    # likewise model.features.time {fields, buckets} - the time-of-interaction context features
+    when = time_features_from_dict(doc)
     cfg = TwoTowerConfig(
+        time_fields=when["fields"], time_buckets=when["buckets"],
         sampling_bias_estimator=bias["estimator"], freq_alpha=bias["alpha"], freq_hashes=bias["hashes"], freq_slots=bias["slots"],
         global_clipnorm=opt["global_clipnorm"], lr_warmup_steps=opt["warmup_steps"], lr_decay=opt["decay"],
         lr_decay_steps=0 if opt["decay_steps"] == "auto" else opt["decay_steps"], lr_min_ratio=opt["min_ratio"],

@@ -1306,6 +1306,114 @@ def dense_features_bwd(*problems):
     return tuple(outs)
 
 
+# ----------------------------------------------------------------------------- time-of-interaction context features
+TIME_FIELDS = ("hour", "day_of_week", "month", "period")       # the fixed field order (bit f of the C ABI's field_mask)
+TIME_FIELD_ROWS = {"hour": 24, "day_of_week": 7, "month": 12}  # "period": the caller's bucket count
+TIME_MISSING = -2 ** 63                                         # a pair without a timestamp
+MAX_TIME_BUCKETS = 4096
+
+
+def _time_fields(fields, buckets: int):
+    """The validated (fields in the fixed order, field_mask) of a field selection."""
+    fields = tuple(fields)
+    bad = [f for f in fields if f not in TIME_FIELDS]
+    if bad or not fields or len(set(fields)) != len(fields):
+        raise ValueError(f"time fields must be a non-empty subset of {TIME_FIELDS} without repeats, got {fields!r}")
+    if isinstance(buckets, bool) or not isinstance(buckets, int):
+        raise ValueError("time buckets must be an int")
+    if "period" in fields and not 1 <= buckets <= MAX_TIME_BUCKETS:
+        raise ValueError(f"the 'period' field needs buckets in 1..{MAX_TIME_BUCKETS}, got {buckets}")
+    if "period" not in fields and buckets != 0:
+        raise ValueError("buckets must be 0 without the 'period' field")
+    ordered = tuple(f for f in TIME_FIELDS if f in fields)
+    return ordered, sum(1 << TIME_FIELDS.index(f) for f in ordered)
+
+
+def time_field_layout(fields, buckets: int = 0):
+    """(offsets, R) of the time table: ``offsets[f]`` = first row of enabled field f's block, in the fixed field order (hour 24
+    rows, day_of_week 7, month 12, period ``buckets``); R = the rows of the table.  A host function (no device, no library)."""
+    ordered, _ = _time_fields(fields, buckets)
+    offsets, r = {}, 0
+    for f in ordered:
+        offsets[f] = r
+        r += buckets if f == "period" else TIME_FIELD_ROWS[f]
+    return offsets, r
+
+
+def _chk_time_range(time_min: int, time_max: int):
+    for v, name in ((time_min, "time_min"), (time_max, "time_max")):
+        if isinstance(v, bool) or not isinstance(v, int) or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError(f"{name} must be an int64")
+    if time_min > time_max or time_max - time_min >= 2 ** 40:
+        raise ValueError("need time_min <= time_max and time_max - time_min < 2^40")
+
+
+def time_context(timestamps: torch.Tensor, table: torch.Tensor, fields, buckets: int, time_min: int, time_max: int,
+                 out: torch.Tensor | None = None, accumulate: bool = False, base=None, idx_out: torch.Tensor | None = None,
+                 oob_flag: torch.Tensor | None = None) -> torch.Tensor:
+    """out[p] (+)= the sum, in field order, of the time table's rows a pair's timestamp picks (``tt_time_context_fwd_f32``).
+    ``timestamps`` [n] int64 (whole seconds since the epoch, UTC; ``TIME_MISSING``: adds nothing, indices -1); ``table``
+    [R, dim] f32 (``time_field_layout``); ``base`` = (base_table [rows, dim], base_ids [n] int64): out[p] = base_table[base_ids[p]]
+    + the sum, in ONE launch (in the place of ``accumulate``; an out-of-range base id: a zero row and ``oob_flag``);
+    ``idx_out`` [n, F] int32: the F row indices of every pair, for ``time_context_bwd``."""
+    ordered, mask = _time_fields(fields, buckets)
+    _chk_time_range(time_min, time_max)
+    _chk(timestamps, torch.int64, "timestamps", 1)
+    _chk(table, torch.float32, "table", 2)
+    n, (rows, d) = timestamps.numel(), table.shape
+    if rows != time_field_layout(ordered, buckets)[1]:
+        raise RuntimeError(f"time_context: the table must have {time_field_layout(ordered, buckets)[1]} rows for {ordered}, got {rows}")
+    if base is not None and accumulate:
+        raise ValueError("time_context: the base row takes the place of out's row: accumulate must be False with a base")
+    if out is None:
+        if accumulate:
+            raise ValueError("time_context: accumulate=True adds into `out`, which must be given")
+        out = torch.empty((n, d), dtype=torch.float32, device=table.device)
+    _chk(out, torch.float32, "out", 2)
+    if tuple(out.shape) != (n, d):
+        raise RuntimeError(f"time_context: out must be [{n}, {d}] (n, dim), got {tuple(out.shape)}")
+    base_table = base_ids = None
+    if base is not None:
+        base_table, base_ids = base
+        _chk(base_table, torch.float32, "base_table", 2)
+        _chk(base_ids, torch.int64, "base_ids", 1)
+        if base_table.shape[1] != d or base_ids.numel() != n:
+            raise RuntimeError(f"time_context: base must be ([rows, {d}] f32, [{n}] int64), got {tuple(base_table.shape)} and "
+                               f"{tuple(base_ids.shape)}")
+    if idx_out is not None:
+        _chk(idx_out, torch.int32, "idx_out", 2)
+        if tuple(idx_out.shape) != (n, len(ordered)):
+            raise RuntimeError(f"time_context: idx_out must be [{n}, {len(ordered)}] (n, fields), got {tuple(idx_out.shape)}")
+    if oob_flag is not None:
+        _chk(oob_flag, torch.int32, "oob_flag")
+    _lib.check(_lib.load().tt_time_context_fwd_f32(_p(timestamps), n, _p(table), rows, d, mask, buckets, time_min, time_max, _p(out),
+                                                   int(bool(accumulate)), _p(base_table),
+                                                   0 if base_table is None else base_table.shape[0], _p(base_ids), _p(idx_out),
+                                                   _p(oob_flag), _stream()), "tt_time_context_fwd_f32")
+    return out
+
+
+def time_context_bwd(idx: torch.Tensor, dy: torch.Tensor, fields, buckets: int, grad: torch.Tensor | None = None) -> torch.Tensor:
+    """The time table's fully reduced gradient [R, dim] from the forward's ``idx`` [n, F] int32 and ``dy`` [n, dim]
+    (``tt_time_context_bwd_f32``): one launch, no atomics, every row written (a row nobody hit: zeros - ``grad`` need not be
+    cleared), the summation order a fixed function of (n, idx)."""
+    ordered, mask = _time_fields(fields, buckets)
+    rows = time_field_layout(ordered, buckets)[1]
+    _chk(idx, torch.int32, "idx", 2)
+    _chk(dy, torch.float32, "dy", 2)
+    n, d = dy.shape
+    if tuple(idx.shape) != (n, len(ordered)):
+        raise RuntimeError(f"time_context_bwd: idx must be [{n}, {len(ordered)}] (n, fields), got {tuple(idx.shape)}")
+    if grad is None:
+        grad = torch.empty((rows, d), dtype=torch.float32, device=dy.device)
+    _chk(grad, torch.float32, "grad", 2)
+    if tuple(grad.shape) != (rows, d):
+        raise RuntimeError(f"time_context_bwd: grad must be [{rows}, {d}] (R, dim), got {tuple(grad.shape)}")
+    _lib.check(_lib.load().tt_time_context_bwd_f32(_p(idx), _p(dy), n, d, mask, buckets, rows, _p(grad), _stream()),
+               "tt_time_context_bwd_f32")
+    return grad
+
+
 # ----------------------------------------------------------------------------- rating-prediction head
 RATING_DIMS = (32, 64, 128, 256)
 

@@ -61,7 +61,15 @@ def parse(argv=None):
     ap.add_argument("--rank-by", choices=("score", "rating"), default="score",
                     help="score: the retrieval order (default); rating: each user's k retrieved items re-ordered by the "
                          "predicted rating, best first (implies --predict-ratings)")
+    ap.add_argument("--at-time", default=None, metavar="SECONDS|YYYY-MM-DD",
+                    help="models trained with --time-features: the time the recommendations are asked for - whole seconds since the "
+                         "epoch, or a UTC date (its midnight); default: the checkpoint's time_max, the newest training timestamp")
     args = ap.parse_args(argv)
+    if args.at_time is not None:
+        try:
+            args.at_time = parse_time(args.at_time)
+        except ValueError:
+            ap.error(f"--at-time must be whole seconds since the epoch or a date YYYY-MM-DD, got {args.at_time!r}")
     args.predict_ratings = args.predict_ratings or args.rank_by == "rating"
     if not 1 <= args.k <= MAX_K:
         ap.error(f"--k must be in [1, {MAX_K}], got {args.k}")
@@ -91,6 +99,16 @@ def parse(argv=None):
     if not os.path.exists(args.checkpoint):
         ap.error(f"--checkpoint {args.checkpoint}: no such file")
     return args
+
+
+def parse_time(text: str) -> int:
+    """Whole seconds since the epoch from "SECONDS" or a UTC date "YYYY-MM-DD" (its midnight)."""
+    import datetime
+    try:
+        return int(text)
+    except ValueError:
+        day = datetime.date.fromisoformat(text)
+        return (day - datetime.date(1970, 1, 1)).days * 86400
 
 
 def seen_csr(user_idx: np.ndarray, item_idx: np.ndarray, n_users: int):
@@ -131,6 +149,9 @@ def main(argv=None) -> int:
     if args.predict_ratings and not cfg.rating_weight > 0:
         raise SystemExit(f"{args.checkpoint}: the model has no rating head (trained without --rating-weight): "
                          "--predict-ratings / --rank-by rating cannot be answered")
+    if args.at_time is not None and not cfg.time_fields:
+        raise SystemExit(f"{args.checkpoint}: the model has no time features (trained without --time-features): --at-time has no meaning")
+    at_time = None if not cfg.time_fields else cfg.time_max if args.at_time is None else args.at_time
     cfg.dropout_rate = 0.0
     cfg.candidate_sampling, cfg.n_sampled_negatives = "in_batch", 0      # serving scores the whole corpus: nothing is sampled
     cfg.sampling_bias_estimator = "none"                                  # ... and nothing is corrected: no sketch is allocated
@@ -162,14 +183,14 @@ def main(argv=None) -> int:
         if args.nlist > cfg.n_items:
             raise SystemExit(f"--nlist {args.nlist} exceeds the model's {cfg.n_items} items")
         if args.index == "ivf":
-            bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat)
+            bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat, at_time)
         else:
             bf = Int8IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed,
-                         rerank=args.rerank).index_from_trainer(trainer, item_cat)
+                         rerank=args.rerank).index_from_trainer(trainer, item_cat, at_time)
     elif args.index == "int8":
-        bf = Int8BruteForce(k=k, rerank=args.rerank).index_from_trainer(trainer, item_cat)
+        bf = Int8BruteForce(k=k, rerank=args.rerank).index_from_trainer(trainer, item_cat, at_time)
     else:
-        bf = BruteForce(k=k).index_from_trainer(trainer, item_cat)
+        bf = BruteForce(k=k).index_from_trainer(trainer, item_cat, at_time)
     seen = seen_csr(user_idx, item_idx, cfg.n_users) if args.exclude_seen else None
 
     cols = {"user_idx": [], "rank": [], "item_idx": [], "score": []}
@@ -192,7 +213,8 @@ def main(argv=None) -> int:
     out = {name: np.concatenate(v) if v else np.zeros(0) for name, v in cols.items()}
     if args.predict_ratings and len(out["user_idx"]):
         ui, ii = torch.from_numpy(out["user_idx"]).to(dev), torch.from_numpy(out["item_idx"].astype(np.int64)).to(dev)
-        pred = trainer.predict_ratings(ui, ii, None if item_cat is None else item_cat[ii]).cpu().numpy()
+        when = None if at_time is None else torch.full((len(ui),), at_time, dtype=torch.int64, device=dev)
+        pred = trainer.predict_ratings(ui, ii, None if item_cat is None else item_cat[ii], timestamps=when).cpu().numpy()
         out["predicted_rating"] = pred
         if args.rank_by == "rating":    # inside every user's rows: best predicted rating first, ties in retrieval order
             grp = np.concatenate(group)

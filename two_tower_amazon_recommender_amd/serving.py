@@ -32,6 +32,26 @@ import torch
 from . import ops
 
 
+def _trainer_query_model(trainer, at_time):
+    """The default query model of ``index_from_trainer``: the user tower, with the time context where the model has one."""
+    if not getattr(trainer.cfg, "time_fields", ()):
+        if at_time is not None:
+            raise ValueError("index_from_trainer: at_time was given but the model has no time features (cfg.time_fields == ())")
+        return trainer.user_embeddings
+    if at_time is not None:
+        at = int(at_time)
+
+        def as_of(user_ids):
+            return trainer.user_embeddings(user_ids, timestamps=torch.full((user_ids.numel(),), at, dtype=torch.int64, device=trainer.dev))
+        return as_of
+
+    def with_timestamps(queries):
+        if not isinstance(queries, (tuple, list)) or len(queries) != 2:
+            raise ValueError("the model has time features: a query is (user_ids, timestamps [n] int64) - or index with at_time=")
+        return trainer.user_embeddings(queries[0], timestamps=queries[1])
+    return with_timestamps
+
+
 class BruteForce:
     """Exact top-k retrieval index.  ``query_model``: a callable mapping the queries passed to ``__call__`` to
     [nq, D] f32 embeddings (None: the queries ARE the embeddings).  ``k``: default number of results."""
@@ -59,12 +79,14 @@ class BruteForce:
         self._identifiers = identifiers
         return self
 
-    def index_from_trainer(self, trainer, item_category_ids: torch.Tensor | None = None) -> "BruteForce":
+    def index_from_trainer(self, trainer, item_category_ids: torch.Tensor | None = None, at_time: int | None = None) -> "BruteForce":
         """Index the trainer's whole item corpus (``item_corpus_embeddings``); unless a query model was given, queries
-        are user ids run through the user tower (``user_embeddings``)."""
+        are user ids run through the user tower (``user_embeddings``).  A model with time features (cfg.time_fields): with
+        ``at_time`` (whole seconds since the epoch) the queries stay plain user ids, scored "as of" that second; without it
+        a query is the pair (user_ids, timestamps [n] int64)."""
         self.index(trainer.item_corpus_embeddings(item_category_ids))
         if self.query_model is None:
-            self.query_model = trainer.user_embeddings
+            self.query_model = _trainer_query_model(trainer, at_time)
         return self
 
     def _workspace(self, nq: int, k: int) -> torch.Tensor:

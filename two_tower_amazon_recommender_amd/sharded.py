@@ -457,6 +457,10 @@ class ShardedTwoTowerTrainer:
             # the sketch would have to see every rank's positives each step (an all-gather of the ids) to count one stream
             raise NotImplementedError("the streaming frequency estimator (sampling_bias_estimator='streaming') is not implemented "
                                       "for the row-sharded trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "time_fields", ()):
+            # the time table's gradient would join the dense all-reduce and the timestamps travel with the exchanged user rows
+            raise NotImplementedError("the time context features (time_fields) are not implemented for the row-sharded trainer "
+                                      "(ShardedTwoTowerTrainer): use TwoTowerTrainer")
         if getattr(cfg, "global_clipnorm", 0.0) > 0:
             # the norm would have to be all-reduced over the ranks' table shards between the gradient exchange and the update
             raise NotImplementedError("gradient clipping (global_clipnorm > 0) is not implemented for the row-sharded trainer "

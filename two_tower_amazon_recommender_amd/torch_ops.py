@@ -12,6 +12,7 @@ is no CPU implementation: the ops are registered for ``device_types="cuda"`` onl
     x, w, pooled, slot_ids = torch.ops.twotower.history_attention(hist_table, histories, user_ids, item_ids, user_table, user_ids,
                                                                   attn)        # autograd w.r.t. attn = [query | recency bias]
     x = x + torch.ops.twotower.dense_features(feat, ids, mean, inv_std, proj, clip)   # autograd w.r.t. proj
+    x = x + torch.ops.twotower.time_context(timestamps, time_table, "hour,day_of_week", 0, t_min, t_max)   # autograd w.r.t. time_table
     y    = torch.ops.twotower.dense_fwd(x, w, b, relu)                  # autograd through twotower::dense_bwd
     torch.ops.twotower.sparse_update_(table, accum, grads, ids, "adagrad", lr, eps)
     torch.ops.twotower.sparse_adam_(table, exp_avg, exp_avg_sq, grads, ids, step, lr, 0.9, 0.999, 1e-7)
@@ -600,6 +601,51 @@ def _features_backward(ctx, dy):
 dense_features.register_autograd(_features_backward, setup_context=_features_setup)
 
 
+# --------------------------------------------------------------------------------------------- time-of-interaction context
+@torch.library.custom_op(f"{NS}::time_context", mutates_args=(), device_types="cuda")
+def time_context(timestamps: Tensor, table: Tensor, fields: str, buckets: int, time_min: int, time_max: int) -> Tensor:
+    """out[p] = the sum, in field order, of the rows of ``table`` [R, dim] that ``timestamps[p]`` (int64 seconds since the epoch)
+    picks (``ops.time_context``).  ``fields``: the enabled fields, comma separated ("hour,day_of_week,month,period").  Autograd
+    with respect to ``table``, through ``twotower::time_context_bwd``."""
+    return ops.time_context(timestamps.contiguous(), table.contiguous(), tuple(fields.split(",")), buckets, time_min, time_max)
+
+
+@time_context.register_fake
+def _(timestamps, table, fields, buckets, time_min, time_max):
+    return table.new_empty((timestamps.shape[0], table.shape[1]))
+
+
+@torch.library.custom_op(f"{NS}::time_context_bwd", mutates_args=(), device_types="cuda")
+def time_context_bwd(timestamps: Tensor, table: Tensor, dy: Tensor, fields: str, buckets: int, time_min: int, time_max: int) -> Tensor:
+    """dL/dtable [R, dim] of ``time_context`` given dL/dout: the row indices are recomputed by the forward launch (the forward op
+    keeps nothing but its inputs), the backward launch writes the fully reduced gradient."""
+    f = tuple(fields.split(","))
+    idx = torch.empty((timestamps.shape[0], len(f)), dtype=torch.int32, device=table.device)
+    ops.time_context(timestamps.contiguous(), table.contiguous(), f, buckets, time_min, time_max, idx_out=idx)
+    return ops.time_context_bwd(idx, dy.contiguous(), f, buckets)
+
+
+@time_context_bwd.register_fake
+def _(timestamps, table, dy, fields, buckets, time_min, time_max):
+    return torch.empty_like(table, memory_format=torch.contiguous_format)
+
+
+def _time_setup(ctx, inputs, output):
+    timestamps, table, ctx.fields, ctx.buckets, ctx.time_min, ctx.time_max = inputs
+    ctx.save_for_backward(timestamps, table)
+
+
+def _time_backward(ctx, dy):
+    timestamps, table = ctx.saved_tensors
+    dtable = None
+    if ctx.needs_input_grad[1]:
+        dtable = torch.ops.twotower.time_context_bwd(timestamps, table, dy, ctx.fields, ctx.buckets, ctx.time_min, ctx.time_max)
+    return None, dtable, None, None, None, None
+
+
+time_context.register_autograd(_time_backward, setup_context=_time_setup)
+
+
 # --------------------------------------------------------------------------------------------- rating-prediction head
 @torch.library.custom_op(f"{NS}::rating_head", mutates_args=(), device_types="cuda")
 def rating_head(q: Tensor, c: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor) -> Tensor:
@@ -817,4 +863,4 @@ def _(sketch, ids, n_update, step, alpha, n_items, seed, tensor_id, sampler_prob
 
 
 OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
-       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")
+       "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "time_context", "time_context_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")

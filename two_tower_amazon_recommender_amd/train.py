@@ -99,6 +99,13 @@ def parse(argv=None):
                     help="an external [n_users, F] f32 matrix (F in 1..32) of numeric user features; takes precedence over "
                          "rating_stats on the user side")
     ap.add_argument("--item-features", default=None, metavar="FILE.npy", help="likewise [n_items, F] for the item side")
+    ap.add_argument("--time-features", default=None, metavar="FIELDS",
+                    help="add the time-of-interaction context features: a comma-separated subset of hour,day_of_week,month,period "
+                         "(or none) - the rows the pair's timestamp (column timestamp) picks in one small trained table are added to "
+                         "the user tower input (overrides model.features.time.fields); single-GPU trainer only")
+    ap.add_argument("--time-buckets", type=int, default=None, metavar="N",
+                    help="rows of the period field: N equal periods of the training split's time range (1..4096; later pairs land in "
+                         "the last one; overrides model.features.time.buckets)")
     ap.add_argument("--rating-weight", type=float, default=None, metavar="W",
                     help="add the rating-prediction head (joint retrieval + ranking): one hidden ReLU layer over the pair's two "
                          "tower outputs trained with MSE on the rating column, total loss = retrieval + W * MSE (overrides "
@@ -208,6 +215,17 @@ def main(argv=None) -> int:
         raise SystemExit("--layer-norm-epsilon needs --layer-norm (or model.layer_norm.enabled)")
     if distributed and layer_norm:
         raise NotImplementedError("layer normalisation is not implemented for the row-sharded (--distributed) trainer")
+    when = cfgmod.time_features_from_dict(doc)
+    if args.time_features is not None or args.time_buckets is not None:
+        fields = when["fields"] if args.time_features is None else \
+            [f for f in args.time_features.split(",") if f and f != "none"]
+        buckets = args.time_buckets if args.time_buckets is not None else when["buckets"] if "period" in fields else 0
+        try:
+            when = cfgmod.check_time_features(list(fields), buckets, "--time-features / --time-buckets")
+        except ValueError as e:
+            raise SystemExit(str(e))
+    if distributed and when["fields"]:
+        raise NotImplementedError("the time context features are not implemented for the row-sharded (--distributed) trainer")
     sched = cfgmod.optimization_from_dict(doc)
     for key, arg in (("global_clipnorm", args.global_clipnorm), ("warmup_steps", args.lr_warmup_steps), ("decay", args.lr_decay),
                      ("min_ratio", args.lr_min_ratio)):
@@ -321,6 +339,28 @@ def main(argv=None) -> int:
     tr_idx, va_idx = perm[n_val:], perm[:n_val]
     log.info("users %d items %d interactions %d (train %d, val %d); batch %d; optimizer %s", n_users, n_items, n,
              len(tr_idx), len(va_idx), cfg.batch_size, cfg.optimizer)
+    # time context features: every pair's int64 timestamp; the periods cut the range of the TRAINING split's finite timestamps
+    cfg.time_fields, cfg.time_buckets = when["fields"], when["buckets"]
+    stamps = None
+    if cfg.time_fields:
+        if args.synthetic:                  # synthetic interactions carry no timestamp: five years from 2001-09-09, from the run's seed
+            from . import ops
+            t = torch.empty(n, dtype=torch.int64, device=torch.device(args.device))
+            ops.fill_ids_(t, args.seed, 61, 5 * 365 * 86400, "U")
+            stamps = t.cpu().numpy() + 1_000_000_000
+        else:
+            ts = datamod.read_timestamps(args.data)
+            if ts is None:
+                raise SystemExit(f"--time-features: {args.data} has no column {datamod.TIMESTAMP_COLUMN!r}")
+            stamps = datamod.timestamps_to_int64(ts)
+        seen = stamps[tr_idx][stamps[tr_idx] != datamod.TIME_MISSING]
+        if not seen.size:
+            raise SystemExit("--time-features: no training pair has a finite timestamp")
+        cfg.time_min, cfg.time_max = int(seen.min()), int(seen.max())
+        if cfg.time_max - cfg.time_min >= 2 ** 40:
+            raise SystemExit(f"--time-features: the training timestamps span {cfg.time_max - cfg.time_min} s; whole seconds since the "
+                             "epoch are expected (a range below 2^40)")
+        log.info("time features %s (period buckets %d) over [%d, %d]", cfg.time_fields, cfg.time_buckets, cfg.time_min, cfg.time_max)
     histories = None
     if cfg.user_history_len:                # the TRAINING pairs only, in the order of the timestamps (else: of the file)
         rows = np.sort(tr_idx)
@@ -394,10 +434,12 @@ def main(argv=None) -> int:
         return x.item()
     train_it = datamod.BatchIterator(user_idx[tr_idx], item_idx[tr_idx], cfg.batch_size, trainer.dev, args.seed,
                                      category_bucket=None if cat is None else cat[tr_idx],
-                                     ratings=rating[tr_idx] if cfg.rating_weight > 0 else None)
+                                     ratings=rating[tr_idx] if cfg.rating_weight > 0 else None,
+                                     timestamps=None if stamps is None else stamps[tr_idx])
     val_it = datamod.BatchIterator(user_idx[va_idx], item_idx[va_idx], cfg.batch_size, trainer.dev, args.seed, shuffle=False,
                                    category_bucket=None if cat is None else cat[va_idx],
-                                   ratings=rating[va_idx] if cfg.rating_weight > 0 else None)
+                                   ratings=rating[va_idx] if cfg.rating_weight > 0 else None,
+                                   timestamps=None if stamps is None else stamps[va_idx])
 
     item_prob = None
     mixed = cfg.candidate_sampling == "mixed"
@@ -414,6 +456,8 @@ def main(argv=None) -> int:
 
     def kw(batch):
         k = {"category_ids": batch[2]} if cat is not None else {}
+        if stamps is not None:              # the pairs' timestamps come last
+            k["timestamps"], batch = batch[-1], batch[:-1]
         if cfg.rating_weight > 0:           # the pairs' ratings ride behind the ids (NaN: no label)
             k["ratings"] = batch[-1]
         if item_prob is not None:
@@ -476,7 +520,7 @@ def main(argv=None) -> int:
             item_cat = torch.from_numpy(datamod.item_categories(item_idx, cat, n_items)).to(trainer.dev)
         corpus = trainer.item_corpus_embeddings(item_cat)
         for batch in val_it:
-            trainer.evaluate_topk(batch[0], batch[1], metric, corpus)
+            trainer.evaluate_topk(batch[0], batch[1], metric, corpus, **({} if stamps is None else {"timestamps": batch[-1]}))
         if distributed and metric._n:           # every rank ranked its own held-out pairs: sum the tallies
             dist.all_reduce(metric._hits); dist.all_reduce(metric._dcg)
             metric._n *= world

@@ -43,6 +43,8 @@ TID_DENSE_BASE = 16
 TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
 TID_CROSS_BASE = 48                          # the cross kernels: layer l of tower t is 48 + 2 l + t (48..53)
 TID_FREQ_HASH_BASE = 56                      # the streaming frequency estimator's hash rows: row h is 56 + h (56..59)
+TID_TIME_BASE = 60                           # the time-of-interaction context: the table is 60, synthetic_timestamps 61
+TIME_MISSING = ops.TIME_MISSING              # a pair without a timestamp
 MAX_CROSS_LAYERS = 3
 # poolings of the user-history feature: the bag launch's three and the attention pool (csrc/history_attn.hip), history only
 HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention",)
@@ -115,6 +117,19 @@ class TwoTowerConfig:
     freq_alpha: float = 0.01
     freq_hashes: int = 2
     freq_slots: int = 0
+    # time-of-interaction context features (the reference's create_temporal_features; TFRS's context-feature recipe: timestamp ->
+    # Discretization -> Embedding and the calendar fields in the query model): every pair carries its int64 timestamp (whole seconds
+    # since the Unix epoch, UTC; TIME_MISSING: none) and the rows it picks in ONE trained table - 24 hours, 7 days of the week
+    # (Monday 0), 12 months, time_buckets equal periods of [time_min, time_max] (the training split's range; later pairs land in
+    # the last bucket, as Keras Discretization does) - are ADDED to the user tower's input.  time_fields: a subset of ("hour",
+    # "day_of_week", "month", "period"), kept in that order; () = no such feature.  The table is a DENSE parameter (a full batch
+    # hits every row; csrc/time_context.hip): no l2; under optimizer="adam" it takes the dense Adam of the other dense parameters -
+    # Keras's non-lazy Adam on an Embedding, not LazyAdam -, and global_clipnorm counts its gradient merged over the batch (Keras
+    # would count IndexedSlices.values per occurrence).  Single-GPU trainer, materialised tower inputs, no graph capture.
+    time_fields: tuple = ()
+    time_buckets: int = 0
+    time_min: int = 0
+    time_max: int = 0
     # rating-prediction head (tfrs.tasks.Ranking beside tfrs.tasks.Retrieval): rating_weight > 0 adds one hidden ReLU layer of
     # rating_hidden units (a multiple of 32 in 32..256) over the pair's two tower outputs - the vectors the scorer reads - and a
     # scalar output trained with MSE on the interaction's rating: total = retrieval + rating_weight * L_r, L_r = mean over the
@@ -160,6 +175,15 @@ class TwoTowerConfig:
     n_title_buckets: int = 0
     title_max_tokens: int = 16
     title_pooling: str = "mean"
+    def __post_init__(self):
+        if isinstance(self.time_fields, (list, tuple)) and all(f in ops.TIME_FIELDS for f in self.time_fields) \
+                and len(set(self.time_fields)) == len(self.time_fields):
+            self.time_fields = tuple(f for f in ops.TIME_FIELDS if f in self.time_fields)       # the fixed order
+
+    @property
+    def time_rows(self) -> int:
+        """Rows of the time table (0: the feature is off)."""
+        return ops.time_field_layout(self.time_fields, self.time_buckets)[1] if self.time_fields else 0
 
     @property
     def lr_schedule_on(self) -> bool:
@@ -259,6 +283,21 @@ class TwoTowerConfig:
             f = getattr(self, name)
             if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= ops.MAX_DENSE_FEATURES:
                 raise ValueError(f"{name} must be 0 (no numeric features) or an int in 1..{ops.MAX_DENSE_FEATURES}")
+        if not isinstance(self.time_fields, tuple) or any(f not in ops.TIME_FIELDS for f in self.time_fields) \
+                or len(set(self.time_fields)) != len(self.time_fields):
+            raise ValueError(f"time_fields must be a tuple of distinct fields out of {ops.TIME_FIELDS}, got {self.time_fields!r}")
+        tb = self.time_buckets
+        if isinstance(tb, bool) or not isinstance(tb, int) or not 0 <= tb <= ops.MAX_TIME_BUCKETS:
+            raise ValueError(f"time_buckets must be an int in 0..{ops.MAX_TIME_BUCKETS}")
+        if ("period" in self.time_fields) != (tb > 0):
+            raise ValueError("time_buckets must be >= 1 exactly when time_fields holds 'period' "
+                             f"(got time_fields {self.time_fields!r}, time_buckets {tb})")
+        for name in ("time_min", "time_max"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not -2 ** 63 <= v < 2 ** 63:
+                raise ValueError(f"{name} must be an int64 (whole seconds since the epoch)")
+        if self.time_min > self.time_max or self.time_max - self.time_min >= 2 ** 40:
+            raise ValueError(f"need time_min <= time_max and time_max - time_min < 2^40 (got {self.time_min}, {self.time_max})")
         if not (self.feature_clip >= 0.0 and math.isfinite(self.feature_clip)):
             raise ValueError("feature_clip must be a finite number >= 0 (0: no clipping)")
         if self.candidate_sampling not in ("in_batch", "mixed"):
@@ -339,18 +378,21 @@ _SEGMENT_GROUPS = {"features": "the numeric side features add one dense segment 
                    "head": "the rating head adds two dense segments",
                    "cross": "the cross layers add two dense segments",
                    "attention": "the history attention adds one dense segment",
-                   "norm": "the layer normalisation adds one dense segment"}
+                   "norm": "the layer normalisation adds one dense segment",
+                   "time": "the time context table adds one dense segment"}
 
 
 @dataclass(frozen=True)
 class DenseBlock:
     """One parameter of ``dense_flat``: the floats [offset, end) viewed as ``shape``.  ``glorot`` = (tensor id of the synthetic
-    initialiser, fan_in + fan_out) of a kernel; None: the parameter starts at ``fill`` (0; the layer normalisation's gammas: 1)."""
+    initialiser, fan_in + fan_out) of a kernel; None: the parameter starts at ``fill`` (0; the layer normalisation's gammas: 1) -
+    or, with ``embedding`` (a tensor id), at Keras Embedding's U(-0.05, 0.05) like the embedding tables (the time table)."""
     name: str
     offset: int
     shape: tuple
     glorot: tuple | None = None
     fill: float = 0.0
+    embedding: int | None = None
 
     @property
     def end(self) -> int:
@@ -369,7 +411,7 @@ class DenseSegment:
     hi: int
     l2: bool
     stride: int
-    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm"
+    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm" | "time"
 
     @property
     def size(self) -> int:
@@ -402,15 +444,18 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         layer normalisation        from a 16-byte boundary (the launches load gamma and beta as float4s): user gamma_0 .. | item
                                    gamma_0 .. | user beta_0 .. | item beta_0 .., one entry per hidden layer; ONE segment, no l2 -
                                    the gradient slabs are laid out like the parameters, so its slab stride is the whole block
+        time table                 from a 16-byte boundary (the launches load its rows as float4s): [time_rows, D], the enabled
+                                   fields' row blocks in their fixed order; ONE segment, no l2, one gradient "slab" - the backward
+                                   launch writes the fully reduced gradient
 
     Every optional block sits BEHIND what was there before it: switching one on moves no existing offset, and without the
     blocks behind it dense_flat ends behind the cross block with no trailing pad."""
     blocks, segs, off = {}, [], 0
     d = cfg.embedding_dim
 
-    def block(name, shape, glorot=None, fill=0.0):
+    def block(name, shape, glorot=None, fill=0.0, embedding=None):
         nonlocal off
-        blocks[name] = blk = DenseBlock(name, off, tuple(shape), glorot, fill)
+        blocks[name] = blk = DenseBlock(name, off, tuple(shape), glorot, fill, embedding)
         off = blk.end
         return blk
 
@@ -452,6 +497,10 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         bs = [block(f"norm.{side}.b{l}", (n,)) for side, dims, _, _ in sides for l, n in enumerate(dims[:-1])]
         if gs:
             segment("norm", "norm", gs[0], bs[-1], False)
+    if cfg.time_fields:
+        off = (off + 3) // 4 * 4
+        t = block("time_table", (cfg.time_rows, d), embedding=TID_TIME_BASE)
+        segment("time", t.name, t, t, False)
     return DenseLayout(blocks, tuple(segs), off)
 
 
@@ -951,7 +1000,9 @@ _CHECKPOINT_CHECKS = (
     ("layer_norm", False, ": the gammas and betas in 'dense' belong to the trained model", None),
     ("layer_norm_epsilon", TwoTowerConfig.layer_norm_epsilon, "", "layer_norm"),
     ("n_title_buckets", 0, "", None), ("user_history_len", 0, "", None), ("history_pooling", "mean", "", "user_history_len"),
-    ("title_max_tokens", None, "", "n_title_buckets"), ("title_pooling", None, "", "n_title_buckets"))
+    ("title_max_tokens", None, "", "n_title_buckets"), ("title_pooling", None, "", "n_title_buckets"),
+    ("time_fields", (), ": the time table in 'dense' belongs to the trained model", None),
+    ("time_buckets", 0, "", "time_fields"), ("time_min", 0, "", "time_fields"), ("time_max", 0, "", "time_fields"))
 
 
 # what graph replay is not implemented for: (config -> bool, the refusal)
@@ -974,6 +1025,8 @@ _GRAPH_REFUSALS = (
     (lambda c: c.cross_layers, "cross layers (cross_layers > 0) is not implemented: the step is the Python sequence of launches over "
      "materialised tower inputs"),
     (lambda c: c.layer_norm, "layer normalisation (layer_norm=True) is not implemented: the step is the Python sequence of launches"),
+    (lambda c: c.time_fields, "the time context features (time_fields) is not implemented: the step is the Python sequence of "
+     "launches over materialised tower inputs"),
     (lambda c: c.global_clipnorm > 0, "gradient clipping (global_clipnorm > 0) is not implemented: the step is the Python sequence of "
      "launches"),
     (lambda c: c.lr_schedule_on, "a learning-rate schedule (lr_warmup_steps / lr_decay): the step's rate is a kernel argument"))
@@ -1147,6 +1200,15 @@ class TwoTowerTrainer:
                                      [self._ln_slabs[g.offset - norm.lo:] for g in gs], [self._ln_slabs[x.offset - norm.lo:] for x in bs],
                                      ns, norm.stride)
             grad_slabs["norm"] = (self._ln_slabs, ns)
+        # time context: the table (a view of dense_flat), the step's kept row indices and the fully reduced gradient the
+        # backward launch writes - the ONE "slab" of the table's dense segment
+        self.time_on = bool(cfg.time_fields)
+        self.time_table = self._time_idx = self._time_grad = None
+        if self.time_on:
+            self.time_table = lay.blocks["time_table"].view(self.dense_flat)
+            self._time_idx = torch.empty(b, len(cfg.time_fields), dtype=torch.int32, device=dev)
+            self._time_grad = torch.empty_like(self.time_table)
+            grad_slabs["time_table"] = (self._time_grad, 1)
         # high priority = a hardware queue of its own (ROCm pools queues per priority): the sort plans always run BESIDE
         # the main stream's kernels, whatever other streams the process has created
         self._side = torch.cuda.Stream(device=dev, priority=-1)
@@ -1174,6 +1236,8 @@ class TwoTowerTrainer:
         if self._feature_sides:                  # the projected features are added to the materialised tower inputs (_tower_inputs)
             self.fuse_lookup = False
         if cfg.cross_layers:                     # the cross layers read the materialised tower inputs (Tower.forward)
+            self.fuse_lookup = False
+        if self.time_on:                         # the time rows are added to the materialised user-tower input (_tower_inputs)
             self.fuse_lookup = False
         self.fuse_sort = os.environ.get("TT_FUSE_SORT", "1") != "0"   # the optimizer launch sorts the ids itself (no plan launch)
         self.fuse_optimizer = True               # sparse + dense optimizer in one launch (False: dense_update, sparse_update2 [, cat])
@@ -1242,9 +1306,11 @@ class TwoTowerTrainer:
             t.init_synthetic(self.cfg, seed)
         self.dense_flat.zero_()
         self._fill_constant_blocks()
-        for blk in self.layout.blocks.values():                # Glorot-uniform kernels, zero biases
+        for blk in self.layout.blocks.values():                # Glorot-uniform kernels, zero biases, the time table like an Embedding
             if blk.glorot is not None:
                 _glorot_uniform_(blk.view(self.dense_flat), seed, *blk.glorot)
+            elif blk.embedding is not None:
+                ops.fill_uniform_(blk.view(self.dense_flat), seed, blk.embedding, -0.05, 0.1)
         if self.dense_accum is not None:
             self.dense_accum.fill_(self.cfg.adagrad_initial_accumulator)
         if self.dense_m is not None:
@@ -1281,6 +1347,15 @@ class TwoTowerTrainer:
             out = torch.empty(b, dtype=torch.int64, device=self.dev)
         ops.fill_ids_(out, seed, TID_CATEGORY_IDS, self.cfg.n_category_buckets, variant, start=step * b)
         return out
+
+    def synthetic_timestamps(self, seed: int, step: int, out=None) -> torch.Tensor:
+        """The int64 timestamps of synthetic step ``step``, uniform over [time_min, time_max] from the counter-based generator
+        (tensor id 61, elements step * batch ..)."""
+        b, cfg = self.cfg.batch_size, self.cfg
+        if out is None:
+            out = torch.empty(b, dtype=torch.int64, device=self.dev)
+        ops.fill_ids_(out, seed, TID_TIME_BASE + 1, cfg.time_max - cfg.time_min + 1, "U", start=step * b)
+        return out.add_(cfg.time_min)
 
     def synthetic_item_titles(self, seed: int, variant: str = "Z") -> torch.Tensor:
         """A synthetic [n_items, title_max_tokens] int32 token matrix from the id generator: power-law tokens (a few frequent
@@ -1411,10 +1486,13 @@ class TwoTowerTrainer:
         return (ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob),
                 ops.make_lookup(self.item_table, item_ids, self.cat_table, category_ids, self.oob))
 
-    def _tower_inputs(self, user=None, item=None, *, category_ids=None, exclude=None, keep: bool = False, features_only: bool = False):
+    def _tower_inputs(self, user=None, item=None, *, category_ids=None, exclude=None, keep: bool = False, features_only: bool = False,
+                      timestamps=None):
         """Materialised tower-input rows (no fused lookup), and the ONE place that knows what is summed into them: the id's table
         row + the hashed category's row (item) + the pooled title rows (item) + the pooled or attended history rows (user) + the
-        projected numeric features.  ``user`` / ``item`` = (ids, rows to write) or None: any number of ids, either side alone.
+        time rows of the pairs' ``timestamps`` (user; without a history ONE launch with the user row as its base, else added
+        behind the history launch) + the projected numeric features.
+        ``user`` / ``item`` = (ids, rows to write) or None: any number of ids, either side alone.
         ``exclude``: the items the history launch leaves out (the train step's positives); ``keep``: the train step - the slot
         tokens, pooling scales and normalised feature rows stay for the backward launches and the update; an inference pass
         writes none of those buffers, so it may run between a step's backward pass and its ``apply_gradients``.
@@ -1434,6 +1512,13 @@ class TwoTowerTrainer:
                 ops.history_bag(self.history_table, self.user_history, bag_rows=user[0], exclude=exclude, base=(self.user_table, user[0]),
                                 pooling=cfg.history_pooling, out=user[1], batch_ids=self.history_ids if keep else None,
                                 inv=self.history_inv if keep else None, oob_flag=self.oob)
+            if user is not None and self.time_on:
+                self._time_context(timestamps, user, keep, base=False)
+        elif self.time_on:                       # the item gather, then ONE launch for the user side: user row + time rows
+            if item is not None:
+                ops.embedding_gather(self.item_table, item[0], out=item[1], oob_flag=self.oob)
+            if user is not None:
+                self._time_context(timestamps, user, keep, base=True)
         elif user is not None and item is not None and user[0].numel() == item[0].numel():
             ops.embedding_gather2(self.user_table, user[0], user[1], self.item_table, item[0], item[1], self.oob)
         else:
@@ -1454,6 +1539,32 @@ class TwoTowerTrainer:
                 probs.append((fs.features, side[0], fs.mean, fs.inv_std, fs.P, side[1], True, fs.z if keep else None))
         if probs:
             ops.dense_features(*probs, clip=cfg.feature_clip, oob_flag=self.oob)
+
+    def _time_context(self, timestamps, user, keep: bool, base: bool):
+        """The time launch of ``_tower_inputs``: the rows ``timestamps`` pick, summed, on top of the user row (``base``) or of
+        what the history launch wrote; ``keep``: the row indices stay for ``_time_backward``."""
+        cfg, (ids, out) = self.cfg, user
+        ops.time_context(timestamps, self.time_table, cfg.time_fields, cfg.time_buckets, cfg.time_min, cfg.time_max, out=out,
+                         accumulate=not base, base=(self.user_table, ids) if base else None,
+                         idx_out=self._time_idx[:ids.numel()] if keep else None, oob_flag=self.oob)
+
+    def _time_backward(self):
+        """The time table's gradient, fully reduced, from the user tower's input gradient (demb) and the kept row indices: one
+        launch after the towers' backward - the ONE slab of the table's dense segment."""
+        ops.time_context_bwd(self._time_idx, self.user_tower.demb, self.cfg.time_fields, self.cfg.time_buckets, grad=self._time_grad)
+
+    def _check_timestamps(self, timestamps, n: int | None = None, where: str = "step"):
+        """``timestamps`` are required exactly when the model has the time features; int64 [n] on the device."""
+        if self.time_on and timestamps is None:
+            raise ValueError(f"{where}: the model has time features (cfg.time_fields = {self.cfg.time_fields}): pass "
+                             "timestamps=<int64 [batch], seconds since the epoch, TIME_MISSING = none>")
+        if not self.time_on and timestamps is not None:
+            raise ValueError(f"{where}: timestamps were passed but the model has no time features (cfg.time_fields == ())")
+        if timestamps is not None:
+            ops._chk(timestamps, torch.int64, "timestamps", 1)
+            n = self.cfg.batch_size if n is None else n
+            if timestamps.numel() != n:
+                raise ValueError(f"{where}: timestamps must have {n} entries (one per pair), got {timestamps.numel()}")
 
     def _features_backward(self):
         """The projection kernels' gradient slabs from the towers' input gradients (demb) and the kept normalised rows: one
@@ -1533,14 +1644,18 @@ class TwoTowerTrainer:
         return self._r_se.sum() / self.cfg.batch_size
 
     def forward_backward(self, user_ids: torch.Tensor, item_ids: torch.Tensor, sample_weight=None,
-                         candidate_sampling_probability=None, candidate_ids=None, category_ids=None, ratings=None, *,
-                         _sampled: bool = False):
+                         candidate_sampling_probability=None, candidate_ids=None, category_ids=None, ratings=None,
+                         timestamps=None, *, _sampled: bool = False):
         """Loss and every gradient of one step, for both samplings.  In-batch: the item side is the pairs' items.  Mixed negative
         sampling: the item side is ``cand_ids`` (B + N rows: the sampler launch runs here unless ``step`` has run it,
         ``_sampled``), the scorer works at [B] x [B + N] with the positive of query i at candidate i, and ``cand_ids`` always
-        goes to it - a sampled id equal to a row's own positive is a false negative, which the scorer masks."""
+        goes to it - a sampled id equal to a row's own positive is a false negative, which the scorer masks.
+        ``timestamps`` [batch] int64: the pairs' interaction times (required iff cfg.time_fields; the context is on the user
+        side only, so mixed sampling takes it too)."""
         cfg, ut, it = self.cfg, self.user_tower, self.item_tower
         self._check_ratings(ratings)
+        if self.time_on or timestamps is not None:
+            self._check_timestamps(timestamps, where="forward_backward")
         if self.mixed:
             if candidate_sampling_probability is not None or candidate_ids is not None or category_ids is not None:
                 raise ValueError("candidate_sampling='mixed': the trainer draws the candidates itself - candidate_ids, "
@@ -1558,7 +1673,8 @@ class TwoTowerTrainer:
             ids = item_ids
         lks = self._lookups(user_ids, ids, category_ids)
         if lks is None:                          # (the history launch leaves out the pair's own item)
-            self._tower_inputs((user_ids, ut.acts[0]), (ids, it.acts[0]), category_ids=category_ids, exclude=item_ids, keep=True)
+            self._tower_inputs((user_ids, ut.acts[0]), (ids, it.acts[0]), category_ids=category_ids, exclude=item_ids, keep=True,
+                               timestamps=timestamps)
         # the dropout streams count rows per tower: consecutive steps never share a position
         step, rate, seed = self.step_index, cfg.dropout_rate, self.dropout_seed
         towers_forward((ut, it), ((rate, seed, 0, step * ut.rows), (rate, seed, 1, step * it.rows)), lookups=lks)
@@ -1574,6 +1690,8 @@ class TwoTowerTrainer:
         self._outputs_backward((ut, it), (dq, dc))
         towers_backward((ut, it), cfg.dropout_rate, lookups=lks, bwd2_ws=self.bwd2_ws)
         self._features_backward()
+        if self.time_on:
+            self._time_backward()
         self._history_backward()
         self._lr_step = self.step_index
         self.step_index += 1
@@ -1765,8 +1883,12 @@ class TwoTowerTrainer:
         self._check_ratings(loss_kw.get("ratings"))
         if not self.rating_on:
             loss_kw.pop("ratings", None)
+        if self.time_on:
+            self._check_timestamps(loss_kw.get("timestamps"))
+        elif "timestamps" in loss_kw:            # (None is dropped: the composite call does not know the argument)
+            self._check_timestamps(loss_kw.pop("timestamps"))
         if self.mixed:
-            bad = [k for k, v in loss_kw.items() if v is not None and k not in ("sample_weight", "ratings")]
+            bad = [k for k, v in loss_kw.items() if v is not None and k not in ("sample_weight", "ratings", "timestamps")]
             if bad:
                 raise ValueError(f"candidate_sampling='mixed': the trainer draws the candidates itself - {', '.join(sorted(bad))} cannot "
                                  "be passed to step() (the correction comes from set_item_frequencies)")
@@ -1911,6 +2033,7 @@ class TwoTowerTrainer:
         cfg, ut, it = self.cfg, self.user_tower, self.item_tower
         ratings = loss_kw.get("ratings")
         self._check_ratings(ratings)
+        self._check_timestamps(loss_kw.get("timestamps"), where="evaluate")
         self._check_categories(loss_kw.get("category_ids"))
         self._check_batch(loss_kw.get("sample_weight"), loss_kw.get("candidate_sampling_probability"),
                           loss_kw.get("candidate_ids"))
@@ -1924,7 +2047,8 @@ class TwoTowerTrainer:
         self._check_batch(user_ids, item_ids)
         lks = None if self.mixed else self._lookups(user_ids, item_ids, loss_kw.get("category_ids"))
         if lks is None:
-            self._tower_inputs((user_ids, ut.acts[0]), (item_ids, it.acts[0][:b]), category_ids=loss_kw.get("category_ids"))
+            self._tower_inputs((user_ids, ut.acts[0]), (item_ids, it.acts[0][:b]), category_ids=loss_kw.get("category_ids"),
+                               timestamps=loss_kw.get("timestamps"))
         towers_forward((ut, it), lookups=lks, rows=rows)
         q, c = self._outputs((ut, it), rows)
         if self.rating_on:
@@ -1944,10 +2068,12 @@ class TwoTowerTrainer:
         self.eval_rating_count = ok.sum()
 
     @torch.no_grad()
-    def predict_ratings(self, user_ids: torch.Tensor, item_ids: torch.Tensor, category_ids: torch.Tensor | None = None) -> torch.Tensor:
+    def predict_ratings(self, user_ids: torch.Tensor, item_ids: torch.Tensor, category_ids: torch.Tensor | None = None,
+                        timestamps: torch.Tensor | None = None) -> torch.Tensor:
         """The head's prediction for ANY number of (user, item) pairs ([n] f32), computed cfg.batch_size pairs at a time on the
         towers' buffers (inference: no dropout, the stored histories in full).  ``category_ids`` [n]: the pairs' category
-        buckets (required iff the model has the feature)."""
+        buckets (required iff the model has the feature); ``timestamps`` [n] int64: the pairs' times (required iff the model
+        has the time features)."""
         if not self.rating_on:
             raise ValueError("predict_ratings: the model has no rating head (cfg.rating_weight == 0)")
         if (category_ids is None) != (self.cat_table is None):
@@ -1958,12 +2084,14 @@ class TwoTowerTrainer:
         n = uid.numel()
         if iid.numel() != n or (category_ids is not None and category_ids.numel() != n):
             raise ValueError(f"predict_ratings: user_ids, item_ids (and category_ids) must have one length, got {n} and {iid.numel()}")
+        ts = self._inference_timestamps(timestamps, n, "predict_ratings")
         out = torch.empty(n, device=self.dev)
         for s in range(0, n, b):
             e = min(s + b, n)
             m = e - s
             self._tower_inputs((uid[s:e], ut.acts[0][:m]), (iid[s:e], it.acts[0][:m]),
-                               category_ids=None if category_ids is None else category_ids[s:e].to(self.dev).contiguous())
+                               category_ids=None if category_ids is None else category_ids[s:e].to(self.dev).contiguous(),
+                               timestamps=None if ts is None else ts[s:e])
             ut.forward()
             it.forward()
             q, c = self._outputs((ut, it))
@@ -1998,32 +2126,44 @@ class TwoTowerTrainer:
             out[s:e].copy_(self._outputs((it,))[0][:e - s])
         return out
 
+    def _inference_timestamps(self, timestamps, n: int, where: str):
+        """``timestamps`` of an inference pass over ``n`` queries, on the device (None: the model has no time features)."""
+        if timestamps is not None and torch.is_tensor(timestamps) and timestamps.dtype == torch.int64:
+            timestamps = timestamps.to(self.dev).reshape(-1).contiguous()
+        self._check_timestamps(timestamps, n, where)
+        return timestamps
+
     @torch.no_grad()
-    def user_embeddings(self, user_ids: torch.Tensor) -> torch.Tensor:
+    def user_embeddings(self, user_ids: torch.Tensor, timestamps: torch.Tensor | None = None) -> torch.Tensor:
         """User-tower output (inference: no dropout; unit-norm rows with cfg.normalize_embeddings) for ANY number of user ids
         ([n, scorer_dim]), computed cfg.batch_size
         ids at a time on the tower's buffers.  Out-of-range ids give the tower output of a zero row and set the trainer's
-        out-of-range flag (``check_ids``)."""
+        out-of-range flag (``check_ids``).  ``timestamps`` [n] int64: the time every query is asked at (required iff the model
+        has the time features)."""
         ut, b = self.user_tower, self.cfg.batch_size
         ids = user_ids.to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
         n = ids.numel()
+        ts = self._inference_timestamps(timestamps, n, "user_embeddings")
         out = torch.empty(n, ut.dims[-1], device=self.dev)
         for s in range(0, n, b):
             e = min(s + b, n)
-            self._tower_inputs(user=(ids[s:e], ut.acts[0][:e - s]))     # (the full stored history: nothing is left out at inference)
+            # (the full stored history: nothing is left out at inference)
+            self._tower_inputs(user=(ids[s:e], ut.acts[0][:e - s]), timestamps=None if ts is None else ts[s:e])
             ut.forward()
             out[s:e].copy_(self._outputs((ut,))[0][:e - s])
         return out
 
     @torch.no_grad()
-    def evaluate_topk(self, user_ids: torch.Tensor, item_ids: torch.Tensor, metric, corpus: torch.Tensor | None = None):
+    def evaluate_topk(self, user_ids: torch.Tensor, item_ids: torch.Tensor, metric, corpus: torch.Tensor | None = None,
+                      timestamps: torch.Tensor | None = None):
         """Updates ``metric`` (metrics.FactorizedTopK) with one batch of (user, true item) pairs scored against the
-        whole item corpus; returns the ranks."""
+        whole item corpus; returns the ranks.  ``timestamps`` [batch] int64: required iff the model has the time features."""
         self._check_batch(user_ids, item_ids)
+        self._check_timestamps(timestamps, where="evaluate_topk")
         if corpus is None:
             corpus = self.item_corpus_embeddings()
-        if self.history_table is not None or self.user_features is not None or self.cfg.cross_layers:
-            self._tower_inputs(user=(user_ids, self.user_tower.acts[0]))
+        if self.history_table is not None or self.user_features is not None or self.cfg.cross_layers or self.time_on:
+            self._tower_inputs(user=(user_ids, self.user_tower.acts[0]), timestamps=timestamps)
             self.user_tower.forward()
         else:
             self.user_tower.forward(lookup=ops.make_lookup(self.user_table, user_ids, oob_flag=self.oob))
