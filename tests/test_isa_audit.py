@@ -120,6 +120,34 @@ def _resources(tmp_path, name):
     return out
 
 
+# waves per SIMD of the four select kernels at dim 32 / 64 / 128 / 256 when each carried its own copy of the selection body
+SELECT_OCCUPANCY_FLOOR = {
+    ("topk", "topk_select_kernel"): (2, 2, 1, 1),
+    ("ivf", "ivf_select_kernel"): (2, 1, 1, 1),
+    ("topk_i8", "i8_scan_kernel"): (2, 2, 2, 1),
+    ("ivf_i8", "ivf_i8_select_kernel"): (2, 2, 2, 1),
+}
+
+
+def test_select_kernels_on_the_shared_core_keep_their_occupancy_and_use_no_scratch(tmp_path):
+    """topk_select_kernel selects through the core topk::Select (csrc/topk_select.h); the other three select kernels keep
+    their own bodies until they are as fast on it.  No kernel of the four translation units may spill, and no select kernel
+    may fit fewer waves per SIMD than it did when every kernel carried a hand copy (the floors above).
+    VGPRs at dim 32 / 64 / 128 / 256 (informative, not pinned):
+      topk_select_kernel    186 / 234 / 254 / 254 as a hand copy  ->  152 / 205 / 256 / 256 on the core (3 waves at dim 32)
+      ivf_select_kernel     200 / 248 / 256 / 256
+      i8_scan_kernel        178 / 198 / 238 / 254
+      ivf_i8_select_kernel  178 / 198 / 238 / 256"""
+    for (tu, kernel), floor in SELECT_OCCUPANCY_FLOOR.items():
+        res = _resources(tmp_path, tu)
+        for name, (v, a, scr, occ) in res.items():
+            assert scr == 0, (tu, name, v, a, scr, occ)
+        for dim, occ_floor in zip((32, 64, 128, 256), floor):
+            v, a, scr, occ = res[f"{kernel}<{dim}>"]
+            print(f"{kernel}<{dim}>: {v} VGPRs, {a} AGPRs, {occ} waves/SIMD")
+            assert occ >= occ_floor, (kernel, dim, v, a, occ, occ_floor)
+
+
 def test_no_kernel_of_the_train_step_uses_scratch(tmp_path):
     """r03 left 40-132 B of scratch per lane in the exact-f32 dim-256 online-softmax kernels with accidental-hit ids / hard
     negatives (cfg5 with remove_accidental_hits runs one of them) and 20 B in a dim-128 gradient kernel; r04 keeps the last

@@ -21,7 +21,7 @@
 //      independent of its tile mates, and every result is written to its slot.
 //   3. ivf_select_kernel: one wave per (list, chunk, tile of <= 32 queries probing that list).  The wave gathers its
 //      queries' rows into the B operand and streams the chunk's rows of list_vectors through the A operand, selecting
-//      with the shared body of topk_select.h keyed on list_ids[row].  It writes the sorted list of k of every
+//      with topk::select_run_ids (topk_select.h) keyed on list_ids[row].  It writes the sorted list of k of every
 //      (query, probe, chunk) to a [nq][nprobe * S][k] workspace; empty chunks write padding.  The grid is a host-side upper
 //      bound; surplus waves exit after reading the scanned work count.
 //   4. topk_merge_kernel rounds over the nprobe * S lists of each query (they cover disjoint candidates; padding is a
@@ -45,7 +45,7 @@ constexpr int kCoarseMinCols = 32;          // the coarse probe's split: one 32-
 constexpr int kBucketThreads = 1024;
 constexpr int kBucketLdsLists = 8192;       // list counters in LDS (32 KiB) up to this nlist, in the workspace above it
 
-int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+using tt::align256;
 
 struct IvfPlan {
   int S;                        // chunks per list
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64) void ivf_select_kernel(IvfSelArgs p) {
   int64_t c_end = c_begin + cps;
   if (c_end > L1) c_end = L1;
 
-  tt::topk::Stream s;
+  tt::topk::ListStream s;
   s.r_ok = ln < tn;
   const int64_t qid = s.r_ok ? p.pairs[p0 + ln] / p.nprobe : 0;
   s.qrow = p.q + qid * D;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(64) void ivf_select_kernel(IvfSelArgs p) {
   s.ws_i = p.ws_i;
   const int32_t* pairs = p.pairs;
   const int64_t k = p.k;
-  tt::topk::select_run<D, true>(s, [&](int rr) -> int64_t {
+  tt::topk::select_run_ids<D, true>(s, [&](int rr) -> int64_t {
     // slot q * nprobe + probe: list (q, probe, chunk) of the [nq][nprobe * S][k] workspace
     return rr >= tn ? -1 : ((int64_t)__builtin_amdgcn_readfirstlane(pairs[p0 + rr]) * S + chunk) * k;
   });
@@ -221,14 +221,8 @@ __global__ __launch_bounds__(64) void ivf_select_kernel(IvfSelArgs p) {
 
 template <int D>
 int launch_ivf_select(const IvfSelArgs& a, int rows, int64_t blocks, hipStream_t stream) {
-  const int lds = tt::topk::select_lds_bytes(rows, a.k);
-  auto kern = ivf_select_kernel<D>;
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return tt::fail(TT_ERR_LAUNCH, "tt_ivf_search_f32: hipFuncSetAttribute(LDS %d) failed", lds);
-  }
-  tt::launch("ivf_select", kern, dim3((unsigned)blocks), dim3(64), (unsigned)lds, stream, a);
-  return tt::check_launch("ivf_select");
+  return tt::topk::launch_select("ivf_select", ivf_select_kernel<D>, tt::topk::select_lds_bytes(rows, a.k), blocks, stream, a,
+                                 "tt_ivf_search_f32");
 }
 
 bool shape_ok(int64_t nq, int64_t nlist, int64_t n, int32_t dim, int32_t k, int32_t nprobe) {

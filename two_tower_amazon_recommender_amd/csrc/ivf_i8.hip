@@ -28,7 +28,7 @@
 //   5. tt::i8_finish_launch (topk_i8.hip): i8_rerank_kernel with c, i8_scale_kernel without.
 // Chunks: tt::ivf_probe_plan's rule (ivf.hip) with lists of k1 entries: S from nq * nprobe so that a small batch fills the
 // chip, at most one chunk per 64 rows of the average list, at most 64, and the [nq][nprobe * S][k1] lists within 1 GiB.
-// LDS: min(nq, 32) x (k1 + 48) x 8 B (78 KB at k1 = 256: the dynamic limit is raised as launch_ivf_select does).
+// LDS: min(nq, 32) x (k1 + 48) x 8 B (78 KB at k1 = 256: topk::launch_select raises the dynamic limit).
 #include "topk_select.h"
 #include "quant_i8.h"
 
@@ -45,7 +45,7 @@ using tt::topk::beats;
 using tt::topk::kMaxEntries;
 using tt::topk::kQueue;
 
-int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+using tt::align256;
 
 struct IvfI8Plan {
   tt::IvfProbePlan probe;
@@ -312,14 +312,8 @@ __global__ __launch_bounds__(64) void ivf_i8_select_kernel(IvfI8SelArgs p) {
 
 template <int D>
 int launch_ivf_i8_select(const IvfI8SelArgs& a, int rows, int64_t blocks, hipStream_t stream) {
-  const int lds = tt::topk::select_lds_bytes(rows, a.k);
-  auto kern = ivf_i8_select_kernel<D>;
-  if (lds > 64 * 1024) {   // above the 64 KiB default the limit must be raised (cheap, idempotent)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return tt::fail(TT_ERR_LAUNCH, "tt_ivf_search_i8_f32: hipFuncSetAttribute(LDS %d) failed", lds);
-  }
-  tt::launch("ivf_i8_select", kern, dim3((unsigned)blocks), dim3(64), (unsigned)lds, stream, a);
-  return tt::check_launch("ivf_i8_select");
+  return tt::topk::launch_select("ivf_i8_select", ivf_i8_select_kernel<D>, tt::topk::select_lds_bytes(rows, a.k), blocks, stream, a,
+                                 "tt_ivf_search_i8_f32");
 }
 
 bool shape_ok(int64_t nq, int64_t nlist, int64_t n, int32_t dim, int32_t k, int32_t k1, int32_t nprobe) {

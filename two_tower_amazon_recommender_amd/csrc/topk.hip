@@ -27,6 +27,11 @@
 //   list and count the queue - and entries of rank < k are written to that position.  After the first k candidates the
 //   threshold rises quickly, survivors are ~k ln(n/k) of a split's n candidates, and the merges become rare.
 //   Each (query, split) writes its sorted list of k (padded with (-inf, -1)) to the workspace.
+//   The code is in topk_select.h: the selection is topk::Select (state, push, flush, write_out) and the kernel below is
+//   its work-item decode around topk::select_run, the f32 tile stream on that core.  Select's per-tile test is branch-free
+//   and does no 64-bit arithmetic; on it the kernel measured 0.8-8 % faster than its former hand-written body on every
+//   shape of bench_topk.py (profiles/retrieval_select_core_ab.jsonl).  The IVF and int8 select kernels still carry bodies
+//   of their own (topk::select_run_ids, topk_i8.hip, ivf_i8.hip): on Select they were slower on some shapes.
 // Launch 2.., merge (topk_merge_kernel): one 256-thread workgroup per (query, group of kMergeFan lists) loads the group into
 //   LDS; every entry's rank in the merged order = its position + the number of entries of each other list that beat it
 //   (binary search); ranks < k are written.  Lists come from disjoint candidate ranges, so the ranks are unique and dense.
@@ -40,15 +45,10 @@
 
 namespace {
 
-// topk_select_kernel keeps its own copy of the select body (topk_select.h holds the same scheme for ivf.hip, with an id
-// hook): compiled from the shared template it allocated registers differently and ran 2-4 % slower in a same-box A/B.
-using tt::f32x4;
-using tt::f32x16;
+using tt::align256;
 using tt::topk::beats;
-using tt::topk::kMaxEntries;
 using tt::topk::kMergeFan;
 using tt::topk::kMergeThreads;
-using tt::topk::kQueue;
 
 constexpr int kTargetWaves = 2048;       // 256 CUs x 8
 constexpr int kMinColsPerSplit = 512;
@@ -62,8 +62,6 @@ struct TopkPlan {
   int64_t off_b;          // workspace: buffer A at 0 ([nq][nsplit][k] scores, then indices), buffer B here
   int64_t total;
 };
-
-int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 TopkPlan topk_plan(int64_t nq, int64_t nc, int k, int min_cols = kMinColsPerSplit) {
   TopkPlan p{};
@@ -101,187 +99,25 @@ struct SelArgs {
 
 template <int D>
 __global__ __launch_bounds__(64) void topk_select_kernel(SelArgs p) {
-  constexpr int NG = D / 8;                         // k-groups of 8 (4 per lane half), as score_kernel's GEMM1
-  constexpr bool PREFETCH = D <= 128;               // dim 256: the rows (128 VGPRs) and one tile (128) fill the budget
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x;
-  const int h = lane >> 5;
-  const int ln = lane & 31;
-  const int k = p.k;
-  const int RS = 2 * (k + kQueue);                  // LDS words per query row: list scores, list indices, queue scores, queue indices
-
-  // every quantity that steers a loop with a barrier in it is wave-uniform by construction (readfirstlane)
-  const int split = __builtin_amdgcn_readfirstlane((int)(blockIdx.x % (unsigned)p.nsplit));
-  const int rblk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)p.nsplit));
-  const int rows_lds = __builtin_amdgcn_readfirstlane(p.rows_lds);
-  const int64_t r0 = (int64_t)rblk * 32;
-  const int64_t r = r0 + ln;
-  const bool r_ok = r < p.nq;
-  const int64_t c_begin = (int64_t)split * p.c_per_split;
-  int64_t c_end = c_begin + p.c_per_split;
-  if (c_end > p.nc) c_end = p.nc;
-  const int ntiles = __builtin_amdgcn_readfirstlane((int)((c_end - c_begin + 31) >> 5));
-
-  // stationary fragment: rf[g] = q[r][8g + 4h .. +3]
-  f32x4 rf[NG];
-  {
-    const f32x4* R4 = reinterpret_cast<const f32x4*>(p.q + (r_ok ? r : 0) * D) + h;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) rf[g] = r_ok ? R4[2 * g] : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  int64_t ex_lo = 0, ex_hi = 0;
-  if (p.excl_off != nullptr && r_ok) {
-    ex_lo = p.excl_off[r];
-    ex_hi = p.excl_off[r + 1];
-  }
-  auto excluded = [&](int64_t cand) -> bool {
-    int64_t lo = ex_lo, hi = ex_hi;
-    while (lo < hi) {
-      const int64_t mid = lo + ((hi - lo) >> 1);
-      if (p.excl_idx[mid] < cand) lo = mid + 1; else hi = mid;
-    }
-    return lo < ex_hi && p.excl_idx[lo] == cand;
-  };
-
-  // per-row selection state (lanes ln and ln + 32 hold the same copy)
-  int m = 0;                    // list length
-  int qn = 0;                   // queue length
-  bool full = false;
-  float thr_s = 0.f;
-  int thr_i = 0;
-  float* row = smem + (r_ok ? ln : 0) * RS;
-  float* qs = row + 2 * k;
-  int* qi = reinterpret_cast<int*>(row + 2 * k + kQueue);
-
-  auto load_tile = [&](f32x4 (&a)[NG], int t) {
-    const int64_t cand = c_begin + 32 * (int64_t)t + ln;
-    const bool ok = cand < c_end;
-    const f32x4* src = reinterpret_cast<const f32x4*>(p.c + (ok ? cand : 0) * D) + h;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) a[g] = ok ? src[2 * g] : f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-
-  // merge every non-empty queue into its row's list (wave-cooperative; called on wave-uniform control only)
-  auto flush = [&]() {
-    for (int rr = 0; rr < rows_lds; ++rr) {
-      const int qn_r = __builtin_amdgcn_readlane(qn, rr);
-      const int m_r = __builtin_amdgcn_readlane(m, rr);
-      if (qn_r == 0) continue;
-      float* Ls = smem + rr * RS;
-      int* Li = reinterpret_cast<int*>(Ls + k);
-      const float* Qs = Ls + 2 * k;
-      const int* Qi = reinterpret_cast<const int*>(Ls + 2 * k + kQueue);
-      const int tot = m_r + qn_r;
-      float es[kMaxEntries];
-      int ei[kMaxEntries], er[kMaxEntries];
-#pragma unroll
-      for (int j = 0; j < kMaxEntries; ++j) {
-        const int e = lane + 64 * j;
-        er[j] = INT_MAX;
-        es[j] = 0.f;
-        ei[j] = 0;
-        if (e < tot) {
-          float s;
-          int i, rank;
-          if (e < m_r) {
-            s = Ls[e]; i = Li[e]; rank = e;
-          } else {
-            s = Qs[e - m_r]; i = Qi[e - m_r];
-            int lo = 0, hi = m_r;                    // list entries that beat it: a prefix of the sorted list
-            while (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              if (beats(Ls[mid], Li[mid], s, i)) lo = mid + 1; else hi = mid;
-            }
-            rank = lo;
-          }
-          for (int t = 0; t < qn_r; ++t) rank += beats(Qs[t], Qi[t], s, i) ? 1 : 0;
-          es[j] = s; ei[j] = i; er[j] = rank;
-        }
-      }
-      __syncthreads();                               // every read of the old list is done (one wave: orders the LDS ops)
-#pragma unroll
-      for (int j = 0; j < kMaxEntries; ++j)
-        if (er[j] < k) { Ls[er[j]] = es[j]; Li[er[j]] = ei[j]; }
-      __syncthreads();
-      if (ln == rr) {
-        m = tot < k ? tot : k;
-        qn = 0;
-        if (m == k) { full = true; thr_s = Ls[k - 1]; thr_i = Li[k - 1]; }
-      }
-    }
-  };
-
-  auto process = [&](int t, const f32x4 (&a)[NG]) {
-    f32x16 X;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) X[i] = 0.f;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][0], rf[g][0], X, 0, 0, 0);
-      X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][1], rf[g][1], X, 0, 0, 0);
-      X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][2], rf[g][2], X, 0, 0, 0);
-      X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][3], rf[g][3], X, 0, 0, 0);
-    }
-    // X[reg] = score(query r, candidate c0 + acc_row(reg, h))
-    const int64_t c0 = c_begin + 32 * (int64_t)t;
-    uint32_t mask = 0;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int64_t cand = c0 + tt::acc_row(reg, h);
-      const bool ok = r_ok && cand < c_end && (!full || beats(X[reg], (int)cand, thr_s, thr_i));
-      mask |= ok ? (1u << reg) : 0u;
-    }
-    if (ex_hi > ex_lo && mask != 0u) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg)
-        if (((mask >> reg) & 1u) && excluded(c0 + tt::acc_row(reg, h))) mask &= ~(1u << reg);
-    }
-    const int n = __builtin_popcount(mask);
-    const int n_other = __shfl_xor(n, 32);
-    int pos = qn + (h ? n_other : 0);
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg)
-      if ((mask >> reg) & 1u) {
-        qs[pos] = X[reg];
-        qi[pos] = (int)(c0 + tt::acc_row(reg, h));
-        ++pos;
-      }
-    qn += n + n_other;
-    if (__ballot(qn > kQueue - 32) != 0ull) flush();
-  };
-
-  f32x4 a0[NG];
-  if (ntiles > 0) load_tile(a0, 0);
-  if constexpr (PREFETCH) {
-    f32x4 a1[NG];
-    for (int t = 0; t < ntiles; t += 2) {
-      if (t + 1 < ntiles) load_tile(a1, t + 1);
-      process(t, a0);
-      if (t + 1 < ntiles) {
-        if (t + 2 < ntiles) load_tile(a0, t + 2);
-        process(t + 1, a1);
-      }
-    }
-  } else {
-    for (int t = 0; t < ntiles; ++t) {
-      if (t > 0) load_tile(a0, t);
-      process(t, a0);
-    }
-  }
-  if (__ballot(qn > 0) != 0ull) flush();
-
-  // this (query, split)'s sorted list, padded with (-inf, -1)
-  for (int rr = 0; rr < rows_lds; ++rr) {
-    if (r0 + rr >= p.nq) break;
-    const int m_r = __builtin_amdgcn_readlane(m, rr);
-    const float* Ls = smem + rr * RS;
-    const int* Li = reinterpret_cast<const int*>(Ls + k);
-    const int64_t o = ((r0 + rr) * p.nsplit + split) * (int64_t)k;
-    for (int e = lane; e < k; e += 64) {
-      p.ws_s[o + e] = e < m_r ? Ls[e] : -__builtin_inff();
-      p.ws_i[o + e] = e < m_r ? Li[e] : -1;
-    }
-  }
+  const tt::topk::SplitWork w = tt::topk::split_work(p.nsplit, p.c_per_split, p.nc);
+  const int64_t r = w.r0 + (threadIdx.x & 31);
+  tt::topk::Stream s;
+  s.r_ok = r < p.nq;
+  s.qid = s.r_ok ? r : 0;
+  s.qrow = p.q + s.qid * D;
+  s.rows_lds = p.rows_lds;
+  s.k = p.k;
+  s.excl_off = p.excl_off;
+  s.excl_idx = p.excl_idx;
+  s.ids = nullptr;
+  s.c_begin = w.c_begin;
+  s.c_end = w.c_end;
+  s.ws_s = p.ws_s;
+  s.ws_i = p.ws_i;
+  tt::topk::select_run<D, false>(s, p.c, [&](int rr) -> int64_t {
+    // this (query, split)'s list of the [nq][nsplit][k] workspace
+    return w.r0 + rr >= p.nq ? -1 : ((w.r0 + rr) * p.nsplit + w.split) * (int64_t)p.k;
+  });
 }
 
 struct MergeArgs {
@@ -357,14 +193,8 @@ __global__ __launch_bounds__(kMergeThreads) void topk_merge_kernel(MergeArgs p) 
 
 template <int D>
 int launch_select(const SelArgs& a, int64_t blocks, hipStream_t stream) {
-  const int lds = tt::topk::select_lds_bytes(a.rows_lds, a.k);
-  auto kern = topk_select_kernel<D>;
-  if (lds > 64 * 1024) {   // above the 64 KiB default the limit must be raised (cheap, idempotent)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return tt::fail(TT_ERR_LAUNCH, "tt_retrieval_topk_f32: hipFuncSetAttribute(LDS %d) failed", lds);
-  }
-  tt::launch("topk_select", kern, dim3((unsigned)blocks), dim3(64), (unsigned)lds, stream, a);
-  return tt::check_launch("topk_select");
+  return tt::topk::launch_select("topk_select", topk_select_kernel<D>, tt::topk::select_lds_bytes(a.rows_lds, a.k), blocks, stream, a,
+                                 "tt_retrieval_topk_f32");
 }
 
 }  // namespace

@@ -58,7 +58,7 @@ constexpr int kMinColsPerSplit = 2048;
 constexpr int kMaxSplits = 4096;
 constexpr int kQuantThreads = 256;
 
-int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+using tt::align256;
 
 // ---------------------------------------------------------------------------------------------------- quantiser
 struct QuantArgs {
@@ -432,14 +432,8 @@ __global__ __launch_bounds__(64) void i8_rerank_kernel(FinArgs p) {
 
 template <int D>
 int launch_scan(const ScanArgs& a, int64_t blocks, hipStream_t stream) {
-  const int lds = tt::topk::select_lds_bytes(a.rows_lds, a.k);
-  auto kern = i8_scan_kernel<D>;
-  if (lds > 64 * 1024) {   // above the 64 KiB default the limit must be raised (cheap, idempotent)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return tt::fail(TT_ERR_LAUNCH, "tt_retrieval_topk_i8_f32: hipFuncSetAttribute(LDS %d) failed", lds);
-  }
-  tt::launch("topk_i8_scan", kern, dim3((unsigned)blocks), dim3(64), (unsigned)lds, stream, a);
-  return tt::check_launch("topk_i8_scan");
+  return tt::topk::launch_select("topk_i8_scan", i8_scan_kernel<D>, tt::topk::select_lds_bytes(a.rows_lds, a.k), blocks, stream, a,
+                                 "tt_retrieval_topk_i8_f32");
 }
 
 template <int D>
