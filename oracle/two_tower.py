@@ -169,7 +169,7 @@ def retrieval_rank_bounds(q, c, pos_index, temperature=None, candidate_sampling_
 
 
 # --------------------------------------------------------------------------- a5
-PIECE = 64      # sorted slots per piece (csrc/sparse.hip kPiece)
+PIECE = 64      # sorted slots per piece (csrc/sparse_runs.h kPiece)
 
 
 def dedup_sum(ids, grads):

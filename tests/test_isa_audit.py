@@ -148,6 +148,35 @@ def test_select_kernels_on_the_shared_core_keep_their_occupancy_and_use_no_scrat
             assert occ >= occ_floor, (kernel, dim, v, a, occ, occ_floor)
 
 
+# waves per SIMD of the sparse optimizer kernels when each translation unit carried its own copy of the run / piece decode
+SPARSE_RUNS_OCCUPANCY_FLOOR = {
+    "sparse": {"sparse_apply_kernel<0>": 8, "sparse_apply_kernel<1>": 8, "optimizer_kernel<0>": 8, "optimizer_kernel<1>": 8},
+    "adam": {"adam_sparse_kernel": 5, "adam_finish_kernel": 5},
+    "rowwise": {"rowwise_sparse_kernel<1>": 8, "rowwise_sparse_kernel<2>": 5, "rowwise_sparse_kernel<4>": 4,
+                "rowwise_finish_kernel<1>": 7, "rowwise_finish_kernel<2>": 4, "rowwise_finish_kernel<4>": 5},
+}
+
+
+def test_sparse_optimizer_kernels_on_the_shared_decode_keep_their_occupancy_and_use_no_scratch(tmp_path):
+    """The SGD / Adagrad, lazy Adam and row-wise Adagrad kernels decode runs and pieces through csrc/sparse_runs.h.  No kernel of
+    the three translation units may spill, and none that calls the helpers may fit fewer waves per SIMD than it did with a hand
+    copy of the decode (the floors above).
+    VGPRs (informative, not pinned), hand copies -> shared helpers:
+      sparse_apply_kernel<SGD / Adagrad>   64 / 58        ->  64 / 58
+      optimizer_kernel<SGD / Adagrad>      59 / 59        ->  59 / 59
+      adam_sparse_kernel / adam_finish     85 / 82        ->  85 / 82
+      rowwise_sparse_kernel<1 / 2 / 4>     50 / 88 / 114  ->  50 / 88 / 116
+      rowwise_finish_kernel<1 / 2 / 4>     57 / 97 / 83   ->  57 / 97 / 81"""
+    for tu, floor in SPARSE_RUNS_OCCUPANCY_FLOOR.items():
+        res = _resources(tmp_path, tu)
+        for name, (v, a, scr, occ) in res.items():
+            assert scr == 0, (tu, name, v, a, scr, occ)
+        for kernel, occ_floor in floor.items():
+            v, a, scr, occ = res[kernel]
+            print(f"{kernel}: {v} VGPRs, {a} AGPRs, {occ} waves/SIMD")
+            assert occ >= occ_floor, (kernel, v, a, occ, occ_floor)
+
+
 def test_no_kernel_of_the_train_step_uses_scratch(tmp_path):
     """r03 left 40-132 B of scratch per lane in the exact-f32 dim-256 online-softmax kernels with accidental-hit ids / hard
     negatives (cfg5 with remove_accidental_hits runs one of them) and 20 B in a dim-128 gradient kernel; r04 keeps the last

@@ -1,8 +1,7 @@
 // Lazy Adam (TF-Addons LazyAdam / torch.optim.SparseAdam) on embedding rows and on the dense tower parameters.
 //
-// Only the rows of this batch's ids are touched; duplicates are summed first, in exactly the order of csrc/sparse.hip
-// (oracle.two_tower.dedup_sum: runs cut at global multiples of 64 sorted slots, pieces sequential, pieces added in index
-// order), so g is bit-identical to what SGD and Adagrad see.  Per element, every operation rounded once, no contraction:
+// Only the rows of this batch's ids are touched; duplicates are summed first, in the run / piece order of csrc/sparse_runs.h,
+// so g is bit-identical to what SGD and Adagrad see.  Per element, every operation rounded once, no contraction:
 //   m' = m + (g - m) * omb1          v' = v + (g*g - v) * omb2          w' = w - (alpha_t * m') / (sqrt(v') + eps)
 // with omb1 = 1 - beta1, omb2 = 1 - beta2, alpha_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) computed on the host in f64 and
 // rounded once to f32.
@@ -10,24 +9,22 @@
 // TWO stream-ordered launches, no communication inside a launch (no arrival tickets, no in-kernel wait between workgroups):
 //   A  adam_sparse_kernel   one lane group per sorted slot; only piece heads work.  A run inside its 64-slot block - the
 //                           common case - is summed and updated on the spot (g, w, m, v rows requested together).  A piece of
-//                           a run that crosses a block boundary stores its sum with plain stores: the head piece to P[block],
-//                           a piece that starts on a boundary to S[block].
-//   B  adam_finish_kernel   one lane group per 64-slot block: if the block holds a run head that continues past its end, it
-//                           finds the run's end (bounded binary search in the sorted ids), adds P[head block], S[head + 1] ...
-//                           S[last] in index order and applies the update.  The dense segments ride in this launch as extra
+//                           a run that crosses a block boundary stores its sum (P / S of its block) with plain stores.
+//   B  adam_finish_kernel   one lane group per 64-slot block: if a run crosses the block's end with its head in the block, it
+//                           adds the run's pieces and applies the update.  The dense segments ride in this launch as extra
 //                           workgroups (blockIdx.y >= n_tables).
 // B reads only what A wrote in the same call (the launch boundary is the synchronisation), so the workspace needs no
 // initialisation.
 // HBM-bound.  Algorithmic bytes per distinct row: 4*dim (grad) + 3 * 8*dim (w, m, v read + write) = 28*dim, + 12 (sorted id +
 // position); Adagrad moves 20*dim + 12.
 #include "common.h"
+#include "sparse_runs.h"
 #include <cmath>
 
 namespace {
 
 using tt::f32x4;
 
-constexpr int kPiece = 64;            // sorted slots per piece (csrc/sparse.hip kPiece, oracle.two_tower.PIECE)
 constexpr int kMaxAdamTables = 3;     // user, item, hashed category
 
 struct AdamTab {
@@ -84,59 +81,23 @@ __global__ __launch_bounds__(256) void adam_sparse_kernel(AdamArgs a, int dim4, 
   const int64_t k = (int64_t)blockIdx.x * groups + (threadIdx.x >> lpr_log2);   // sorted slot
   const int l = threadIdx.x & (lpr - 1);
   if (k >= n_ids) return;
-  // one round trip for everything the slot's position gives: its id, both neighbours, its batch position
-  const int64_t id = sid[k];
-  const int64_t id_left = sid[k > 0 ? k - 1 : 0], id_right = sid[k + 1 < n_ids ? k + 1 : n_ids - 1];
-  const int32_t ord0 = order[k];
-  const bool run_head = (k == 0) || (id_left != id);
-  const bool boundary = (k % kPiece) == 0;
-  if (!run_head && !boundary) return;             // inside a piece
-  if (id < 0 || id >= rows) return;               // out-of-range / padding ids (the plan's sentinel) are skipped
-  // ... then ONE more for the gradient row together with the table row and both moment rows (a piece that is not a whole
-  // run - rare - does not use the three: its id is valid, so the loads are in bounds)
+  tt::PieceHead hd;
+  if (!tt::piece_head(sid, order, k, n_ids, rows, hd)) return;   // inside a piece, or an out-of-range / padding id
+  // ... then ONE more round trip for the gradient row together with the table row and both moment rows (a piece that is not
+  // a whole run - rare - does not use the three: its id is valid, so the loads are in bounds)
   const int lc = l < dim4 ? l : dim4 - 1;
-  const int64_t row = id * dim4;
-  const f32x4 g_first = grads[(int64_t)ord0 * dim4 + lc];
+  const int64_t row = hd.id * dim4;
+  const f32x4 g_first = grads[(int64_t)hd.ord0 * dim4 + lc];
   const f32x4 w_first = table[row + lc];
   const f32x4 m_first = mom[row + lc];
   const f32x4 v_first = var[row + lc];
-  int64_t pend = (k / kPiece + 1) * kPiece;       // this piece ends at the next 64-slot boundary at the latest
-  if (pend > n_ids) pend = n_ids;
-  int64_t e = k + 1;                              // end of this piece: known from the right neighbour for the usual run of length 1,
-  if (e < pend && id_right == id) {               // else a binary search (sorted ids): <= 6 dependent loads per piece
-    int64_t lo = e + 1, hi = pend;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sid[mid] == id) lo = mid + 1; else hi = mid;
-    }
-    e = lo;
-  }
-  const bool continues = (e == pend) && (pend < n_ids) && (sid[pend] == id);
-  const bool whole = run_head && !continues;      // the usual case: the whole run is this piece
-  const int64_t blk = k / kPiece;
-  f32x4* __restrict__ piece_out = reinterpret_cast<f32x4*>(run_head ? a.tab[t].p_sum : a.tab[t].s_sum) + blk * dim4;
+  const tt::PieceExtent x = tt::piece_extent(sid, k, n_ids, hd);   // (behind the row requests: they fly during the search)
+  f32x4* __restrict__ piece_out = reinterpret_cast<f32x4*>(hd.run_head ? a.tab[t].p_sum : a.tab[t].s_sum) + x.blk * dim4;
 
   for (int c = l; c < dim4; c += lpr) {
-    f32x4 g = c == l ? g_first : grads[(int64_t)ord0 * dim4 + c];
-    // sequential walk over [k, e); four independent row loads in flight
-    int64_t j = k + 1;
-    while (j + 3 < e) {
-      f32x4 r[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = grads[(int64_t)order[j + u] * dim4 + c];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], r[u][q]);
-      j += 4;
-    }
-    while (j < e) {
-      const f32x4 g1 = grads[(int64_t)order[j] * dim4 + c];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], g1[q]);
-      ++j;
-    }
-    if (whole) {                                  // whole run summed: fused update
+    f32x4 g = c == l ? g_first : grads[(int64_t)hd.ord0 * dim4 + c];
+    tt::piece_walk<1, 4>(grads, order, dim4, &c, k + 1, x.e, &g);
+    if (x.whole) {                                // whole run summed: fused update
       if (c == l) adam_store(table, mom, var, row + c, w_first, m_first, v_first, g, h);
       else adam_store(table, mom, var, row + c, table[row + c], mom[row + c], var[row + c], g, h);
     } else {
@@ -158,40 +119,13 @@ __device__ __forceinline__ void adam_finish_body(const AdamArgs& a, const int t,
   const int groups = 256 >> lpr_log2;
   const int l = threadIdx.x & (lpr - 1);
   const int64_t jh = bx * groups + (threadIdx.x >> lpr_log2);   // 64-slot block
-  const int64_t nxt = (jh + 1) * kPiece;                        // first slot of the next block
-  if (nxt >= n_ids) return;                                     // nothing lies past the last block
-  const int64_t id = sid[nxt - 1];
-  const int64_t id_next = sid[nxt];
-  const int64_t id_before = sid[jh > 0 ? jh * kPiece - 1 : 0];
-  if (id_next != id) return;                                    // no run crosses this block's end
-  if (id < 0 || id >= a.tab[t].rows) return;                        // skipped ids wrote no pieces
-  if (jh > 0 && id_before == id) return;                        // the run's head lies in an earlier block, which finishes it
-  int64_t lo = nxt + 1, hi = n_ids;                             // one past the last slot of the run
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (sid[mid] <= id) lo = mid + 1; else hi = mid;            // sentinel / valid ids ascend
-  }
-  const int64_t jl = (lo - 1) / kPiece;                         // block of the run's last piece (> jh)
+  int64_t id, jl;                                               // the run that crosses this block's end, its last piece's block
+  if (!tt::crossing_run(sid, jh, n_ids, a.tab[t].rows, id, jl)) return;
   const int64_t row = id * dim4;
   for (int c = l; c < dim4; c += lpr) {
     const f32x4 w = table[row + c], m = mom[row + c], v = var[row + c];
-    f32x4 g = P[jh * dim4 + c];
-    int64_t b = jh + 1;
-    while (b + 3 <= jl) {                                       // four piece sums in flight, added in index order
-      f32x4 s[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] = S[(b + u) * dim4 + c];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], s[u][q]);
-      b += 4;
-    }
-    for (; b <= jl; ++b) {
-      const f32x4 s = S[b * dim4 + c];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], s[q]);
-    }
+    f32x4 g;
+    tt::add_pieces<1, 4>(P, S, dim4, &c, jh, jl, &g);
     adam_store(table, mom, var, row + c, w, m, v, g, h);
   }
 }
@@ -274,14 +208,11 @@ __global__ __launch_bounds__(256) void adam_finish_kernel(AdamArgs a, int n_tabl
   }
 }
 
-int64_t piece_blocks(int64_t n_ids) { return (n_ids + kPiece - 1) / kPiece; }
-int64_t piece_array_bytes(int64_t n_ids, int32_t dim) { return (piece_blocks(n_ids) * dim * 4 + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" int64_t tt_adam_workspace_bytes(int64_t n_ids, int32_t dim) {
   if (n_ids <= 0 || dim <= 0) return 0;
-  return 2 * piece_array_bytes(n_ids, dim);
+  return 2 * tt::piece_array_bytes(n_ids, dim);
 }
 
 extern "C" int tt_adam_step_f32(const tt_adam_table* tables, int32_t n_tables, int32_t dim, int64_t n_ids, const tt_adam_seg* segs,
@@ -307,24 +238,20 @@ extern "C" int tt_adam_step_f32(const tt_adam_table* tables, int32_t n_tables, i
     TT_REQUIRE(!sparse || (s.grads && s.sorted_ids && s.order), "%s: table %d: null pointer", who, t);
     TT_REQUIRE(tt::aligned16(s.table) && tt::aligned16(s.m) && tt::aligned16(s.v) && tt::aligned16(s.grads),
                "%s: table %d: table, m, v and grads must be 16-byte aligned", who, t);
-    TT_REQUIRE(!sparse || (s.workspace != nullptr && (reinterpret_cast<uintptr_t>(s.workspace) & 255u) == 0),
-               "%s: table %d: workspace must be non-null, 256-byte aligned", who, t);
+    if (sparse) {
+      const int rc = tt::split_piece_ws(who, t, s.workspace, n_ids, dim, a.tab[t].p_sum, a.tab[t].s_sum);
+      if (rc != TT_OK) return rc;
+    }
     a.tab[t].table = s.table; a.tab[t].m = s.m; a.tab[t].v = s.v; a.tab[t].grads = s.grads; a.tab[t].sorted_ids = s.sorted_ids; a.tab[t].order = s.order;
     a.tab[t].rows = s.rows;
-    if (sparse) {
-      a.tab[t].p_sum = static_cast<float*>(s.workspace);
-      a.tab[t].s_sum = reinterpret_cast<float*>(static_cast<char*>(s.workspace) + piece_array_bytes(n_ids, dim));
-    }
   }
   AdamSegTable tbl{};
   int64_t max_count = 0;
   for (int i = 0; i < n_segs; ++i) {
-    const tt_adam_seg& s = segs[i];
-    TT_REQUIRE(s.count > 0 && s.n_slabs >= 1 && s.grad_slabs != nullptr && s.param != nullptr, "%s: segment %d: bad count/slabs/param", who, i);
-    TT_REQUIRE(s.m != nullptr && s.v != nullptr, "%s: segment %d: Adam needs both moment arrays m and v", who, i);
-    TT_REQUIRE(s.n_slabs == 1 || s.slab_stride >= s.count, "%s: segment %d: slab_stride must be >= count", who, i);
-    tbl.seg[i] = s;
-    if (s.count > max_count) max_count = s.count;
+    const int rc = tt::check_dense_seg(who, i, segs[i], segs[i].m != nullptr && segs[i].v != nullptr,
+                                       "Adam needs both moment arrays m and v", max_count);
+    if (rc != TT_OK) return rc;
+    tbl.seg[i] = segs[i];
   }
   if (!sparse && n_segs == 0) return TT_OK;
   // the step's three scalars: f64 on the host, each rounded once to f32
@@ -337,10 +264,8 @@ extern "C" int tt_adam_step_f32(const tt_adam_table* tables, int32_t n_tables, i
 
   hipStream_t stream = tt::as_stream(stream_);
   const int dim4 = sparse ? dim / 4 : 1;
-  int lpr_log2 = 0;
-  while ((1 << lpr_log2) < dim4 && lpr_log2 < 5) ++lpr_log2;      // min(dim / 4, 32) lanes per row
+  const int lpr_log2 = tt::lanes_per_row_log2(dim4, 5);           // min(dim / 4, 32) lanes per row
   const int groups = 256 >> lpr_log2;
-  int64_t finish_blocks = 0;
   const int nt = sparse ? n_tables : 0;
   if (sparse) {
     const int64_t blocks = (n_ids + groups - 1) / groups;
@@ -348,14 +273,9 @@ extern "C" int tt_adam_step_f32(const tt_adam_table* tables, int32_t n_tables, i
     tt::launch("adam_sparse", adam_sparse_kernel, dim3((unsigned)blocks, (unsigned)nt), dim3(256), 0, stream, a, dim4, lpr_log2, n_ids, h);
     const int rc = tt::check_launch(who);
     if (rc != TT_OK) return rc;
-    finish_blocks = (piece_blocks(n_ids) + groups - 1) / groups;
   }
-  int64_t dense_blocks = (max_count / 4 + 255) / 256;
-  if (dense_blocks < 1) dense_blocks = 1;
-  if (dense_blocks > 512) dense_blocks = 512;
-  if (n_segs == 0) dense_blocks = 0;
-  const int64_t gx = finish_blocks > dense_blocks ? finish_blocks : dense_blocks;
-  tt::launch("adam_finish", adam_finish_kernel, dim3((unsigned)gx, (unsigned)(nt + n_segs)), dim3(256), 0, stream, a, nt, dim4, lpr_log2,
-             n_ids, finish_blocks, tbl, (int)dense_blocks, h);
+  const tt::FinishGrid f = tt::finish_grid(sparse, n_ids, groups, max_count, n_segs);
+  tt::launch("adam_finish", adam_finish_kernel, dim3((unsigned)f.gx, (unsigned)(nt + n_segs)), dim3(256), 0, stream, a, nt, dim4, lpr_log2,
+             n_ids, f.finish_blocks, tbl, (int)f.dense_blocks, h);
   return tt::check_launch(who);
 }

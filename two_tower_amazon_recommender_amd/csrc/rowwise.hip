@@ -2,8 +2,8 @@
 // Keras epsilon placement - and the existing element-wise Adagrad on the dense tower parameters.
 //
 // ONE accumulator float per table row, fed with the mean of the row's squared gradient.  Only the rows of this batch's ids are
-// touched (their accumulator included); duplicates are summed first, in exactly the order of csrc/sparse.hip
-// (oracle.two_tower.dedup_sum), so g is bit-identical to what SGD, Adagrad and lazy Adam see.  Every operation rounded once:
+// touched (their accumulator included); duplicates are summed first, in the run / piece order of csrc/sparse_runs.h, so g is
+// bit-identical to what SGD, Adagrad and lazy Adam see.  Every operation rounded once:
 //   q_j = g_j * g_j      S = sum_j q_j (fixed order, below)      a' = a + S * inv_dim      w' = w - (lr * g) / sqrt(a' + eps)
 // Order of S (a function of dim alone, the same in both launches): a lane group of lpr = min(32, dim/4 rounded up to a power of
 // two) lanes owns the row; lane l holds the float4 chunks c = l, l + lpr, ...; it adds its q values one after the other (chunks
@@ -13,11 +13,11 @@
 // TWO stream-ordered launches shaped like csrc/adam.hip's, no communication inside either (no tickets, no wait, no atomics):
 //   A  rowwise_sparse_kernel   one lane group per sorted slot; only piece heads work.  A run inside its 64-slot block is summed,
 //                              reduced to S and applied on the spot (gradient row, table row and the accumulator scalar are
-//                              requested together).  A piece of a run that crosses a block boundary stores its sum with plain
-//                              stores: the head piece to P[block], a piece that starts on a boundary to S[block].
-//   B  rowwise_finish_kernel   one lane group per 64-slot block finishes the run that crosses its end: P[head], S[head + 1] ...
-//                              S[last] in index order, then the same reduction and update (rowwise_update, shared with A).  The
-//                              dense segments ride as extra workgroups (blockIdx.y >= n_tables) in the dense Adagrad body.
+//                              requested together).  A piece of a run that crosses a block boundary stores its sum (P / S of
+//                              its block) with plain stores.
+//   B  rowwise_finish_kernel   one lane group per 64-slot block finishes the run that crosses its end: the pieces added, then
+//                              the same reduction and update (rowwise_update, shared with A).  The dense segments ride as
+//                              extra workgroups (blockIdx.y >= n_tables) in the dense Adagrad body.
 // A lane keeps its CPL = ceil(dim / (4 lpr)) chunks of g and w in registers (the kernels are instantiated for CPL 1, 2, 4:
 // dim <= 512); nothing spills.  The butterfly sits behind the chunk loops, and a lane group leaves or stays as a whole, so a
 // cross-lane read never leaves the active lanes.
@@ -25,13 +25,13 @@
 // position) = 12*dim + 20; Adagrad moves 20*dim + 12.
 #include "common.h"
 #include "dense_update_body.h"
+#include "sparse_runs.h"
 #include <cmath>
 
 namespace {
 
 using tt::f32x4;
 
-constexpr int kPiece = 64;              // sorted slots per piece (csrc/sparse.hip kPiece, oracle.two_tower.PIECE)
 constexpr int kMaxRowwiseTables = 3;    // user, item, hashed category
 constexpr int kMaxChunksPerLane = 4;    // 32 lanes x 4 float4 chunks: dim <= 512
 
@@ -99,74 +99,27 @@ __global__ __launch_bounds__(256) void rowwise_sparse_kernel(RowArgs a, int dim4
   const int64_t k = (int64_t)blockIdx.x * groups + (threadIdx.x >> lpr_log2);   // sorted slot
   const int l = threadIdx.x & (lpr - 1);
   if (k >= n_ids) return;
-  // one round trip for everything the slot's position gives: its id, both neighbours, its batch position
-  const int64_t id = sid[k];
-  const int64_t id_left = sid[k > 0 ? k - 1 : 0], id_right = sid[k + 1 < n_ids ? k + 1 : n_ids - 1];
-  const int32_t ord0 = order[k];
-  const bool run_head = (k == 0) || (id_left != id);
-  const bool boundary = (k % kPiece) == 0;
-  if (!run_head && !boundary) return;             // inside a piece
-  if (id < 0 || id >= rows) return;               // out-of-range / padding ids (the plan's sentinel) are skipped
-  // ... then ONE more for the gradient row together with the table row and the accumulator (a piece that is not a whole run -
-  // rare - does not use the two: its id is valid, so the loads are in bounds).  A chunk past the row re-reads the last one.
+  tt::PieceHead hd;
+  if (!tt::piece_head(sid, order, k, n_ids, rows, hd)) return;   // inside a piece, or an out-of-range / padding id
+  const int64_t id = hd.id;
+  // ... then ONE more round trip for the gradient row together with the table row and the accumulator (a piece that is not a
+  // whole run - rare - does not use the two: its id is valid, so the loads are in bounds).  A chunk past the row re-reads the last.
   int cc[CPL];
 #pragma unroll
   for (int i = 0; i < CPL; ++i) cc[i] = l + i * lpr < dim4 ? l + i * lpr : dim4 - 1;
   const int64_t row = id * dim4;
   f32x4 g[CPL], w[CPL];
 #pragma unroll
-  for (int i = 0; i < CPL; ++i) g[i] = grads[(int64_t)ord0 * dim4 + cc[i]];
+  for (int i = 0; i < CPL; ++i) g[i] = grads[(int64_t)hd.ord0 * dim4 + cc[i]];
 #pragma unroll
   for (int i = 0; i < CPL; ++i) w[i] = table[row + cc[i]];
   const float acc = accum[id];
-  int64_t pend = (k / kPiece + 1) * kPiece;       // this piece ends at the next 64-slot boundary at the latest
-  if (pend > n_ids) pend = n_ids;
-  int64_t e = k + 1;                              // end of this piece: known from the right neighbour for the usual run of length 1,
-  if (e < pend && id_right == id) {               // else a binary search (sorted ids): <= 6 dependent loads per piece
-    int64_t lo = e + 1, hi = pend;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sid[mid] == id) lo = mid + 1; else hi = mid;
-    }
-    e = lo;
-  }
-  const bool continues = (e == pend) && (pend < n_ids) && (sid[pend] == id);
-  const bool whole = run_head && !continues;      // the usual case: the whole run is this piece
-  const int64_t blk = k / kPiece;
-
-  // sequential walk over [k, e); U rows' loads in flight, every chunk of the lane
-  constexpr int U = CPL <= 2 ? 4 : 2;
-  int64_t j = k + 1;
-  while (j + U - 1 < e) {
-    f32x4 r[U][CPL];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t base = (int64_t)order[j + u] * dim4;
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) r[u][i] = grads[base + cc[i]];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int i = 0; i < CPL; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[i][q] = __fadd_rn(g[i][q], r[u][i][q]);
-    j += U;
-  }
-  while (j < e) {
-    const int64_t base = (int64_t)order[j] * dim4;
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const f32x4 g1 = grads[base + cc[i]];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[i][q] = __fadd_rn(g[i][q], g1[q]);
-    }
-    ++j;
-  }
-  if (whole) {                                    // (the same for every lane of the group) whole run summed: fused update
+  const tt::PieceExtent x = tt::piece_extent(sid, k, n_ids, hd);   // (behind the row requests: they fly during the search)
+  tt::piece_walk<CPL, (CPL <= 2 ? 4 : 2)>(grads, order, dim4, cc, k + 1, x.e, g);
+  if (x.whole) {                                  // (the same for every lane of the group) whole run summed: fused update
     rowwise_update<CPL>(table, accum, id, dim4, l, lpr, g, w, acc, h);
   } else {                                        // plain stores: launch B reads them behind the launch boundary
-    f32x4* __restrict__ piece_out = reinterpret_cast<f32x4*>(run_head ? a.tab[t].p_sum : a.tab[t].s_sum) + blk * dim4;
+    f32x4* __restrict__ piece_out = reinterpret_cast<f32x4*>(hd.run_head ? a.tab[t].p_sum : a.tab[t].s_sum) + x.blk * dim4;
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
       if (l + i * lpr < dim4) piece_out[l + i * lpr] = g[i];
@@ -186,54 +139,16 @@ __device__ __forceinline__ void rowwise_finish_body(const RowArgs& a, const int 
   const int groups = 256 >> lpr_log2;
   const int l = threadIdx.x & (lpr - 1);
   const int64_t jh = bx * groups + (threadIdx.x >> lpr_log2);   // 64-slot block
-  const int64_t nxt = (jh + 1) * kPiece;                        // first slot of the next block
-  if (nxt >= n_ids) return;                                     // nothing lies past the last block
-  const int64_t id = sid[nxt - 1];
-  const int64_t id_next = sid[nxt];
-  const int64_t id_before = sid[jh > 0 ? jh * kPiece - 1 : 0];
-  if (id_next != id) return;                                    // no run crosses this block's end
-  if (id < 0 || id >= a.tab[t].rows) return;                    // skipped ids wrote no pieces
-  if (jh > 0 && id_before == id) return;                        // the run's head lies in an earlier block, which finishes it
-  int64_t lo = nxt + 1, hi = n_ids;                             // one past the last slot of the run
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (sid[mid] <= id) lo = mid + 1; else hi = mid;            // sentinel / valid ids ascend
-  }
-  const int64_t jl = (lo - 1) / kPiece;                         // block of the run's last piece (> jh)
+  int64_t id, jl;                                               // the run that crosses this block's end, its last piece's block
+  if (!tt::crossing_run(sid, jh, n_ids, a.tab[t].rows, id, jl)) return;
   int cc[CPL];
 #pragma unroll
   for (int i = 0; i < CPL; ++i) cc[i] = l + i * lpr < dim4 ? l + i * lpr : dim4 - 1;
-  const int64_t row = id * dim4;
   f32x4 g[CPL], w[CPL];
 #pragma unroll
-  for (int i = 0; i < CPL; ++i) g[i] = P[jh * dim4 + cc[i]];
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) w[i] = table[row + cc[i]];
+  for (int i = 0; i < CPL; ++i) w[i] = table[id * dim4 + cc[i]];
   const float acc = accum[id];
-  constexpr int U = CPL <= 2 ? 4 : 1;                           // (4 chunks per lane: the registers go to g and w)
-  int64_t b = jh + 1;
-  while (b + U - 1 <= jl) {                                     // U piece sums in flight, added in index order
-    f32x4 s[U][CPL];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) s[u][i] = S[(b + u) * dim4 + cc[i]];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int i = 0; i < CPL; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[i][q] = __fadd_rn(g[i][q], s[u][i][q]);
-    b += U;
-  }
-  for (; b <= jl; ++b) {
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      const f32x4 s = S[b * dim4 + cc[i]];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[i][q] = __fadd_rn(g[i][q], s[q]);
-    }
-  }
+  tt::add_pieces<CPL, (CPL <= 2 ? 4 : 1)>(P, S, dim4, cc, jh, jl, g);   // (4 chunks per lane: the registers go to g and w)
   rowwise_update<CPL>(table, accum, id, dim4, l, lpr, g, w, acc, h);
 }
 
@@ -248,14 +163,10 @@ __global__ __launch_bounds__(256) void rowwise_finish_kernel(RowArgs a, int n_ta
   }
 }
 
-int64_t piece_blocks(int64_t n_ids) { return (n_ids + kPiece - 1) / kPiece; }
-int64_t piece_array_bytes(int64_t n_ids, int32_t dim) { return (piece_blocks(n_ids) * dim * 4 + 255) / 256 * 256; }
-
 template <int CPL>
 int launch_rowwise(const char* who, const RowArgs& a, int nt, bool sparse, int dim4, int lpr_log2, int64_t n_ids, const tt::SegTable& tbl,
                    int n_segs, int64_t max_count, RowCoef h, hipStream_t stream) {
   const int groups = 256 >> lpr_log2;
-  int64_t finish_blocks = 0;
   if (sparse) {
     const int64_t blocks = (n_ids + groups - 1) / groups;
     TT_REQUIRE(blocks <= 0x7fffffff, "%s: n_ids too large", who);
@@ -263,15 +174,10 @@ int launch_rowwise(const char* who, const RowArgs& a, int nt, bool sparse, int d
                n_ids, h);
     const int rc = tt::check_launch(who);
     if (rc != TT_OK) return rc;
-    finish_blocks = (piece_blocks(n_ids) + groups - 1) / groups;
   }
-  int64_t dense_blocks = (max_count / 4 + 255) / 256;
-  if (dense_blocks < 1) dense_blocks = 1;
-  if (dense_blocks > 512) dense_blocks = 512;
-  if (n_segs == 0) dense_blocks = 0;
-  const int64_t gx = finish_blocks > dense_blocks ? finish_blocks : dense_blocks;
-  tt::launch("rowwise_finish", rowwise_finish_kernel<CPL>, dim3((unsigned)gx, (unsigned)(nt + n_segs)), dim3(256), 0, stream, a, nt, dim4,
-             lpr_log2, n_ids, finish_blocks, tbl, (int)dense_blocks, h);
+  const tt::FinishGrid f = tt::finish_grid(sparse, n_ids, groups, max_count, n_segs);
+  tt::launch("rowwise_finish", rowwise_finish_kernel<CPL>, dim3((unsigned)f.gx, (unsigned)(nt + n_segs)), dim3(256), 0, stream, a, nt, dim4,
+             lpr_log2, n_ids, f.finish_blocks, tbl, (int)f.dense_blocks, h);
   return tt::check_launch(who);
 }
 
@@ -279,7 +185,7 @@ int launch_rowwise(const char* who, const RowArgs& a, int nt, bool sparse, int d
 
 extern "C" int64_t tt_rowwise_adagrad_workspace_bytes(int64_t n_ids, int32_t dim) {
   if (n_ids <= 0 || dim <= 0) return 0;
-  return 2 * piece_array_bytes(n_ids, dim);
+  return 2 * tt::piece_array_bytes(n_ids, dim);
 }
 
 extern "C" int tt_rowwise_adagrad_step_f32(const tt_rowwise_table* tables, int32_t n_tables, int32_t dim, int64_t n_ids,
@@ -301,31 +207,25 @@ extern "C" int tt_rowwise_adagrad_step_f32(const tt_rowwise_table* tables, int32
     TT_REQUIRE(!sparse || (s.grads && s.sorted_ids && s.order), "%s: table %d: null pointer", who, t);
     TT_REQUIRE(tt::aligned16(s.table) && tt::aligned16(s.grads), "%s: table %d: table and grads must be 16-byte aligned", who, t);
     TT_REQUIRE((reinterpret_cast<uintptr_t>(s.row_accum) & 3u) == 0, "%s: table %d: row_accum must be 4-byte aligned", who, t);
-    TT_REQUIRE(!sparse || (s.workspace != nullptr && (reinterpret_cast<uintptr_t>(s.workspace) & 255u) == 0),
-               "%s: table %d: workspace must be non-null, 256-byte aligned", who, t);
+    if (sparse) {
+      const int rc = tt::split_piece_ws(who, t, s.workspace, n_ids, dim, a.tab[t].p_sum, a.tab[t].s_sum);
+      if (rc != TT_OK) return rc;
+    }
     a.tab[t].table = s.table; a.tab[t].accum = s.row_accum; a.tab[t].grads = s.grads; a.tab[t].sorted_ids = s.sorted_ids;
     a.tab[t].order = s.order;
     a.tab[t].rows = s.rows;
-    if (sparse) {
-      a.tab[t].p_sum = static_cast<float*>(s.workspace);
-      a.tab[t].s_sum = reinterpret_cast<float*>(static_cast<char*>(s.workspace) + piece_array_bytes(n_ids, dim));
-    }
   }
   tt::SegTable tbl{};
   int64_t max_count = 0;
   for (int i = 0; i < n_segs; ++i) {
-    const tt_dense_seg& s = segs[i];
-    TT_REQUIRE(s.count > 0 && s.n_slabs >= 1 && s.grad_slabs != nullptr && s.param != nullptr, "%s: segment %d: bad count/slabs/param", who, i);
-    TT_REQUIRE(s.accum != nullptr, "%s: segment %d: Adagrad needs accum", who, i);
-    TT_REQUIRE(s.n_slabs == 1 || s.slab_stride >= s.count, "%s: segment %d: slab_stride must be >= count", who, i);
-    tbl.seg[i] = s;
-    if (s.count > max_count) max_count = s.count;
+    const int rc = tt::check_dense_seg(who, i, segs[i], segs[i].accum != nullptr, "Adagrad needs accum", max_count);
+    if (rc != TT_OK) return rc;
+    tbl.seg[i] = segs[i];
   }
   if (!sparse && n_segs == 0) return TT_OK;
 
   const int dim4 = sparse ? dim / 4 : 1;
-  int lpr_log2 = 0;
-  while ((1 << lpr_log2) < dim4 && lpr_log2 < 5) ++lpr_log2;      // min(32, dim / 4 rounded up to a power of two) lanes per row
+  const int lpr_log2 = tt::lanes_per_row_log2(dim4, 5);           // min(32, dim / 4 rounded up to a power of two) lanes per row
   const int cpl = (dim4 + (1 << lpr_log2) - 1) >> lpr_log2;       // float4 chunks per lane
   if (cpl > kMaxChunksPerLane)
     return tt::fail(TT_ERR_UNSUPPORTED, "%s: dim %d: rows of more than %d floats are not built", who, dim, 128 * kMaxChunksPerLane);

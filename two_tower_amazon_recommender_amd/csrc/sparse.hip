@@ -16,14 +16,14 @@
 #include "common.h"
 #include "dense_update_body.h"
 #include "part_sort.h"
+#include "sparse_runs.h"
 #include <cstdlib>
 #include <cstring>
 
 namespace {
 
 using tt::f32x4;
-
-constexpr int kPiece = 64;   // sorted slots per piece: runs are cut at global multiples of 64 slots
+using tt::kPiece;
 
 constexpr int kMaxSparseTables = 3;   // user, item, hashed category
 struct ApplyArgs {
@@ -93,6 +93,9 @@ __device__ __forceinline__ f32x4 load_piece(const f32x4* p) {
   return f32x4{__uint_as_float((uint32_t)lo), __uint_as_float((uint32_t)(lo >> 32)), __uint_as_float((uint32_t)hi),
                __uint_as_float((uint32_t)(hi >> 32))};
 }
+struct PieceLoad {
+  __device__ __forceinline__ f32x4 operator()(const f32x4* p) const { return load_piece(p); }
+};
 
 // A piece of a run that spans several 64-slot blocks (rare): find the run's extent, publish, take a ticket; the last
 // arriver adds the pieces in index order and applies the update.  (Inlined: as a real call it costs the callers 32-76 bytes of
@@ -104,24 +107,8 @@ __device__ __forceinline__ void finish_run_piece(f32x4* __restrict__ table, f32x
                                                  const int dim4, const int lpr_log2, const int64_t n_ids, const float lr, const float eps) {
   const int lpr = 1 << lpr_log2;
   const int l = threadIdx.x & (lpr - 1);
-  int64_t first = k;                              // first slot of the run (lower bound of id in the sorted ids)
-  if (!run_head) {
-    int64_t lo = 0, hi = k;                       // sid[k] == id, and the slot before a boundary piece holds id too
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sid[mid] < id) lo = mid + 1; else hi = mid;
-    }
-    first = lo;
-  }
-  int64_t last = e;                               // one past the last slot of the run
-  if (continues) {
-    int64_t lo = pend + 1, hi = n_ids;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sid[mid] <= id) lo = mid + 1; else hi = mid;      // sentinel / valid ids ascend; nothing sorts below 0
-    }
-    last = lo;
-  }
+  const int64_t first = run_head ? k : tt::run_begin(sid, k, id);                    // first slot of the run
+  const int64_t last = continues ? tt::run_end(sid, pend + 1, n_ids, id) : e;        // one past its last slot
   const int64_t jh = first / kPiece, jl = (last - 1) / kPiece;
   const int npieces = (int)(jl - jh + 1);
   // publish: this lane group's write-through stores (all in this wave) have left the CU before the ticket is drawn
@@ -144,23 +131,8 @@ __device__ __forceinline__ void finish_run_piece(f32x4* __restrict__ table, f32x
   // dependent L2 reads: the hottest id of a 1M-id power-law batch is 18,000 slots = 281 pieces = ~250 us of a 522 us launch.
   // Four, not eight: they reuse the registers of the walk's four gradient rows; more would cost the kernel a wave of occupancy.)
   for (int c = l; c < dim4; c += lpr) {
-    f32x4 g = load_piece(P + jh * dim4 + c);
-    int64_t m = jh + 1;
-    while (m + 3 <= jl) {
-      f32x4 s[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] = load_piece(S + (m + u) * dim4 + c);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], s[u][q]);
-      m += 4;
-    }
-    for (; m <= jl; ++m) {
-      const f32x4 s = load_piece(S + m * dim4 + c);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], s[q]);
-    }
+    f32x4 g;
+    tt::add_pieces<1, 4>(P, S, dim4, &c, jh, jl, &g, PieceLoad{});
     update_row<OPT>(table, accum, id * dim4 + c, g, lr, eps);
   }
 }
@@ -193,70 +165,37 @@ __device__ __forceinline__ void sparse_apply_body(const ApplyArgs& a, const int 
   // One round trip for everything the slot's position gives: its id, both neighbours, its batch position - then ONE more for
   // the gradient row together with the table (accumulator) row.  (Through r02 five dependent ones: id and left neighbour,
   // right neighbour, batch position, gradient row, table row; the 1M-id Adagrad line was 11 % behind r01h.)
-  const int64_t id = sid[k];
-  const int64_t id_left = sid[k > 0 ? k - 1 : 0], id_right = sid[k + 1 < n_ids ? k + 1 : n_ids - 1];
-  const int32_t ord0 = order[k];
-  const bool run_head = (k == 0) || (id_left != id);
-  const bool boundary = (k % kPiece) == 0;
-  if (!run_head && !boundary) return;             // inside a piece
-  if (id < 0 || id >= rows) return;               // out-of-range / padding ids (the plan's sentinel) are skipped
+  tt::PieceHead h;
+  if (!tt::piece_head(sid, order, k, n_ids, rows, h)) return;   // inside a piece, or an out-of-range / padding id
+  const int64_t id = h.id;
   const int lc = l < dim4 ? l : dim4 - 1;
   // (SGD: the table row with the gradient row.  Adagrad has no registers left for two more rows at 8 waves per SIMD - with
   // them it spills 20-72 B per lane and the 1M-id lines get 6 % slower, at 6 waves they are level - so its rows are read
   // where they are needed; r03 A/B on one box, SGD U/Z 371/544 -> 354/523 us.)
   // (AHEAD = false: inside optimizer_kernel, whose dense half needs the registers too)
   constexpr bool ROW_AHEAD = AHEAD && OPT == TT_OPT_SGD;
-  const f32x4 g_first = grads[(int64_t)ord0 * dim4 + lc];
+  const f32x4 g_first = grads[(int64_t)h.ord0 * dim4 + lc];
   f32x4 w_first = f32x4{0.f, 0.f, 0.f, 0.f};
   if constexpr (ROW_AHEAD) w_first = table[id * dim4 + lc];
-  int64_t pend = (k / kPiece + 1) * kPiece;       // this piece ends at the next 64-slot boundary at the latest
-  if (pend > n_ids) pend = n_ids;
-  int64_t e = k + 1;                              // end of this piece: known from the right neighbour for the usual run of length 1,
-  if (e < pend && id_right == id) {               // else a binary search (sorted ids): <= 6 dependent loads per piece
-    int64_t lo = e + 1, hi = pend;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sid[mid] == id) lo = mid + 1; else hi = mid;
-    }
-    e = lo;
-  }
-  const bool continues = (e == pend) && (pend < n_ids) && (sid[pend] == id);
-  const bool whole = run_head && !continues;      // the usual case: the whole run is this piece
-  const int64_t blk = k / kPiece;
-
+  const tt::PieceExtent x = tt::piece_extent(sid, k, n_ids, h);   // (behind the row requests: they fly during the search)
+  const bool whole = x.whole;                     // the usual case: the whole run is this piece
   for (int c = l; c < dim4; c += lpr) {
-    f32x4 g = c == l ? g_first : grads[(int64_t)ord0 * dim4 + c];
-    // sequential walk over [k, e); four independent row loads in flight (more would cost a wave of occupancy,
-    // which the random single-row case — almost every slot — needs more)
-    int64_t j = k + 1;
-    while (j + 3 < e) {
-      f32x4 r[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = grads[(int64_t)order[j + u] * dim4 + c];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = __fadd_rn(g[q], r[u][q]);
-      j += 4;
-    }
-    while (j < e) {
-      const f32x4 g1 = grads[(int64_t)order[j] * dim4 + c];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = __fadd_rn(g[e], g1[e]);
-      ++j;
-    }
+    f32x4 g = c == l ? g_first : grads[(int64_t)h.ord0 * dim4 + c];
+    // four independent row loads in flight (more would cost a wave of occupancy, which the random single-row case — almost
+    // every slot — needs more)
+    tt::piece_walk<1, 4>(grads, order, dim4, &c, k + 1, x.e, &g);
     if (whole) {                                                          // whole run summed: fused update
       if (ROW_AHEAD && c == l) update_store<OPT>(table, accum, id * dim4 + c, w_first, w_first, g, lr, eps);
       else update_row<OPT>(table, accum, id * dim4 + c, g, lr, eps);
-    } else if (run_head) {
-      store_piece(reinterpret_cast<f32x4*>(a.p_sum[t]) + blk * dim4 + c, g);   // first piece of a long run
+    } else if (h.run_head) {
+      store_piece(reinterpret_cast<f32x4*>(a.p_sum[t]) + x.blk * dim4 + c, g);   // first piece of a long run
     } else {
-      store_piece(reinterpret_cast<f32x4*>(a.s_sum[t]) + blk * dim4 + c, g);   // later piece (starts at slot 64*blk)
+      store_piece(reinterpret_cast<f32x4*>(a.s_sum[t]) + x.blk * dim4 + c, g);   // later piece (starts at slot 64*blk)
     }
   }
   if (whole) return;
   finish_run_piece<OPT>(table, accum, sid, reinterpret_cast<const f32x4*>(a.p_sum[t]), reinterpret_cast<const f32x4*>(a.s_sum[t]),
-                        a.p_flag[t], k, e, pend, id, run_head, continues, dim4, lpr_log2, n_ids, lr, eps);
+                        a.p_flag[t], k, x.e, x.pend, id, h.run_head, x.continues, dim4, lpr_log2, n_ids, lr, eps);
 }
 
 // r03, a prefetch in the fused optimizer (optimizer_ids_kernel) that touched every line of a row the moment the scan found its id.
@@ -831,11 +770,11 @@ struct PieceWs {
 };
 PieceWs piece_ws(int64_t n_ids, int32_t dim) {
   PieceWs w{};
-  w.nblk = (n_ids + kPiece - 1) / kPiece;
+  w.nblk = tt::piece_blocks(n_ids);
   w.off_flag = 0;
   w.off_p = align_up(w.nblk * 4, 256);
-  w.off_s = w.off_p + align_up(w.nblk * (int64_t)dim * 4, 256);
-  w.total = w.off_s + align_up(w.nblk * (int64_t)dim * 4, 256);
+  w.off_s = w.off_p + tt::piece_array_bytes(n_ids, dim);
+  w.total = w.off_s + tt::piece_array_bytes(n_ids, dim);
   w.off_pairs = w.off_keys = w.off_pos = 0;
   if (n_ids > tt::kPartSortMaxIds && n_ids <= tt::kPartSortBigMaxIds) {       // (scratch of a degenerate batch's global sort)
     w.off_pairs = w.total;
@@ -867,19 +806,12 @@ int launch_apply(int opt, ApplyArgs a, void* const ws[2], int n_tables, int32_t 
                  hipStream_t stream, const char* what) {
   if (n_ids == 0) return TT_OK;
   const int dim4 = dim / 4;
-  int lpr_log2 = 0;
-  while ((1 << lpr_log2) < dim4 && lpr_log2 < 6) ++lpr_log2;
+  const int lpr_log2 = tt::lanes_per_row_log2(dim4, 6);
   const int groups = 256 >> lpr_log2;
   const int64_t blocks = (n_ids + groups - 1) / groups;
   TT_REQUIRE(blocks <= 0x7fffffff, "%s: n_ids too large", what);
-  const PieceWs w = piece_ws(n_ids, dim);
-  for (int t = 0; t < n_tables; ++t) {
-    TT_REQUIRE(ws[t] != nullptr && (reinterpret_cast<uintptr_t>(ws[t]) & 255u) == 0, "%s: apply workspace must be non-null, 256-byte aligned", what);
-    char* base = static_cast<char*>(ws[t]);
-    a.p_flag[t] = reinterpret_cast<int32_t*>(base + w.off_flag);
-    a.p_sum[t] = reinterpret_cast<float*>(base + w.off_p);
-    a.s_sum[t] = reinterpret_cast<float*>(base + w.off_s);
-  }
+  const int rc = prepare_ws(a, ws, n_tables, dim, n_ids, what);
+  if (rc != TT_OK) return rc;
   if (opt == TT_OPT_SGD)
     tt::launch("sparse_apply", sparse_apply_kernel<TT_OPT_SGD>, dim3((unsigned)blocks, n_tables), dim3(256), 0, stream, a, dim4,
                        lpr_log2, n_ids, lr, eps);
@@ -973,8 +905,7 @@ extern "C" int tt_optimizer_step_f32(int32_t opt, const tt_sparse_table* tables,
     if (s.count > max_count) max_count = s.count;
   }
   const int dim4 = dim / 4;
-  int lpr_log2 = 0;
-  while ((1 << lpr_log2) < dim4 && lpr_log2 < 6) ++lpr_log2;
+  const int lpr_log2 = tt::lanes_per_row_log2(dim4, 6);
   const int groups = 256 >> lpr_log2;
   const int64_t sparse_blocks = (n_ids + groups - 1) / groups;
   int64_t dense_blocks = (max_count + 255) / 256;
@@ -1019,14 +950,9 @@ void ids_geometry(const int64_t* rows, int n_tables, int64_t n_ids, const tt_den
     if (ge.width[t] < 2u) ge.width[t] = 2u;
   }
 }
-int lanes_per_row_log2(int dim4) {
-  int l = 0;
-  while ((1 << l) < dim4 && l < 6) ++l;
-  return l;
-}
 // entries per row-range id list: what fast_apply finishes without ranks (kRowsAhead pairs per lane group), at most 256
 int bucket_cap(int32_t dim, int64_t n_ids) {
-  const int l = lanes_per_row_log2(dim / 4);
+  const int l = tt::lanes_per_row_log2(dim / 4, 6);
   if (l > 5 || n_ids > tt::kPartSortMaxIds) return 0;
   const int c = kRowsAhead * (1024 >> l);
   return c < 256 ? c : 256;
@@ -1193,8 +1119,7 @@ extern "C" int tt_optimizer_step_ids_f32(int32_t opt, const tt_sparse_table_ids*
     if (s.count > max_count) max_count = s.count;
   }
   const int dim4 = dim / 4;
-  int lpr_log2 = 0;
-  while ((1 << lpr_log2) < dim4 && lpr_log2 < 6) ++lpr_log2;
+  const int lpr_log2 = tt::lanes_per_row_log2(dim4, 6);
   (void)max_count; (void)max_groups;
   const int64_t gx = (int64_t)ft.first[n_tables] + ft.seg_first[n_segs];
   ft.cap = big ? tt::kPartSortMaxIds : (int32_t)((n_ids + 1023) / 1024 * 1024);
