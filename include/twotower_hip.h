@@ -19,6 +19,9 @@
  *   - Inputs are the int64 ids produced by
  *       scripts/data_processing/prepare_training_data.py:113-123,209-210 (user_idx,item_idx)
  *       src/data/preprocessor.py:478-491 (user_id_encoded, item_id_encoded, category_encoded).
+ *   - Serving - the exact, IVF and int8 top-K indices, and the MMR diversified re-ranking of the pool they return
+ *     (tt_mmr_rerank_f32, the last group below) - is what tfrs.layers.factorized_top_k would have served; the
+ *     reference's README promises it and its src/serving/ is empty.
  */
 #ifndef TWOTOWER_HIP_H
 #define TWOTOWER_HIP_H
@@ -67,7 +70,8 @@ int64_t tt_abi_struct_bytes(int32_t which);
  * topk_i8_rerank, topk_i8_scale), l2norm_fwd, l2norm_bwd, adam_sparse, adam_finish (the two launches of tt_adam_step_f32), bag_fwd, bag_bwd, sample (tt_sample_candidates_i64),
  * features_fwd, features_bwd (tt_dense_features_*_f32), rating_fwd, rating_bwd (tt_rating_head_*_f32), cross_fwd, cross_bwd
  * (tt_cross_*_f32), layer_norm_fwd, layer_norm_bwd (tt_layer_norm_*_f32), rowwise_sparse, rowwise_finish (the two launches of
- * tt_rowwise_adagrad_step_f32), freq_update, freq_estimate (the two launches of tt_frequency_estimate_i64).
+ * tt_rowwise_adagrad_step_f32), freq_update, freq_estimate (the two launches of tt_frequency_estimate_i64), mmr
+ * (tt_mmr_rerank_f32).
  * An empty string (or NULL) disables it.
  * tt_profile_read synchronises on the recorded events, writes up to `cap` durations in
  * milliseconds (launch order) to the HOST array `ms`, stores the number of durations written in
@@ -1181,6 +1185,34 @@ int tt_time_context_fwd_f32(const int64_t* timestamps, int64_t n, const float* t
                             const int64_t* base_ids, int32_t* idx_out, int32_t* oob_flag, tt_stream_t stream);
 int tt_time_context_bwd_f32(const int32_t* idx, const float* dy, int64_t n, int32_t dim, int32_t field_mask,
                             int32_t buckets, int64_t table_rows, float* grad, tt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * MMR diversified re-ranking with per-group caps (added to v10: a new symbol only, the version is unchanged; csrc/mmr.hip) -
+ * Maximal Marginal Relevance (Carbonell & Goldstein 1998) over the pool of candidates a top-K call returned.
+ * Per query: scores f32 [k1] (best first) and idx int64 [k1] (rows of c, -1 = padding) as every index writes them; c f32
+ * [nc, dim], the corpus in ORIGINAL row order; groups int32 [nc] (NULL: no cap) with max_per_group = m (0: no cap; groups is
+ * then not read); lambda in [0, 1]; k <= k1.  Every operation is ONE IEEE f32 operation, rounded once:
+ *   valid(j)  = 0 <= idx[j] < nc and scores[j] finite; an invalid candidate is never read from c and never picked
+ *   dot(a, b) = four partial sums s_e, e = d mod 4, from +0: s_e = s_e + a[d] * b[d] for d ascending (product rounded, then the
+ *               sum), joined as (s0 + s1) + (s2 + s3)
+ *   n2_j = dot(c_j, c_j);  inv_j = n2_j > 0 ? 1 / sqrt(n2_j) : 0
+ *   lo, hi = min, max of the valid scores;  rel_j = hi > lo ? (s_j - lo) / (hi - lo) : 0
+ *   pen_j = 0, cnt_j = 0, om = 1 - lambda; then for t = 0 .. k - 1:
+ *     eligible(j) = valid, unpicked and - with m > 0 and groups[idx[j]] >= 0 - cnt_j < m
+ *     p = the eligible j with the largest val_j = lambda * rel_j - om * pen_j, ties to the lower position j; none: stop
+ *     out_scores[t] = scores[p] (the ORIGINAL score: the list need not be monotone), out_idx[t] = idx[p]
+ *     every valid j: sim = (dot(c_j, c_p) * inv_j) * inv_p;  pen_j = max(pen_j, sim)  (cosine, floored at 0);
+ *                    cnt_j += 1 where groups[idx[j]] == groups[idx[p]] >= 0
+ *   the unfilled tail is (-inf, -1).
+ * Hence lambda = 1 without a cap returns the first k valid candidates unchanged; a group id of -1 is never capped; a
+ * query's row is bit-identical alone, in any batch and on any run.  c must be finite.
+ * One launch, one workgroup per query, no workspace, no atomics, nothing copied to the host; nq == 0 launches nothing.
+ * Refused with TT_ERR_INVALID_ARG before any launch: a null pointer (groups excepted), nq < 0 (or > 2^31 - 1), k1 outside
+ * 1..TT_TOPK_MAX_K, k outside 1..k1, dim not a multiple of 4 in 4..1024, nc outside 1..2^31 - 1, lambda outside [0, 1] or
+ * NaN, max_per_group < 0, max_per_group > 0 with groups == NULL, c not 16-byte aligned.  Profiling tag: mmr.             */
+int tt_mmr_rerank_f32(const float* scores, const int64_t* idx, int64_t nq, int32_t k1, const float* c, int64_t nc, int32_t dim,
+                      const int32_t* groups /* NULL: no cap */, int32_t max_per_group, float lambda, int32_t k,
+                      float* out_scores, int64_t* out_idx, tt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -295,6 +295,7 @@ SIGNATURES = {
     "tt_retrieval_bwd_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _p, _p, _f, _p, _i64, _p, _p, _p]),
     "tt_time_context_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i64, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p]),
     "tt_time_context_bwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i64, _p, _p]),
+    "tt_mmr_rerank_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i32, _f, _i32, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

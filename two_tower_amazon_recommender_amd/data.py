@@ -67,6 +67,17 @@ def item_categories(item_idx: np.ndarray, category_bucket: np.ndarray, n_items: 
     return out
 
 
+def item_category_groups(item_idx: np.ndarray, category_codes: np.ndarray, n_items: int) -> np.ndarray:
+    """Group id of every item row (int32 [n_items]) for a per-category cap (``serving.MMR``): the category CODE
+    (``read_category_values``) of the item's first interaction; -1 - never capped - for items never seen.  Ids outside
+    [0, n_items) are ignored."""
+    out = np.full(n_items, -1, dtype=np.int32)
+    items, first = np.unique(item_idx, return_index=True)
+    keep = (items >= 0) & (items < n_items)
+    out[items[keep]] = category_codes[first[keep]]
+    return out
+
+
 TIMESTAMP_COLUMN = "timestamp"  # prepare_training_data.py:93-94: written as a number
 
 

@@ -2013,6 +2013,44 @@ def retrieval_topk_i8(q, codes, scales, k: int, c=None, k1: int | None = None, e
     return scores, indices
 
 
+def mmr_rerank(scores, idx, c, k: int, lam: float, groups=None, max_per_group: int = 0, out=None):
+    """MMR diversified re-ranking (``tt_mmr_rerank_f32``) of the pool a top-k call returned: ``scores`` f32 [nq, k1] best
+    first and ``idx`` int64 [nq, k1] rows of the f32 corpus ``c`` [nc, D] in original order (-1 = padding).  Greedily picks
+    ``k`` <= k1 candidates per query by lam * (min-max normalised score) - (1 - lam) * (largest cosine to an item already
+    picked, floored at 0), ties to the earlier candidate; with ``groups`` int32 [nc] and ``max_per_group`` = m > 0 at most m
+    picks share a group id (-1: never capped).  Returns (scores f32 [nq, k] - the original scores, in pick order -, indices
+    int64 [nq, k]); when the pool runs out the tail is (-inf, -1).  ``lam`` = 1 without a cap keeps the first k valid
+    candidates.  One launch, no workspace.  ``out``: optional (scores, indices) to write into."""
+    _chk(scores, torch.float32, "scores", 2)
+    _chk(idx, torch.int64, "idx", 2)
+    _chk(c, torch.float32, "candidate_embeddings", 2)
+    nq, k1 = scores.shape
+    if tuple(idx.shape) != (nq, k1):
+        raise ValueError(f"mmr_rerank: idx must be [{nq}, {k1}] like scores, got {tuple(idx.shape)}")
+    nc, d = c.shape
+    k, max_per_group, lam = int(k), int(max_per_group), float(lam)
+    if not 1 <= k1 <= TOPK_MAX_K:
+        raise ValueError(f"mmr_rerank: the pool k1 = {k1} must be in [1, {TOPK_MAX_K}]")
+    if not 1 <= k <= k1:
+        raise ValueError(f"mmr_rerank: k = {k} must be in [1, k1 = {k1}]")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"mmr_rerank: lam = {lam} must be in [0, 1]")
+    if max_per_group < 0:
+        raise ValueError(f"mmr_rerank: max_per_group = {max_per_group} must be >= 0")
+    if groups is not None:
+        _chk(groups, torch.int32, "groups", 1)
+        if groups.numel() != nc:
+            raise ValueError(f"mmr_rerank: groups needs {nc} entries (one per corpus row), got {groups.numel()}")
+    elif max_per_group > 0:
+        raise ValueError(f"mmr_rerank: max_per_group = {max_per_group} needs groups")
+    _, out_s, out_i = _topk_buffers("mmr_rerank", 0, nq, k, scores.device, None, out)
+    if nq == 0:                                              # (empty tensors have no address to hand over)
+        return out_s, out_i
+    _lib.check(_lib.load().tt_mmr_rerank_f32(_p(scores), _p(idx), nq, k1, _p(c), nc, d, _p(groups), max_per_group, lam, k,
+                                             _p(out_s), _p(out_i), _stream()), "tt_mmr_rerank_f32")
+    return out_s, out_i
+
+
 def check_list_offsets(list_offsets, n: int, what: str) -> None:
     """Raise unless list_offsets starts at 0, is non-decreasing and ends at n (checked on the device)."""
     bad = (list_offsets[0] != 0) | (list_offsets[-1] != n) | (list_offsets.diff() < 0).any()

@@ -14,6 +14,12 @@ Output parquet: one row per (user, rank) with columns user_idx, rank (0 = best),
 than k unexcluded items gets fewer rows.  For a model trained with the rating head (``train.py --rating-weight``),
 ``--predict-ratings`` adds the column predicted_rating - the head's prediction for every returned (user, item) - and
 ``--rank-by rating`` re-orders each user's k retrieved items by it (retrieve, then rank; the item set is the retrieval's).
+
+``--diversify LAMBDA`` re-ranks every user's list by Maximal Marginal Relevance (``serving.MMR`` around the chosen index):
+the index is asked for ``--diversify-pool`` x k candidates and k of them are picked greedily, LAMBDA x relevance against
+(1 - LAMBDA) x the largest cosine to an item already picked (1.0 = the plain top-k, 0.0 = diversity only);
+``--max-per-category M`` also allows at most M items of one category per user (the category of an item's first interaction
+in ``--data``).  The rank column is then the diversified order and the scores need not descend.
 """
 from __future__ import annotations
 
@@ -64,6 +70,15 @@ def parse(argv=None):
     ap.add_argument("--at-time", default=None, metavar="SECONDS|YYYY-MM-DD",
                     help="models trained with --time-features: the time the recommendations are asked for - whole seconds since the "
                          "epoch, or a UTC date (its midnight); default: the checkpoint's time_max, the newest training timestamp")
+    ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA",
+                    help="re-rank every user's list by Maximal Marginal Relevance: LAMBDA in [0, 1] weighs relevance against the "
+                         "cosine to the items already picked (1.0: the plain top-k; 0.0: diversity only)")
+    ap.add_argument("--diversify-pool", type=int, default=None, metavar="P",
+                    help=f"--diversify: candidates the index is asked for per user, as a multiple of --k (default 4; at least 32 "
+                         f"and at most {MAX_K} candidates)")
+    ap.add_argument("--max-per-category", type=int, default=None, metavar="M",
+                    help="at most M items of one category per user (the category column of --data, an item's category being that "
+                         "of its first interaction); implies --diversify 1.0 when that flag is absent")
     args = ap.parse_args(argv)
     if args.at_time is not None:
         try:
@@ -90,6 +105,22 @@ def parse(argv=None):
             ap.error(f"--nlist must be positive, got {args.nlist}")
         if not 1 <= args.nprobe <= min(MAX_K, args.nlist):
             ap.error(f"--nprobe must be in [1, min({MAX_K}, --nlist {args.nlist})], got {args.nprobe}")
+    if args.max_per_category is not None:
+        if args.max_per_category < 1:
+            ap.error(f"--max-per-category must be positive, got {args.max_per_category}")
+        if args.data is None:
+            ap.error("--max-per-category needs --data (the interactions that give every item its category)")
+        if args.diversify is None:
+            args.diversify = 1.0
+    if args.diversify is not None and not 0.0 <= args.diversify <= 1.0:         # (NaN fails both comparisons)
+        ap.error(f"--diversify must be in [0, 1], got {args.diversify}")
+    if args.diversify_pool is not None:
+        if args.diversify is None:
+            ap.error("--diversify-pool needs --diversify or --max-per-category")
+        if args.diversify_pool < 1:
+            ap.error(f"--diversify-pool must be positive, got {args.diversify_pool}")
+    elif args.diversify is not None:
+        args.diversify_pool = 4
     if args.exclude_seen and args.data is None:
         ap.error("--exclude-seen needs --data (the interactions that define what each user has seen)")
     if _SHARDED.search(args.checkpoint) or (not os.path.exists(args.checkpoint)
@@ -138,7 +169,7 @@ def main(argv=None) -> int:
     import pyarrow as pa
     import pyarrow.parquet as pq
     from . import data as datamod
-    from .serving import IVF, BruteForce, Int8BruteForce, Int8IVF
+    from .serving import IVF, MMR, BruteForce, Int8BruteForce, Int8IVF
     from .trainer import TwoTowerConfig, TwoTowerTrainer
 
     dev = torch.device(args.device)
@@ -183,14 +214,24 @@ def main(argv=None) -> int:
         if args.nlist > cfg.n_items:
             raise SystemExit(f"--nlist {args.nlist} exceeds the model's {cfg.n_items} items")
         if args.index == "ivf":
-            bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed).index_from_trainer(trainer, item_cat, at_time)
+            bf = IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed)
         else:
-            bf = Int8IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed,
-                         rerank=args.rerank).index_from_trainer(trainer, item_cat, at_time)
+            bf = Int8IVF(k=k, nlist=args.nlist, nprobe=args.nprobe, seed=args.seed, rerank=args.rerank)
     elif args.index == "int8":
-        bf = Int8BruteForce(k=k, rerank=args.rerank).index_from_trainer(trainer, item_cat, at_time)
+        bf = Int8BruteForce(k=k, rerank=args.rerank)
     else:
-        bf = BruteForce(k=k).index_from_trainer(trainer, item_cat, at_time)
+        bf = BruteForce(k=k)
+    if args.diversify is None:
+        bf.index_from_trainer(trainer, item_cat, at_time)
+    else:
+        item_groups = None
+        if args.max_per_category is not None:
+            cv = datamod.read_category_values(args.data)
+            if cv is None:
+                raise SystemExit(f"{args.data} has none of the columns {datamod.CATEGORY_COLUMNS} --max-per-category needs")
+            item_groups = torch.from_numpy(datamod.item_category_groups(item_idx, cv[0], cfg.n_items)).to(dev)
+        bf = MMR(bf, lambda_=args.diversify, pool=args.diversify_pool,
+                 max_per_group=args.max_per_category or 0).index_from_trainer(trainer, item_cat, at_time, groups=item_groups)
     seen = seen_csr(user_idx, item_idx, cfg.n_users) if args.exclude_seen else None
 
     cols = {"user_idx": [], "rank": [], "item_idx": [], "score": []}

@@ -24,6 +24,13 @@ with ``keep_f32=False`` it serves the quantised order alone, from a quarter of t
 re-rank; it answers what ``Int8BruteForce`` answers over the items of the probed lists.
 
     i8ivf = Int8IVF(k=10, nlist=1024, nprobe=32, rerank=4).index_from_trainer(trainer)
+
+``MMR`` wraps any of the four and diversifies what it returns: the index is asked for a pool of ``pool * k`` candidates,
+and one ``tt_mmr_rerank_f32`` launch per call picks k of them greedily, trading the (min-max normalised) score against the
+largest cosine to an item already picked (Maximal Marginal Relevance), optionally with at most ``max_per_group`` items of
+one group.  ``lambda_ = 1`` without a cap is the index's own top-k.
+
+    mmr = MMR(BruteForce(k=10), lambda_=0.7, pool=4, max_per_group=2).index_from_trainer(trainer, groups=item_groups)
 """
 from __future__ import annotations
 
@@ -462,3 +469,120 @@ class Int8IVF(IVF):
             return scores, idx
         ids = self._identifiers[idx.clamp(min=0)]
         return scores, torch.where(idx >= 0, ids, torch.full_like(ids, -1))
+
+
+class MMR:
+    """Diversified re-ranking (Maximal Marginal Relevance, ``ops.mmr_rerank``) over any of the indices above.
+
+    ``index``: a ``BruteForce`` / ``IVF`` / ``Int8BruteForce`` / ``Int8IVF`` (its ``k`` is the default number of results and its
+    query model is used).  ``lambda_`` in [0, 1]: 1 = relevance only, 0 = diversity only.  ``pool``: the candidates asked of
+    the index, as a multiple of k (``ops.default_k1``: at least 32, at most ``TOPK_MAX_K`` and the corpus).
+    ``max_per_group``: at most that many results share a group id (0: no cap; needs ``groups`` when indexing).
+
+    The wrapper keeps the f32 corpus in ORIGINAL row order (the index's own copy where it has one in that order) and the
+    identifiers; the inner index is built without identifiers, so what it returns are corpus rows."""
+
+    def __init__(self, index, lambda_: float = 0.7, pool: int = 4, max_per_group: int = 0):
+        self.inner = index
+        self.lambda_, self.pool, self.max_per_group = float(lambda_), int(pool), int(max_per_group)
+        if not 0.0 <= self.lambda_ <= 1.0:
+            raise ValueError(f"MMR: lambda_ = {lambda_} must be in [0, 1]")
+        if self.pool < 1:
+            raise ValueError(f"MMR: pool must be >= 1, got {self.pool}")
+        if self.max_per_group < 0:
+            raise ValueError(f"MMR: max_per_group must be >= 0, got {self.max_per_group}")
+        self._corpus = self._identifiers = self._groups = None
+
+    @property
+    def k(self) -> int:
+        return self.inner.k
+
+    def _set_groups(self, groups, n: int, device):
+        if groups is not None:
+            g = torch.as_tensor(groups, device=device)
+            if g.dim() != 1 or g.numel() != n:
+                raise ValueError(f"MMR.index: groups must be [{n}], got {tuple(g.shape)}")
+            if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+                raise TypeError(f"MMR.index: groups must be integers, got {g.dtype}")
+            groups = g.to(torch.int32).contiguous()
+        elif self.max_per_group > 0:
+            raise ValueError(f"MMR.index: max_per_group = {self.max_per_group} needs groups")
+        self._groups = groups
+
+    def index(self, candidates: torch.Tensor, identifiers=None, groups=None) -> "MMR":
+        """candidates, identifiers: as ``BruteForce.index``.  groups: optional [n] integer tensor, the group id of every
+        candidate (-1: never capped)."""
+        if candidates.dim() != 2:
+            raise ValueError(f"MMR.index: candidates must be [n, D], got shape {tuple(candidates.shape)}")
+        x = candidates.detach().to(torch.float32).contiguous()
+        n = x.shape[0]
+        if identifiers is not None:
+            ids = torch.as_tensor(identifiers, device=x.device)
+            if ids.dim() != 1 or ids.numel() != n:
+                raise ValueError(f"MMR.index: identifiers must be [{n}], got {tuple(ids.shape)}")
+            if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+                raise TypeError(f"MMR.index: identifiers must be integers, got {ids.dtype}")
+            identifiers = ids.to(torch.int64).contiguous()
+        self._set_groups(groups, n, x.device)
+        self.inner.index(x)                                  # no identifiers: the index answers corpus rows
+        self._corpus, self._identifiers = x, identifiers
+        return self
+
+    def index_from_trainer(self, trainer, item_category_ids: torch.Tensor | None = None, at_time: int | None = None,
+                           groups=None) -> "MMR":
+        """As ``BruteForce.index_from_trainer``; ``groups`` as in ``index``."""
+        self.index(trainer.item_corpus_embeddings(item_category_ids), groups=groups)
+        if self.inner.query_model is None:
+            self.inner.query_model = _trainer_query_model(trainer, at_time)
+        return self
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self) -> dict:
+        """The inner index's state (plus ``groups`` where there are any)."""
+        if not hasattr(self.inner, "state_dict"):
+            raise RuntimeError(f"MMR: {type(self.inner).__name__} has no state to save; index() it again instead")
+        state = dict(self.inner.state_dict())
+        if self._groups is not None:
+            state["groups"] = self._groups
+        return state
+
+    def load_state_dict(self, state: dict) -> "MMR":
+        if not hasattr(self.inner, "load_state_dict"):
+            raise RuntimeError(f"MMR: {type(self.inner).__name__} has no state to load; index() it instead")
+        inner = self.inner.load_state_dict(state)
+        if getattr(inner, "list_vectors", None) is not None:     # IVF keeps its rows list by list: back to original order
+            corpus = torch.empty_like(inner.list_vectors)
+            corpus[inner.list_ids.to(torch.int64)] = inner.list_vectors
+        elif inner._candidates is not None:
+            corpus = inner._candidates
+        else:
+            raise ValueError("MMR.load_state_dict: the state holds no f32 corpus (an int8 index saved with keep_f32=False)")
+        self._set_groups(state.get("groups"), corpus.shape[0], corpus.device)
+        self._corpus, self._identifiers = corpus, None
+        return self
+
+    # ------------------------------------------------------------------ query
+    def _query(self, queries, exclusions, k):
+        if self._corpus is None:
+            raise RuntimeError("MMR: call index() or index_from_trainer() first")
+        k = self.inner.k if k is None else int(k)
+        n = self._corpus.shape[0]
+        if not 1 <= k <= min(ops.TOPK_MAX_K, n):
+            raise ValueError(f"MMR: k = {k} must be in [1, min({ops.TOPK_MAX_K}, n = {n})]")
+        k1 = ops.default_k1(k, n, True, self.pool)
+        scores, idx = self.inner._query(queries, exclusions, k1)
+        scores, idx = ops.mmr_rerank(scores, idx, self._corpus, k, self.lambda_, groups=self._groups,
+                                     max_per_group=self.max_per_group)
+        if self._identifiers is None:
+            return scores, idx
+        ids = self._identifiers[idx.clamp(min=0)]
+        return scores, torch.where(idx >= 0, ids, torch.full_like(ids, -1))
+
+    def __call__(self, queries, k: int | None = None):
+        """(scores f32 [nq, k], identifiers or indices int64 [nq, k]) in the diversified order; the scores are the index's
+        own, so they need not descend.  When the pool runs out (exclusions, caps) the tail is (-inf, -1)."""
+        return self._query(queries, None, k)
+
+    def query_with_exclusions(self, queries, exclusions, k: int | None = None):
+        """As ``__call__``, never returning an excluded candidate (``exclusions`` as ``BruteForce.query_with_exclusions``)."""
+        return self._query(queries, exclusions, k)

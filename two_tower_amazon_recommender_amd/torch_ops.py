@@ -428,6 +428,22 @@ def _(q, codes, scales, c, k, k1, exclusion_offsets, exclusion_indices):
     return q.new_empty((q.shape[0], k)), q.new_empty((q.shape[0], k), dtype=torch.int64)
 
 
+@torch.library.custom_op(f"{NS}::mmr_rerank", mutates_args=(), device_types="cuda")
+def mmr_rerank(scores: Tensor, idx: Tensor, candidate_embeddings: Tensor, k: int, lam: float, groups: Optional[Tensor],
+               max_per_group: int) -> Tuple[Tensor, Tensor]:
+    """MMR diversified re-ranking of a top-k pool (ops.mmr_rerank): k of the k1 candidates per query, relevance traded
+    against the cosine to the items already picked, optionally at most max_per_group per group id.  Not differentiable
+    (serving)."""
+    g = None if groups is None else groups.contiguous()
+    return ops.mmr_rerank(scores.contiguous(), idx.contiguous(), candidate_embeddings.contiguous(), k, lam, groups=g,
+                          max_per_group=max_per_group)
+
+
+@mmr_rerank.register_fake
+def _(scores, idx, c, k, lam, groups, max_per_group):
+    return scores.new_empty((scores.shape[0], k)), scores.new_empty((scores.shape[0], k), dtype=torch.int64)
+
+
 _IVF_I8_WS: dict = {}
 
 
@@ -862,5 +878,5 @@ def _(sketch, ids, n_update, step, alpha, n_items, seed, tensor_id, sampler_prob
     return ids.new_empty((ids.shape[0],), dtype=torch.float32)
 
 
-OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "dense_fwd",
+OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "mmr_rerank", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "time_context", "time_context_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")
