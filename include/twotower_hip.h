@@ -1214,6 +1214,42 @@ int tt_mmr_rerank_f32(const float* scores, const int64_t* idx, int64_t nq, int32
                       const int32_t* groups /* NULL: no cap */, int32_t max_per_group, float lambda, int32_t k,
                       float* out_scores, int64_t* out_idx, tt_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * GRU encoder of the user history (added to v10: new symbols only, the version is unchanged; csrc/history_gru.hip) - Keras
+ * GRU(units = dim, reset_after = True), zero initial state, mask-aware stepping over the kept slots of a bag in slot order (the
+ * newest kept item is the last step).  W, U [dim, 3 dim] f32 row-major with the gate column blocks z | r | n, b_i, b_r [3 dim]:
+ *   a = x_t W + b_i     g = h U + b_r     z = sigmoid(a_z + g_z)     r = sigmoid(a_r + g_r)     n = tanh(a_n + r g_n)
+ *   h <- z h + (1 - z) n              a skipped slot leaves h untouched, bit for bit; a bag without a kept slot: h = 0
+ * dim a multiple of 32 in 32..256, L in 1..64, n_bags * L < 2^31.  All f32; the products run on the f32-input MFMA.
+ * tt_history_gru_resolve_f32, one launch: batch_ids [n_bags * L] (may be NULL) = every slot's token, -1 where skipped, and
+ *   x [n_bags * L, dim] = the slot's table row, zeros where skipped - tokens, bag_rows, exclude and *oob_flag follow
+ *   tt_history_attention_fwd_f32's rules (padding, out-of-range tokens and bag rows, the excluded token).
+ * The input projection a = x W + b_i over all n_bags * L rows is tt_dense_fwd_batched_f32 (m = n_bags * L, k = dim, n = 3 dim).
+ * tt_history_gru_fwd_f32, one launch: out[b] = base_table[base_ids[b]] + h_final (base_table / base_ids both or neither; a base
+ *   id out of range: a zero row and, unless -1, the flag; a bag without a kept slot: the base row itself).  gates
+ *   [n_bags * L, 3 dim], gn [n_bags * L, dim] and hprev [n_bags * L, dim] (all three or none) keep what the backward needs:
+ *   z | r | n and g_n of every KEPT slot (a skipped slot's row of gates is its row of a, its row of gn zeros) and h_{t-1} of
+ *   every slot - all three written in full.  gates may BE a (in place); no other buffers may alias.  A bag's bits depend on
+ *   that bag alone.
+ * tt_history_gru_bwd_f32, one launch, slots in reverse from dh = dy [n_bags, dim]:
+ *   dn = dh (1 - z)   dz = dh (h_{t-1} - n)   da_n = dn (1 - n^2)   da_z = dz z (1 - z)   da_r = da_n g_n r (1 - r)
+ *   da [n_bags * L, 3 dim] = [da_z | da_r | da_n]    dg [n_bags * L, 3 dim] = [da_z | da_r | da_n r]    dh <- z dh + dg U^T
+ *   every row of da and dg is written (a skipped slot: zeros, dh carried).  Then, through tt_dense_bwd_batched_f32:
+ *   slot_grads = da W^T (one row per slot, what the sort plan over batch_ids feeds the sparse optimizers), dW = x^T da,
+ *   db_i = sum da, dU = hprev^T dg, db_r = sum dg - as slabs the dense segments sum.
+ * No atomics (but the flag), nothing read back, bit-identical run to run.  n_bags == 0 launches nothing; anything else wrong is
+ * TT_ERR_INVALID_ARG before any launch.                                                                                    */
+int tt_history_gru_resolve_f32(const float* table, int64_t table_rows, int32_t dim, const int32_t* tokens,
+                               int64_t n_token_rows, int32_t L, const int64_t* bag_rows, int64_t n_bags,
+                               const int64_t* exclude, float* x, int64_t* batch_ids, int32_t* oob_flag, tt_stream_t stream);
+int tt_history_gru_fwd_f32(const float* a, const int64_t* batch_ids, int64_t n_bags, int32_t L, int32_t dim,
+                           const float* u, const float* b_r, float* out, const float* base_table, int64_t base_rows,
+                           const int64_t* base_ids, int32_t* oob_flag, float* gates, float* gn, float* hprev,
+                           tt_stream_t stream);
+int tt_history_gru_bwd_f32(const int64_t* batch_ids, const float* gates, const float* gn, const float* hprev,
+                           const float* dy, int64_t n_bags, int32_t L, int32_t dim, const float* u, float* da, float* dg,
+                           tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,6 +296,9 @@ SIGNATURES = {
     "tt_time_context_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i64, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p]),
     "tt_time_context_bwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i64, _p, _p]),
     "tt_mmr_rerank_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i32, _f, _i32, _p, _p, _p]),
+    "tt_history_gru_resolve_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p]),
+    "tt_history_gru_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "tt_history_gru_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
 }
 
 _lock = threading.Lock()

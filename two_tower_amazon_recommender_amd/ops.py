@@ -335,6 +335,160 @@ def history_attention_bwd(table: torch.Tensor, batch_ids: torch.Tensor, weights:
     return slot_grads, dattn_slabs
 
 
+class GruBuffers:
+    """What ``history_gru(keep=...)`` leaves for ``history_gru_bwd``, for ``n_bags`` bags of ``L`` slots at width ``dim``:
+    ``batch_ids`` [n_bags * L] int64 (the slots' tokens, -1 where skipped), ``x`` [n_bags * L, dim] (the slot rows, zeros where
+    skipped), ``gates`` [n_bags * L, 3 dim] (the input projection, overwritten in place by z | r | n of every kept slot),
+    ``gn`` [n_bags * L, dim] (g_n of every kept slot), ``hprev`` [n_bags * L, dim] (h_{t-1} of every slot) and the backward's
+    ``da`` / ``dg`` [n_bags * L, 3 dim].  4 * n_bags * L * dim * 12 bytes (+ the ids)."""
+
+    def __init__(self, n_bags: int, L: int, dim: int, device, backward: bool = True):
+        m = int(n_bags) * int(L)
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        self.n_bags, self.L, self.dim = int(n_bags), int(L), int(dim)
+        self.batch_ids = torch.empty(m, dtype=torch.int64, device=device)
+        self.x, self.gates, self.gn, self.hprev = f(m, dim), f(m, 3 * dim), f(m, dim), f(m, dim)
+        self.da, self.dg = (f(m, 3 * dim), f(m, 3 * dim)) if backward else (None, None)
+
+    @classmethod
+    def wrap(cls, L: int, batch_ids, x, gates, gn, hprev):
+        """The buffers of a forward whose kept tensors were handed out one by one (``torch.ops.twotower.history_gru``)."""
+        for t, name in ((x, "x"), (gates, "gates"), (gn, "gn"), (hprev, "hprev")):
+            _chk(t, torch.float32, name, 2)
+        _chk(batch_ids, torch.int64, "batch_ids", 1)
+        m, d = x.shape
+        if m % L or batch_ids.numel() != m or tuple(gates.shape) != (m, 3 * d) or tuple(gn.shape) != (m, d) or tuple(hprev.shape) != (m, d):
+            raise RuntimeError(f"GruBuffers.wrap: need batch_ids [{m}], x / gn / hprev [{m}, {d}] and gates [{m}, {3 * d}] with "
+                               f"n_bags * L = {m} a multiple of L = {L}")
+        self = cls(0, L, d, x.device)
+        self.n_bags, self.batch_ids, self.x, self.gates, self.gn, self.hprev = m // L, batch_ids, x, gates, gn, hprev
+        self.da, self.dg = torch.empty_like(gates), torch.empty_like(gates)
+        return self
+
+
+def _chk_gru(what: str, d: int, L: int, W, U, b):
+    _chk(W, torch.float32, "W", 2)
+    _chk(U, torch.float32, "U", 2)
+    if b is not None:
+        _chk(b, torch.float32, "b", 2)
+    if d % 32 or not 32 <= d <= 256:
+        raise RuntimeError(f"{what}: dim must be a multiple of 32 in 32..256, got {d}")
+    if not 1 <= L <= 64:
+        raise RuntimeError(f"{what}: L must be in 1..64, got {L}")
+    if tuple(W.shape) != (d, 3 * d) or tuple(U.shape) != (d, 3 * d) or (b is not None and tuple(b.shape) != (2, 3 * d)):
+        raise RuntimeError(f"{what}: W and U must be [{d}, {3 * d}] (dim, 3 dim: z | r | n) and b [2, {3 * d}] (b_i, b_r), got "
+                           f"{tuple(W.shape)}, {tuple(U.shape)} and {None if b is None else tuple(b.shape)}")
+
+
+def history_gru(table: torch.Tensor, tokens: torch.Tensor, W: torch.Tensor, U: torch.Tensor, b: torch.Tensor,
+                bag_rows: torch.Tensor | None = None, exclude: torch.Tensor | None = None, base=None,
+                out: torch.Tensor | None = None, batch_ids: torch.Tensor | None = None, oob_flag: torch.Tensor | None = None,
+                keep=False, scratch: "GruBuffers | None" = None):
+    """The history bag encoded by a GRU (Keras ``GRU(dim, reset_after=True)``, zero initial state, mask-aware): over the kept
+    slots of a bag in slot order - ``history_bag``'s rules: padding, out-of-range tokens and ``exclude`` skipped; the newest
+    kept item is the last step - a = x W + b[0], g = h U + b[1], z = sigmoid(a_z + g_z), r = sigmoid(a_r + g_r),
+    n = tanh(a_n + r g_n), h <- z h + (1 - z) n; out[b] = base row + h_final (no kept slot: the base row itself).  ``W``, ``U``
+    [dim, 3 dim] with the gate column blocks z | r | n, ``b`` [2, 3 dim].  Three launches: the slot resolve
+    (``tt_history_gru_resolve_f32``), the input projection over all slots (``tt_dense_fwd_batched_f32``) and the recurrence
+    (``tt_history_gru_fwd_f32``).  ``tokens``, ``bag_rows``, ``exclude``, ``base``, ``batch_ids`` and ``oob_flag`` are
+    ``history_attention``'s.  dim a multiple of 32 in 32..256, L in 1..64.  ``keep``: False - returns ``out``, nothing else is
+    kept; True or a ``GruBuffers`` of this shape - returns (out, buffers) for ``history_gru_bwd`` (``batch_ids`` is then the
+    buffers' own unless given).  ``scratch`` (inference only, ``keep`` False): a ``GruBuffers`` for AT LEAST n_bags bags of this
+    (L, dim) whose ``x`` / ``gates`` / ``batch_ids`` serve as the call's workspace instead of fresh allocations."""
+    n_rows, L, d, n_bags, out = _bag_args("history_gru", table, tokens, bag_rows, "sum", out, False, batch_ids, None, oob_flag)
+    _chk_gru("history_gru", d, L, W, U, b)
+    if exclude is not None:
+        _chk(exclude, torch.int64, "exclude", 1)
+        if exclude.numel() != n_bags:
+            raise RuntimeError(f"history_gru: exclude must hold n_bags = {n_bags} entries, got {exclude.numel()}")
+    base_table = base_ids = None
+    if base is not None:
+        base_table, base_ids = base
+        _chk(base_table, torch.float32, "base_table", 2)
+        _chk(base_ids, torch.int64, "base_ids", 1)
+        if base_table.shape[1] != d or base_ids.numel() != n_bags:
+            raise RuntimeError(f"history_gru: base must be ([rows, {d}] f32, [{n_bags}] int64), got "
+                               f"{tuple(base_table.shape)} and {tuple(base_ids.shape)}")
+    bufs = None
+    if keep is not False and keep is not None:
+        bufs = GruBuffers(n_bags, L, d, table.device) if keep is True else keep
+        if not isinstance(bufs, GruBuffers) or (bufs.n_bags, bufs.L, bufs.dim) != (n_bags, L, d):
+            raise RuntimeError(f"history_gru: keep must be a bool or a GruBuffers for ({n_bags}, {L}, {d}) (n_bags, L, dim)")
+        if batch_ids is None:
+            batch_ids = bufs.batch_ids
+        x, a = bufs.x, bufs.gates
+    elif scratch is not None:
+        if not isinstance(scratch, GruBuffers) or (scratch.L, scratch.dim) != (L, d) or scratch.n_bags < n_bags:
+            raise RuntimeError(f"history_gru: scratch must be a GruBuffers for at least {n_bags} bags of ({L}, {d}) (L, dim)")
+        x, a = scratch.x[:n_bags * L], scratch.gates[:n_bags * L]
+        if batch_ids is None:
+            batch_ids = scratch.batch_ids[:n_bags * L]
+    else:
+        x = torch.empty((n_bags * L, d), dtype=torch.float32, device=table.device)
+        a = torch.empty((n_bags * L, 3 * d), dtype=torch.float32, device=table.device)
+        if batch_ids is None:
+            batch_ids = torch.empty(n_bags * L, dtype=torch.int64, device=table.device)
+    if n_bags == 0:
+        return out if bufs is None else (out, bufs)
+    lib = _lib.load()
+    _lib.check(lib.tt_history_gru_resolve_f32(_p(table), table.shape[0], d, _p(tokens), n_rows, L, _p(bag_rows), n_bags, _p(exclude),
+                                              _p(x), _p(batch_ids), _p(oob_flag), _stream()), "tt_history_gru_resolve_f32")
+    dense_fwd(x, W, b[0], False, out=a)
+    if bufs is not None and batch_ids is not bufs.batch_ids:
+        bufs.batch_ids = batch_ids.view(-1)
+    _lib.check(lib.tt_history_gru_fwd_f32(_p(a), _p(batch_ids), n_bags, L, d, _p(U), _p(b[1]), _p(out), _p(base_table),
+                                          0 if base_table is None else base_table.shape[0], _p(base_ids), _p(oob_flag),
+                                          _p(None if bufs is None else bufs.gates), _p(None if bufs is None else bufs.gn),
+                                          _p(None if bufs is None else bufs.hprev), _stream()), "tt_history_gru_fwd_f32")
+    return out if bufs is None else (out, bufs)
+
+
+def history_gru_bwd(bufs: GruBuffers, dy: torch.Tensor, W: torch.Tensor, U: torch.Tensor, slot_grads: torch.Tensor | None = None,
+                    dw_slabs: torch.Tensor | None = None, du_slabs: torch.Tensor | None = None,
+                    db_slabs: torch.Tensor | None = None):
+    """The backward of ``history_gru`` from its kept ``GruBuffers`` and ``dy`` [n_bags, dim]: the recurrent launch
+    (``tt_history_gru_bwd_f32``: the slots in reverse from dh = dy, writing the pre-activation gradients ``da`` / ``dg``) and
+    two ``tt_dense_bwd_batched_f32`` launches over all n_bags * L slots.  ``slot_grads`` [n_bags * L, dim] = da W^T gets ONE
+    gradient row per slot (zeros for a skipped one) - what the sparse optimizers take with a plain ``SparsePlan(n_bags * L)``
+    run over ``bufs.batch_ids``; ``dw_slabs`` / ``du_slabs`` [n_slabs, dim, 3 dim] and ``db_slabs`` [2, n_slabs, 3 dim] (b_i,
+    b_r) are the parameters' gradients as ``dense_bwd_num_slabs(n_bags * L)`` slabs, every slab written in full: the form
+    ``make_dense_seg`` / ``make_adam_seg`` sum.  All are allocated when None.  Returns (slot_grads, dw_slabs, du_slabs, db_slabs)."""
+    if not isinstance(bufs, GruBuffers) or bufs.da is None:
+        raise RuntimeError("history_gru_bwd: bufs must be the GruBuffers history_gru(keep=...) returned (with backward buffers)")
+    n_bags, L, d = bufs.n_bags, bufs.L, bufs.dim
+    _chk_gru("history_gru_bwd", d, L, W, U, None)
+    _chk(dy, torch.float32, "dy", 2)
+    if tuple(dy.shape) != (n_bags, d):
+        raise RuntimeError(f"history_gru_bwd: dy must be [{n_bags}, {d}] (n_bags, dim), got {tuple(dy.shape)}")
+    m = n_bags * L
+    ns = dense_bwd_num_slabs(max(m, 1))
+    dev = dy.device
+    if slot_grads is None:
+        slot_grads = torch.empty((m, d), dtype=torch.float32, device=dev)
+    _chk(slot_grads, torch.float32, "slot_grads", 2)
+    if tuple(slot_grads.shape) != (m, d):
+        raise RuntimeError(f"history_gru_bwd: slot_grads must be [{m}, {d}] (n_bags * L, dim), got {tuple(slot_grads.shape)}")
+    if dw_slabs is None:
+        dw_slabs = torch.empty((ns, d, 3 * d), dtype=torch.float32, device=dev)
+    if du_slabs is None:
+        du_slabs = torch.empty((ns, d, 3 * d), dtype=torch.float32, device=dev)
+    if db_slabs is None:
+        db_slabs = torch.empty((2, ns, 3 * d), dtype=torch.float32, device=dev)
+    for t, name, shape in ((dw_slabs, "dw_slabs", (ns, d, 3 * d)), (du_slabs, "du_slabs", (ns, d, 3 * d)), (db_slabs, "db_slabs", (2, ns, 3 * d))):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"history_gru_bwd: {name} must be {list(shape)} (n_slabs = dense_bwd_num_slabs(n_bags * L) = {ns}), got "
+                               f"{tuple(t.shape)}")
+    if n_bags == 0:
+        dw_slabs.zero_(), du_slabs.zero_(), db_slabs.zero_()
+        return slot_grads, dw_slabs, du_slabs, db_slabs
+    _lib.check(_lib.load().tt_history_gru_bwd_f32(_p(bufs.batch_ids), _p(bufs.gates), _p(bufs.gn), _p(bufs.hprev), _p(dy), n_bags, L, d,
+                                                  _p(U), _p(bufs.da), _p(bufs.dg), _stream()), "tt_history_gru_bwd_f32")
+    dense_bwd(bufs.x, W, bufs.da, slot_grads, None, dw_slabs, db_slabs[0])
+    dense_bwd(bufs.hprev, U, bufs.dg, None, None, du_slabs, db_slabs[1])
+    return slot_grads, dw_slabs, du_slabs, db_slabs
+
+
 def embedding_bag_bwd(dy: torch.Tensor, inv: torch.Tensor | None, order: torch.Tensor, L: int, order_bags: torch.Tensor,
                       gs: torch.Tensor | None = None):
     """The backward launch of ``embedding_bag`` (``tt_embedding_bag_bwd_f32``): ``gs[b, :] = dy[b, :] * inv[b]`` (``gs`` None -

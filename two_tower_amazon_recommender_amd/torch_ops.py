@@ -181,6 +181,66 @@ def _attention_backward(ctx, d_out, d_weights, d_pooled, d_ids):
 history_attention.register_autograd(_attention_backward, setup_context=_attention_setup)
 
 
+@torch.library.custom_op(f"{NS}::history_gru", mutates_args=(), device_types="cuda")
+def history_gru(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], exclude: Optional[Tensor], base_table: Optional[Tensor],
+                base_ids: Optional[Tensor], W: Tensor, U: Tensor, b: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The history bag encoded by a GRU (``ops.history_gru``; ``W``, ``U`` [dim, 3 dim] with the gate blocks z | r | n, ``b``
+    [2, 3 dim] = b_i, b_r): (out [n_bags, dim] = base row + h_final, batch_ids [n_bags * L] int64 - the slots' tokens, -1 where
+    skipped -, and the kept buffers x [n_bags * L, dim], gates [n_bags * L, 3 dim], gn and hprev [n_bags * L, dim]).  Autograd
+    with respect to ``W``, ``U`` and ``b`` (from the gradient of ``out``), through ``twotower::history_gru_bwd``.  The table's
+    gradient is sparse - one row per slot, the first result of ``history_gru_bwd`` - and goes through ``sparse_update_`` /
+    ``sparse_adam_`` with ``batch_ids`` as the ids; the base table's gradient rows are the gradient of ``out`` itself."""
+    if (base_table is None) != (base_ids is None):
+        raise ValueError("history_gru: base_table and base_ids go together")
+    c = lambda t: None if t is None else t.contiguous()
+    out, bufs = ops.history_gru(table.contiguous(), tokens.contiguous(), W.contiguous(), U.contiguous(), b.contiguous(), c(bag_rows),
+                                c(exclude), None if base_table is None else (c(base_table), c(base_ids)), keep=True)
+    return out, bufs.batch_ids, bufs.x, bufs.gates, bufs.gn, bufs.hprev
+
+
+@history_gru.register_fake
+def _(table, tokens, bag_rows, exclude, base_table, base_ids, W, U, b):
+    n_bags, L, d = (tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), tokens.shape[1], table.shape[1]
+    return (table.new_empty((n_bags, d)), tokens.new_empty((n_bags * L,), dtype=torch.int64), table.new_empty((n_bags * L, d)),
+            table.new_empty((n_bags * L, 3 * d)), table.new_empty((n_bags * L, d)), table.new_empty((n_bags * L, d)))
+
+
+@torch.library.custom_op(f"{NS}::history_gru_bwd", mutates_args=(), device_types="cuda")
+def history_gru_bwd(batch_ids: Tensor, x: Tensor, gates: Tensor, gn: Tensor, hprev: Tensor, dy: Tensor, W: Tensor,
+                    U: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(slot_grads [n_bags * L, dim], dW [dim, 3 dim], dU [dim, 3 dim], db [2, 3 dim]) of ``history_gru`` given dL/dout and what
+    the forward returned: one gradient row per slot (zeros for a skipped one) for ``sparse_update_`` / ``sparse_adam_`` with
+    ``batch_ids`` as the ids, and the parameters' gradients, the backward launches' slabs summed."""
+    L = x.shape[0] // dy.shape[0] if dy.shape[0] else 1
+    bufs = ops.GruBuffers.wrap(L, batch_ids.contiguous(), x.contiguous(), gates.contiguous(), gn.contiguous(), hprev.contiguous())
+    slot_grads, dw, du, db = ops.history_gru_bwd(bufs, dy.contiguous(), W.contiguous(), U.contiguous())
+    return slot_grads, dw.sum(dim=0), du.sum(dim=0), db.sum(dim=1)
+
+
+@history_gru_bwd.register_fake
+def _(batch_ids, x, gates, gn, hprev, dy, W, U):
+    return (x.new_empty(x.shape), torch.empty_like(W, memory_format=torch.contiguous_format),
+            torch.empty_like(U, memory_format=torch.contiguous_format), W.new_empty((2, W.shape[1])))
+
+
+def _gru_setup(ctx, inputs, output):
+    W, U = inputs[6], inputs[7]
+    _, batch_ids, x, gates, gn, hprev = output
+    ctx.save_for_backward(batch_ids, x, gates, gn, hprev, W, U)
+
+
+def _gru_backward(ctx, d_out, d_ids, d_x, d_gates, d_gn, d_hprev):
+    batch_ids, x, gates, gn, hprev, W, U = ctx.saved_tensors
+    dW = dU = db = None
+    if d_out is not None and any(ctx.needs_input_grad[6:9]):
+        _, dW, dU, db = torch.ops.twotower.history_gru_bwd(batch_ids, x, gates, gn, hprev, d_out, W, U)
+    pick = lambda g, i: g if ctx.needs_input_grad[i] else None
+    return None, None, None, None, None, None, pick(dW, 6), pick(dU, 7), pick(db, 8)
+
+
+history_gru.register_autograd(_gru_backward, setup_context=_gru_setup)
+
+
 @torch.library.custom_op(f"{NS}::sample_candidates", mutates_args=(), device_types="cuda")
 def sample_candidates(pos_ids: Tensor, n_items: int, n_neg: int, seed: int, tensor_id: int, start: int,
                       alias_thr: Optional[Tensor], alias_idx: Optional[Tensor], item_freq: Optional[Tensor],
@@ -878,5 +938,5 @@ def _(sketch, ids, n_update, step, alpha, n_items, seed, tensor_id, sampler_prob
     return ids.new_empty((ids.shape[0],), dtype=torch.float32)
 
 
-OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "mmr_rerank", "dense_fwd",
+OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "history_gru", "history_gru_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "mmr_rerank", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "time_context", "time_context_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")

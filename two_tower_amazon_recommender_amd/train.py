@@ -87,8 +87,9 @@ def parse(argv=None):
                     help="add the pooled user-history feature: every user's last L training interactions (1..64, by the "
                          "timestamp column where there is one) are pooled into the user tower input, the pair's own item left "
                          "out (overrides model.features.history.max_items); single-GPU trainer only")
-    ap.add_argument("--history-pooling", default=None, choices=["sum", "mean", "sqrtn", "attention"],
-                    help="how the history rows are pooled (default mean; attention: a learned query with a recency bias)")
+    ap.add_argument("--history-pooling", default=None, choices=["sum", "mean", "sqrtn", "attention", "gru"],
+                    help="how the history rows are pooled (default mean; attention: a learned query with a recency bias; gru: a GRU "
+                         "over the items, oldest first)")
     ap.add_argument("--side-features", default=None, choices=["none", "rating_stats"],
                     help="add the dense numeric side features: rating_stats = every user's and every item's rating count / mean / "
                          "std / min / max over the training pairs (column rating), normalised, projected by a trained kernel and "

@@ -41,13 +41,15 @@ TID_USER_FEATURES, TID_ITEM_FEATURES = 14, 15               # synthetic_user_fea
 TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of step s is element s * n_sampled_negatives + i
 TID_DENSE_BASE = 16
 TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
+TID_GRU_BASE = 42                            # the history GRU: the input kernel W is 42, the recurrent kernel U 43
 TID_CROSS_BASE = 48                          # the cross kernels: layer l of tower t is 48 + 2 l + t (48..53)
 TID_FREQ_HASH_BASE = 56                      # the streaming frequency estimator's hash rows: row h is 56 + h (56..59)
 TID_TIME_BASE = 60                           # the time-of-interaction context: the table is 60, synthetic_timestamps 61
 TIME_MISSING = ops.TIME_MISSING              # a pair without a timestamp
 MAX_CROSS_LAYERS = 3
-# poolings of the user-history feature: the bag launch's three and the attention pool (csrc/history_attn.hip), history only
-HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention",)
+# poolings of the user-history feature: the bag launch's three, the attention pool (csrc/history_attn.hip) and the GRU encoder
+# (csrc/history_gru.hip), history only
+HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention", "gru")
 LR_DECAYS = ("none", "cosine", "linear", "inverse_sqrt")
 SAMPLING_BIAS_ESTIMATORS = ("none", "streaming")
 TID_DROPOUT_BASE = 64
@@ -166,6 +168,11 @@ class TwoTowerConfig:
     # history_pooling "attention": a softmax over the kept slots of e_j = <row_j, a> / sqrt(embedding_dim) + p[recency rank of j]
     # with one trained vector [a | p] (embedding_dim + user_history_len floats, zero-initialised: a fresh model pools by the
     # mean; no l2 penalty) - the histories are stored oldest first, and the rank counts the kept slots behind j.
+    # history_pooling "gru": TFRS's sequential-retrieval recipe, Embedding -> GRU(embedding_dim) - Keras GRU(reset_after=True) with
+    # zero initial state stepping over the kept slots oldest first (a skipped slot carries the state, as Keras masking does); its
+    # final state is added to the user tower's input.  W, U [D, 3D] (gate blocks z | r | n) are BOTH Glorot-uniform (Keras
+    # initialises U orthogonally), b [2, 3D] = b_i, b_r starts at zero; none carries the l2 penalty.  embedding_dim must be a
+    # multiple of 32 in 32..256.
     user_history_len: int = 0
     history_pooling: str = "mean"
     # pooled item-title feature (the reference's preprocessing.text_fields: title; TFRS TextVectorization -> Embedding ->
@@ -228,11 +235,17 @@ class TwoTowerConfig:
         """The history feature is on and pooled by attention."""
         return self.user_history_len > 0 and self.history_pooling == "attention"
 
-    def dense_segment_count(self, cross: bool = True, attention: bool = True) -> int:
+    @property
+    def history_gru(self) -> bool:
+        """The history feature is on and encoded by the GRU."""
+        return self.user_history_len > 0 and self.history_pooling == "gru"
+
+    def dense_segment_count(self, cross: bool = True, attention: bool = True, gru: bool = True) -> int:
         """Segments of the dense optimizer launches (``dense_layout``): a kernel and a bias per Dense layer, a projection kernel
         per side with numeric features, two for the rating head, two for the cross layers (``cross=False``: without those), one
-        for the history attention's vector (``attention=False``: without it), one for the layer normalisation's gammas and betas."""
-        skip = {g for g, on in (("cross", cross), ("attention", attention)) if not on}
+        for the history attention's vector (``attention=False``: without it), one for the layer normalisation's gammas and betas,
+        one for the time table, four for the history GRU - W, U, b_i, b_r - (``gru=False``: without those)."""
+        skip = {g for g, on in (("cross", cross), ("attention", attention), ("gru", gru)) if not on}
         return sum(s.group not in skip for s in dense_layout(self).segments)
 
     def validate(self):
@@ -274,6 +287,8 @@ class TwoTowerConfig:
             raise ValueError("user_history_len must be 0 (no history feature) or in 1..64")
         if self.history_pooling not in HISTORY_POOLINGS:
             raise ValueError(f"history_pooling must be one of {HISTORY_POOLINGS}")
+        if self.history_gru and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
+            raise ValueError(f"history_pooling='gru' needs an embedding_dim that is a multiple of 32 in 32..256 (got {self.embedding_dim})")
         if self.user_history_len and self.n_items >= 2 ** 31:
             raise ValueError("user_history_len > 0 needs n_items < 2^31: the history tokens are int32")
         if self.user_history_len and self.candidate_sampling == "mixed":
@@ -379,7 +394,8 @@ _SEGMENT_GROUPS = {"features": "the numeric side features add one dense segment 
                    "cross": "the cross layers add two dense segments",
                    "attention": "the history attention adds one dense segment",
                    "norm": "the layer normalisation adds one dense segment",
-                   "time": "the time context table adds one dense segment"}
+                   "time": "the time context table adds one dense segment",
+                   "gru": "the history GRU adds four dense segments"}
 
 
 @dataclass(frozen=True)
@@ -411,7 +427,7 @@ class DenseSegment:
     hi: int
     l2: bool
     stride: int
-    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm" | "time"
+    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm" | "time" | "gru"
 
     @property
     def size(self) -> int:
@@ -447,6 +463,9 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         time table                 from a 16-byte boundary (the launches load its rows as float4s): [time_rows, D], the enabled
                                    fields' row blocks in their fixed order; ONE segment, no l2, one gradient "slab" - the backward
                                    launch writes the fully reduced gradient
+        history GRU                from a 16-byte boundary (the launches load its rows as float4s): W [D, 3D] | U [D, 3D] |
+                                   b [2, 3D] = b_i, b_r; four segments - W, U, b_i, b_r -, none with l2: the gradient GEMMs write
+                                   one slab array per kernel and one per bias row
 
     Every optional block sits BEHIND what was there before it: switching one on moves no existing offset, and without the
     blocks behind it dense_flat ends behind the cross block with no trailing pad."""
@@ -501,6 +520,15 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         off = (off + 3) // 4 * 4
         t = block("time_table", (cfg.time_rows, d), embedding=TID_TIME_BASE)
         segment("time", t.name, t, t, False)
+    if cfg.history_gru:
+        off = (off + 3) // 4 * 4
+        w = block("history_gru.W", (d, 3 * d), (TID_GRU_BASE, 4 * d))
+        u = block("history_gru.U", (d, 3 * d), (TID_GRU_BASE + 1, 4 * d))
+        b = block("history_gru.b", (2, 3 * d))
+        segment("gru", w.name, w, w, False)
+        segment("gru", u.name, u, u, False)
+        segs.append(DenseSegment("history_gru.b_i", b.offset, b.offset + 3 * d, False, 3 * d, "gru"))
+        segs.append(DenseSegment("history_gru.b_r", b.offset + 3 * d, b.end, False, 3 * d, "gru"))
     return DenseLayout(blocks, tuple(segs), off)
 
 
@@ -1050,6 +1078,8 @@ class TwoTowerTrainer:
         self.layout = lay = dense_layout(cfg)
         self.rating_on = cfg.rating_weight > 0
         self._attn_on = cfg.history_attention
+        self._gru_on = cfg.history_gru
+        self._slot_rows = self._attn_on or self._gru_on        # the history update takes one gradient row per slot
         sd, rh, ncl = cfg.tower_dims[-1], cfg.rating_hidden, cfg.cross_layers
         self.dense_flat = torch.zeros(lay.total, device=dev)
         self._fill_constant_blocks()             # (the layer normalisation's gammas start at 1 with or without a seed)
@@ -1104,6 +1134,7 @@ class TwoTowerTrainer:
         # every user's history row (all padding until set_user_histories) and the per-step buffers of the bag launches
         self.user_history = self.history_ids = self.history_inv = self.history_gs = None
         self.history_attn = self.history_weights = self.history_pooled = self.history_slot_grads = self._ha_slabs = None
+        self.gru_W = self.gru_U = self.gru_b = self._gru_bufs = self._gru_slabs = self._gru_scratch = None
         if cfg.user_history_len:
             lh = cfg.user_history_len
             self.user_history = torch.full((cfg.n_users, lh), -1, dtype=torch.int32, device=dev)
@@ -1120,6 +1151,20 @@ class TwoTowerTrainer:
                 ns = ops.history_attention_num_slabs(b)
                 self._ha_slabs = torch.empty(ns, self.history_attn.numel(), device=dev)
                 grad_slabs["history_attn"] = (self._ha_slabs, ns)
+            elif self._gru_on:
+                # GRU encoder: one gradient row per slot through a plain sort plan, as under attention; the step keeps the slot
+                # rows, the gate activations and the states (ops.GruBuffers: 48 * b * lh * d bytes with the backward's da / dg)
+                # and the gradient GEMMs write the slabs of the four dense segments
+                plan = ops.SparsePlan(b * lh, dev)
+                self.gru_W, self.gru_U, self.gru_b = (lay.blocks[f"history_gru.{k}"].view(self.dense_flat) for k in ("W", "U", "b"))
+                self._gru_bufs = ops.GruBuffers(b, lh, d, dev)
+                self._gru_bufs.batch_ids = self.history_ids
+                self.history_slot_grads = torch.zeros(b * lh, d, device=dev)
+                ns = ops.dense_bwd_num_slabs(b * lh)
+                self._gru_slabs = (torch.empty(ns, d, 3 * d, device=dev), torch.empty(ns, d, 3 * d, device=dev),
+                                   torch.empty(2, ns, 3 * d, device=dev))
+                grad_slabs["history_gru.W"], grad_slabs["history_gru.U"] = (self._gru_slabs[0], ns), (self._gru_slabs[1], ns)
+                grad_slabs["history_gru.b_i"], grad_slabs["history_gru.b_r"] = (self._gru_slabs[2][0], ns), (self._gru_slabs[2][1], ns)
             else:
                 plan = ops.BagPlan(b, lh, dev)
                 self.history_inv = torch.empty(b, device=dev)
@@ -1489,7 +1534,7 @@ class TwoTowerTrainer:
     def _tower_inputs(self, user=None, item=None, *, category_ids=None, exclude=None, keep: bool = False, features_only: bool = False,
                       timestamps=None):
         """Materialised tower-input rows (no fused lookup), and the ONE place that knows what is summed into them: the id's table
-        row + the hashed category's row (item) + the pooled title rows (item) + the pooled or attended history rows (user) + the
+        row + the hashed category's row (item) + the pooled title rows (item) + the pooled, attended or GRU-encoded history (user) + the
         time rows of the pairs' ``timestamps`` (user; without a history ONE launch with the user row as its base, else added
         behind the history launch) + the projected numeric features.
         ``user`` / ``item`` = (ids, rows to write) or None: any number of ids, either side alone.
@@ -1508,6 +1553,8 @@ class TwoTowerTrainer:
                 ops.history_attention(self.history_table, self.user_history, self.history_attn, bag_rows=ids, exclude=exclude,
                                       base=(self.user_table, ids), out=user[1], batch_ids=self.history_ids if keep else None,
                                       weights=self.history_weights[:n], pooled=self.history_pooled[:n], oob_flag=self.oob)
+            elif user is not None and self._gru_on:
+                self._history_gru(user, exclude, keep)
             elif user is not None:
                 ops.history_bag(self.history_table, self.user_history, bag_rows=user[0], exclude=exclude, base=(self.user_table, user[0]),
                                 pooling=cfg.history_pooling, out=user[1], batch_ids=self.history_ids if keep else None,
@@ -1539,6 +1586,25 @@ class TwoTowerTrainer:
                 probs.append((fs.features, side[0], fs.mean, fs.inv_std, fs.P, side[1], True, fs.z if keep else None))
         if probs:
             ops.dense_features(*probs, clip=cfg.feature_clip, oob_flag=self.oob)
+
+    def _history_gru(self, user, exclude, keep: bool, chunk: int = 4096):
+        """The GRU launches of ``_tower_inputs``: user row + the final state over the kept slots.  The train step (``keep``)
+        runs on the step's kept buffers; an inference pass takes any number of ids, ``chunk`` bags at a time on ONE scratch of
+        its own (allocated on first use, grown when a longer chunk comes), so it writes nothing a pending step still needs."""
+        ids, out = user
+        args = (self.history_table, self.user_history, self.gru_W, self.gru_U, self.gru_b)
+        if keep:
+            ops.history_gru(*args, bag_rows=ids, exclude=exclude, base=(self.user_table, ids), out=out, batch_ids=self.history_ids,
+                            oob_flag=self.oob, keep=self._gru_bufs)
+            return
+        need = min(ids.numel(), chunk)
+        if self._gru_scratch is None or self._gru_scratch.n_bags < need:
+            self._gru_scratch = None
+            self._gru_scratch = ops.GruBuffers(need, self.cfg.user_history_len, self.cfg.embedding_dim, self.dev, backward=False)
+        for lo in range(0, ids.numel(), chunk):
+            part = ids[lo:lo + chunk]
+            ops.history_gru(*args, bag_rows=part, exclude=None if exclude is None else exclude[lo:lo + chunk],
+                            base=(self.user_table, part), out=out[lo:lo + chunk], oob_flag=self.oob, scratch=self._gru_scratch)
 
     def _time_context(self, timestamps, user, keep: bool, base: bool):
         """The time launch of ``_tower_inputs``: the rows ``timestamps`` pick, summed, on top of the user row (``base``) or of
@@ -1574,11 +1640,16 @@ class TwoTowerTrainer:
 
     def _history_backward(self):
         """Attention pooling: the slots' gradient rows and the attention vector's gradient slabs from the user tower's input
-        gradient (demb), one launch after the towers' backward - in front of the optimizer launches, which update the vector."""
+        gradient (demb), one launch after the towers' backward - in front of the optimizer launches, which update the vector.
+        GRU: the same from three launches - the reverse recurrence, then the slot rows with dW / db_i and dU / db_r as GEMMs."""
         if self._attn_on:
             ops.history_attention_bwd(self.history_table, self.history_ids, self.history_weights, self.history_pooled,
                                       self.user_tower.demb, self.history_attn, self.cfg.user_history_len,
                                       slot_grads=self.history_slot_grads, dattn_slabs=self._ha_slabs)
+        elif self._gru_on:                       # the recurrent backward launch and the two gradient GEMM launches
+            dw, du, db = self._gru_slabs
+            ops.history_gru_bwd(self._gru_bufs, self.user_tower.demb, self.gru_W, self.gru_U, slot_grads=self.history_slot_grads,
+                                dw_slabs=dw, du_slabs=du, db_slabs=db)
 
     def _outputs(self, towers, rows=None):
         """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
@@ -1716,13 +1787,13 @@ class TwoTowerTrainer:
         every dense segment's slabs are summed before they are squared."""
         cfg = self.cfg
         user = dict(weight=1.0)
-        if self.history_table is not None and not self._attn_on:
+        if self.history_table is not None and not self._slot_rows:
             user.update(slot_ids=self.history_ids, mode=cfg.history_pooling)
         item = dict(weight=2.0 if self.cat_table is not None else 1.0)
         if self.title_table is not None:
             item.update(slot_ids=self.title_ids, mode=cfg.title_pooling)
         rows = [ops.make_clip_rows(self.user_tower.demb, **user), ops.make_clip_rows(self.item_tower.demb, **item)]
-        if self._attn_on:
+        if self._slot_rows:                      # attention and GRU alike: a kept slot's row counts once
             rows.append(ops.make_clip_rows(self.history_slot_grads, 0.0, self.history_ids, "mask"))
         return ops.ClipList(rows, self._segs if self._adam_segs is None else self._adam_segs)
 
@@ -1835,7 +1906,7 @@ class TwoTowerTrainer:
         Attention pooling: the slots' own gradient rows (``_history_backward`` wrote them) through the plain sort plan."""
         cfg, plan = self.cfg, self.history_plan
         plan.run(self.history_ids, cfg.n_items)
-        if self._attn_on:                        # one gradient row per kept slot, written by the step's backward launch
+        if self._slot_rows:                      # one gradient row per kept slot, written by the step's backward launch
             gs = self.history_slot_grads
         else:
             gs = plan.backward(self.user_tower.demb, self.history_inv, self.history_gs)
