@@ -1250,6 +1250,51 @@ int tt_history_gru_bwd_f32(const int64_t* batch_ids, const float* gates, const f
                            const float* dy, int64_t n_bags, int32_t L, int32_t dim, const float* u, float* da, float* dg,
                            tt_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Multi-head self-attention encoder of the user history (added to v10: new symbols only, the version is unchanged;
+ * csrc/history_selfattn.hip) - one causal attention block read at the last position: the newest kept item n of a bag is the one
+ * query.  With x_j the table rows of the kept slots, r_j the kept slots behind j, heads H, Wqk [dim, H dim], Wvo [H dim, dim],
+ * p [H, L], all f32 row-major:
+ *   T = x_n Wqk     e_hj = <x_j, T_h> / sqrt(dim) + p[h, r_j]     w_h = softmax_j(e_h)     P_h = sum_j w_hj x_j
+ *   out[b] = base row + concat_h(P_h) Wvo            a bag without a kept slot: the base row itself
+ * dim a multiple of 32 in 32..256, L in 1..64, heads in {1, 2, 4, 8}, n_bags * L < 2^31.  The two products over n_bags rows are
+ * tt_dense_fwd_batched_f32 (T: m = n_bags, k = dim, n = H dim, no bias; O: k = H dim, n = dim) and, backward,
+ * tt_dense_bwd_batched_f32 ((dP, dWvo) from dy and (dxn, dWqk) from dT).
+ * tt_history_self_attention_resolve_f32, one launch: batch_ids [n_bags * L] = every slot's token, -1 where skipped, newest
+ *   [n_bags] = the slot of n (-1: no kept slot), xn [n_bags, dim] = its row (+0 for such a bag) - tokens, bag_rows, exclude and
+ *   *oob_flag follow tt_history_attention_fwd_f32's rules; base_ids (may be NULL) [n_bags] only sets the flag for an id outside
+ *   0..base_rows other than -1.
+ * tt_history_self_attention_pool_fwd_f32, one launch: from batch_ids, t [n_bags, H dim] and p: pooled [n_bags, H, dim] and weights
+ *   [n_bags, H, L] - exactly 0 in a skipped slot, exactly 1 for a single kept slot, both written in full.  A slot's row is
+ *   loaded once for all heads; a bag's bits depend on that bag alone.
+ * tt_history_self_attention_combine_f32, one launch, in place: out[b] = base_table[base_ids[b]] + out[b] (a base id out of range: a
+ *   zero row), and for newest[b] < 0 the base row itself.
+ * tt_history_self_attention_pool_bwd_f32, one launch, with dpooled [n_bags, H, dim] = dy Wvo^T:
+ *   G_h = <dP_h, P_h>    t_hj = <dP_h, x_j>    de_hj = w_hj (t_hj - G_h)
+ *   slot_grads[b L + j] = sum_h (w_hj dP_h + de_hj T_h / sqrt(dim))   one row per KEPT slot, a skipped slot's row untouched
+ *   dt [n_bags, H dim]: dT_h = sum_j de_hj x_j / sqrt(dim), every row written;    dp[h, r_j] += de_hj as dp_slabs [n_slabs, H L]
+ *   over contiguous bags, every slab written in full and summed in a fixed order - the form tt_dense_seg / tt_adam_seg sum
+ *   (slab_stride = H L).  tt_history_self_attention_num_slabs(n_bags) is a host query for a good n_slabs.
+ * tt_history_self_attention_query_grad_f32, one launch: slot_grads[b L + newest[b]] += dxn[b] where newest[b] >= 0 (dxn = dT Wqk^T).
+ * No atomics (but the flag), no workspace to zero, nothing read back, bit-identical run to run.  n_bags == 0 launches nothing;
+ * anything else wrong is TT_ERR_INVALID_ARG before any launch.                                                             */
+int tt_history_self_attention_resolve_f32(const float* table, int64_t table_rows, int32_t dim, const int32_t* tokens,
+                                          int64_t n_token_rows, int32_t L, const int64_t* bag_rows, int64_t n_bags,
+                                          const int64_t* exclude, const int64_t* base_ids, int64_t base_rows, int64_t* batch_ids,
+                                          int32_t* newest, float* xn, int32_t* oob_flag, tt_stream_t stream);
+int tt_history_self_attention_pool_fwd_f32(const float* table, int64_t table_rows, int32_t dim, int32_t L, int32_t heads,
+                                           const int64_t* batch_ids, int64_t n_bags, const float* t, const float* p, float* pooled,
+                                           float* weights, tt_stream_t stream);
+int tt_history_self_attention_combine_f32(float* out, const int32_t* newest, int64_t n_bags, int32_t dim, const float* base_table,
+                                          int64_t base_rows, const int64_t* base_ids, tt_stream_t stream);
+int32_t tt_history_self_attention_num_slabs(int64_t n_bags);
+int tt_history_self_attention_pool_bwd_f32(const float* table, int64_t table_rows, int32_t dim, int32_t L, int32_t heads,
+                                           const int64_t* batch_ids, const float* weights, const float* pooled, const float* dpooled,
+                                           const float* t, int64_t n_bags, float* slot_grads, float* dt, float* dp_slabs,
+                                           int32_t n_slabs, tt_stream_t stream);
+int tt_history_self_attention_query_grad_f32(const int32_t* newest, const float* dxn, int64_t n_bags, int32_t L, int32_t dim,
+                                             float* slot_grads, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,6 +299,12 @@ SIGNATURES = {
     "tt_history_gru_resolve_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p]),
     "tt_history_gru_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "tt_history_gru_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
+    "tt_history_self_attention_resolve_f32": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "tt_history_self_attention_pool_fwd_f32": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p]),
+    "tt_history_self_attention_combine_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _p, _p]),
+    "tt_history_self_attention_num_slabs": (_i32, [_i64]),
+    "tt_history_self_attention_pool_bwd_f32": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p]),
+    "tt_history_self_attention_query_grad_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
 }
 
 _lock = threading.Lock()

@@ -200,7 +200,7 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     dropout = float(m.get("dropout_rate", 0.0)) if dropout_override is None else dropout_override
     # not in the reference's schema: model.features.title {buckets, max_tokens, pooling} - the pooled item-title feature
     title = (m.get("features") or {}).get("title") or {}
-    # likewise model.features.history {max_items, pooling} - the pooled user-history feature
+    # likewise model.features.history {max_items, pooling, heads} - the pooled user-history feature (heads: pooling self_attention)
     hist = (m.get("features") or {}).get("history") or {}
     # likewise model.features.numeric {source: rating_stats | none, clip} - the dense numeric side features (the column counts
     # come from the data: train.py sets n_user_features / n_item_features once it has the matrices)
@@ -233,6 +233,7 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
         # not in the reference's schema (left open): an optional key beside retrieval.temperature
         normalize_embeddings=bool(rt.get("normalize_embeddings", False)),
         user_history_len=int(hist.get("max_items", 0)), history_pooling=str(hist.get("pooling", "mean")),
+        history_heads=int(hist.get("heads", 1)),
         feature_clip=numeric["clip"], rating_weight=ranking["weight"], rating_hidden=ranking["hidden_dim"],
         n_title_buckets=int(title.get("buckets", 0)), title_max_tokens=int(title.get("max_tokens", 16)),
         title_pooling=str(title.get("pooling", "mean")), cross_layers=cross["layers"],

@@ -489,6 +489,199 @@ def history_gru_bwd(bufs: GruBuffers, dy: torch.Tensor, W: torch.Tensor, U: torc
     return slot_grads, dw_slabs, du_slabs, db_slabs
 
 
+SELF_ATTENTION_HEADS = (1, 2, 4, 8)
+
+
+class SelfAttnBuffers:
+    """What ``history_self_attention(keep=...)`` leaves for ``history_self_attention_bwd``, for ``n_bags`` bags of ``L`` slots at
+    width ``dim`` with ``heads`` heads: ``batch_ids`` [n_bags * L] int64 (the slots' tokens, -1 where skipped), ``newest``
+    [n_bags] int32 (the slot of the newest kept item, -1 for an emptied bag), ``xn`` [n_bags, dim] (its row), ``T`` and ``P``
+    [n_bags, heads * dim] (the queries and the pooled rows), ``weights`` [n_bags, heads, L] and the backward's ``dP`` / ``dT``
+    [n_bags, heads * dim] and ``dxn`` [n_bags, dim].  Nothing is n_bags * L * dim: 4 * n_bags * (4 heads + 2) * dim bytes (+ the
+    ids and weights)."""
+
+    def __init__(self, n_bags: int, L: int, dim: int, heads: int, device, backward: bool = True):
+        n, hd = int(n_bags), int(heads) * int(dim)
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        self.n_bags, self.L, self.dim, self.heads = n, int(L), int(dim), int(heads)
+        self.batch_ids = torch.empty(n * int(L), dtype=torch.int64, device=device)
+        self.newest = torch.empty(n, dtype=torch.int32, device=device)
+        self.xn, self.T, self.P, self.weights = f(n, dim), f(n, hd), f(n, hd), f(n, int(heads), int(L))
+        self.dP, self.dT, self.dxn = (f(n, hd), f(n, hd), f(n, dim)) if backward else (None, None, None)
+        self.table = self.db = None              # the table of the last forward; the backward GEMMs' throwaway bias slabs
+
+    @classmethod
+    def wrap(cls, table, batch_ids, newest, xn, T, P, weights):
+        """The buffers of a forward whose kept tensors were handed out one by one (``torch.ops.twotower.history_self_attention``)."""
+        for t, name in ((table, "table"), (xn, "xn"), (T, "T"), (P, "P")):
+            _chk(t, torch.float32, name, 2)
+        _chk(weights, torch.float32, "weights", 3)
+        _chk(batch_ids, torch.int64, "batch_ids", 1)
+        _chk(newest, torch.int32, "newest", 1)
+        n, d = xn.shape
+        _, h, L = weights.shape
+        if (table.shape[1] != d or weights.shape[0] != n or newest.numel() != n or batch_ids.numel() != n * L or tuple(T.shape) != (n, h * d)
+                or tuple(P.shape) != (n, h * d)):
+            raise RuntimeError(f"SelfAttnBuffers.wrap: need table [rows, {d}], batch_ids [{n * L}], newest [{n}], xn [{n}, {d}], T / P [{n}, {h * d}] and "
+                               f"weights [{n}, {h}, {L}], got {tuple(batch_ids.shape)}, {tuple(newest.shape)}, {tuple(xn.shape)}, "
+                               f"{tuple(T.shape)}, {tuple(P.shape)} and {tuple(weights.shape)}")
+        self = cls(0, L, d, h, xn.device)
+        self.n_bags, self.batch_ids, self.newest, self.xn, self.T, self.P, self.weights = n, batch_ids, newest, xn, T, P, weights
+        self.dP, self.dT, self.dxn, self.table = torch.empty_like(P), torch.empty_like(T), torch.empty_like(xn), table
+        return self
+
+
+def _chk_self_attention(what: str, d: int, L: int, Wqk, Wvo, p) -> int:
+    """The shape checks of the self-attention ops; returns the head count (read from ``Wqk``)."""
+    _chk(Wqk, torch.float32, "Wqk", 2)
+    _chk(Wvo, torch.float32, "Wvo", 2)
+    if p is not None:
+        _chk(p, torch.float32, "p", 2)
+    if d % 32 or not 32 <= d <= 256:
+        raise RuntimeError(f"{what}: dim must be a multiple of 32 in 32..256, got {d}")
+    if not 1 <= L <= 64:
+        raise RuntimeError(f"{what}: L must be in 1..64, got {L}")
+    h = Wqk.shape[1] // d
+    if h not in SELF_ATTENTION_HEADS or tuple(Wqk.shape) != (d, h * d) or tuple(Wvo.shape) != (h * d, d) or (
+            p is not None and tuple(p.shape) != (h, L)):
+        raise RuntimeError(f"{what}: Wqk must be [{d}, H * {d}], Wvo [H * {d}, {d}] and p [H, {L}] with H heads in "
+                           f"{SELF_ATTENTION_HEADS}, got {tuple(Wqk.shape)}, {tuple(Wvo.shape)} and "
+                           f"{None if p is None else tuple(p.shape)}")
+    return h
+
+
+def history_self_attention_num_slabs(n: int) -> int:
+    """Slab count of ``history_self_attention_bwd``'s ``dp_slabs`` for ``n`` bags (``tt_history_self_attention_num_slabs``)."""
+    return int(_lib.load().tt_history_self_attention_num_slabs(n))
+
+
+def history_self_attention(table: torch.Tensor, tokens: torch.Tensor, Wqk: torch.Tensor, Wvo: torch.Tensor, p: torch.Tensor,
+                           bag_rows: torch.Tensor | None = None, exclude: torch.Tensor | None = None, base=None,
+                           out: torch.Tensor | None = None, oob_flag: torch.Tensor | None = None, keep=False,
+                           scratch: "SelfAttnBuffers | None" = None):
+    """The history bag encoded by one multi-head self-attention block read at the last position: the newest kept item n of a
+    bag is the query.  Over the kept slots j (``history_bag``'s rules: padding, out-of-range tokens and ``exclude`` skipped), with
+    r_j the kept slots behind j: T = x_n Wqk, e_hj = <x_j, T_h> / sqrt(dim) + p[h, r_j], w_h = softmax_j(e_h), P_h = sum_j w_hj x_j,
+    out[b] = base row + concat_h(P_h) Wvo (no kept slot: the base row itself).  ``Wqk`` [dim, H dim], ``Wvo`` [H dim, dim], ``p``
+    [H, L]; H in {1, 2, 4, 8}, dim a multiple of 32 in 32..256, L in 1..64.  Five launches (four without a base): the resolve
+    (``tt_history_self_attention_resolve_f32``), T (``tt_dense_fwd_batched_f32``), the pool
+    (``tt_history_self_attention_pool_fwd_f32``), O (the GEMM again, into ``out``) and the base-row add
+    (``tt_history_self_attention_combine_f32``).  ``tokens``, ``bag_rows``, ``exclude``, ``base`` and ``oob_flag`` are
+    ``history_attention``'s.  ``keep``: False - returns ``out``, nothing else is kept; True or a ``SelfAttnBuffers`` of this shape -
+    returns (out, buffers) for ``history_self_attention_bwd`` (the slots' ids are the buffers' ``batch_ids``).  ``scratch``
+    (inference only, ``keep`` False): a ``SelfAttnBuffers`` for AT LEAST n_bags bags of this (L, dim, heads) whose tensors serve as
+    the call's workspace instead of fresh allocations."""
+    what = "history_self_attention"
+    n_rows, L, d, n_bags, out = _bag_args(what, table, tokens, bag_rows, "sum", out, False, None, None, oob_flag)
+    h = _chk_self_attention(what, d, L, Wqk, Wvo, p)
+    if exclude is not None:
+        _chk(exclude, torch.int64, "exclude", 1)
+        if exclude.numel() != n_bags:
+            raise RuntimeError(f"{what}: exclude must hold n_bags = {n_bags} entries, got {exclude.numel()}")
+    base_table = base_ids = None
+    if base is not None:
+        base_table, base_ids = base
+        _chk(base_table, torch.float32, "base_table", 2)
+        _chk(base_ids, torch.int64, "base_ids", 1)
+        if base_table.shape[1] != d or base_ids.numel() != n_bags:
+            raise RuntimeError(f"{what}: base must be ([rows, {d}] f32, [{n_bags}] int64), got "
+                               f"{tuple(base_table.shape)} and {tuple(base_ids.shape)}")
+    bufs = None
+    if keep is not False and keep is not None:
+        bufs = SelfAttnBuffers(n_bags, L, d, h, table.device) if keep is True else keep
+        if not isinstance(bufs, SelfAttnBuffers) or (bufs.n_bags, bufs.L, bufs.dim, bufs.heads) != (n_bags, L, d, h):
+            raise RuntimeError(f"{what}: keep must be a bool or a SelfAttnBuffers for ({n_bags}, {L}, {d}, {h}) (n_bags, L, dim, heads)")
+        w = bufs
+    elif scratch is not None:
+        if not isinstance(scratch, SelfAttnBuffers) or (scratch.L, scratch.dim, scratch.heads) != (L, d, h) or scratch.n_bags < n_bags:
+            raise RuntimeError(f"{what}: scratch must be a SelfAttnBuffers for at least {n_bags} bags of ({L}, {d}, {h}) (L, dim, heads)")
+        w = scratch
+    else:
+        w = SelfAttnBuffers(n_bags, L, d, h, table.device, backward=False)
+    if bufs is not None:
+        bufs.table = table
+    if n_bags == 0:
+        return out if bufs is None else (out, bufs)
+    batch_ids, newest, xn, T, P, weights = (w.batch_ids.view(-1)[:n_bags * L], w.newest[:n_bags], w.xn[:n_bags], w.T[:n_bags],
+                                            w.P[:n_bags], w.weights[:n_bags])
+    lib = _lib.load()
+    base_rows = 0 if base_table is None else base_table.shape[0]
+    _lib.check(lib.tt_history_self_attention_resolve_f32(_p(table), table.shape[0], d, _p(tokens), n_rows, L, _p(bag_rows), n_bags,
+                                                         _p(exclude), _p(base_ids), base_rows, _p(batch_ids), _p(newest), _p(xn),
+                                                         _p(oob_flag), _stream()), "tt_history_self_attention_resolve_f32")
+    dense_fwd(xn, Wqk, None, False, out=T)
+    _lib.check(lib.tt_history_self_attention_pool_fwd_f32(_p(table), table.shape[0], d, L, h, _p(batch_ids), n_bags, _p(T), _p(p),
+                                                          _p(P), _p(weights), _stream()), "tt_history_self_attention_pool_fwd_f32")
+    dense_fwd(P, Wvo, None, False, out=out)
+    if base_table is not None:
+        _lib.check(lib.tt_history_self_attention_combine_f32(_p(out), _p(newest), n_bags, d, _p(base_table), base_rows, _p(base_ids),
+                                                             _stream()), "tt_history_self_attention_combine_f32")
+    return out if bufs is None else (out, bufs)
+
+
+def history_self_attention_bwd(bufs: SelfAttnBuffers, dy: torch.Tensor, Wqk: torch.Tensor, Wvo: torch.Tensor,
+                               slot_grads: torch.Tensor | None = None, dwqk_slabs: torch.Tensor | None = None,
+                               dwvo_slabs: torch.Tensor | None = None, dp_slabs: torch.Tensor | None = None):
+    """The backward of ``history_self_attention`` from its kept ``SelfAttnBuffers`` (which remember the table the forward read)
+    and ``dy`` [n_bags, dim]: (dP, dWvo) = ``tt_dense_bwd_batched_f32`` of dy, the pool backward
+    (``tt_history_self_attention_pool_bwd_f32``), (dxn, dWqk) = the GEMM again from dT, and the query gradient
+    (``tt_history_self_attention_query_grad_f32``) - four launches.  ``slot_grads`` [n_bags * L, dim] gets ONE gradient row per
+    kept slot (a skipped slot's row is left untouched) - what the sparse optimizers take with a plain ``SparsePlan(n_bags * L)``
+    run over ``bufs.batch_ids``; ``dwqk_slabs`` [n_slabs, dim, H dim] and ``dwvo_slabs`` [n_slabs, H dim, dim]
+    (n_slabs = ``dense_bwd_num_slabs(n_bags)``) and ``dp_slabs`` [``history_self_attention_num_slabs(n_bags)``, H * L] are the
+    parameters' gradients as slabs, every slab written in full: the form ``make_dense_seg`` / ``make_adam_seg`` sum.  All are
+    allocated when None.  Returns (slot_grads, dwqk_slabs, dwvo_slabs, dp_slabs)."""
+    what = "history_self_attention_bwd"
+    if not isinstance(bufs, SelfAttnBuffers) or bufs.dP is None:
+        raise RuntimeError(f"{what}: bufs must be the SelfAttnBuffers history_self_attention(keep=...) returned (with backward buffers)")
+    n_bags, L, d, h = bufs.n_bags, bufs.L, bufs.dim, bufs.heads
+    if _chk_self_attention(what, d, L, Wqk, Wvo, None) != h:
+        raise RuntimeError(f"{what}: Wqk / Wvo are not the {h}-head kernels of the forward")
+    _chk(dy, torch.float32, "dy", 2)
+    table = bufs.table
+    if table is None:
+        raise RuntimeError(f"{what}: bufs have been through no forward yet")
+    if tuple(dy.shape) != (n_bags, d):
+        raise RuntimeError(f"{what}: dy must be [{n_bags}, {d}] (n_bags, dim), got {tuple(dy.shape)}")
+    m = n_bags * L
+    ns, nsp = dense_bwd_num_slabs(max(n_bags, 1)), history_self_attention_num_slabs(n_bags)
+    dev = dy.device
+    if slot_grads is None:
+        slot_grads = torch.empty((m, d), dtype=torch.float32, device=dev)
+    _chk(slot_grads, torch.float32, "slot_grads", 2)
+    if tuple(slot_grads.shape) != (m, d):
+        raise RuntimeError(f"{what}: slot_grads must be [{m}, {d}] (n_bags * L, dim), got {tuple(slot_grads.shape)}")
+    if dwqk_slabs is None:
+        dwqk_slabs = torch.empty((ns, d, h * d), dtype=torch.float32, device=dev)
+    if dwvo_slabs is None:
+        dwvo_slabs = torch.empty((ns, h * d, d), dtype=torch.float32, device=dev)
+    if dp_slabs is None:
+        dp_slabs = torch.empty((nsp, h * L), dtype=torch.float32, device=dev)
+    for t, name, shape in ((dwqk_slabs, "dwqk_slabs", (ns, d, h * d)), (dwvo_slabs, "dwvo_slabs", (ns, h * d, d))):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{what}: {name} must be {list(shape)} (n_slabs = dense_bwd_num_slabs(n_bags) = {ns}), got {tuple(t.shape)}")
+    _chk(dp_slabs, torch.float32, "dp_slabs", 2)
+    if dp_slabs.shape[0] < 1 or dp_slabs.shape[1] != h * L:
+        raise RuntimeError(f"{what}: dp_slabs must be [n_slabs, {h * L}] (heads * L), got {tuple(dp_slabs.shape)}")
+    if n_bags == 0:
+        dwqk_slabs.zero_(), dwvo_slabs.zero_(), dp_slabs.zero_()
+        return slot_grads, dwqk_slabs, dwvo_slabs, dp_slabs
+    if bufs.db is None:                          # the GEMMs' bias slabs: there is no bias, they are written and thrown away
+        bufs.db = torch.empty((ns, h * d), dtype=torch.float32, device=dev)
+    db = bufs.db
+    dense_bwd(bufs.P, Wvo, dy, bufs.dP, None, dwvo_slabs, db)
+    lib = _lib.load()
+    _lib.check(lib.tt_history_self_attention_pool_bwd_f32(_p(table), table.shape[0], d, L, h, _p(bufs.batch_ids), _p(bufs.weights),
+                                                          _p(bufs.P), _p(bufs.dP), _p(bufs.T), n_bags, _p(slot_grads), _p(bufs.dT),
+                                                          _p(dp_slabs), dp_slabs.shape[0], _stream()),
+               "tt_history_self_attention_pool_bwd_f32")
+    dense_bwd(bufs.xn, Wqk, bufs.dT, bufs.dxn, None, dwqk_slabs, db)
+    _lib.check(lib.tt_history_self_attention_query_grad_f32(_p(bufs.newest), _p(bufs.dxn), n_bags, L, d, _p(slot_grads), _stream()),
+               "tt_history_self_attention_query_grad_f32")
+    return slot_grads, dwqk_slabs, dwvo_slabs, dp_slabs
+
+
 def embedding_bag_bwd(dy: torch.Tensor, inv: torch.Tensor | None, order: torch.Tensor, L: int, order_bags: torch.Tensor,
                       gs: torch.Tensor | None = None):
     """The backward launch of ``embedding_bag`` (``tt_embedding_bag_bwd_f32``): ``gs[b, :] = dy[b, :] * inv[b]`` (``gs`` None -

@@ -241,6 +241,72 @@ def _gru_backward(ctx, d_out, d_ids, d_x, d_gates, d_gn, d_hprev):
 history_gru.register_autograd(_gru_backward, setup_context=_gru_setup)
 
 
+@torch.library.custom_op(f"{NS}::history_self_attention", mutates_args=(), device_types="cuda")
+def history_self_attention(table: Tensor, tokens: Tensor, bag_rows: Optional[Tensor], exclude: Optional[Tensor],
+                           base_table: Optional[Tensor], base_ids: Optional[Tensor], Wqk: Tensor, Wvo: Tensor,
+                           p: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The history bag encoded by multi-head self-attention read at the newest kept item (``ops.history_self_attention``;
+    ``Wqk`` [dim, H dim], ``Wvo`` [H dim, dim], ``p`` [H, L]): (out [n_bags, dim] = base row + concat_h(P_h) Wvo, batch_ids
+    [n_bags * L] int64 - the slots' tokens, -1 where skipped -, and the kept buffers newest [n_bags] int32, xn [n_bags, dim], T and P
+    [n_bags, H dim], weights [n_bags, H, L]).  Autograd with respect to ``Wqk``, ``Wvo`` and ``p`` (from the gradient of ``out``),
+    through ``twotower::history_self_attention_bwd``.  The table's gradient is sparse - one row per kept slot, the first result of
+    ``history_self_attention_bwd`` - and goes through ``sparse_update_`` / ``sparse_adam_`` with ``batch_ids`` as the ids; the
+    base table's gradient rows are the gradient of ``out`` itself."""
+    if (base_table is None) != (base_ids is None):
+        raise ValueError("history_self_attention: base_table and base_ids go together")
+    c = lambda t: None if t is None else t.contiguous()
+    out, bufs = ops.history_self_attention(table.contiguous(), tokens.contiguous(), Wqk.contiguous(), Wvo.contiguous(), p.contiguous(),
+                                           c(bag_rows), c(exclude), None if base_table is None else (c(base_table), c(base_ids)),
+                                           keep=True)
+    return out, bufs.batch_ids, bufs.newest, bufs.xn, bufs.T, bufs.P, bufs.weights
+
+
+@history_self_attention.register_fake
+def _(table, tokens, bag_rows, exclude, base_table, base_ids, Wqk, Wvo, p):
+    n_bags, L, d = (tokens.shape[0] if bag_rows is None else bag_rows.shape[0]), tokens.shape[1], table.shape[1]
+    hd = Wqk.shape[1]
+    return (table.new_empty((n_bags, d)), tokens.new_empty((n_bags * L,), dtype=torch.int64),
+            tokens.new_empty((n_bags,), dtype=torch.int32), table.new_empty((n_bags, d)), table.new_empty((n_bags, hd)),
+            table.new_empty((n_bags, hd)), table.new_empty((n_bags, p.shape[0], L)))
+
+
+@torch.library.custom_op(f"{NS}::history_self_attention_bwd", mutates_args=(), device_types="cuda")
+def history_self_attention_bwd(table: Tensor, batch_ids: Tensor, newest: Tensor, xn: Tensor, T: Tensor, P: Tensor, weights: Tensor,
+                               dy: Tensor, Wqk: Tensor, Wvo: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(slot_grads [n_bags * L, dim], dWqk [dim, H dim], dWvo [H dim, dim], dp [H, L]) of ``history_self_attention`` given dL/dout
+    and what the forward returned: one gradient row per kept slot (zeros for a skipped one) for ``sparse_update_`` /
+    ``sparse_adam_`` with ``batch_ids`` as the ids, and the parameters' gradients, the backward launches' slabs summed."""
+    c = lambda t: t.contiguous()
+    bufs = ops.SelfAttnBuffers.wrap(c(table), c(batch_ids), c(newest), c(xn), c(T), c(P), c(weights))
+    slot_grads = torch.zeros((bufs.n_bags * bufs.L, bufs.dim), dtype=torch.float32, device=dy.device)
+    _, dwqk, dwvo, dp = ops.history_self_attention_bwd(bufs, c(dy), c(Wqk), c(Wvo), slot_grads=slot_grads)
+    return slot_grads, dwqk.sum(dim=0), dwvo.sum(dim=0), dp.sum(dim=0).view(bufs.heads, bufs.L)
+
+
+@history_self_attention_bwd.register_fake
+def _(table, batch_ids, newest, xn, T, P, weights, dy, Wqk, Wvo):
+    return (xn.new_empty((batch_ids.shape[0], xn.shape[1])), torch.empty_like(Wqk, memory_format=torch.contiguous_format),
+            torch.empty_like(Wvo, memory_format=torch.contiguous_format), xn.new_empty((weights.shape[1], weights.shape[2])))
+
+
+def _self_attention_setup(ctx, inputs, output):
+    table, Wqk, Wvo = inputs[0], inputs[6], inputs[7]
+    _, batch_ids, newest, xn, T, P, weights = output
+    ctx.save_for_backward(table, batch_ids, newest, xn, T, P, weights, Wqk, Wvo)
+
+
+def _self_attention_backward(ctx, d_out, d_ids, d_newest, d_xn, d_T, d_P, d_weights):
+    table, batch_ids, newest, xn, T, P, weights, Wqk, Wvo = ctx.saved_tensors
+    dWqk = dWvo = dp = None
+    if d_out is not None and any(ctx.needs_input_grad[6:9]):
+        _, dWqk, dWvo, dp = torch.ops.twotower.history_self_attention_bwd(table, batch_ids, newest, xn, T, P, weights, d_out, Wqk, Wvo)
+    pick = lambda g, i: g if ctx.needs_input_grad[i] else None
+    return None, None, None, None, None, None, pick(dWqk, 6), pick(dWvo, 7), pick(dp, 8)
+
+
+history_self_attention.register_autograd(_self_attention_backward, setup_context=_self_attention_setup)
+
+
 @torch.library.custom_op(f"{NS}::sample_candidates", mutates_args=(), device_types="cuda")
 def sample_candidates(pos_ids: Tensor, n_items: int, n_neg: int, seed: int, tensor_id: int, start: int,
                       alias_thr: Optional[Tensor], alias_idx: Optional[Tensor], item_freq: Optional[Tensor],
@@ -938,5 +1004,5 @@ def _(sketch, ids, n_update, step, alpha, n_items, seed, tensor_id, sampler_prob
     return ids.new_empty((ids.shape[0],), dtype=torch.float32)
 
 
-OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "history_gru", "history_gru_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "mmr_rerank", "dense_fwd",
+OPS = ("frequency_estimate_", "clip_by_global_norm_", "embedding_gather","embedding_bag", "history_bag", "history_attention", "history_attention_bwd", "history_gru", "history_gru_bwd", "history_self_attention", "history_self_attention_bwd", "retrieval_loss", "retrieval_loss_value", "retrieval_rank", "retrieval_batch_rank", "retrieval_topk", "ivf_search", "quantize_rows_i8", "retrieval_topk_i8", "ivf_search_i8", "mmr_rerank", "dense_fwd",
        "dense_bwd", "l2_normalize", "l2_normalize_bwd", "dense_features", "dense_features_bwd", "time_context", "time_context_bwd", "rating_head", "rating_head_bwd", "cross_layer", "cross_layer_bwd", "layer_norm", "layer_norm_bwd", "sparse_update_", "sparse_adam_", "sparse_rowwise_adagrad_")

@@ -87,9 +87,12 @@ def parse(argv=None):
                     help="add the pooled user-history feature: every user's last L training interactions (1..64, by the "
                          "timestamp column where there is one) are pooled into the user tower input, the pair's own item left "
                          "out (overrides model.features.history.max_items); single-GPU trainer only")
-    ap.add_argument("--history-pooling", default=None, choices=["sum", "mean", "sqrtn", "attention", "gru"],
+    ap.add_argument("--history-pooling", default=None, choices=["sum", "mean", "sqrtn", "attention", "gru", "self_attention"],
                     help="how the history rows are pooled (default mean; attention: a learned query with a recency bias; gru: a GRU "
-                         "over the items, oldest first)")
+                         "over the items, oldest first; self_attention: multi-head self-attention with the newest item as the query)")
+    ap.add_argument("--history-heads", type=int, default=None, choices=[1, 2, 4, 8], metavar="H",
+                    help="heads of --history-pooling self_attention (1, 2, 4 or 8; default 1; overrides "
+                         "model.features.history.heads)")
     ap.add_argument("--side-features", default=None, choices=["none", "rating_stats"],
                     help="add the dense numeric side features: rating_stats = every user's and every item's rating count / mean / "
                          "std / min / max over the training pairs (column rating), normalised, projected by a trained kernel and "
@@ -313,6 +316,8 @@ def main(argv=None) -> int:
     cfg.user_history_len = history_len
     if args.history_pooling is not None:
         cfg.history_pooling = args.history_pooling
+    if args.history_heads is not None:
+        cfg.history_heads = args.history_heads
     if args.batch_size:
         cfg.batch_size = args.batch_size
     cfg.sampling_bias_estimator = bias["estimator"]

@@ -42,6 +42,7 @@ TID_SAMPLED_NEGATIVES = 10               # candidate_sampling="mixed": draw i of
 TID_DENSE_BASE = 16
 TID_RATING_W1, TID_RATING_W2 = 40, 41        # the rating head's two kernels (between the Dense kernels' 16..31 and the dropout streams)
 TID_GRU_BASE = 42                            # the history GRU: the input kernel W is 42, the recurrent kernel U 43
+TID_SELF_ATTENTION_BASE = 44                 # the history self-attention: Wqk is 44, Wvo 45
 TID_CROSS_BASE = 48                          # the cross kernels: layer l of tower t is 48 + 2 l + t (48..53)
 TID_FREQ_HASH_BASE = 56                      # the streaming frequency estimator's hash rows: row h is 56 + h (56..59)
 TID_TIME_BASE = 60                           # the time-of-interaction context: the table is 60, synthetic_timestamps 61
@@ -50,6 +51,8 @@ MAX_CROSS_LAYERS = 3
 # poolings of the user-history feature: the bag launch's three, the attention pool (csrc/history_attn.hip) and the GRU encoder
 # (csrc/history_gru.hip), history only
 HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention", "gru")
+# every encoder history_pooling takes: the poolings and the multi-head self-attention block (csrc/history_selfattn.hip)
+HISTORY_ENCODERS = HISTORY_POOLINGS + ("self_attention",)
 LR_DECAYS = ("none", "cosine", "linear", "inverse_sqrt")
 SAMPLING_BIAS_ESTIMATORS = ("none", "streaming")
 TID_DROPOUT_BASE = 64
@@ -132,6 +135,8 @@ class TwoTowerConfig:
     time_buckets: int = 0
     time_min: int = 0
     time_max: int = 0
+    # heads of history_pooling "self_attention" (1, 2, 4 or 8; described with the history feature below)
+    history_heads: int = 1
     # rating-prediction head (tfrs.tasks.Ranking beside tfrs.tasks.Retrieval): rating_weight > 0 adds one hidden ReLU layer of
     # rating_hidden units (a multiple of 32 in 32..256) over the pair's two tower outputs - the vectors the scorer reads - and a
     # scalar output trained with MSE on the interaction's rating: total = retrieval + rating_weight * L_r, L_r = mean over the
@@ -173,6 +178,13 @@ class TwoTowerConfig:
     # final state is added to the user tower's input.  W, U [D, 3D] (gate blocks z | r | n) are BOTH Glorot-uniform (Keras
     # initialises U orthogonally), b [2, 3D] = b_i, b_r starts at zero; none carries the l2 penalty.  embedding_dim must be a
     # multiple of 32 in 32..256.
+    # history_pooling "self_attention": one SASRec-style causal self-attention block with history_heads heads (1, 2, 4 or 8), read
+    # at the last position - the NEWEST kept item n is the one query: T = x_n Wqk, e_hj = <x_j, T_h> / sqrt(D) + p[h, recency rank
+    # of j], w_h = softmax_j, out = user row + concat_h(sum_j w_hj x_j) Wvo.  Wqk [D, H D] holds Wq_h Wk_h^T per head as one D x D
+    # form and Wvo [H D, D] holds Wv_h Wo_h (exact generalisations: every GEMM runs over batch rows, never batch * L); both are
+    # Glorot-uniform, p [H, L] starts at zero; none carries the l2 penalty.  Deviations from SASRec: the block's feed-forward half
+    # is the user tower's Dense stack that follows, there is no LayerNorm and no residual of x_n, and positions enter as the
+    # per-head recency bias p instead of position embeddings.  embedding_dim must be a multiple of 32 in 32..256.
     user_history_len: int = 0
     history_pooling: str = "mean"
     # pooled item-title feature (the reference's preprocessing.text_fields: title; TFRS TextVectorization -> Embedding ->
@@ -240,12 +252,18 @@ class TwoTowerConfig:
         """The history feature is on and encoded by the GRU."""
         return self.user_history_len > 0 and self.history_pooling == "gru"
 
-    def dense_segment_count(self, cross: bool = True, attention: bool = True, gru: bool = True) -> int:
+    @property
+    def history_self_attention(self) -> bool:
+        """The history feature is on and encoded by the multi-head self-attention block."""
+        return self.user_history_len > 0 and self.history_pooling == "self_attention"
+
+    def dense_segment_count(self, cross: bool = True, attention: bool = True, gru: bool = True, self_attention: bool = True) -> int:
         """Segments of the dense optimizer launches (``dense_layout``): a kernel and a bias per Dense layer, a projection kernel
         per side with numeric features, two for the rating head, two for the cross layers (``cross=False``: without those), one
         for the history attention's vector (``attention=False``: without it), one for the layer normalisation's gammas and betas,
-        one for the time table, four for the history GRU - W, U, b_i, b_r - (``gru=False``: without those)."""
-        skip = {g for g, on in (("cross", cross), ("attention", attention), ("gru", gru)) if not on}
+        one for the time table, four for the history GRU - W, U, b_i, b_r - (``gru=False``: without those), three for the history
+        self-attention - Wqk, Wvo, p - (``self_attention=False``: without those)."""
+        skip = {g for g, on in (("cross", cross), ("attention", attention), ("gru", gru), ("self_attention", self_attention)) if not on}
         return sum(s.group not in skip for s in dense_layout(self).segments)
 
     def validate(self):
@@ -285,8 +303,13 @@ class TwoTowerConfig:
             raise ValueError(f"title_pooling must be one of {tuple(ops.POOLINGS)}")
         if not 0 <= self.user_history_len <= 64:
             raise ValueError("user_history_len must be 0 (no history feature) or in 1..64")
-        if self.history_pooling not in HISTORY_POOLINGS:
-            raise ValueError(f"history_pooling must be one of {HISTORY_POOLINGS}")
+        if self.history_pooling not in HISTORY_ENCODERS:
+            raise ValueError(f"history_pooling must be one of {HISTORY_ENCODERS}")
+        if self.history_self_attention and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
+            raise ValueError("history_pooling='self_attention' needs an embedding_dim that is a multiple of 32 in 32..256 "
+                             f"(got {self.embedding_dim})")
+        if isinstance(self.history_heads, bool) or self.history_heads not in ops.SELF_ATTENTION_HEADS:
+            raise ValueError(f"history_heads must be one of {ops.SELF_ATTENTION_HEADS}, got {self.history_heads!r}")
         if self.history_gru and not (32 <= self.embedding_dim <= 256 and self.embedding_dim % 32 == 0):
             raise ValueError(f"history_pooling='gru' needs an embedding_dim that is a multiple of 32 in 32..256 (got {self.embedding_dim})")
         if self.user_history_len and self.n_items >= 2 ** 31:
@@ -395,7 +418,8 @@ _SEGMENT_GROUPS = {"features": "the numeric side features add one dense segment 
                    "attention": "the history attention adds one dense segment",
                    "norm": "the layer normalisation adds one dense segment",
                    "time": "the time context table adds one dense segment",
-                   "gru": "the history GRU adds four dense segments"}
+                   "gru": "the history GRU adds four dense segments",
+                   "self_attention": "the history self-attention adds three dense segments"}
 
 
 @dataclass(frozen=True)
@@ -427,7 +451,7 @@ class DenseSegment:
     hi: int
     l2: bool
     stride: int
-    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm" | "time" | "gru"
+    group: str                                   # "towers" | "features" | "head" | "cross" | "attention" | "norm" | "time" | "gru" | "self_attention"
 
     @property
     def size(self) -> int:
@@ -466,6 +490,8 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         history GRU                from a 16-byte boundary (the launches load its rows as float4s): W [D, 3D] | U [D, 3D] |
                                    b [2, 3D] = b_i, b_r; four segments - W, U, b_i, b_r -, none with l2: the gradient GEMMs write
                                    one slab array per kernel and one per bias row
+        history self-attention     from a 16-byte boundary: Wqk [D, H D] | Wvo [H D, D] | p [H, L]; three segments, none with l2:
+                                   the gradient GEMMs write one slab array per kernel, the pool backward launch p's
 
     Every optional block sits BEHIND what was there before it: switching one on moves no existing offset, and without the
     blocks behind it dense_flat ends behind the cross block with no trailing pad."""
@@ -529,6 +555,14 @@ def dense_layout(cfg: TwoTowerConfig) -> DenseLayout:
         segment("gru", u.name, u, u, False)
         segs.append(DenseSegment("history_gru.b_i", b.offset, b.offset + 3 * d, False, 3 * d, "gru"))
         segs.append(DenseSegment("history_gru.b_r", b.offset + 3 * d, b.end, False, 3 * d, "gru"))
+    if cfg.history_self_attention:
+        off = (off + 3) // 4 * 4
+        hd = cfg.history_heads * d
+        wqk = block("history_sa.Wqk", (d, hd), (TID_SELF_ATTENTION_BASE, d + d))
+        wvo = block("history_sa.Wvo", (hd, d), (TID_SELF_ATTENTION_BASE + 1, hd + d))
+        pb = block("history_sa.p", (cfg.history_heads, cfg.user_history_len))
+        for blk in (wqk, wvo, pb):
+            segment("self_attention", blk.name, blk, blk, False)
     return DenseLayout(blocks, tuple(segs), off)
 
 
@@ -1028,6 +1062,7 @@ _CHECKPOINT_CHECKS = (
     ("layer_norm", False, ": the gammas and betas in 'dense' belong to the trained model", None),
     ("layer_norm_epsilon", TwoTowerConfig.layer_norm_epsilon, "", "layer_norm"),
     ("n_title_buckets", 0, "", None), ("user_history_len", 0, "", None), ("history_pooling", "mean", "", "user_history_len"),
+    ("history_heads", 1, ": the self-attention kernels in 'dense' belong to the trained model", "history_self_attention"),
     ("title_max_tokens", None, "", "n_title_buckets"), ("title_pooling", None, "", "n_title_buckets"),
     ("time_fields", (), ": the time table in 'dense' belongs to the trained model", None),
     ("time_buckets", 0, "", "time_fields"), ("time_min", 0, "", "time_fields"), ("time_max", 0, "", "time_fields"))
@@ -1079,7 +1114,8 @@ class TwoTowerTrainer:
         self.rating_on = cfg.rating_weight > 0
         self._attn_on = cfg.history_attention
         self._gru_on = cfg.history_gru
-        self._slot_rows = self._attn_on or self._gru_on        # the history update takes one gradient row per slot
+        self._sa_on = cfg.history_self_attention
+        self._slot_rows = self._attn_on or self._gru_on or self._sa_on     # the history update takes one gradient row per slot
         sd, rh, ncl = cfg.tower_dims[-1], cfg.rating_hidden, cfg.cross_layers
         self.dense_flat = torch.zeros(lay.total, device=dev)
         self._fill_constant_blocks()             # (the layer normalisation's gammas start at 1 with or without a seed)
@@ -1135,6 +1171,7 @@ class TwoTowerTrainer:
         self.user_history = self.history_ids = self.history_inv = self.history_gs = None
         self.history_attn = self.history_weights = self.history_pooled = self.history_slot_grads = self._ha_slabs = None
         self.gru_W = self.gru_U = self.gru_b = self._gru_bufs = self._gru_slabs = self._gru_scratch = None
+        self.sa_Wqk = self.sa_Wvo = self.sa_p = self._sa_bufs = self._sa_slabs = self._sa_scratch = None
         if cfg.user_history_len:
             lh = cfg.user_history_len
             self.user_history = torch.full((cfg.n_users, lh), -1, dtype=torch.int32, device=dev)
@@ -1165,6 +1202,21 @@ class TwoTowerTrainer:
                                    torch.empty(2, ns, 3 * d, device=dev))
                 grad_slabs["history_gru.W"], grad_slabs["history_gru.U"] = (self._gru_slabs[0], ns), (self._gru_slabs[1], ns)
                 grad_slabs["history_gru.b_i"], grad_slabs["history_gru.b_r"] = (self._gru_slabs[2][0], ns), (self._gru_slabs[2][1], ns)
+            elif self._sa_on:
+                # self-attention encoder: one gradient row per kept slot through a plain sort plan, as under attention; the step
+                # keeps the newest rows, the queries, the pooled rows and the weights (ops.SelfAttnBuffers: nothing of b * lh * d);
+                # the gradient GEMMs write the slabs of the two kernels' segments, the pool backward launch those of p
+                plan = ops.SparsePlan(b * lh, dev)
+                hh = cfg.history_heads
+                self.sa_Wqk, self.sa_Wvo, self.sa_p = (lay.blocks[f"history_sa.{k}"].view(self.dense_flat) for k in ("Wqk", "Wvo", "p"))
+                self._sa_bufs = ops.SelfAttnBuffers(b, lh, d, hh, dev)
+                self._sa_bufs.batch_ids = self.history_ids
+                self.history_slot_grads = torch.zeros(b * lh, d, device=dev)
+                ns, nsp = ops.dense_bwd_num_slabs(b), ops.history_self_attention_num_slabs(b)
+                self._sa_slabs = (torch.empty(ns, d, hh * d, device=dev), torch.empty(ns, hh * d, d, device=dev),
+                                  torch.empty(nsp, hh * lh, device=dev))
+                grad_slabs["history_sa.Wqk"], grad_slabs["history_sa.Wvo"] = (self._sa_slabs[0], ns), (self._sa_slabs[1], ns)
+                grad_slabs["history_sa.p"] = (self._sa_slabs[2], nsp)
             else:
                 plan = ops.BagPlan(b, lh, dev)
                 self.history_inv = torch.empty(b, device=dev)
@@ -1555,6 +1607,8 @@ class TwoTowerTrainer:
                                       weights=self.history_weights[:n], pooled=self.history_pooled[:n], oob_flag=self.oob)
             elif user is not None and self._gru_on:
                 self._history_gru(user, exclude, keep)
+            elif user is not None and self._sa_on:
+                self._history_self_attention(user, exclude, keep)
             elif user is not None:
                 ops.history_bag(self.history_table, self.user_history, bag_rows=user[0], exclude=exclude, base=(self.user_table, user[0]),
                                 pooling=cfg.history_pooling, out=user[1], batch_ids=self.history_ids if keep else None,
@@ -1606,6 +1660,29 @@ class TwoTowerTrainer:
             ops.history_gru(*args, bag_rows=part, exclude=None if exclude is None else exclude[lo:lo + chunk],
                             base=(self.user_table, part), out=out[lo:lo + chunk], oob_flag=self.oob, scratch=self._gru_scratch)
 
+    def _history_self_attention(self, user, exclude, keep: bool, chunk: int = 4096):
+        """The self-attention launches of ``_tower_inputs``: user row + the attended history read at the newest kept item.  The
+        train step (``keep``) runs on the step's kept buffers; an inference pass takes any number of ids, ``chunk`` bags at a
+        time on ONE scratch of its own (allocated on first use, grown when a longer chunk comes): never more than chunk * H * D
+        floats per buffer, and nothing a pending step still needs is written."""
+        ids, out = user
+        cfg = self.cfg
+        args = (self.history_table, self.user_history, self.sa_Wqk, self.sa_Wvo, self.sa_p)
+        if keep:
+            ops.history_self_attention(*args, bag_rows=ids, exclude=exclude, base=(self.user_table, ids), out=out, oob_flag=self.oob,
+                                       keep=self._sa_bufs)
+            return
+        need = min(ids.numel(), chunk)
+        if self._sa_scratch is None or self._sa_scratch.n_bags < need:
+            self._sa_scratch = None
+            self._sa_scratch = ops.SelfAttnBuffers(need, cfg.user_history_len, cfg.embedding_dim, cfg.history_heads, self.dev,
+                                                   backward=False)
+        for lo in range(0, ids.numel(), chunk):
+            part = ids[lo:lo + chunk]
+            ops.history_self_attention(*args, bag_rows=part, exclude=None if exclude is None else exclude[lo:lo + chunk],
+                                       base=(self.user_table, part), out=out[lo:lo + chunk], oob_flag=self.oob,
+                                       scratch=self._sa_scratch)
+
     def _time_context(self, timestamps, user, keep: bool, base: bool):
         """The time launch of ``_tower_inputs``: the rows ``timestamps`` pick, summed, on top of the user row (``base``) or of
         what the history launch wrote; ``keep``: the row indices stay for ``_time_backward``."""
@@ -1641,7 +1718,8 @@ class TwoTowerTrainer:
     def _history_backward(self):
         """Attention pooling: the slots' gradient rows and the attention vector's gradient slabs from the user tower's input
         gradient (demb), one launch after the towers' backward - in front of the optimizer launches, which update the vector.
-        GRU: the same from three launches - the reverse recurrence, then the slot rows with dW / db_i and dU / db_r as GEMMs."""
+        GRU: the same from three launches - the reverse recurrence, then the slot rows with dW / db_i and dU / db_r as GEMMs.
+        Self-attention: the same from four - two gradient GEMMs round the pool backward, then the newest rows' query share."""
         if self._attn_on:
             ops.history_attention_bwd(self.history_table, self.history_ids, self.history_weights, self.history_pooled,
                                       self.user_tower.demb, self.history_attn, self.cfg.user_history_len,
@@ -1650,6 +1728,10 @@ class TwoTowerTrainer:
             dw, du, db = self._gru_slabs
             ops.history_gru_bwd(self._gru_bufs, self.user_tower.demb, self.gru_W, self.gru_U, slot_grads=self.history_slot_grads,
                                 dw_slabs=dw, du_slabs=du, db_slabs=db)
+        elif self._sa_on:                        # (dP, dWvo), the pool backward, (dxn, dWqk), the newest rows' += dxn: four launches
+            dwqk, dwvo, dp = self._sa_slabs
+            ops.history_self_attention_bwd(self._sa_bufs, self.user_tower.demb, self.sa_Wqk, self.sa_Wvo,
+                                           slot_grads=self.history_slot_grads, dwqk_slabs=dwqk, dwvo_slabs=dwvo, dp_slabs=dp)
 
     def _outputs(self, towers, rows=None):
         """The embeddings of ``towers`` (whose forward pass has just run) as everything downstream sees them - scorer, metrics,
@@ -1793,7 +1875,7 @@ class TwoTowerTrainer:
         if self.title_table is not None:
             item.update(slot_ids=self.title_ids, mode=cfg.title_pooling)
         rows = [ops.make_clip_rows(self.user_tower.demb, **user), ops.make_clip_rows(self.item_tower.demb, **item)]
-        if self._slot_rows:                      # attention and GRU alike: a kept slot's row counts once
+        if self._slot_rows:                      # attention, GRU and self-attention alike: a kept slot's row counts once
             rows.append(ops.make_clip_rows(self.history_slot_grads, 0.0, self.history_ids, "mask"))
         return ops.ClipList(rows, self._segs if self._adam_segs is None else self._adam_segs)
 
