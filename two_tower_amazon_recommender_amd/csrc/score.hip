@@ -44,9 +44,26 @@ enum { MODE_FWD = 0, MODE_BWD = 1, MODE_FUSED = 2, MODE_RANK = 3, MODE_FUSED_S =
        // The plain train step's pair (no sampling probability, ids or hard negatives), chosen on the host in launch_score:
        // MODE_FUSED_S_NC = MODE_FUSED_S without a column bias (a_c == nullptr), MODE_BWD_S_NR = MODE_BWD_S without a row bias or row
        // scale (a_r == s_r == nullptr; a_c and s_c given).  Same passes, same arithmetic on every live value; see FAST in score_kernel.
-       MODE_FUSED_S_NC = 6, MODE_BWD_S_NR = 7 };
-constexpr int base_mode(int m) { return m == MODE_FUSED_S_NC ? (int)MODE_FUSED_S : (m == MODE_BWD_S_NR ? (int)MODE_BWD_S : m); }
+       MODE_FUSED_S_NC = 6, MODE_BWD_S_NR = 7,
+       // MODE_BWD_S_NR at D <= 128 keeps a_c / s_c of ALL the split's streamed rows in LDS, staged once per workgroup (kRowTermRows);
+       // MODE_BWD_S_NR_T is the same kernel staging them per tile beside the tile, for splits longer than that array
+       MODE_BWD_S_NR_T = 8 };
+constexpr int base_mode(int m) {
+  return m == MODE_FUSED_S_NC ? (int)MODE_FUSED_S : ((m == MODE_BWD_S_NR || m == MODE_BWD_S_NR_T) ? (int)MODE_BWD_S : m);
+}
+constexpr int kRowTermRows = 4096;        // streamed rows per split whose two row terms the LDS array holds (32 KB)
+template <int D, int MODE_T> constexpr bool row_terms_in_lds() { return MODE_T == MODE_BWD_S_NR && D <= 128; }
 template <bool B> struct BoolC { static constexpr bool value = B; };     // compile-time flag of a generic lambda
+// FAST forms: a wave-uniform per-tile base pointer, pinned to an SGPR pair (an empty statement, no instruction).  The compiler
+// may no longer fold the thread's loop-invariant offset into the base - that fold made every per-tile base a 64-bit VECTOR
+// induction pointer (v_lshl_add_u64, v_add_co / v_addc per tile) - so the base advances on the scalar unit and the load takes it
+// as `saddr` beside one loop-invariant 32-bit VGPR offset.  (The result is typed as a global-memory pointer: behind the statement the
+// compiler no longer sees that the address came from a kernel argument, and a generic pointer would make the access a flat one.)
+template <class T> using global_ptr = __attribute__((address_space(1))) T*;
+template <class T> __device__ __forceinline__ global_ptr<T> uniform_base(T* p) {
+  asm("" : "+s"(p));
+  return (global_ptr<T>)p;
+}
 constexpr float kRescaleThr = 8.0f;   // FUSED: rescale the accumulators only when a row max grows by > 2^8 (p stays <= 256)
 
 struct ScoreArgs {
@@ -160,6 +177,10 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
   //    block (the coefficient is the B operand: MFMA output column j depends on B column j alone), and that column is dropped at
   //    the slab store - no mask needed.  Only an invalid STREAMED row (a register of X, a row of the LDS tile) is summed into
   //    valid outputs, and invalid streamed rows exist in a split's last tile only.
+  //  * both: nothing wave-uniform or constant is computed on the vector ALU per tile - the per-tile bases are SGPR pairs
+  //    (uniform_base) beside one loop-invariant 32-bit VGPR offset, the positive-tile test is two scalar compares of the tile index.
+  //  * MODE_BWD_S_NR at D <= 128: a_c / s_c of the split's streamed rows are staged ONCE, in the prologue, into an LDS array
+  //    (ROW_LDS); MODE_BWD_S_NR_T stages them per tile, for splits longer than the array.
   constexpr int MODE = base_mode(MODE_T);
   constexpr bool FAST = MODE_T != MODE;
   static_assert(!FAST || (PREC == 0 && !HAS_IDS && !HAS_HN), "the fast forms: exact f32, no ids, no hard negatives");
@@ -167,6 +188,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
   constexpr BoolC<true> FULL_TILE{};
   constexpr bool NO_AC = FAST && MODE == MODE_FUSED_S;      // no column bias: nothing staged for it
   constexpr bool NO_ROW = FAST && MODE == MODE_BWD_S;       // no row bias / scale; column bias and scale are non-null
+  // ROW_LDS: a_c / s_c of the split's streamed rows sit in one LDS array behind the tile ring, written once in the prologue: the
+  // tile loops load and stage no side values at all (a workgroup uses the same c_per_split values for the whole launch)
+  constexpr bool ROW_LDS = row_terms_in_lds<D, MODE_T>();
   constexpr bool IS_FUSED = MODE == MODE_FUSED || MODE == MODE_FUSED_S;     // online softmax + dq
   constexpr bool IS_BWD = MODE == MODE_BWD || MODE == MODE_BWD_S;            // gradient pass with given row statistics
   constexpr bool FROM_S = MODE == MODE_BWD_S, TO_S = MODE == MODE_FUSED_S;
@@ -264,6 +288,18 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
   int64_t idr = 0;
   if constexpr (HAS_IDS) idr = r_ok ? p.id_r[r] : (int64_t)-1;
   const int64_t cpos = p.pos_idx != nullptr ? (r_ok ? p.pos_idx[r] : (int64_t)-1) : r + p.diag;   // positive column
+  // FAST (no explicit positives: launch_score checks): the positive-tile test as two scalar 32-bit compares on the tile index.
+  // d = r0w + diag - c_begin is where the fragment's first positive sits in the split; tile t holds a positive of the fragment iff
+  // -32 < d - 32 t < 32, i.e. floor(d / 32) <= t <= floor((d + 31) / 32) (clamped to the tile indices an int holds; an empty range
+  // where none qualifies).  Inside such a tile the lane's positive row is ln + (d - 32 t), a small number, taken modulo 2^32.
+  const int64_t dfrag = r0w + p.diag - c_begin;
+  const int64_t dt_lo64 = dfrag >> 5, dt_hi64 = (dfrag + 31) >> 5;
+  const bool dt_none = dt_hi64 < 0 || dt_lo64 > 0x7fffffff;
+  const int dt_lo = FAST ? __builtin_amdgcn_readfirstlane(dt_none ? 1 : (dt_lo64 < 0 ? 0 : (int)dt_lo64)) : 0;
+  const int dt_hi = FAST ? __builtin_amdgcn_readfirstlane(dt_none ? 0 : (dt_hi64 > 0x7fffffff ? 0x7fffffff : (int)dt_hi64)) : 0;
+  const unsigned dfrag_lo = FAST ? (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)dfrag) : 0u;
+  const int lnh = ln - 4 * h;
+  const int xor32_addr = (lane ^ 32) << 2;            // ds_bpermute address of the lane that holds the row's other half
 
   // ---- staging (global -> regs -> LDS, TPB tiles ahead).  Thread `tid` moves float4 number
   // tid + THREADS*j of the tile (row = f / ROW4, col4 = f % ROW4).
@@ -292,20 +328,27 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
   const int ncols = (int)(c_end - c_begin);         // columns of this split (<= c_per_split)
 
   constexpr bool ST_FULL = NV * THREADS == 32 * ROW4;              // every thread stages NV float4 of every tile
+  // FAST: the byte offset of the thread's float4 within a full tile, kept in a register of its own (not recomputed from tid at
+  // every load)
+  unsigned st_offb = 16u * (unsigned)((ST_FULL ? st_row : (st_row < 31 ? st_row : 31)) * ROW4 + st_col4);
   // t: a tile that exists (0 <= t < ntiles).  Rows past the tile's last valid row read that row.
   // full (FAST kernels' main loop): tile t has 32 valid rows - `last` is the constant 31, the clamps are loop-invariant.
   auto load_tile = [&](int t, auto full) {
     constexpr bool FULL = decltype(full)::value;
     const f32x4* src = kp + (int64_t)t * (32 * ROW4);
     if constexpr (FULL) {
-      // a wave-uniform base per tile and per j (SALU) + one loop-invariant unsigned 32-bit offset per thread: no VALU per tile
+      // a wave-uniform base per tile and per j (an SGPR pair, see uniform_base) + one loop-invariant unsigned 32-bit offset per
+      // thread: no VALU per tile
       static_assert(ST_FULL || NV == 1, "threads past row 31 exist only where a thread stages one float4");
-      const unsigned off0 = (unsigned)((ST_FULL ? st_row : (st_row < 31 ? st_row : 31)) * ROW4 + st_col4);
+      // (a base per j as well: j * RPJ rows are 8 KB and more, past what the load's immediate offset holds.  The 32-bit offset is
+      // widened HERE, beside the loads: hoisted out of the loop as a 64-bit value it no longer fits the load's offset operand.)
+      asm volatile("" : "+v"(st_offb));
 #pragma unroll
-      for (int j = 0; j < NV; ++j) st[j] = (src + (ST_FULL ? j * RPJ * ROW4 : 0))[off0];
+      for (int j = 0; j < NV; ++j)
+        st[j] = *(global_ptr<const f32x4>)((global_ptr<const char>)uniform_base(src + (ST_FULL ? j * RPJ * ROW4 : 0)) + st_offb);
       const unsigned c31 = (unsigned)(tid < 31 ? tid : 31);
-      if constexpr (!NO_AC) st_a = (acp + 32 * (int64_t)t)[c31];
-      if constexpr (IS_BWD) st_s = (scp + 32 * (int64_t)t)[c31];
+      if constexpr (!NO_AC && !ROW_LDS) st_a = uniform_base(acp + 32 * (int64_t)t)[c31];
+      if constexpr (IS_BWD && !ROW_LDS) st_s = uniform_base(scp + 32 * (int64_t)t)[c31];
       return;
     }
     const int nvalid = ncols - 32 * t;              // valid rows of tile t (may exceed 32)
@@ -316,9 +359,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
       st[j] = src[(row < last ? row : last) * ROW4 + st_col4];
     }
     const int c = 32 * t + (tid < last ? tid : last);
-    if constexpr (!NO_AC) st_a = acp[c];
+    if constexpr (!NO_AC && !ROW_LDS) st_a = acp[c];
     if constexpr (HAS_HN) st_h = hcp[c];
-    if constexpr (IS_BWD) st_s = scp[c];              // (the only passes whose epilogue reads s_c)
+    if constexpr (IS_BWD && !ROW_LDS) st_s = scp[c];  // (the only passes whose epilogue reads s_c)
     if constexpr (HAS_IDS) st_id = idp[c];
   };
   // t: the tile the staging registers were loaded for.  Past the split's end (t >= ntiles: the registers hold the last tile
@@ -368,8 +411,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
         }
       }
     }
-    if constexpr (NO_AC) {
-      return;                                          // no side values at all: the epilogue derives the bias (0 / -big) from t
+    if constexpr (NO_AC || ROW_LDS) {
+      return;                                          // no side values at all: the epilogue derives the bias (0 / -big) from t (NO_AC)
+                                                       // or reads the row terms from the workgroup's LDS array (ROW_LDS)
     } else if constexpr (NO_ROW) {
       asm volatile("" : : "v"(st_a));
       asm volatile("" : : "v"(st_s));
@@ -410,10 +454,10 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
     if (!frag_ok) return;
     const int64_t ctile = (c_begin >> 5) + t;
     if constexpr (FAST) {                              // wave-uniform block address + a loop-invariant 32-bit lane offset
-      float* blk_u = p.S + (ctile * p.ldS + (r0w >> 5)) * 1024;
-      const unsigned lo = (unsigned)(ln * 32 + 4 * h);
+      const global_ptr<f32x4> blk_u = uniform_base(reinterpret_cast<f32x4*>(p.S + (ctile * p.ldS + (r0w >> 5)) * 1024));
+      const unsigned lo4 = (unsigned)(ln * 8 + h);
 #pragma unroll
-      for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(blk_u + (lo + 8u * g)) = f32x4{X[4 * g], X[4 * g + 1], X[4 * g + 2], X[4 * g + 3]};
+      for (int g = 0; g < 4; ++g) (blk_u + 2 * g)[lo4] = f32x4{X[4 * g], X[4 * g + 1], X[4 * g + 2], X[4 * g + 3]};
       return;
     }
     float* blk = p.S + (ctile * p.ldS + (r0w >> 5)) * 1024 + ln * 32 + 4 * h;
@@ -444,10 +488,10 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
   auto load_S = [&](int t, f32x16& X) {
     const int64_t q0 = c_begin + 32 * (int64_t)t;
     if constexpr (FAST) {                              // wave-uniform block address + a loop-invariant 32-bit lane offset
-      const float* blk_u = p.S + ((frag_ok ? (r0w >> 5) : 0) * p.ldS + (q0 >> 5)) * 1024;
+      const global_ptr<const float> blk_u = uniform_base((const float*)p.S + ((frag_ok ? (r0w >> 5) : 0) * p.ldS + (q0 >> 5)) * 1024);
       const unsigned lo = (unsigned)(4 * h * 32 + ln);
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) X[reg] = blk_u[lo + (unsigned)(tt::acc_row(reg, 0) * 32)];
+      for (int reg = 0; reg < 16; ++reg) X[reg] = (blk_u + tt::acc_row(reg, 0) * 32)[lo];
       return;
     }
     const float* blk = p.S + ((frag_ok ? (r0w >> 5) : 0) * p.ldS + (q0 >> 5)) * 1024 + 4 * h * 32 + ln;
@@ -479,6 +523,27 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
   // added the delay: 174.9 -> 175.5 .. 177.7 us for the dc pass.  Ablation of that pass: GEMM2 alone 112 us = the matrix pipe's
   // time; everything else - tile staging 25, dot-product loads 6-19, epilogue 9, loop skeleton 23 - adds to it instead of
   // hiding under it, with or without a phase shift between the waves.)
+  // ROW_LDS: the row terms of the split's ntiles * 32 streamed rows, [a_c | s_c] with kRowTermRows floats each, behind the tile ring.
+  // Two rows per thread and trip, all four loads unconditional from clamped indices; a row past the split's end gets what
+  // store_tile stages for it (-big, 0).  launch_score takes this form only where c_per_split <= kRowTermRows.  The barrier below
+  // publishes the array with the first tiles.
+  float* rowterm = smem + NBUF * BUF_F;
+  if constexpr (ROW_LDS) {
+    const int nrt = 32 * ntiles;
+    for (int i0 = 0; i0 < nrt; i0 += 2 * THREADS) {
+      const int i_a = i0 + tid, i_b = i0 + THREADS + tid;
+      const int c_a = i_a < ncols ? i_a : ncols - 1, c_b = i_b < ncols ? i_b : ncols - 1;     // (nrt > 0: ncols >= 1)
+      const float a_a = acp[c_a], s_a = scp[c_a], a_b = acp[c_b], s_b = scp[c_b];
+      if (i_a < nrt) {
+        rowterm[i_a] = i_a < ncols ? a_a : kNegBig;
+        rowterm[kRowTermRows + i_a] = i_a < ncols ? s_a : 0.f;
+      }
+      if (i_b < nrt) {
+        rowterm[i_b] = i_b < ncols ? a_b : kNegBig;
+        rowterm[kRowTermRows + i_b] = i_b < ncols ? s_b : 0.f;
+      }
+    }
+  }
 #pragma unroll
   for (int t0 = 0; t0 < TPB; ++t0)
     if (t0 < ntiles) {
@@ -552,12 +617,12 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
       if constexpr (NO_AC) {
         // nothing staged: the bias store_tile would have staged for a null a_c - 0, or -big past the end - is applied below
       } else {
-        const f32x4 va = *reinterpret_cast<const f32x4*>(T + TILE_F + 8 * q + 4 * h);
+        const f32x4 va = *reinterpret_cast<const f32x4*>((ROW_LDS ? rowterm + 32 * t : T + TILE_F) + 8 * q + 4 * h);
 #pragma unroll
         for (int i = 0; i < 4; ++i) ac[4 * q + i] = va[i];
       }
       if constexpr (IS_BWD) {
-        const f32x4 vs = *reinterpret_cast<const f32x4*>(T + TILE_F + 32 + 8 * q + 4 * h);
+        const f32x4 vs = *reinterpret_cast<const f32x4*>((ROW_LDS ? rowterm + kRowTermRows + 32 * t : T + TILE_F + 32) + 8 * q + 4 * h);
 #pragma unroll
         for (int i = 0; i < 4; ++i) sc[4 * q + i] = vs[i];
       }
@@ -573,7 +638,9 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
     }
     // wave-uniform: does this tile hold the positive of any row of this wave?
     bool diag_tile;
-    if (p.pos_idx != nullptr) {
+    if constexpr (FAST) {
+      diag_tile = t >= dt_lo && t <= dt_hi;
+    } else if (p.pos_idx != nullptr) {
       const int64_t dd0 = cpos - c0;
       diag_tile = __any(dd0 >= 0 && dd0 < 32) != 0;
     } else {
@@ -582,8 +649,13 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
     // tile-local row (minus the lane half's +4h) of this lane's positive, or a value no row matches
     int dloc = -100;
     if (diag_tile) {
-      const int64_t dd = cpos - c0;
-      dloc = (dd >= 0 && dd < 32) ? (int)dd - 4 * h : -100;
+      if constexpr (FAST) {
+        // (no range test: a positive outside the tile gives a value outside 0 .. 31 - 4h, which no accumulator row equals)
+        dloc = lnh + (int)(dfrag_lo - 32u * (unsigned)t);
+      } else {
+        const int64_t dd = cpos - c0;
+        dloc = (dd >= 0 && dd < 32) ? (int)dd - 4 * h : -100;
+      }
     }
     // The positive pair's fix-ups under the wave-uniform `if (diag_tile)` are selects: an `if` per register was a tree of ~25
     // nested exec branches per tile step.  Except the capture of the positive logit in the kernels with accidental-hit ids:
@@ -683,7 +755,10 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
 #pragma unroll
           for (int reg = 0; reg < 16; ++reg) take_pos(tt::acc_row(reg, 0) == dloc, coef[reg]);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        if constexpr (FAST)      // (the other half's lane by its byte address, computed once: __shfl_xor rebuilds it on every tile)
+          mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(xor32_addr, __builtin_bit_cast(int, mx))));
+        else
+          mx = fmaxf(mx, __shfl_xor(mx, 32));
         if (__any(mx - run_m > kRescaleThr)) {
           const float m_new = fmaxf(run_m, mx);
           const float alpha = __builtin_amdgcn_exp2f(run_m - m_new);
@@ -815,14 +890,16 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
     };
     // FAST: tiles t, t + TPB and t + 2 exist and are full (t + 2 < nfull) - the dot products are used as loaded, the loads and
     // the LDS store of tile t + TPB take no clamp and no select
-    auto full_step = [&](int t, f32x16& xs_t) {
-      const float* T = smem + (t % NBUF) * BUF_F;
+    // rb = t % NBUF, carried by the loop: the two steps of a trip sit one buffer apart, so both take their LDS addresses from
+    // the trip's one base (a compile-time offset apart) instead of each from its own t % NBUF
+    auto full_step = [&](int t, int rb, int rn, f32x16& xs_t) {
+      const float* T = smem + rb * BUF_F;
       float coef[16];
       epilogue(T, t, xs_t, coef, FULL_TILE);
       load_tile(t + TPB, FULL_TILE);
       load_S(t + 2, xs_t);
       gemm2(T, coef);
-      store_tile(t + TPB, (t + TPB) % NBUF, FULL_TILE);
+      store_tile(t + TPB, rn, FULL_TILE);
       if ((t % TPB) == TPB - 1) __syncthreads();
     };
     if (ntiles > 0) {                                  // (an empty split issues nothing at all)
@@ -833,10 +910,12 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mo
       int t = 0;
       if constexpr (FAST) {                            // whole pairs of steps whose tiles and prefetches are full tiles
         static_assert(TPB <= 2, "full_step prefetches at most two tiles ahead");
+        static_assert(NBUF == 2 || NBUF == 4, "a trip of two steps starts at an even buffer");
         const int nfast = (nfull > 2 ? nfull - 2 : 0) & ~1;
-        for (; t < nfast; t += 2) {
-          full_step(t, xa);
-          full_step(t + 1, xb);
+        for (int rb = 0; t < nfast; t += 2, rb = (rb + 2) % NBUF) {
+          const int rn = (rb + TPB) % NBUF;            // where tile t + TPB is staged; tile t + 1 + TPB goes one buffer further
+          full_step(t, rb, rn, xa);
+          full_step(t + 1, rb + 1, TPB == 2 ? rn + 1 : (rb + 1 + TPB) % NBUF, xb);
         }
       }
       for (; t + 1 < ntiles; t += 2) {
@@ -1380,8 +1459,8 @@ int launch_score(const ScoreArgs& a_in, hipStream_t stream) {
   const bool has_ids = a_in.id_c != nullptr;       // every pass sets the id pair together (pass_args)
   const bool has_hn = (a_in.h_r != nullptr) || (a_in.h_c != nullptr);
   const ScoreArgs& a = a_in;
-  auto go = [&](auto kern, int rfl_groups = 0) -> int {
-    const int lds = lds_base + W * rfl_groups * 64 * 16;        // + the LDS-resident k-groups of the stationary fragment
+  auto go = [&](auto kern, int rfl_groups = 0, int extra_lds = 0) -> int {
+    const int lds = lds_base + W * rfl_groups * 64 * 16 + extra_lds;     // + the LDS-resident k-groups of the stationary fragment
     if (lds > 64 * 1024) {   // above the 64 KiB default the limit must be raised (cheap, idempotent)
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return tt::fail(TT_ERR_LAUNCH, "hipFuncSetAttribute(LDS %d) failed", lds);
@@ -1402,8 +1481,14 @@ int launch_score(const ScoreArgs& a_in, hipStream_t stream) {
           if (a.a_c == nullptr) return go(score_kernel<D, MODE_FUSED_S_NC, false, false, W, 0>);
         }
       } else {
-        if (a.a_r == nullptr && a.s_r == nullptr && a.a_c != nullptr && a.s_c != nullptr)
+        if (a.a_r == nullptr && a.s_r == nullptr && a.a_c != nullptr && a.s_c != nullptr) {
+          if constexpr (row_terms_in_lds<D, MODE_BWD_S_NR>()) {
+            // the row terms once per workgroup in LDS where a split's rows fit the array, else per tile as ever
+            if (a.c_per_split > kRowTermRows) return go(score_kernel<D, MODE_BWD_S_NR_T, false, false, W, 0>);
+            return go(score_kernel<D, MODE_BWD_S_NR, false, false, W, 0>, 0, 2 * kRowTermRows * 4);
+          }
           return go(score_kernel<D, MODE_BWD_S_NR, false, false, W, 0>);
+        }
       }
     }
   }
