@@ -1071,6 +1071,47 @@ int tt_retrieval_batch_rank_f32(const float* q, const float* c, int64_t nq, int6
                                 float inv_temperature, const float* cand_prob, const int64_t* cand_ids,
                                 void* workspace, int64_t workspace_bytes, int32_t* rank, tt_stream_t stream);
 
+/* Pairwise retrieval losses over the in-batch negatives (added to v10: new symbols only, the version is unchanged): BPR /
+ * pairwise logistic (Rendle 2009) and the pairwise hinge (triplet) loss, on the logits the softmax above sees.
+ *
+ *   s_ij  = <q_i, c_j> * inv_temperature - log(clip(cand_prob_j, 1e-6, 1))          (cand_prob NULL: no correction)
+ *   pos_i = s_{i, i+diag_offset}
+ *   N_i   = { j != i+diag_offset :  not (cand_ids given and cand_ids_j == cand_ids_{i+diag_offset})
+ *                                   and not (hard_thr given and s_ij below hard_thr_i) } ;   n_i = |N_i|
+ *   x_ij  = pos_i - s_ij
+ *   phi   = TT_PAIRWISE_LOGISTIC: softplus(-x) = max(-x, 0) + log1p(exp(-|x|))       phi' = -sigmoid(-x)
+ *           TT_PAIRWISE_HINGE:    max(0, margin - x)                                 phi' = -[x < margin]   (x == margin: 0)
+ *   r_i   = 1 / max(n_i, 1)  (TT_PAIRWISE_MEAN)   or   1  (TT_PAIRWISE_SUM)
+ *   row_i = w_i * r_i * sum_{j in N_i} phi(x_ij) ;   loss = sum_i row_i              (w = sample_weight, NULL: 1)
+ *   h_ij  = -w_i * r_i * phi'(x_ij) for j in N_i, else 0 ;   H_i = sum_j h_ij
+ *   dq_i  = grad_scale * inv_temperature * (sum_j h_ij c_j - H_i c_{i+diag_offset})
+ *   dc_j  = grad_scale * inv_temperature * (sum_i h_ij q_i - [j == i'+diag_offset] H_i' q_i')
+ *
+ * A row without negatives (n_i = 0) has row_i = 0 and no gradient.  hard_thr is what
+ * tt_retrieval_hard_negative_thresholds_f32 returns (the comparison is the scorer's, on its log2-domain logits).  margin is
+ * read by the hinge only but must be finite.  Arguments and limits as tt_retrieval_fwd_f32 / tt_retrieval_fwd_bwd_f32 (there
+ * is no lse); exact f32 products only.  Two passes over the logits (stationary q, then stationary c, which recomputes the
+ * products: 8*nq*nc*dim executed FLOPs), no atomics - the results are bit-identical run to run - and no [nq, nc] array:
+ * the workspace (256-byte aligned, tt_retrieval_pairwise_workspace_bytes; 0 for a degenerate shape) holds row terms,
+ * per-split row partials and the gradient slabs, and is never larger than tt_retrieval_workspace_bytes plus the row terms. */
+#define TT_PAIRWISE_LOGISTIC 0
+#define TT_PAIRWISE_HINGE 1
+#define TT_PAIRWISE_MEAN 0
+#define TT_PAIRWISE_SUM 1
+int64_t tt_retrieval_pairwise_workspace_bytes(int64_t nq, int64_t nc, int32_t dim);
+int tt_retrieval_pairwise_fwd_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
+                                  int64_t diag_offset, float inv_temperature,
+                                  const float* sample_weight, const float* cand_prob, const int64_t* cand_ids,
+                                  const float* hard_thr, void* workspace, int64_t workspace_bytes,
+                                  float* per_row, float* loss, int32_t kind, float margin, int32_t reduction,
+                                  tt_stream_t stream);
+int tt_retrieval_pairwise_fwd_bwd_f32(const float* q, const float* c, int64_t nq, int64_t nc, int32_t dim,
+                                      int64_t diag_offset, float inv_temperature,
+                                      const float* sample_weight, const float* cand_prob, const int64_t* cand_ids,
+                                      const float* hard_thr, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                      float* per_row, float* loss, float* dq, float* dc,
+                                      int32_t kind, float margin, int32_t reduction, tt_stream_t stream);
+
 /* Exact top-K retrieval (tfrs.layers.factorized_top_k.BruteForce; ABI v10): the k best candidates of every query,
  * scored and selected in one pass over the corpus (no [nq x nc] score matrix) and merged across corpus splits.
  * score[i][j] = q_i . c_j (plain dot product, exact f32 products on the f32 MFMA).  q [nq, dim], c [nc, dim] f32, 16-byte

@@ -282,6 +282,10 @@ SIGNATURES = {
     "tt_retrieval_hard_negative_thresholds_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _i32, _p, _i64, _p, _i64, _p, _p]),
     "tt_retrieval_rank_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _f, _p, _p, _p, _i64, _p, _p]),
     "tt_retrieval_batch_rank_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _i64, _p, _p]),
+    "tt_retrieval_pairwise_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "tt_retrieval_pairwise_fwd_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _p, _p, _i64, _p, _p, _i32, _f, _i32, _p]),
+    "tt_retrieval_pairwise_fwd_bwd_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _f, _p, _p, _p, _p, _f, _p, _i64, _p, _p, _p, _p,
+                                                   _i32, _f, _i32, _p]),
     "tt_retrieval_topk_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "tt_retrieval_topk_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p]),
     "tt_ivf_search_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32]),

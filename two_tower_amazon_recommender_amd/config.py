@@ -6,7 +6,7 @@ import math
 
 import yaml
 
-from .trainer import LR_DECAYS, SAMPLING_BIAS_ESTIMATORS, TwoTowerConfig
+from .trainer import LR_DECAYS, RETRIEVAL_LOSSES, SAMPLING_BIAS_ESTIMATORS, TwoTowerConfig
 
 
 def load_yaml(path) -> dict:
@@ -181,6 +181,34 @@ def sampling_bias_from_dict(doc: dict) -> dict:
     return {"estimator": est, "alpha": float(alpha), "hashes": hashes, "slots": slots}
 
 
+RETRIEVAL_LOSS_KEYS = ("kind", "margin", "reduction")
+PAIRWISE_REDUCTIONS = ("mean", "sum")
+
+
+def retrieval_loss_from_dict(doc: dict) -> dict:
+    """{kind, margin, reduction} of the optional ``model.retrieval.loss`` block (not in the reference's schema): ``kind``
+    softmax (the in-batch sampled softmax, the default) | bpr (pairwise logistic) | hinge (pairwise hinge with ``margin``);
+    ``reduction`` mean (every query's sum over its negatives divided by their number) | sum.  Without the block: softmax."""
+    block = ((doc.get("model") or {}).get("retrieval") or {}).get("loss")
+    d = TwoTowerConfig
+    if block is None:
+        block = {}
+    if not isinstance(block, dict):
+        raise ValueError("model.retrieval.loss must be a mapping {kind, margin, reduction}")
+    unknown = sorted(set(block) - set(RETRIEVAL_LOSS_KEYS))
+    if unknown:
+        raise ValueError(f"model.retrieval.loss: unknown keys {unknown} (known: {list(RETRIEVAL_LOSS_KEYS)})")
+    kind = str(block.get("kind", d.retrieval_loss)).lower()
+    if kind not in RETRIEVAL_LOSSES:
+        raise ValueError(f"model.retrieval.loss.kind must be one of {RETRIEVAL_LOSSES}, got {kind!r}")
+    margin, reduction = block.get("margin", d.pairwise_margin), str(block.get("reduction", d.pairwise_reduction)).lower()
+    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin):
+        raise ValueError(f"model.retrieval.loss.margin must be a finite number, got {margin!r}")
+    if reduction not in PAIRWISE_REDUCTIONS:
+        raise ValueError(f"model.retrieval.loss.reduction must be one of {PAIRWISE_REDUCTIONS}, got {reduction!r}")
+    return {"kind": kind, "margin": float(margin), "reduction": reduction}
+
+
 def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str = "adagrad",
                            dropout_override: float | None = None) -> tuple[TwoTowerConfig, dict]:
     """Returns (TwoTowerConfig, training-loop settings {epochs, patience, validation_freq, top_k_eval})."""
@@ -218,7 +246,10 @@ def model_config_from_dict(doc: dict, n_users: int, n_items: int, optimizer: str
     bias = sampling_bias_from_dict(doc)
     # likewise model.features.time {fields, buckets} - the time-of-interaction context features
     when = time_features_from_dict(doc)
+    # likewise model.retrieval.loss {kind, margin, reduction} - the pairwise retrieval losses
+    rloss = retrieval_loss_from_dict(doc)
     cfg = TwoTowerConfig(
+        retrieval_loss=rloss["kind"], pairwise_margin=rloss["margin"], pairwise_reduction=rloss["reduction"],
         time_fields=when["fields"], time_buckets=when["buckets"],
         sampling_bias_estimator=bias["estimator"], freq_alpha=bias["alpha"], freq_hashes=bias["hashes"], freq_slots=bias["slots"],
         global_clipnorm=opt["global_clipnorm"], lr_warmup_steps=opt["warmup_steps"], lr_decay=opt["decay"],

@@ -2188,6 +2188,50 @@ def retrieval_fwd_bwd(q, c, inv_temperature: float, workspace, lse, per_row, los
     return loss
 
 
+PAIRWISE_KINDS = {"logistic": 0, "hinge": 1}          # TT_PAIRWISE_LOGISTIC / TT_PAIRWISE_HINGE
+PAIRWISE_REDUCTIONS = {"mean": 0, "sum": 1}           # TT_PAIRWISE_MEAN / TT_PAIRWISE_SUM
+
+
+def retrieval_pairwise_workspace_bytes(nq: int, nc: int, dim: int) -> int:
+    """Workspace of the pairwise-loss entries: row terms, per-split row partials and gradient slabs - no [nq, nc] buffer."""
+    return int(_lib.load().tt_retrieval_pairwise_workspace_bytes(nq, nc, dim))
+
+
+def _pairwise_codes(kind: str, margin: float, reduction: str):
+    if kind not in PAIRWISE_KINDS:
+        raise ValueError(f"pairwise loss kind must be one of {tuple(PAIRWISE_KINDS)}, got {kind!r}")
+    if reduction not in PAIRWISE_REDUCTIONS:
+        raise ValueError(f"pairwise loss reduction must be one of {tuple(PAIRWISE_REDUCTIONS)}, got {reduction!r}")
+    return PAIRWISE_KINDS[kind], float(margin), PAIRWISE_REDUCTIONS[reduction]
+
+
+def retrieval_pairwise_fwd(q, c, inv_temperature: float, workspace, per_row, loss, kind: str = "logistic", margin: float = 1.0,
+                           reduction: str = "mean", sample_weight=None, cand_prob=None, cand_ids=None, diag_offset: int = 0,
+                           hard_thr=None):
+    """Forward only (validation) of the pairwise loss ``kind`` ("logistic" = BPR, "hinge") over the in-batch negatives: writes
+    per_row [nq] and loss [1].  ``reduction`` "mean": every row's sum is divided by its number of negatives; "sum": it is not."""
+    _chk_retrieval(q, c, sample_weight, cand_prob, cand_ids, hard_thr, None, per_row)
+    k, m, r = _pairwise_codes(kind, margin, reduction)
+    _lib.check(_lib.load().tt_retrieval_pairwise_fwd_f32(
+        _p(q), _p(c), q.shape[0], c.shape[0], q.shape[1], diag_offset, inv_temperature, _p(sample_weight), _p(cand_prob),
+        _p(cand_ids), _p(hard_thr), _p(workspace), workspace.numel(), _p(per_row), _p(loss), k, m, r, _stream()),
+        "tt_retrieval_pairwise_fwd_f32")
+    return loss
+
+
+def retrieval_pairwise_fwd_bwd(q, c, inv_temperature: float, workspace, per_row, loss, dq, dc, kind: str = "logistic",
+                               margin: float = 1.0, reduction: str = "mean", sample_weight=None, cand_prob=None, cand_ids=None,
+                               diag_offset: int = 0, grad_scale: float = 1.0, hard_thr=None):
+    """The pairwise loss and both gradients (training form): two passes over the logits, exact f32 products, no atomics."""
+    _chk_retrieval(q, c, sample_weight, cand_prob, cand_ids, hard_thr, None, per_row, dq, dc)
+    k, m, r = _pairwise_codes(kind, margin, reduction)
+    _lib.check(_lib.load().tt_retrieval_pairwise_fwd_bwd_f32(
+        _p(q), _p(c), q.shape[0], c.shape[0], q.shape[1], diag_offset, inv_temperature, _p(sample_weight), _p(cand_prob),
+        _p(cand_ids), _p(hard_thr), grad_scale, _p(workspace), workspace.numel(), _p(per_row), _p(loss), _p(dq), _p(dc), k, m, r,
+        _stream()), "tt_retrieval_pairwise_fwd_bwd_f32")
+    return loss
+
+
 def retrieval_rank(q, c, inv_temperature: float, pos_index, workspace=None, cand_prob=None, out=None, precision: str = "f32"):
     """rank[i] = #candidates scoring strictly above query i's true candidate ``pos_index[i]`` (int32 [nq]).
     precision "bf16x3": the logits' products on the bf16 MFMA (dim 128 / 256)."""

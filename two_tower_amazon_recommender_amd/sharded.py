@@ -468,6 +468,10 @@ class ShardedTwoTowerTrainer:
         if getattr(cfg, "lr_schedule_on", False):
             raise NotImplementedError("a learning-rate schedule (lr_warmup_steps / lr_decay) is not implemented for the row-sharded "
                                       "trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
+        if getattr(cfg, "retrieval_loss", "softmax") != "softmax":
+            # the row normalisers n_i and H_i would have to be combined over the ranks' candidate slabs between the two passes
+            raise NotImplementedError("a pairwise retrieval loss (retrieval_loss='bpr' / 'hinge') is not implemented for the "
+                                      "row-sharded trainer (ShardedTwoTowerTrainer): use TwoTowerTrainer")
         from . import ops
         from .trainer import Tower, TID_USER_TABLE, TID_ITEM_TABLE
         cfg.validate()

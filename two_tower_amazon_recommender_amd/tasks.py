@@ -9,10 +9,21 @@ The task dispatches through the registered custom ops ``torch.ops.twotower.retri
 both gradients in the fused two-pass form, 6*Bq*Bc*D executed FLOPs, gradients saved for autograd) and
 ``torch.ops.twotower.retrieval_loss_value`` (no gradient needed: one statistics pass) — ``torch_ops.py``.
 
+Pairwise losses over the in-batch negatives run in a kernel family of their own (csrc/pairwise.hip, the ops
+``torch.ops.twotower.retrieval_pairwise_loss`` / ``retrieval_pairwise_loss_value``): ``loss=tasks.PairwiseLogisticLoss()``
+(alias ``tasks.BPRLoss``: sum over the negatives j of softplus(s_ij - s_i,pos), Rendle 2009) and
+``loss=tasks.PairwiseHingeLoss(margin=1.0)`` (sum of max(0, margin - (s_i,pos - s_ij)): the triplet loss, with
+``num_hard_negatives=k`` over the k hardest negatives).  The logits are the ones the softmax sees (temperature,
+sampling-probability correction), accidental hits and mined-out negatives are not pairs, ``sample_weight`` weights a query's
+row.  A stated choice: ``reduction="mean"`` (the default) divides every query's sum by ITS number of negatives, so that a
+margin and a learning rate keep their meaning when the batch size changes, and ``reduction="sum"`` is the plain sum over all
+pairs; the loss is then summed over the queries, like the softmax loss.  This is NOT TF-Ranking's normalisation (which
+averages over all pairs of the batch).  A query without negatives contributes nothing.  f32 only.
+
 Differences from TFRS, all loud:
-  * ``loss`` must be None or ``tasks.CategoricalCrossentropy(from_logits=True, reduction="sum")`` - the TFRS default, the
-    one loss the fused kernels implement; anything else (hinge / pairwise / MSE losses of tfrs.losses, or another
-    reduction) needs the [queries x candidates] score matrix and raises NotImplementedError;
+  * ``loss`` must be None, ``tasks.CategoricalCrossentropy(from_logits=True, reduction="sum")`` - the TFRS default - or one of
+    the two pairwise losses above; anything else (pointwise / MSE losses of tfrs.losses, another reduction of the
+    cross-entropy) needs the [queries x candidates] score matrix and raises NotImplementedError;
   * ``metrics`` takes a ``metrics.FactorizedTopK`` built WITH its candidate corpus (``FactorizedTopK(candidates=...)``);
     it is updated when ``compute_metrics`` is true, and ``candidate_ids`` must then be the int64 index of every
     candidate in that corpus (the reference's ``item_idx``); ``loss_metrics`` takes objects with
@@ -42,16 +53,49 @@ class CategoricalCrossentropy:
         self.from_logits, self.reduction = bool(from_logits), str(reduction).lower()
 
 
+class _PairwiseLoss:
+    kind = None
+
+    def __init__(self, reduction: str = "mean"):
+        self.reduction = str(reduction).lower()
+        if self.reduction not in ("mean", "sum"):
+            raise ValueError(f"{type(self).__name__}(reduction=...): 'mean' (per query, over its negatives) or 'sum', "
+                             f"got {reduction!r}")
+        self.margin = 1.0                    # (read by the hinge only)
+
+
+class PairwiseLogisticLoss(_PairwiseLoss):
+    """BPR / pairwise logistic loss over the in-batch negatives: softplus(s_neg - s_pos) per (positive, negative) pair."""
+    kind = "logistic"
+
+
+BPRLoss = PairwiseLogisticLoss
+
+
+class PairwiseHingeLoss(_PairwiseLoss):
+    """Pairwise hinge (triplet) loss over the in-batch negatives: max(0, margin - (s_pos - s_neg)) per pair."""
+    kind = "hinge"
+
+    def __init__(self, margin: float = 1.0, reduction: str = "mean"):
+        super().__init__(reduction)
+        self.margin = float(margin)
+        if self.margin != self.margin or self.margin in (float("inf"), float("-inf")):
+            raise ValueError(f"PairwiseHingeLoss(margin=...): must be finite, got {margin!r}")
+
+
 class Retrieval:
-    """A factorized retrieval task: in-batch softmax over query x candidate dot products."""
+    """A factorized retrieval task: in-batch softmax (or a pairwise loss) over query x candidate dot products."""
 
     def __init__(self, loss=None, metrics=None, batch_metrics=None, loss_metrics=None, temperature=None,
                  num_hard_negatives=None, remove_accidental_hits=False, name="retrieval_task", precision="f32"):
-        if loss is not None and not (isinstance(loss, CategoricalCrossentropy) and loss.from_logits and loss.reduction == "sum"):
-            raise NotImplementedError("Retrieval(loss=...): only the TFRS default loss - tasks.CategoricalCrossentropy("
-                                      "from_logits=True, reduction='sum') - is implemented in the HIP path; hinge, pairwise "
-                                      "and pointwise losses (and other reductions) need the [queries x candidates] score "
-                                      "matrix, which the fused kernels never materialise")
+        self._pairwise = loss if isinstance(loss, _PairwiseLoss) else None
+        if loss is not None and self._pairwise is None and not (
+                isinstance(loss, CategoricalCrossentropy) and loss.from_logits and loss.reduction == "sum"):
+            raise NotImplementedError("Retrieval(loss=...): the HIP path implements the TFRS default loss - tasks."
+                                      "CategoricalCrossentropy(from_logits=True, reduction='sum') - and the pairwise losses "
+                                      "tasks.PairwiseLogisticLoss / BPRLoss and tasks.PairwiseHingeLoss; pointwise losses (and "
+                                      "other reductions of the cross-entropy) need the [queries x candidates] score matrix, "
+                                      "which the fused kernels never materialise")
         from .metrics import TopKCategoricalAccuracy
         self._batch_metrics = list(batch_metrics) if batch_metrics is not None else []
         for m in self._batch_metrics:
@@ -80,6 +124,8 @@ class Retrieval:
         self._remove_accidental_hits = remove_accidental_hits
         if precision not in ("f32", "bf16x3"):
             raise ValueError("precision must be 'f32' or 'bf16x3'")
+        if self._pairwise is not None and precision != "f32":
+            raise NotImplementedError("Retrieval(loss=<pairwise loss>, precision='bf16x3'): the pairwise kernels are exact f32 only")
         self._precision = precision          # (extension) matrix-product precision of the training passes: torch_ops.py
         self.name = name
         self.last_per_example_loss = None
@@ -102,7 +148,14 @@ class Retrieval:
         sw = None if sample_weight is None else sample_weight.to(torch.float32).contiguous()
         cp = None if candidate_sampling_probability is None else candidate_sampling_probability.to(torch.float32).contiguous()
         k = 0 if self._num_hard_negatives is None else int(self._num_hard_negatives)
-        if torch.is_grad_enabled() and (q.requires_grad or c.requires_grad):
+        pw = self._pairwise
+        if pw is not None and torch.is_grad_enabled() and (q.requires_grad or c.requires_grad):
+            loss, per_example, _, _ = torch.ops.twotower.retrieval_pairwise_loss(q, c, sw, cp, ids, inv_t, diag_offset, k, pw.kind,
+                                                                                 pw.margin, pw.reduction)
+        elif pw is not None:
+            loss, per_example = torch.ops.twotower.retrieval_pairwise_loss_value(q, c, sw, cp, ids, inv_t, diag_offset, k, pw.kind,
+                                                                                 pw.margin, pw.reduction)
+        elif torch.is_grad_enabled() and (q.requires_grad or c.requires_grad):
             loss, per_example, _, _ = torch.ops.twotower.retrieval_loss(q, c, sw, cp, ids, inv_t, diag_offset, k, self._precision)
         else:
             loss, per_example = torch.ops.twotower.retrieval_loss_value(q, c, sw, cp, ids, inv_t, diag_offset, k, self._precision)

@@ -73,6 +73,7 @@ def release_workspaces() -> None:
     _WS_CACHE.clear()
     _PLAN_CACHE.clear()
     _TOPK_WS.clear()
+    _PW_WS.clear()
 
 
 # --------------------------------------------------------------------------------------------- a1 lookup
@@ -414,6 +415,91 @@ def retrieval_loss_value(query_embeddings: Tensor, candidate_embeddings: Tensor,
 @retrieval_loss_value.register_fake
 def _(q, c, sample_weight, candidate_sampling_probability, candidate_ids, inv_temperature, diag_offset, num_hard_negatives,
       precision="f32"):
+    return q.new_empty(()), q.new_empty((q.shape[0],))
+
+
+_PW_WS: dict = {}
+
+
+def _pairwise_ws(nq: int, nc: int, d: int, device) -> Tensor:
+    """Workspace of the pairwise-loss ops, kept per (device, stream) like the scorer's (the largest one seen)."""
+    n = max(ops.retrieval_pairwise_workspace_bytes(nq, nc, d), 1)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(n, dtype=torch.uint8, device=device)
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    hit = _PW_WS.get(key)
+    if hit is not None and hit.numel() >= n:
+        return hit
+    _PW_WS.pop(key, None)
+    buf = _PW_WS[key] = torch.empty(n, dtype=torch.uint8, device=device)
+    return buf
+
+
+def _pairwise_thresholds(q, c, sample_prob, candidate_ids, inv_temperature, diag_offset, num_hard_negatives):
+    """hard_thr of the pairwise ops: the scorer's hard-negative thresholds (its own forward workspace), None without mining."""
+    if num_hard_negatives <= 0:
+        return None
+    ws = _ws(q.shape[0], c.shape[0], q.shape[1], q.device, forward_only=True)
+    return ops.retrieval_hard_negative_thresholds(q, c, inv_temperature, num_hard_negatives, ws, cand_prob=sample_prob,
+                                                  cand_ids=candidate_ids, diag_offset=diag_offset)
+
+
+@torch.library.custom_op(f"{NS}::retrieval_pairwise_loss", mutates_args=(), device_types="cuda")
+def retrieval_pairwise_loss(query_embeddings: Tensor, candidate_embeddings: Tensor, sample_weight: Optional[Tensor],
+                            candidate_sampling_probability: Optional[Tensor], candidate_ids: Optional[Tensor],
+                            inv_temperature: float, diag_offset: int, num_hard_negatives: int, kind: str, margin: float,
+                            reduction: str) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Pairwise loss over the in-batch negatives AND its gradients (``ops.retrieval_pairwise_fwd_bwd``): ``kind`` "logistic"
+    (BPR: softplus(s_neg - s_pos)) or "hinge" (max(0, margin - (s_pos - s_neg))) on the logits ``retrieval_loss`` sees;
+    ``reduction`` "mean" (per row, over its negatives) or "sum".  Returns (loss [], per-example loss [Bq], dLoss/dq, dLoss/dc);
+    the autograd formula multiplies the saved gradients by the incoming scalar gradient.  ``candidate_ids`` given = accidental-hit
+    removal; ``num_hard_negatives`` > 0 keeps the k hardest negatives per query (the triplet setting)."""
+    q, c = query_embeddings.contiguous(), candidate_embeddings.contiguous()
+    nq, nc, d = q.shape[0], c.shape[0], q.shape[1]
+    thr = _pairwise_thresholds(q, c, candidate_sampling_probability, candidate_ids, inv_temperature, diag_offset, num_hard_negatives)
+    per_row, loss = q.new_empty(nq), q.new_empty(1)
+    dq, dc = torch.empty_like(q), torch.empty_like(c)
+    ops.retrieval_pairwise_fwd_bwd(q, c, inv_temperature, _pairwise_ws(nq, nc, d, q.device), per_row, loss, dq, dc, kind=kind,
+                                   margin=margin, reduction=reduction, sample_weight=sample_weight,
+                                   cand_prob=candidate_sampling_probability, cand_ids=candidate_ids, diag_offset=diag_offset,
+                                   hard_thr=thr)
+    return loss.reshape(()), per_row, dq, dc
+
+
+@retrieval_pairwise_loss.register_fake
+def _(q, c, sample_weight, candidate_sampling_probability, candidate_ids, inv_temperature, diag_offset, num_hard_negatives, kind,
+      margin, reduction):
+    return q.new_empty(()), q.new_empty((q.shape[0],)), torch.empty_like(q), torch.empty_like(c)
+
+
+def _pairwise_backward(ctx, g_loss, g_per_example, g_dq, g_dc):
+    dq, dc = ctx.saved_tensors
+    sdq, sdc = torch._foreach_mul((dq, dc), g_loss)
+    return sdq, sdc, None, None, None, None, None, None, None, None, None
+
+
+retrieval_pairwise_loss.register_autograd(_pairwise_backward, setup_context=_retrieval_setup)
+
+
+@torch.library.custom_op(f"{NS}::retrieval_pairwise_loss_value", mutates_args=(), device_types="cuda")
+def retrieval_pairwise_loss_value(query_embeddings: Tensor, candidate_embeddings: Tensor, sample_weight: Optional[Tensor],
+                                  candidate_sampling_probability: Optional[Tensor], candidate_ids: Optional[Tensor],
+                                  inv_temperature: float, diag_offset: int, num_hard_negatives: int, kind: str, margin: float,
+                                  reduction: str) -> Tuple[Tensor, Tensor]:
+    """Forward only (validation) of ``retrieval_pairwise_loss``: (loss [], per-example loss [Bq]) in one pass."""
+    q, c = query_embeddings.contiguous(), candidate_embeddings.contiguous()
+    nq, nc, d = q.shape[0], c.shape[0], q.shape[1]
+    thr = _pairwise_thresholds(q, c, candidate_sampling_probability, candidate_ids, inv_temperature, diag_offset, num_hard_negatives)
+    per_row, loss = q.new_empty(nq), q.new_empty(1)
+    ops.retrieval_pairwise_fwd(q, c, inv_temperature, _pairwise_ws(nq, nc, d, q.device), per_row, loss, kind=kind, margin=margin,
+                               reduction=reduction, sample_weight=sample_weight, cand_prob=candidate_sampling_probability,
+                               cand_ids=candidate_ids, diag_offset=diag_offset, hard_thr=thr)
+    return loss.reshape(()), per_row
+
+
+@retrieval_pairwise_loss_value.register_fake
+def _(q, c, sample_weight, candidate_sampling_probability, candidate_ids, inv_temperature, diag_offset, num_hard_negatives, kind,
+      margin, reduction):
     return q.new_empty(()), q.new_empty((q.shape[0],))
 
 

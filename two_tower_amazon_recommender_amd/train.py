@@ -153,6 +153,14 @@ def parse(argv=None):
     ap.add_argument("--scorer-precision", default="f32", choices=["f32", "bf16x3"],
                     help="matrix products of the scorer + softmax loss: exact f32 (default) or f32-emulated split-bf16 on the "
                          "bf16 matrix cores (scorer dim 128 / 256; same 1e-4 parity bars, ~2x faster scorer)")
+    ap.add_argument("--retrieval-loss", default=None, choices=["softmax", "bpr", "hinge"],
+                    help="the retrieval loss over the step's candidates: softmax (the in-batch sampled softmax, default), bpr "
+                         "(pairwise logistic) or hinge (pairwise hinge with --pairwise-margin), on the same logits (overrides "
+                         "model.retrieval.loss.kind); exact f32, single-GPU trainer only")
+    ap.add_argument("--pairwise-margin", type=float, default=None, metavar="M",
+                    help="margin of the pairwise hinge loss (default model.retrieval.loss.margin, else 1.0)")
+    ap.add_argument("--pairwise-reduction", default=None, choices=["mean", "sum"],
+                    help="mean: every query's sum over its negatives is divided by their number (default); sum: it is not")
     ap.add_argument("--normalize-embeddings", action="store_true",
                     help="L2-normalise both towers' outputs before the scorer (cosine scoring; overrides "
                          "model.retrieval.normalize_embeddings to true); single-GPU trainer only")
@@ -171,6 +179,28 @@ def parse(argv=None):
                     help="distributed: in-batch negatives of the rank's own batch (what tfrs.tasks.Retrieval sees under a "
                          "data-parallel strategy) or of the all-gathered global batch")
     return ap.parse_args(argv)
+
+
+def retrieval_loss_settings(args, doc: dict, distributed: bool) -> dict:
+    """{kind, margin, reduction} of the run: the ``model.retrieval.loss`` block overridden by --retrieval-loss / --pairwise-margin /
+    --pairwise-reduction, with the refusals of a pairwise loss (bf16x3 scorer precision, the row-sharded trainer)."""
+    rloss = cfgmod.retrieval_loss_from_dict(doc)
+    for key, arg in (("kind", args.retrieval_loss), ("margin", args.pairwise_margin), ("reduction", args.pairwise_reduction)):
+        if arg is not None:
+            rloss[key] = arg
+    if not np.isfinite(rloss["margin"]):
+        raise SystemExit("--pairwise-margin must be a finite number")
+    if rloss["kind"] == "softmax":
+        if args.pairwise_margin is not None or args.pairwise_reduction is not None:
+            raise SystemExit("--pairwise-margin / --pairwise-reduction need a pairwise loss: --retrieval-loss bpr | hinge (or "
+                             "model.retrieval.loss.kind)")
+        return rloss
+    if args.scorer_precision != "f32":
+        raise SystemExit(f"--retrieval-loss {rloss['kind']} needs --scorer-precision f32: the pairwise kernels are exact f32 only")
+    if distributed:
+        raise NotImplementedError("a pairwise retrieval loss (bpr / hinge) is not implemented for the row-sharded (--distributed) "
+                                  "trainer")
+    return rloss
 
 
 def main(argv=None) -> int:
@@ -249,6 +279,7 @@ def main(argv=None) -> int:
         raise NotImplementedError("gradient clipping (global_clipnorm) is not implemented for the row-sharded (--distributed) trainer")
     if distributed and (sched["warmup_steps"] > 0 or sched["decay"] != "none"):
         raise NotImplementedError("a learning-rate schedule is not implemented for the row-sharded (--distributed) trainer")
+    rloss = retrieval_loss_settings(args, doc, distributed)
     sampling = args.candidate_sampling or ((doc.get("model") or {}).get("retrieval") or {}).get("candidate_sampling", "in_batch")
     if distributed and sampling == "mixed":
         raise NotImplementedError("candidate_sampling 'mixed' is not implemented for the row-sharded (--distributed) trainer")
@@ -303,6 +334,7 @@ def main(argv=None) -> int:
     cfg, loop = cfgmod.model_config_from_dict(doc, n_users, n_items, optimizer=args.optimizer)
     cfg.n_category_buckets = args.category_buckets
     cfg.scorer_precision = args.scorer_precision
+    cfg.retrieval_loss, cfg.pairwise_margin, cfg.pairwise_reduction = rloss["kind"], float(rloss["margin"]), rloss["reduction"]
     cfg.normalize_embeddings = normalize
     cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = args.adam_beta1, args.adam_beta2, args.adam_epsilon
     cfg.n_title_buckets = title_buckets

@@ -55,6 +55,8 @@ HISTORY_POOLINGS = tuple(ops.POOLINGS) + ("attention", "gru")
 HISTORY_ENCODERS = HISTORY_POOLINGS + ("self_attention",)
 LR_DECAYS = ("none", "cosine", "linear", "inverse_sqrt")
 SAMPLING_BIAS_ESTIMATORS = ("none", "streaming")
+RETRIEVAL_LOSSES = ("softmax", "bpr", "hinge")
+PAIRWISE_KIND_OF_LOSS = {"bpr": "logistic", "hinge": "hinge"}     # retrieval_loss -> the kernel family's kind
 TID_DROPOUT_BASE = 64
 
 
@@ -100,6 +102,15 @@ class TwoTowerConfig:
     # matrix products of the scorer + softmax loss: "f32" (exact f32 products on the f32-input MFMA: the parity-safe default
     # and the headline) or "bf16x3" (f32-emulated through a three-way bf16 split on the bf16 MFMA; scorer dim 128 / 256)
     scorer_precision: str = "f32"
+    # the retrieval loss over the step's candidates: "softmax" (the in-batch sampled softmax of tfrs.tasks.Retrieval, the default),
+    # "bpr" (pairwise logistic: softplus(s_neg - s_pos) over a query's negatives, Rendle 2009) or "hinge" (pairwise hinge:
+    # max(0, pairwise_margin - (s_pos - s_neg))), on the same logits - temperature, logQ correction, accidental hits removed
+    # (csrc/pairwise.hip).  pairwise_reduction "mean": every query's sum is divided by ITS number of negatives, so a margin and a
+    # learning rate keep their meaning when the batch size changes; "sum": the plain sum over the pairs.  Exact f32 only;
+    # single-GPU trainer, Python sequence of launches, no graph capture.
+    retrieval_loss: str = "softmax"
+    pairwise_margin: float = 1.0
+    pairwise_reduction: str = "mean"
     # cosine scoring: both towers' outputs are L2-normalised (tf.math.l2_normalize: x / sqrt(max(sum x^2, normalize_eps))) before
     # the scorer, every metric and every embedding the trainer hands out - what the reference's temperature 0.1 is meant for
     # (Yi et al. 2019; SURVEY.md lists the choice as left open).  Off = the towers' raw outputs, as before.
@@ -291,6 +302,16 @@ class TwoTowerConfig:
             raise ValueError(f"scorer_precision must be one of {ops.SCORER_PRECISIONS}")
         if self.scorer_precision == "bf16x3" and self.tower_dims[-1] not in (128, 256):
             raise ValueError("scorer_precision='bf16x3' needs a scorer dim (last tower dim) of 128 or 256")
+        if self.retrieval_loss not in RETRIEVAL_LOSSES:
+            raise ValueError(f"retrieval_loss must be one of {RETRIEVAL_LOSSES}, got {self.retrieval_loss!r}")
+        if isinstance(self.pairwise_margin, bool) or not isinstance(self.pairwise_margin, (int, float)) \
+                or not math.isfinite(self.pairwise_margin):
+            raise ValueError("pairwise_margin must be a finite number")
+        if self.pairwise_reduction not in ops.PAIRWISE_REDUCTIONS:
+            raise ValueError(f"pairwise_reduction must be one of {tuple(ops.PAIRWISE_REDUCTIONS)}, got {self.pairwise_reduction!r}")
+        if self.retrieval_loss != "softmax" and self.scorer_precision != "f32":
+            raise ValueError(f"retrieval_loss={self.retrieval_loss!r} needs scorer_precision='f32': the pairwise kernels are exact "
+                             "f32 only")
         if not isinstance(self.normalize_embeddings, bool):
             raise ValueError("normalize_embeddings must be a bool")
         if not self.normalize_eps > 0:
@@ -1092,6 +1113,8 @@ _GRAPH_REFUSALS = (
      "launches over materialised tower inputs"),
     (lambda c: c.global_clipnorm > 0, "gradient clipping (global_clipnorm > 0) is not implemented: the step is the Python sequence of "
      "launches"),
+    (lambda c: c.retrieval_loss != "softmax", "a pairwise retrieval loss (retrieval_loss='bpr' / 'hinge') is not implemented: the "
+     "step is the Python sequence of launches"),
     (lambda c: c.lr_schedule_on, "a learning-rate schedule (lr_warmup_steps / lr_decay): the step's rate is a kernel argument"))
 
 
@@ -1133,6 +1156,11 @@ class TwoTowerTrainer:
                 grad_slabs[f"{side}.W{l}"] = (tower.dw_slabs[l], tower.n_slabs)
                 grad_slabs[f"{side}.b{l}"] = (tower.db_slabs[l], tower.n_slabs)
         self.ws = torch.empty(ops.retrieval_workspace_bytes(b, bi, sd), dtype=torch.uint8, device=dev)
+        # a pairwise retrieval loss: its kernel family's kind and its own workspace (allocated only with the option on)
+        self.pairwise_kind = PAIRWISE_KIND_OF_LOSS.get(cfg.retrieval_loss)
+        self.pairwise_ws = None
+        if self.pairwise_kind is not None:
+            self.pairwise_ws = torch.empty(ops.retrieval_pairwise_workspace_bytes(b, bi, sd), dtype=torch.uint8, device=dev)
         self.lse = torch.empty(b, device=dev)
         self.per_row = torch.empty(b, device=dev)
         self.loss = torch.empty(1, device=dev)
@@ -1835,9 +1863,15 @@ class TwoTowerTrainer:
         # normalised: the scorer's gradients are w.r.t. the unit vectors; _outputs_backward turns them into the last layer's dz
         dq, dc = (ut.dunit, it.dunit) if cfg.normalize_embeddings else (ut.dz[-1], it.dz[-1])
         # loss + dq + dc in two fused passes over the logits (probabilities never stored; f32: raw dot products kept in self.ws)
-        ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
-                              sample_weight=sample_weight, cand_prob=candidate_sampling_probability, cand_ids=candidate_ids,
-                              precision=cfg.scorer_precision)
+        if self.pairwise_kind is not None:       # (the same outputs; self.lse is not touched)
+            ops.retrieval_pairwise_fwd_bwd(q, c, 1.0 / cfg.temperature, self.pairwise_ws, self.per_row, self.loss, dq, dc,
+                                           kind=self.pairwise_kind, margin=cfg.pairwise_margin, reduction=cfg.pairwise_reduction,
+                                           sample_weight=sample_weight, cand_prob=candidate_sampling_probability,
+                                           cand_ids=candidate_ids)
+        else:
+            ops.retrieval_fwd_bwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss, dq, dc,
+                                  sample_weight=sample_weight, cand_prob=candidate_sampling_probability, cand_ids=candidate_ids,
+                                  precision=cfg.scorer_precision)
         if self.rating_on:                       # the pairs are the first batch_size candidate rows; sampled rows get no head gradient
             self._rating_forward_backward(q, c, dq, dc, ratings, sample_weight)
         self._outputs_backward((ut, it), (dq, dc))
@@ -2071,7 +2105,8 @@ class TwoTowerTrainer:
         fused_sort = shape_ok and not self._skewed()
         # (the clip launches sit between the backward pass and the optimizer: never composite)
         if (fused_sort and not cfg.global_clipnorm > 0 and self.use_composite and self.fuse_lookup and cfg.symmetric
-                and not cfg.normalize_embeddings and not cfg.layer_norm and not self.rating_on and cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
+                and not cfg.normalize_embeddings and not cfg.layer_norm and not self.rating_on and self.pairwise_kind is None
+                and cfg.batch_size <= ops.MAX_FUSED_LOOKUP_ROWS):
             return self._step_composite(ids, **loss_kw)
         side = self._side if (self.plan_on_side_stream and not fused_sort and not self.mixed) else None
         if side is not None:
@@ -2206,6 +2241,12 @@ class TwoTowerTrainer:
         q, c = self._outputs((ut, it), rows)
         if self.rating_on:
             self._rating_evaluate(q, c, ratings, loss_kw.get("sample_weight"))
+        if self.pairwise_kind is not None:
+            return ops.retrieval_pairwise_fwd(q, c, 1.0 / cfg.temperature, self.pairwise_ws, self.per_row, self.loss,
+                                              kind=self.pairwise_kind, margin=cfg.pairwise_margin, reduction=cfg.pairwise_reduction,
+                                              sample_weight=loss_kw.get("sample_weight"),
+                                              cand_prob=loss_kw.get("candidate_sampling_probability"),
+                                              cand_ids=loss_kw.get("candidate_ids"))
         return ops.retrieval_fwd(q, c, 1.0 / cfg.temperature, self.ws, self.lse, self.per_row, self.loss,
                                  sample_weight=loss_kw.get("sample_weight"), cand_prob=loss_kw.get("candidate_sampling_probability"),
                                  cand_ids=loss_kw.get("candidate_ids"), precision=cfg.scorer_precision)
