@@ -51,10 +51,15 @@ enum { MODE_FWD = 0, MODE_BWD = 1, MODE_FUSED = 2, MODE_RANK = 3, MODE_FUSED_S =
        // MODE_FUSED_S_NC with the column splits INSIDE the workgroup (dim 128, 8 splits): all 8 waves hold the same 32-row fragment,
        // wave w runs split w on a private LDS tile, the 8 partial results meet in LDS and the kernel finishes lse, per-row loss, the
        // dc pass's row terms and dq itself - no slab, no part_m / part_l, no combine launch (score_rowfrag_kernel)
-       MODE_FUSED_S_WG = 9 };
+       MODE_FUSED_S_WG = 9,
+       // MODE_BWD_S_NR_T with the query splits INSIDE the workgroup (dim 128, 8 splits of whole tiles): all 8 waves own the same
+       // 32-candidate fragment, wave w runs split w on a private LDS tile, the 8 partial dc blocks are summed in LDS in split order
+       // and one workgroup sums the per-row losses - no slab, no reduce_slabs_kernel launch (score_colfrag_kernel)
+       MODE_BWD_S_WG = 10 };
 constexpr int base_mode(int m) {
-  return (m == MODE_FUSED_S_NC || m == MODE_FUSED_S_WG) ? (int)MODE_FUSED_S
-                                                        : ((m == MODE_BWD_S_NR || m == MODE_BWD_S_NR_T) ? (int)MODE_BWD_S : m);
+  return (m == MODE_FUSED_S_NC || m == MODE_FUSED_S_WG)
+             ? (int)MODE_FUSED_S
+             : ((m == MODE_BWD_S_NR || m == MODE_BWD_S_NR_T || m == MODE_BWD_S_WG) ? (int)MODE_BWD_S : m);
 }
 constexpr int kRowTermRows = 4096;        // streamed rows per split whose two row terms the LDS array holds (32 KB)
 template <int D, int MODE_T> constexpr bool row_terms_in_lds() { return MODE_T == MODE_BWD_S_NR && D <= 128; }
@@ -103,6 +108,9 @@ struct ScoreArgs {
   float* aq;                // [n_r] -lse2: the dc pass's row bias
   float* sq;                // [n_r] w * scale: the dc pass's row scale
   float* dq;                // [n_r][D]
+  // MODE_BWD_S_WG only: the gradient of the stationary side, and the scalar loss = sum(per_row[0 .. n_c)) its first workgroup writes
+  float* dr;                // [n_r][D]
+  float* loss;              // [1]
 };
 
 // The pass-1 combine for one (row, float4 column): the per-split (max, sum, G) of a row -> lse, per-row loss, the dc pass's row
@@ -251,6 +259,7 @@ constexpr int rows_per_wg() { return (split_d<D, MODE, PREC>() ? WAVES / 2 : WAV
 template <int D, int MODE_T, bool HAS_IDS, bool HAS_HN, int WAVES, int PREC>
 __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 ? 2 : (D <= 128 ? ((base_mode(MODE_T) == MODE_BWD_S && PREC == 0) ? kBwdSWaves : 2) : 1))) void score_kernel(ScoreArgs p) {   // (min waves per SIMD)
   static_assert(MODE_T != MODE_FUSED_S_WG, "the form without a barrier in its tile loops is score_rowfrag_kernel");
+  static_assert(MODE_T != MODE_BWD_S_WG, "the form without a barrier in its tile loops is score_colfrag_kernel");
 #include "score_kernel_body.h"
 }
 
@@ -263,6 +272,18 @@ template <int D> constexpr int rowfrag_lds_bytes() { return (kRowfragWaves * Geo
 template <int D>
 __global__ __launch_bounds__(kRowfragWaves * 64, 2) void score_rowfrag_kernel(ScoreArgs p) {
   constexpr int MODE_T = MODE_FUSED_S_WG, WAVES = kRowfragWaves, PREC = 0;
+  constexpr bool HAS_IDS = false, HAS_HN = false;
+#include "score_kernel_body.h"
+}
+
+// The dc pass of the plain train step with the query splits inside the workgroup (MODE_BWD_S_WG): one 32-candidate fragment per
+// workgroup, 8 waves = 8 splits of whole tiles, one workgroup per CU.  LDS: 8 private buffers of a tile and its 64 row terms, and
+// the 512 partial sums of the loss.  A name of its own for the reason score_rowfrag_kernel has one.
+constexpr int kColfragWaves = 8;
+template <int D> constexpr int colfrag_lds_bytes() { return (kColfragWaves * (Geo<D, 0>::TILE_F + 64) + kColfragWaves * 64) * 4; }
+template <int D>
+__global__ __launch_bounds__(kColfragWaves * 64, 2) void score_colfrag_kernel(ScoreArgs p) {
+  constexpr int MODE_T = MODE_BWD_S_WG, WAVES = kColfragWaves, PREC = 0;
   constexpr bool HAS_IDS = false, HAS_HN = false;
 #include "score_kernel_body.h"
 }
@@ -638,6 +659,12 @@ int launch_score(const ScoreArgs& a_in, hipStream_t stream) {
         }
       } else {
         if (a.a_r == nullptr && a.s_r == nullptr && a.a_c != nullptr && a.s_c != nullptr) {
+          // the splits inside the workgroup (the caller asks for it by passing dc itself: dc_in_workgroup): wave w = split w, and
+          // every split whole tiles of equal number - the kernel has no tail loop, no row mask and no clamp on a streamed row
+          if constexpr (D == 128) {
+            if (a.dr != nullptr && a.nsplit == kColfragWaves && a.n_c == kColfragWaves * a.c_per_split)
+              return go_at(score_colfrag_kernel<D>, (a.n_r + 31) / 32, kColfragWaves * 64, colfrag_lds_bytes<D>());
+          }
           if constexpr (row_terms_in_lds<D, MODE_BWD_S_NR>()) {
             // the row terms once per workgroup in LDS where a split's rows fit the array, else per tile as ever
             if (a.c_per_split > kRowTermRows) return go(score_kernel<D, MODE_BWD_S_NR_T, false, false, W, 0>);
@@ -649,6 +676,7 @@ int launch_score(const ScoreArgs& a_in, hipStream_t stream) {
     }
   }
   if (a.dq != nullptr) return tt::fail(TT_ERR_UNSUPPORTED, "score pass 1: no in-workgroup combine for this call");   // (never silently without dq)
+  if (a.dr != nullptr) return tt::fail(TT_ERR_UNSUPPORTED, "score pass 2: no in-workgroup split sum for this call"); // (... nor without dc)
   if (has_ids && has_hn) return go(score_kernel<D, MODE, true, true, W, PREC>, rf_lds_groups<D, MODE, true, true, PREC>());
   if (has_ids) return go(score_kernel<D, MODE, true, false, W, PREC>, rf_lds_groups<D, MODE, true, false, PREC>());
   if (has_hn) return go(score_kernel<D, MODE, false, true, W, PREC>, rf_lds_groups<D, MODE, false, true, PREC>());
@@ -934,8 +962,15 @@ static int retrieval_fwd_bwd(const char* fn, int prec, const float* q, const flo
     hipLaunchKernelGGL(hn_shift_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, hard_thr, aq, hq, nq);
     if ((rc = tt::check_launch("hn_shift")) != TT_OK) return rc;
   }
-  const ScoreArgs a = dc_pass_args(q, c, nq, nc, diag_offset, inv_temperature, w.ns_cs, cand_ids, bias, aq, sq, hq, slab, smat);
+  ScoreArgs a = dc_pass_args(q, c, nq, nc, diag_offset, inv_temperature, w.ns_cs, cand_ids, bias, aq, sq, hq, slab, smat);
+  // The plain step at dim 128 with 8 query splits of whole tiles (nq = 8 * c_per_split, so nq % 256 == 0): one candidate fragment
+  // per workgroup, the splits summed in LDS and the loss summed by the pass itself (MODE_BWD_S_WG) - the slab region stays
+  // untouched and there is no reduction launch.  Independent of pass 1's form.
+  const bool dc_in_workgroup = prec == 0 && dim == 128 && w.ns_cs == kColfragWaves && bias == nullptr && cand_ids == nullptr &&
+                               hard_thr == nullptr && nq == kColfragWaves * a.c_per_split;
+  if (dc_in_workgroup) { a.dr = dc; a.per_row = per_row; a.loss = loss; }
   if ((rc = dispatch_score<MODE_BWD_S>(prec, dim, a, stream)) != TT_OK) return rc;
+  if (dc_in_workgroup) return TT_OK;
   return reduce_slabs("reduce_slabs(dc)", slab, dc, nc, dim, a.nsplit, per_row, nq, loss, stream);
 }
 

@@ -1,4 +1,4 @@
-// The body of score_kernel and of score_rowfrag_kernel (csrc/score.hip), included INSIDE each of the two: one text for both, and the
+// The body of score_kernel, score_rowfrag_kernel and score_colfrag_kernel (csrc/score.hip), included INSIDE each: one text for all, and the
 // kernels compile exactly as if each had it written out (as a function inlined into two wrappers, every instantiation came out
 // with other code).  It sees the kernel's argument `ScoreArgs p` and D, MODE_T, HAS_IDS, HAS_HN, WAVES, PREC as compile-time constants.
   // FAST: the two instantiations of the plain train step.  What they leave out is work on values the step's arguments make dead:
@@ -22,6 +22,12 @@
   // checks).  What differs is where a wave's tiles live (a private LDS buffer, no workgroup barrier) and where the splits meet (LDS).
   constexpr bool WG = MODE_T == MODE_FUSED_S_WG;
   static_assert(!WG || (D == 128 && WAVES == 8), "splits inside the workgroup: dim 128, 8 waves");
+  // CW: MODE_BWD_S_NR_T's arithmetic, one 32-row fragment of the stationary side (the candidates) per workgroup: wave w = split w of
+  // the streamed queries (nsplit == WAVES, n_c == WAVES * c_per_split - whole tiles, the same number for every wave: launch_score
+  // checks).  As in WG, a wave's tiles live in a private LDS buffer (no workgroup barrier) and the splits meet in LDS.
+  constexpr bool CW = MODE_T == MODE_BWD_S_WG;
+  static_assert(!CW || (D == 128 && WAVES == 8), "splits inside the workgroup: dim 128, 8 waves");
+  constexpr bool INWG = WG || CW;                        // one fragment per workgroup, wave = split, private tiles
   constexpr BoolC<false> GEN{};                            // the general form of a step: every clamp and select
   constexpr BoolC<true> FULL_TILE{};
   constexpr bool NO_AC = FAST && MODE == MODE_FUSED_S;      // no column bias: nothing staged for it
@@ -57,10 +63,10 @@
   // vector ALU; whether the quotient comes back to an SGPR is its choice, and a trip count left in VGPRs turns the tile
   // loop's exit test into a vector compare with the barrier inside a loop the compiler treats as divergent.
   // tests/isa_audit/audit_barriers.py checks the built ISA: in all instantiations every barrier loop closes on scalar branches.
-  const int split = __builtin_amdgcn_readfirstlane(WG ? wave : (int)(blockIdx.x % (unsigned)p.nsplit));
-  const int64_t rblk = __builtin_amdgcn_readfirstlane(WG ? (int)blockIdx.x : (int)(blockIdx.x / (unsigned)p.nsplit));
+  const int split = __builtin_amdgcn_readfirstlane(INWG ? wave : (int)(blockIdx.x % (unsigned)p.nsplit));
+  const int64_t rblk = __builtin_amdgcn_readfirstlane(INWG ? (int)blockIdx.x : (int)(blockIdx.x / (unsigned)p.nsplit));
   const int hw = SPLIT ? (wave & 1) : 0;             // SPLIT: the half of the embedding dimension this wave owns
-  const int64_t r0w = WG ? rblk * 32                 // first row of this wave (WG: of all 8)
+  const int64_t r0w = INWG ? rblk * 32               // first row of this wave (WG / CW: of all 8)
                          : rblk * rows_per_wg<D, MODE, PREC, WAVES>() + (SPLIT ? wave >> 1 : wave) * 32;
   const int64_t r = r0w + ln;                       // this lane's row (both halves)
   const bool r_ok = r < p.n_r;
@@ -284,7 +290,10 @@
   // rows and the stream's chunk after next requested into the freed registers: every chunk has half a GEMM2 (a microsecond and
   // more) between request and use, GEMM1 of the next tile starts behind the last quarter's write.  A wave's LDS operations
   // execute in order, the buffer is its own: no barrier.  Loads unconditional from clamped addresses, as everywhere.
-  float* TW = smem + (WG ? wave * TILE_F : 0);
+  // CW: the same chunk stream with the tile's 64 row terms (a_c | s_c, where the epilogue looks for them) behind each wave's tile;
+  // it has no GEMM1, no stationary fragment and only full tiles.
+  constexpr int WBUF_F = CW ? TILE_F + 64 : TILE_F;    // floats of a wave's private buffer
+  float* TW = smem + (INWG ? wave * WBUF_F : 0);
   f32x4 ck[2][4];
   unsigned ck_offb = 16u * (unsigned)lane;             // byte offset of the lane's float4 within a row pair
   // t: a tile that exists; k: chunk 0 .. 3.  full: tile t has 32 valid rows - a scalar base and immediate offsets, no clamp
@@ -428,7 +437,7 @@
       }
     }
   }
-  if constexpr (!WG) {
+  if constexpr (!INWG) {
 #pragma unroll
     for (int t0 = 0; t0 < TPB; ++t0)
       if (t0 < ntiles) {
@@ -669,7 +678,7 @@
     }
   };
 
-  // quarter_done(k) (WG only, else unused): called behind the last read of the tile's rows 8k .. 8k+7
+  // quarter_done(k) (WG and CW only, else unused): called behind the last read of the tile's rows 8k .. 8k+7
   auto gemm2 = [&](const float* T, const float (&coef)[16], auto quarter_done) {
     if constexpr (PREC == 1) {
       // ---- GEMM2 (bf16x3): G^T[d = 32 b + acc row][r] += sum_c K[c][d] * coef[c][r].  The accumulator's registers
@@ -751,7 +760,7 @@
         }
         kc0 = kn0; kc1 = kn1;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (WG) {
+        if constexpr (INWG) {
           // (the reads of step reg + 1 are already issued: they touch rows 8k + 8 and up, or nothing at all behind the last step)
           if ((reg & 3) == 3) {
             quarter_done(reg >> 2);
@@ -799,6 +808,87 @@
       for (; t < nfast; ++t) wg_step(t, FULL_TILE);
       for (; t < ntiles; ++t) wg_step(t, GEN);
     }
+  } else if constexpr (CW) {
+    // ---- CW: epilogue -> GEMM2 per tile on the stored dot products and the wave's private buffer, no barrier.  Every split is
+    // ntiles >= 1 FULL tiles (launch_score checks), so there is one step form: no tail loop, no mask_S, no row clamp; only the tile
+    // INDEX of a prefetch is clamped (a scalar minimum: past its split's end a wave reads its last tile again and nobody consumes
+    // it).  Per step, in order of need: the dot products of tile t + 2 into the register set tile t has just left (full_step's
+    // order), a_c / s_c of tile t + 1 (lane = row, both halves alike), then behind quarter k of GEMM2 chunk k of tile t + 1 is
+    // written and the chunk two further on requested, as in WG; the row terms are written behind the last quarter. ----
+    static_assert(kSPrefetch == 2, "two register sets of stored dot products");
+    f32x16 xa, xb;
+    float sd_a = 0.f, sd_s = 0.f;
+    const unsigned sd_off = (unsigned)ln;
+    auto load_side = [&](int t) {                      // t: a tile that exists
+      sd_a = uniform_base(acp + 32 * (int64_t)t)[sd_off];
+      sd_s = uniform_base(scp + 32 * (int64_t)t)[sd_off];
+    };
+    auto store_side = [&]() { TW[TILE_F + lane] = h ? sd_s : sd_a; };       // [a_c: 32 | s_c: 32]
+    auto cw_step = [&](int t, f32x16& xs_t) {
+      asm volatile("" ::: "memory");                   // (the wave reads back what its own lanes have written: program order)
+      float coef[16];
+      epilogue(TW, t, xs_t, coef, FULL_TILE);
+      load_S(clamp_tile(t + 2), xs_t);
+      load_side(clamp_tile(t + 1));
+      gemm2(TW, coef, [&](int k) {
+        asm volatile("" ::: "memory");
+        store_chunk(ck[k & 1], t + 1, k, FULL_TILE);
+        if (k == 3) store_side();
+        load_chunk(ck[k & 1], clamp_tile(k < 2 ? t + 1 : t + 2), (k + 2) & 3, FULL_TILE);
+      });
+    };
+    // tile 0 whole, in one round trip (the gradient block is not live yet: registers for 16 float4), behind the dot products of the
+    // first two tiles; the stream's first two chunks, which belong to tile 1, are requested behind tile 0's write, so the loop is
+    // entered with exactly what every trip leaves in flight: two chunks
+    load_S(0, xa);
+    load_S(clamp_tile(1), xb);
+    f32x4 t0a[2][4], t0b[2][4];
+    load_chunk(t0a[0], 0, 0, FULL_TILE); load_chunk(t0a[1], 0, 1, FULL_TILE);
+    load_chunk(t0b[0], 0, 2, FULL_TILE); load_chunk(t0b[1], 0, 3, FULL_TILE);
+    load_side(0);
+    if (blockIdx.x == 0) {
+      // loss = sum of the per-row losses pass 1 has written, by the first workgroup, under its first tile's round trip: exactly
+      // sum_rows_kernel's order - 1024 strided partial sums (two per thread), then the binary tree, whose first step (s = 512) is the
+      // sum of a thread's two.  Loads unconditional from clamped rows; the trip count is the workgroup's, not the thread's.
+      float* red = smem + WAVES * WBUF_F;
+      const int64_t nrow = p.n_c;
+      float a0 = 0.f, a1 = 0.f;
+      for (int64_t b0 = 0; b0 < nrow; b0 += 8 * 1024) {
+        float v[8][2];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int64_t rr = b0 + 1024 * i + 512 * j + tid;
+            v[i][j] = p.per_row[rr < nrow ? rr : nrow - 1];
+          }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if (b0 + 1024 * i + tid < nrow) a0 += v[i][0];
+          if (b0 + 1024 * i + 512 + tid < nrow) a1 += v[i][1];
+        }
+      }
+      red[tid] = a0 + a1;
+      __syncthreads();
+      static_assert(THREADS == 512, "a thread holds two of the 1024 partial sums");
+      for (int s2 = 256; s2 > 0; s2 >>= 1) {
+        if (tid < s2) red[tid] += red[tid + s2];
+        __syncthreads();
+      }
+      if (tid == 0) p.loss[0] = red[0];
+    }
+    store_chunk(t0a[0], 0, 0, FULL_TILE); store_chunk(t0a[1], 0, 1, FULL_TILE);
+    store_chunk(t0b[0], 0, 2, FULL_TILE); store_chunk(t0b[1], 0, 3, FULL_TILE);
+    store_side();
+    load_chunk(ck[0], clamp_tile(1), 0, FULL_TILE);
+    load_chunk(ck[1], clamp_tile(1), 1, FULL_TILE);
+    // whole pairs in the loop, an odd last tile behind it (see the slab form below)
+    int t = 0;
+    for (; t + 1 < ntiles; t += 2) {
+      cw_step(t, xa);
+      cw_step(t + 1, xb);
+    }
+    if (t < ntiles) cw_step(t, xa);
   } else if constexpr (FROM_S && kSPrefetch == 2) {
     // ---- BWD_S: epilogue -> GEMM2 per tile on the stored dot products; those of tiles t+1 AND t+2 are in flight while tile
     // t is worked on (two register sets, the body instantiated for each: f32 170 -> 168 us, bf16x3 96 -> 89 us) ----
@@ -982,6 +1072,29 @@
                     [&](int s) { return *reinterpret_cast<const f32x4*>(smem + s * TILE_F + rl * LS + 4 * c4); }, cp[j],
                     stat[2 * WAVES * 32 + rl], wr[j], p.scale, c4 == 0, p.lse + row, p.per_row + row, p.aq + row, p.sq + row,
                     reinterpret_cast<f32x4*>(p.dq + row * D) + c4);
+    }
+    return;
+  }
+  if constexpr (CW) {
+    // The 8 splits of the fragment's 32 rows meet in LDS: every wave leaves its gradient block in its own tile buffer (dead by now;
+    // [32 rows][LS], the slab's row layout).  One barrier; then reduce_slabs_kernel's sum - a = s0; a += s1; ... s7 - on 32 float4
+    // lanes per row, two (row, lane) pairs per thread, stored as 16 bytes per lane.  Rows past n_r are dropped here.
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int i = tt::acc_row(reg, 0) + 4 * h;        // G[b][reg] = G^T[d = NB * i + b][r = ln], NB == 4
+      *reinterpret_cast<f32x4*>(TW + ln * LS + 4 * i) = f32x4{G[0][reg], G[1][reg], G[2][reg], G[3][reg]};
+    }
+    __syncthreads();
+    const int c4 = tid & 31;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int rl = (tid >> 5) + 16 * j;              // the row within the fragment
+      const int64_t row = r0w + rl;
+      f32x4 a = *reinterpret_cast<const f32x4*>(smem + rl * LS + 4 * c4);
+#pragma unroll
+      for (int s = 1; s < WAVES; ++s) a += *reinterpret_cast<const f32x4*>(smem + s * WBUF_F + rl * LS + 4 * c4);
+      if (row < p.n_r) reinterpret_cast<f32x4*>(p.dr + row * D)[c4] = a;
     }
     return;
   }
